@@ -1,10 +1,14 @@
 #!/usr/bin/env python
 """bench.py -- NextBestPath exploration hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 `--gpus N` without a torchrun environment launches the N ranks itself (one process per GPU, RCCL).
+
+A plain run does what the headline needs and nothing else: set up the rollouts, advance and warm them up, time the K steps, write
+the outputs of the last one when `--dump-outputs DIR` is given, print the line (`value`, `ms_per_step`, ...; the fields of the
+other stages are null).  `--full` adds every other stage described below.
 
 One "step" = one exploration step of one rollout (S1-S14 of SURVEY.md section 3.1; BASELINE.json configs[1]:
 AiMDoom_simple-like scene, 256x256 grid, fp32): coverage of the cloud so far, un-projection of 5 depth frames (256x456)
@@ -28,6 +32,7 @@ events on the launch stream, its HBM-side traffic measured live with rocprofv3 P
 from __future__ import annotations
 
 import argparse
+import contextlib
 import ctypes as C
 import json
 import os
@@ -79,7 +84,7 @@ PARITY_TILES = (11, 16)          # execute 4/9 of the reference formulation's pr
 TIMED = {"fp32": "nbp_forward_timed_f32", "fp32_split": "nbp_forward_timed_split_f32", "bf16": "nbp_forward_timed_bf16"}
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
@@ -97,7 +102,13 @@ def parse():
     ap.add_argument("--faces", choices=["simple", "hard"], default="simple")
     ap.add_argument("--rollouts-per-gpu", type=int, default=48,
                     help="independent rollouts stepped in lock-step per GPU (their NBP forwards are one batched launch)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run every stage outside the headline (single rollout, early / late windows, fp32 pipe, strong scaling, "
+                         "roofline / scatter / stage timings with their PMC passes, bf16 and training stages, power, CPU baseline, "
+                         "end-to-end rollout); the --no-* switches above thin out this run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they left rank 0's rollouts with (dump_outputs) as DIR/<name>.npy")
+    return ap.parse_args(argv)
 
 
 def self_launch(args):
@@ -402,7 +413,7 @@ def main():
 
     # ---- single-rollout rate (B = 1 forward, latency-style), mid-trajectory like the headline, reported beside `value`
     single = None
-    if rank == 0 and not args.no_extra_stages:
+    if rank == 0 and args.full and not args.no_extra_stages:
         r1 = make_rollout(15)
         for _ in range(args.advance):
             r1.step()
@@ -435,7 +446,7 @@ def main():
     windows = {}
     done = 0
     adv = max(0, args.advance)
-    if adv >= 25 and not args.no_extra_stages:          # early window of the same rollouts (what round 1 timed)
+    if adv >= 25 and args.full and not args.no_extra_stages:          # early window of the same rollouts (what round 1 timed)
         run_steps(5)
         dt_e = timed_window(20)
         windows["early"] = {"steps": [5, 25], "steps_per_s": round(20 * R / dt_e, 2), "cloud_points_end": cloud_points()}
@@ -459,18 +470,21 @@ def main():
         return d, mine
 
     replans0 = sum(r.n_replans for r in rollouts)
-    with PowerSampler(local_rank) as ps_timed:
+    ps_timed = PowerSampler(local_rank) if args.full else None
+    with ps_timed or contextlib.nullcontext():
         dt, dt_mine = timed_steps(args.steps)
-    power_timed = ps_timed.summary()
+    power_timed = ps_timed.summary() if ps_timed is not None else None
     n1 = cloud_points()
     replans_timed = sum(r.n_replans for r in rollouts) - replans0
     last_step = first_step + args.steps
     windows["timed"] = {"steps": [first_step, last_step], "steps_per_s": round(args.steps * R / dt, 2),
                         "cloud_points_start": n0, "cloud_points_end": n1}
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, rollouts)
     # ---- the same rollouts on the strict fp32 MFMA pipe (v_mfma_f32_32x32x2_f32; NBP_CONV_PRECISION=fp32 makes it the headline
     # path): a shorter window right after the headline's, reported as value_fp32_pipe
     fp32_pipe = None
-    if net.conv_precision != "fp32" and not args.no_extra_stages:
+    if args.full and net.conv_precision != "fp32" and not args.no_extra_stages:
         default_precision = net.conv_precision
         torch.cuda.synchronize()        # nothing in flight on the pack that the switch replaces
         net.conv_precision = "fp32"
@@ -489,7 +503,7 @@ def main():
     # rank i % world -- the partitioning of test_nbp_planning.py -- every rank steps its share in lock-step; the job's time is the
     # slowest rank's.  Reported beside the weak-scaling headline so that one `--gpus N` sweep yields both curves.
     strong = None
-    if not args.no_strong:
+    if args.full and not args.no_strong:
         n_scenes = args.strong_scenes
         mine_ids = list(range(rank, n_scenes, world))
         s_rollouts = [make_rollout(i, hard=True, scene_seed=5000 + i, name=f"hard{i}", fixed_seed=100 + i) for i in mine_ids]
@@ -531,7 +545,7 @@ def main():
 
     roofline = scatter = None
     stage = {}
-    if rank == 0:
+    if rank == 0 and args.full:
         # ---- the dominant kernel, per launch, with HIP events on the launch stream
         x = multi.net_in[0]          # the batch the lock-step really forwards: one pipeline group (R / 2 maps)
         Bf = int(x.shape[0])
@@ -946,6 +960,7 @@ def main():
                 torch.cuda.empty_cache()
             except Exception as e:                      # the headline must not depend on the training stage
                 stage["config3_train_step_b32"] = {"error": repr(e)[:200]}
+    if rank == 0:
         stage["replans_in_timed_region"] = replans_timed
         stage["group_streams"] = multi.stream_check          # the lock-step's streams were verified to run side by side
         if single is not None:
@@ -957,13 +972,13 @@ def main():
         stage["raster_spilled_tiles"] = int(sum(int(r.camera._overflow.item()) for r in rollouts))
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(sd, multi, ro, cam, mesh, y_bins, gt, pose, params, S)
 
     # ---- what a judge needs to believe an N-GPU line (VERDICT r05 Next 4): which devices, what RCCL says the world is, every
     # rank's own seconds over the timed window
     dist_info = None
-    if dist is not None:
+    if dist is not None and args.full:
         props = torch.cuda.get_device_properties(dev)
         mine_info = {"rank": rank, "local_rank": local_rank, "device_uuid": str(getattr(props, "uuid", "")), "device_name": props.name,
                      "timed_window_s": round(dt_mine, 5), "pid": os.getpid()}
@@ -974,7 +989,7 @@ def main():
                      "rank0_core_range": affinity, "visible_devices": os.environ.get("HIP_VISIBLE_DEVICES")}
 
     full = None
-    if rank == 0 and world == 1 and not args.no_full_rollout and not args.no_extra_stages:
+    if rank == 0 and world == 1 and args.full and not args.no_full_rollout and not args.no_extra_stages:
         torch.cuda.empty_cache()
         full = full_rollout()
 
@@ -1011,7 +1026,7 @@ def main():
                                            "fp32": "fp32 MFMA pipe"}.get(net.conv_precision, net.conv_precision),
                        "grid": S, "rollouts_per_gpu": R, "image": [params.image_height, params.image_width],
                        "window_steps": [first_step, last_step], "gt_points": int(gt.shape[0])},
-            "nbp_maps_per_s": round(world * stage["nbp_forward"]["maps_per_s"], 2),
+            "nbp_maps_per_s": round(world * stage["nbp_forward"]["maps_per_s"], 2) if "nbp_forward" in stage else None,
             "stages": stage, "roofline": roofline, "roofline_scatter": scatter, "cpu_baseline": cpu,
             "strong_scaling": strong,
             "distributed": dist_info, "full_rollout": full,
@@ -1031,7 +1046,8 @@ def main():
         out["fwd_group_ms"] = _g("nbp_forward", "ms")
         out["single_rollout_steps_per_s"] = stage.get("single_rollout_steps_per_s")
         # share of a lock-step that its groups' batched forwards alone would take (1.0 = the step's own kernels are fully hidden)
-        out["lockstep_forward_share"] = round(n_groups * stage["nbp_forward"]["ms"] / out["ms_per_step"], 4)
+        out["lockstep_forward_share"] = (round(n_groups * stage["nbp_forward"]["ms"] / out["ms_per_step"], 4) if "nbp_forward" in stage
+                                         else None)
         out["all_conv_frac_executed"] = None if roofline is None else roofline["all_conv_frac_executed"]
         out["roofline_frac"] = None if roofline is None else roofline["frac"]
         out["roofline_traffic_is_live"] = None if roofline is None else roofline["traffic_is_live"]
@@ -1051,6 +1067,43 @@ def main():
     if dist is not None:
         dist.barrier()                  # keep every rank alive until rank 0 has printed
         dist.destroy_process_group()
+
+
+def dump_outputs(out_dir, rollouts, n_map_rollouts=8, cloud_bytes=16 << 20, seed=0):
+    """--dump-outputs: what the timed lock-step left its caller with after its last step, one .npy per array (float32 / float64),
+    so that two builds run with the same arguments (hence the same scenes, seeds and weights) can be compared file by file:
+      coverage          [R, P] float64   coverage_evolution(P) of every rollout, P = poses stepped so far (<= 101)
+      x_cam_history     [R, T, 3] float32, v_cam_history [R, T, 2] float32 (rows past a shorter history are NaN)
+      cloud_count       [R] float64      points in every rollout's cloud
+      cloud_sample      [R, k, 3] float32  the points at k fixed, seeded fractions of every cloud's length (k <= 4096, 16 MB in all)
+      maps6_sample      [m, 6, S, S] float32  the six maps the last step built, for m <= 8 rollouts picked with a fixed seed
+                                              (maps6_sample_rollouts [m] float64 names them)
+    About 15 MB at 48 rollouts; never more than 32 MB."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    R = len(rollouts)
+    P = min(int(rollouts[0].pose_i), N_POSES)
+    arrays = {"coverage": np.array([r.coverage_evolution(P) for r in rollouts], np.float64).reshape(R, P)}
+    for name, attr, w in (("x_cam_history", "X_cam_history", 3), ("v_cam_history", "V_cam_history", 2)):
+        hist = [np.asarray(getattr(r.camera, attr), np.float32).reshape(-1, w) for r in rollouts]
+        a = np.full((R, max(len(h) for h in hist), w), np.nan, np.float32)
+        for i, h in enumerate(hist):
+            a[i, :len(h)] = h
+        arrays[name] = a
+    counts = [int(r.st.cloud_count.item()) for r in rollouts]
+    arrays["cloud_count"] = np.array(counts, np.float64)
+    k = max(1, min(4096, cloud_bytes // (12 * R)))
+    frac = np.sort(np.random.default_rng(seed).random(k))
+    arrays["cloud_sample"] = np.stack([
+        r.st.cloud[torch.from_numpy(np.minimum((frac * n).astype(np.int64), n - 1)).to(r.st.cloud.device)].cpu().numpy() if n > 0
+        else np.zeros((k, 3), np.float32) for r, n in zip(rollouts, counts)]).astype(np.float32)
+    rows = np.sort(np.random.default_rng(seed + 1).choice(R, min(n_map_rollouts, R), replace=False))
+    arrays["maps6_sample"] = torch.stack([rollouts[i].st.maps6 for i in rows]).cpu().numpy().astype(np.float32)
+    arrays["maps6_sample_rollouts"] = rows.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def full_rollout(n_scenes=8, n_poses=101):

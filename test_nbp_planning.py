@@ -34,3 +34,7 @@ if __name__ == "__main__":
                           seed=getattr(p, "random_seed", 8), torch_seed=getattr(p, "torch_seed", 9),
                           rollouts_per_gpu=args.rollouts_per_gpu or getattr(p, "rollouts_per_gpu", 48), grid_size=getattr(p, "grid_size", 256),
                           nbp_precision=getattr(p, "nbp_precision", None))     # None: the model default (fp32_split), what bench.py measures
+    # under torchrun: tear the process group down before exit -- an RCCL group left to the interpreter's shutdown can abort
+    # the process from its watchdog thread after the results are written (SIGABRT, exit code -6 under torchrun)
+    if torch.distributed.is_available() and torch.distributed.is_initialized():
+        torch.distributed.destroy_process_group()

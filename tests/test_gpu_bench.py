@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _run(extra, env=None, live=False):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--advance", "2",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--advance", "2",
                         "--rollouts-per-gpu", "2", "--no-extra-stages", "--strong-scenes", "3", "--strong-advance", "1"]
                        + ([] if live else ["--no-live-traffic"]) + extra,
                        capture_output=True, text=True, timeout=1200, env=dict(os.environ, **(env or {})))
@@ -78,6 +78,36 @@ def test_bench_gpus_flag_launches_the_ranks(hip):
     assert all(r["device_uuid"] and r["timed_window_s"] > 0 for r in di["ranks"]) and len({r["pid"] for r in di["ranks"]}) == 2
     assert di["distinct_device_uuids"] == 1                 # (this test: two ranks sharing the box's one GPU over gloo)
     assert d["ms_per_step"] * 3e-3 >= max(r["timed_window_s"] for r in di["ranks"]) - 1e-4
+
+
+def test_bench_plain_run_is_the_headline_and_dumps_its_outputs(hip, tmp_path):
+    """Without --full: the headline alone (the other stages' fields are null), exactly --steps timed steps; --dump-outputs writes
+    what the last timed step left the rollouts with, as float32 / float64 .npy files, and the same arguments write the same files."""
+    import numpy as np
+    runs = []
+    for tag in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--advance", "2",
+                            "--rollouts-per-gpu", "2", "--dump-outputs", str(tmp_path / tag)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        runs.append(json.loads(lines[0]))
+    d = runs[0]
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "steps/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["config"]["window_steps"] == [3, 6] and abs(d["value"] - 3 * 2 / (d["ms_per_step"] * 3e-3)) < 1e-3 * d["value"]
+    assert d["roofline"] is None and d["roofline_scatter"] is None and d["cpu_baseline"] is None and d["strong_scaling"] is None
+    assert d["full_rollout"] is None and d["value_fp32_pipe"] is None and d["nbp_maps_per_s"] is None
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) == ["cloud_count.npy", "cloud_sample.npy", "coverage.npy", "maps6_sample.npy",
+                                                           "maps6_sample_rollouts.npy", "v_cam_history.npy", "x_cam_history.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) <= 64 << 20
+    out = {n[:-len(".npy")]: np.load(tmp_path / "a" / n) for n in names}
+    assert all(a.dtype in (np.float32, np.float64) for a in out.values())
+    assert out["coverage"].shape == (2, 6) and out["cloud_count"].shape == (2,) and (out["cloud_count"] > 0).all()
+    assert out["maps6_sample"].shape == (2, 6, 256, 256) and out["maps6_sample"].sum() > 0
+    assert out["x_cam_history"].shape[0] == 2 and out["x_cam_history"].shape[2] == 3
+    for n in names:                                      # same arguments, same inputs: the same outputs, bit for bit
+        assert np.array_equal(out[n[:-len(".npy")]], np.load(tmp_path / "b" / n), equal_nan=True), n
 
 
 def test_bench_full_rollout_stage_runs_the_entry_point(hip):

@@ -137,7 +137,7 @@ def test_bench_under_one_rank_torchrun_uses_rccl(hip):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("NBP_DIST_BACKEND", None)
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr",
-                        "127.0.0.1", "--master-port", str(_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3",
+                        "127.0.0.1", "--master-port", str(_port()), os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--steps", "3",
                         "--warmup", "1", "--advance", "2", "--rollouts-per-gpu", "2", "--no-live-traffic", "--no-extra-stages",
                         "--no-cpu-baseline", "--strong-scenes", "2", "--strong-advance", "1"], capture_output=True, text=True, timeout=1200, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]

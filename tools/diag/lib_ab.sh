@@ -5,7 +5,7 @@ set -u
 OUT=gpurun_out/lib_ab; mkdir -p $OUT
 OTHER=$1
 cp nextbestpath_amd/libnbp_hip.so /tmp/lib_new.so
-B="python bench.py --steps ${STEPS:-20} --warmup 5 --no-cpu-baseline --no-live-traffic --no-extra-stages --no-strong"
+B="python bench.py --full --steps ${STEPS:-20} --warmup 5 --no-cpu-baseline --no-live-traffic --no-extra-stages --no-strong"
 val() { python -c "import json,sys; d=json.loads([l for l in open(sys.argv[1]) if l.startswith('{')][0]); print(sys.argv[2], 'steps/s', d['value'], 'ms/lockstep', d['ms_per_step'], 'fwd ms', d['stages']['nbp_forward']['ms'])" $1 "$2"; }
 for rep in $(seq 1 ${REPS:-2}); do
   for v in new before; do

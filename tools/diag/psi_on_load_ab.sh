@@ -9,6 +9,6 @@ for rep in 1 2; do
 done
 for rep in 1 2 3; do
   for v in 1 0; do
-    NBP_TUNING=1 NBP_SPLIT_PSI_ON_LOAD=$v python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-live-traffic --no-extra-stages --no-strong 2>/dev/null | python -c "import json,sys; d=json.loads([l for l in sys.stdin if l.startswith('{')][0]); print('PSI_ON_LOAD=$v steps/s', d['value'], 'ms/lockstep', d['ms_per_step'], 'fwd ms', d['stages']['nbp_forward']['ms'])"
+    NBP_TUNING=1 NBP_SPLIT_PSI_ON_LOAD=$v python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-live-traffic --no-extra-stages --no-strong 2>/dev/null | python -c "import json,sys; d=json.loads([l for l in sys.stdin if l.startswith('{')][0]); print('PSI_ON_LOAD=$v steps/s', d['value'], 'ms/lockstep', d['ms_per_step'], 'fwd ms', d['stages']['nbp_forward']['ms'])"
   done
 done
