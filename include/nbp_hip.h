@@ -527,6 +527,26 @@ int nbp_slice_obstacle_f32(const float* verts, const int* faces, int n_faces, fl
 int nbp_slice_obstacle_fig_f32(const float* verts, const int* faces, int n_faces, float y0, float cx, float cz,
                                int S, float half_u, float scale_u, float half_v, float scale_v, float half_width_px,
                                float cap_px, float* out, void* stream);
+/* nbp_slice_obstacle_fig_f32 for n <= 16 poses in one launch (training collection, round 7): item r has its own mesh (verts[r],
+ * faces[r], n_faces[r]: HOST arrays of device pointers / counts) and y0_cx_cz_host[r][3]; the figure geometry is shared.  out
+ * [n][S][S] (caller-owned, contiguous) is cleared once; bit-identical to n calls of nbp_slice_obstacle_fig_f32.  NBP_E_ARG for
+ * n < 1, n > 16 or a missing / empty item. */
+int nbp_slice_obstacle_fig_batch_f32(int n, const float* const* verts, const int* const* faces, const int* n_faces,
+                                     const float* y0_cx_cz_host, int S, float half_u, float scale_u, float half_v, float scale_v,
+                                     float half_width_px, float cap_px, float* out, void* stream);
+/* Boltzmann goal scores of trajectory collection (next_best_path/utility/nbp_utils.py:695-745) for n <= 16 rollouts that replan,
+ * one launch.  Item r: lattice positions pos3[r] [n_pos[r]][3] (device), the pose's (cx, cz) in cxcz_host[r][2], its value map
+ * out1[r] [8][V][V] (device).  Per node p: cell[r][p] = row * V + col of the node's value-map cell in the pose's frame, -1 outside
+ * the window (the in-window flag); val[r][p] = max over the 8 headings of out1 at the cell clamped into [0, V-1]^2.  Bit-identical
+ * to transform_points_to_n_pieces + get_point_position_in_the_img + out1.amax(0)[clamp, clamp].  Outputs caller-owned. */
+int nbp_goal_values_batch_f32(int n, const float* const* pos3, const int* n_pos, const float* cxcz_host, const float* const* out1,
+                              int V, float lo, float hi, int* const* cell, float* const* val, void* stream);
+/* Hindsight relabelling cells of trajectory collection (nbp_utils.py:655-693) for n <= 16 finished path segments, one launch.
+ * Item r: the segment's poses xz[r] [m[r]][2] = (x, z) fp32 (device), 1 <= m[r] <= 4096.  cells[r] [m][m] int32 (caller-owned):
+ * [i][j] = row * V + col of pose j in the frame of pose i for j > i when it lies in the value map's window, else -1.  Same fp32
+ * operations as transform_points_to_n_pieces + get_point_position_in_the_img (rint, half to even). */
+int nbp_hindsight_cells_batch_i32(int n, const float* const* xz, const int* m, int V, float lo, float hi, int* const* cells,
+                                  void* stream);
 /* Depth-map space carving of proxy points (A20): Camera.get_points_in_fov (mu:2849-2884) +
  * get_signed_distance_to_depth_maps (mu:2900-2949) + Scene.update_proxy_supervision_occ /
  * update_proxy_out_of_field (mu:3329-3363) fused per point.  For each proxy point inside the frustum

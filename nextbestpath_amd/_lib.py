@@ -201,6 +201,9 @@ SIGNATURES["nbp_unproject_append_filed_f32"] = (_i, [_vp, _vp, _vp, _vp, _vp, _v
 SIGNATURES["nbp_step_maps_prefiled_f32"] = SIGNATURES["nbp_step_maps_binned_f32"]
 SIGNATURES["nbp_slice_obstacle_f32"] = (_i, [_vp, _vp, _i, _f, _f, _f, _i, _f, _f, _f, _vp, _vp])
 SIGNATURES["nbp_slice_obstacle_fig_f32"] = (_i, [_vp, _vp, _i, _f, _f, _f, _i, _f, _f, _f, _f, _f, _f, _vp, _vp])
+SIGNATURES["nbp_slice_obstacle_fig_batch_f32"] = (_i, [_i, _vp, _vp, _vp, _vp, _i, _f, _f, _f, _f, _f, _f, _vp, _vp])
+SIGNATURES["nbp_goal_values_batch_f32"] = (_i, [_i, _vp, _vp, _vp, _vp, _i, _f, _f, _vp, _vp, _vp])
+SIGNATURES["nbp_hindsight_cells_batch_i32"] = (_i, [_i, _vp, _vp, _i, _f, _f, _vp, _vp])
 
 _lock = threading.Lock()
 _lib = None

@@ -754,3 +754,88 @@ extern "C" int nbp_step_maps_binned_batch_f32(int n, void* const* stores, const 
                          hipMemcpyDeviceToDevice, st);
     return e == hipSuccess ? 0 : (int)e;
 }
+
+// ------------------------------------------------------------------ training collection: goal scores and hindsight cells
+// Group forms for the lock-step trajectory collection (nbp_utils.CollectionGroup).  Items ride in the kernel arguments;
+// blockIdx.y = item.  Cells are the value map's: the fp32 sequence of transform_points_to_n_pieces (-(z - cz), -(x - cx))
+// followed by get_point_position_in_the_img (rint of (v - lo) * fp32(V / (hi - lo)), half to even) -- cell_of.
+namespace {
+constexpr int PLAN_BATCH = 16;
+struct GoalItem { const float* pos; const float* out1; int* cell; float* val; int P; float cx, cz; };
+struct GoalBatch { GoalItem it[PLAN_BATCH]; };
+struct CellsItem { const float* xz; int* cells; int m; };
+struct CellsBatch { CellsItem it[PLAN_BATCH]; };
+
+// node p: cell[p] = row * V + col of its value-map cell in the pose's frame (-1: outside the window); val[p] = the maximum over
+// the 8 headings of out1 at the cell clamped into the window (torch: out1.amax(0)[r.clamp(0, V-1), c.clamp(0, V-1)]; NaN wins,
+// as in amax).
+__global__ __launch_bounds__(256) void goal_values_batch_kernel(GoalBatch b, int V, float lo, float sc) {
+    const GoalItem& a = b.it[blockIdx.y];
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= a.P) return;
+    const float v0 = -(a.pos[3 * p + 2] - a.cz), v1 = -(a.pos[3 * p] - a.cx);
+    int i0, i1;
+    const bool ok = cell_of(v0, v1, lo, sc, sc, V, V, i0, i1);
+    const float hi_c = (float)(V - 1);
+    const int r = (int)fminf(fmaxf(rintf((v0 - lo) * sc), 0.f), hi_c);
+    const int c = (int)fminf(fmaxf(rintf((v1 - lo) * sc), 0.f), hi_c);
+    const size_t VV = (size_t)V * V, at = (size_t)r * V + c;
+    float m = a.out1[at];
+#pragma unroll
+    for (int h = 1; h < 8; ++h) {
+        const float v = a.out1[h * VV + at];
+        m = (v > m || v != v) ? v : m;
+    }
+    a.cell[p] = ok ? i0 * V + i1 : -1;
+    a.val[p] = m;
+}
+
+// pair (i, j) of an m-pose segment: cells[i * m + j] = the cell of pose j in the frame of pose i when j > i and it lies in the
+// window, else -1.
+__global__ __launch_bounds__(256) void hindsight_cells_batch_kernel(CellsBatch b, int V, float lo, float sc) {
+    const CellsItem& a = b.it[blockIdx.y];
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= a.m * a.m) return;
+    const int i = k / a.m, j = k - i * a.m;
+    int out = -1;
+    if (j > i) {
+        const float v0 = -(a.xz[2 * j + 1] - a.xz[2 * i + 1]), v1 = -(a.xz[2 * j] - a.xz[2 * i]);
+        int i0, i1;
+        if (cell_of(v0, v1, lo, sc, sc, V, V, i0, i1)) out = i0 * V + i1;
+    }
+    a.cells[k] = out;
+}
+}  // namespace
+
+extern "C" int nbp_goal_values_batch_f32(int n, const float* const* pos3, const int* n_pos, const float* cxcz_host,
+                                         const float* const* out1, int V, float lo, float hi, int* const* cell, float* const* val,
+                                         void* stream) {
+    NBP_ENTER();
+    NBP_RETURN_IF(n < 1 || n > PLAN_BATCH || !pos3 || !n_pos || !cxcz_host || !out1 || !cell || !val || V < 1 || !(hi > lo), NBP_E_ARG);
+    GoalBatch b{};
+    int max_p = 1;
+    for (int r = 0; r < n; ++r) {
+        NBP_RETURN_IF(!pos3[r] || !out1[r] || !cell[r] || !val[r] || n_pos[r] < 1, NBP_E_ARG);
+        b.it[r] = GoalItem{pos3[r], out1[r], cell[r], val[r], n_pos[r], cxcz_host[2 * r], cxcz_host[2 * r + 1]};
+        if (n_pos[r] > max_p) max_p = n_pos[r];
+    }
+    goal_values_batch_kernel<<<dim3((unsigned)nbp_cdiv(max_p, 256), (unsigned)n), 256, 0, (hipStream_t)stream>>>(b, V, lo,
+                                                                                                                 grid_scale(V, lo, hi));
+    return nbp_launch_status();
+}
+
+extern "C" int nbp_hindsight_cells_batch_i32(int n, const float* const* xz, const int* m, int V, float lo, float hi, int* const* cells,
+                                             void* stream) {
+    NBP_ENTER();
+    NBP_RETURN_IF(n < 1 || n > PLAN_BATCH || !xz || !m || !cells || V < 1 || !(hi > lo), NBP_E_ARG);
+    CellsBatch b{};
+    long long max_mm = 1;
+    for (int r = 0; r < n; ++r) {
+        NBP_RETURN_IF(!xz[r] || !cells[r] || m[r] < 1 || m[r] > 4096, NBP_E_ARG);
+        b.it[r] = CellsItem{xz[r], cells[r], m[r]};
+        if ((long long)m[r] * m[r] > max_mm) max_mm = (long long)m[r] * m[r];
+    }
+    hindsight_cells_batch_kernel<<<dim3((unsigned)nbp_cdiv(max_mm, 256), (unsigned)n), 256, 0, (hipStream_t)stream>>>(b, V, lo,
+                                                                                                                       grid_scale(V, lo, hi));
+    return nbp_launch_status();
+}

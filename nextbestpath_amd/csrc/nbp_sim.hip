@@ -1460,13 +1460,10 @@ namespace {
 // Pixel coordinates of a world point: u = ((cx - x) + hu) su, v = ((cz - z) + hv) sv.  cap: how far a segment's stroke extends
 // beyond its end points along its direction (0: the round "within half_width of the segment" stroke; > 0: a rectangle with
 // matplotlib's default projecting caps).
-__global__ __launch_bounds__(256) void slice_obstacle_kernel(const float* __restrict__ verts, const int* __restrict__ faces,
-                                                             int F, float y0, float cx, float cz, int S, float hu, float su_,
-                                                             float hv, float sv_, float half_width, float cap,
-                                                             float* __restrict__ out) {
-    const int f = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const int lane = threadIdx.x & 63;
-    if (f >= F) return;
+// One wave draws face f (lane = the wave's lane); shared by the single and the batched label kernels.
+__device__ __forceinline__ void slice_obstacle_face(const float* __restrict__ verts, const int* __restrict__ faces, int f, int lane,
+                                                    float y0, float cx, float cz, int S, float hu, float su_, float hv, float sv_,
+                                                    float half_width, float cap, float* __restrict__ out) {
     float px[3], py[3], pz[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
@@ -1511,6 +1508,28 @@ __global__ __launch_bounds__(256) void slice_obstacle_kernel(const float* __rest
         if (du * du + dv * dv <= h2) out[r * S + c] = 1.0f;
     }
 }
+
+__global__ __launch_bounds__(256) void slice_obstacle_kernel(const float* __restrict__ verts, const int* __restrict__ faces,
+                                                             int F, float y0, float cx, float cz, int S, float hu, float su_,
+                                                             float hv, float sv_, float half_width, float cap,
+                                                             float* __restrict__ out) {
+    const int f = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    if (f >= F) return;
+    slice_obstacle_face(verts, faces, f, threadIdx.x & 63, y0, cx, cz, S, hu, su_, hv, sv_, half_width, cap, out);
+}
+
+// Batched label: item = blockIdx.y, its own mesh and (y0, cx, cz); the figure geometry is shared.
+constexpr int SLICE_BATCH = 16;
+struct SliceItem { const float* verts; const int* faces; float* out; int n_faces; float y0, cx, cz; };
+struct SliceBatch { SliceItem it[SLICE_BATCH]; };
+
+__global__ __launch_bounds__(256) void slice_obstacle_batch_kernel(SliceBatch b, int S, float hu, float su_, float hv, float sv_,
+                                                                   float half_width, float cap) {
+    const SliceItem& a = b.it[blockIdx.y];
+    const int f = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    if (f >= a.n_faces) return;
+    slice_obstacle_face(a.verts, a.faces, f, threadIdx.x & 63, a.y0, a.cx, a.cz, S, hu, su_, hv, sv_, half_width, cap, a.out);
+}
 }  // namespace
 
 extern "C" int nbp_slice_obstacle_f32(const float* verts, const int* faces, int n_faces, float y0, float cx, float cz,
@@ -1538,5 +1557,31 @@ extern "C" int nbp_slice_obstacle_fig_f32(const float* verts, const int* faces, 
     slice_obstacle_kernel<<<(unsigned)nbp_cdiv((long long)n_faces * 64, 256), 256, 0, st>>>(verts, faces, n_faces, y0, cx, cz,
                                                                                           S, half_u, scale_u, half_v, scale_v,
                                                                                           half_width_px, cap_px, out);
+    return nbp_launch_status();
+}
+
+// nbp_slice_obstacle_fig_f32 for n <= 16 poses, each with its own mesh: out [n][S][S] (caller-owned, contiguous) is cleared once,
+// then ONE launch (blockIdx.y = item) draws every item's faces.  The stores only ever write 1.0f: bit-identical to n single calls.
+extern "C" int nbp_slice_obstacle_fig_batch_f32(int n, const float* const* verts, const int* const* faces, const int* n_faces,
+                                                const float* y0_cx_cz_host, int S, float half_u, float scale_u, float half_v,
+                                                float scale_v, float half_width_px, float cap_px, float* out, void* stream) {
+    NBP_ENTER();
+    NBP_RETURN_IF(n < 1 || n > SLICE_BATCH || !verts || !faces || !n_faces || !y0_cx_cz_host || !out || S < 1, NBP_E_ARG);
+    NBP_RETURN_IF(!(scale_u > 0.f) || !(scale_v > 0.f) || !(half_width_px > 0.f) || !(cap_px >= 0.f), NBP_E_ARG);
+    SliceBatch b{};
+    int max_f = 1;
+    for (int r = 0; r < n; ++r) {
+        NBP_RETURN_IF(!verts[r] || !faces[r] || n_faces[r] < 1, NBP_E_ARG);
+        SliceItem& a = b.it[r];
+        a.verts = verts[r]; a.faces = faces[r]; a.n_faces = n_faces[r];
+        a.y0 = y0_cx_cz_host[3 * r]; a.cx = y0_cx_cz_host[3 * r + 1]; a.cz = y0_cx_cz_host[3 * r + 2];
+        a.out = out + (size_t)r * S * S;
+        if (n_faces[r] > max_f) max_f = n_faces[r];
+    }
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipMemsetAsync(out, 0, (size_t)n * S * S * sizeof(float), st);
+    if (e != hipSuccess) return (int)e;
+    slice_obstacle_batch_kernel<<<dim3((unsigned)nbp_cdiv((long long)max_f * 64, 256), (unsigned)n), 256, 0, st>>>(
+        b, S, half_u, scale_u, half_v, scale_v, half_width_px, cap_px);
     return nbp_launch_status();
 }

@@ -236,6 +236,73 @@ def slice_obstacle_fig(verts, faces, y0, cx, cz, S=256, view_size=80.0, out=None
     return out
 
 
+def slice_obstacle_fig_batch(items, S=256, view_size=80.0, out=None):
+    """slice_obstacle_fig for several poses in one launch (nbp_slice_obstacle_fig_batch_f32): items = [(verts, faces, y0, cx, cz)],
+    each its own mesh -> out [n,S,S] fp32 (bit-identical to n single calls).  More than 16 items go in chunks of 16."""
+    import numpy as np
+    n = len(items)
+    if out is None:
+        out = torch.empty(n, S, S, dtype=torch.float32, device=items[0][0].device)
+    if n > 16:
+        for i in range(0, n, 16):
+            slice_obstacle_fig_batch(items[i:i + 16], S, view_size, out[i:i + 16])
+        return out
+    if tuple(out.shape) != (n, S, S) or not out.is_contiguous():
+        raise ValueError("slice_obstacle_fig_batch: a contiguous out [n,S,S] expected")
+    VP, I = C.c_void_p, C.c_int
+    ve, fa, nf = (VP * max(n, 1))(), (VP * max(n, 1))(), (I * max(n, 1))()
+    pose = np.zeros((max(n, 1), 3), np.float32)
+    for i, (verts, faces, y0, cx, cz) in enumerate(items):
+        ve[i], fa[i], nf[i] = verts.data_ptr(), faces.data_ptr(), faces.shape[0]
+        pose[i] = (y0, cx, cz)
+    hu, su, hv, sv, hw, cap = reference_figure_geometry(S, view_size)
+    rc = _lib.lib().nbp_slice_obstacle_fig_batch_f32(n, ve, fa, nf, pose.ctypes.data, S, hu, su, hv, sv, hw, cap,
+                                                     _lib.ptr(out) if n else None, _st())
+    _lib.check(rc, "nbp_slice_obstacle_fig_batch_f32")
+    return out
+
+
+def goal_values_batch(items, V, grid_range=(-40, 40)):
+    """Boltzmann goal scores for the rollouts of a group that replan (nbp_goal_values_batch_f32, one launch per 16): items =
+    [(pos [P,3] device, (cx, cz), out1 [8,V,V] device, cell out [P] int32, val out [P] fp32)]; cell = row * V + col, -1 outside
+    the window; val = out1.amax(0) at the clamped cell."""
+    import numpy as np
+    if len(items) > 16:
+        for i in range(0, len(items), 16):
+            goal_values_batch(items[i:i + 16], V, grid_range)
+        return
+    n = len(items)
+    VP, I = C.c_void_p, C.c_int
+    pos, npos, o1, cell, val = (VP * n)(), (I * n)(), (VP * n)(), (VP * n)(), (VP * n)()
+    cxcz = np.zeros((n, 2), np.float32)
+    for i, (p, (cx, cz), out1, c, v) in enumerate(items):
+        if not (out1.is_contiguous() and c.is_contiguous() and v.is_contiguous() and p.is_contiguous()):
+            raise ValueError("goal_values_batch: contiguous tensors expected")
+        pos[i], npos[i], o1[i], cell[i], val[i] = p.data_ptr(), p.shape[0], out1.data_ptr(), c.data_ptr(), v.data_ptr()
+        cxcz[i] = (cx, cz)
+    rc = _lib.lib().nbp_goal_values_batch_f32(n, pos, npos, cxcz.ctypes.data, o1, int(V), float(grid_range[0]), float(grid_range[1]),
+                                              cell, val, _st())
+    _lib.check(rc, "nbp_goal_values_batch_f32")
+
+
+def hindsight_cells_batch(items, V, grid_range=(-40, 40)):
+    """Hindsight relabelling cells (nbp_hindsight_cells_batch_i32, one launch per 16): items = [(xz [m,2] fp32 device, cells out
+    [m,m] int32)]; cells[i, j] = row * V + col of pose j in the frame of pose i (j > i, inside the window), else -1."""
+    if len(items) > 16:
+        for i in range(0, len(items), 16):
+            hindsight_cells_batch(items[i:i + 16], V, grid_range)
+        return
+    n = len(items)
+    VP, I = C.c_void_p, C.c_int
+    xz, m, cells = (VP * n)(), (I * n)(), (VP * n)()
+    for i, (p, c) in enumerate(items):
+        if not (p.is_contiguous() and c.is_contiguous()) or c.numel() != p.shape[0] ** 2:
+            raise ValueError("hindsight_cells_batch: contiguous xz [m,2] and cells [m,m] expected")
+        xz[i], m[i], cells[i] = p.data_ptr(), p.shape[0], c.data_ptr()
+    rc = _lib.lib().nbp_hindsight_cells_batch_i32(n, xz, m, int(V), float(grid_range[0]), float(grid_range[1]), cells, _st())
+    _lib.check(rc, "nbp_hindsight_cells_batch_i32")
+
+
 def fuse_obstacle(out2, maps6, traj, threshold=0.13):
     S = maps6.shape[-1]
     obst = torch.empty(S, S, dtype=torch.float32, device=maps6.device)

@@ -255,9 +255,14 @@ _last_key = [0]
 def store_experience(env, data):
     """ref :32-44.  The key is the millisecond clock; two records in the same millisecond would overwrite each
     other in the reference -- here the key is bumped so that none is lost."""
+    store_packed(env, pack_record(data))
+
+
+def store_packed(env, value: bytes):
+    """store_experience for a record already packed (pack_record)."""
     ms = max(int(time.time() * 1000), _last_key[0] + 1)
     _last_key[0] = ms
-    env.put(f"{ms:012d}".encode(), pack_record(data))
+    env.put(f"{ms:012d}".encode(), value)
 
 
 def store_validation_data(env, num=600 * 2):
@@ -356,19 +361,38 @@ class CollectionRollout:
         self.unreachable = set()
         self.experiences = []
         self.coverage_evolution = []
+        self.coverage_at_trajectory = None
         self.n_stored = 0
         from ..testers.nbp_planning import _settle_gc
         _settle_gc()                   # the planner's long-lived tables leave the cyclic collector's walks (see there)
 
-    # -- S1-S8 of a step: coverage, current frame, maps, GT label, trajectory image
+    # -- The step in four phases -- observe, inputs, decide, move -- each a GPU half and a host half.  run() composes them for this
+    # rollout alone; CollectionGroup runs the GPU halves of a lock-step group as group launches and calls the same host halves.
     def _observe(self, pose_i):
-        st, cam, params = self.st, self.camera, self.params
+        """S1-S4: coverage of the cloud so far (GPU half + the host half `_observed`)."""
+        st = self.st
         out = st.coverage_counts[pose_i % st.coverage_counts.shape[0]]
         self.cov_plan.count(st.cloud, out, n_dev=st.cloud_count, n=st.cloud.shape[0], seed=self.seed + 7 * pose_i)
-        cov = float(np.float32(out[0].item()) / np.float32(len(self.gt)))
-        return cov
+        return self._coverage(out[0].item())
+
+    def coverage_item(self, pose_i):
+        """The arguments of hipops.coverage_count_batch for this rollout's `_observe`."""
+        st = self.st
+        return (self.cov_plan, st.cloud, st.coverage_counts[pose_i % st.coverage_counts.shape[0]], st.cloud_count, st.cloud.shape[0],
+                self.seed + 7 * pose_i, False)
+
+    def _coverage(self, count):
+        return float(np.float32(count) / np.float32(len(self.gt)))
+
+    def _observed(self, pose_i, cov):
+        """Host half of observe: records the coverage; True when the rollout is done (coverage > 0.95)."""
+        self.coverage_evolution.append(cov)
+        if pose_i == getattr(self.params, "n_poses_in_trajectory", -1):
+            self.coverage_at_trajectory = cov
+        return cov > 0.95
 
     def _inputs(self, pose_i):
+        """S5-S8: current frame, maps, trajectory image, GT label -> (pose, model_input [1,5,S,S], gt_obs [1,1,S,S])."""
         st, cam, params = self.st, self.camera, self.params
         depth, cams = cam.frames_batch([-1])
         hipops.unproject_append(depth, None, cams, st.cloud, st.cloud_count, params.gathering_factor,
@@ -381,36 +405,97 @@ class CollectionRollout:
         gt_obs = get_binary_obstacle_array(self.mesh, pose, self.grid_range[1] * 2, self.S).reshape(1, 1, self.S, self.S)
         return pose, model_input, gt_obs
 
-    def _flush_experiences(self, pose_i):
+    def unproject_item(self, which, seed):
+        """Arguments of hipops.unproject_append_batch (depth only) for frames `which`; None when the camera's frames are not
+        ring slots (the caller then un-projects this rollout alone)."""
+        cam, st = self.camera, self.st
+        if cam._zbuf_ring is None or cam._rgb_ring is not None:
+            return None
+        slots = [cam.frames[w][2] for w in which]
+        hw4 = cam.image_height * cam.image_width * 4
+        z0 = cam._zbuf_ring.data_ptr()
+        cams = np.stack([cam.frames[w][1] for w in which]).astype(np.float32)
+        return (self, [z0 + k * hw4 for k in slots], cams, st.cloud, st.cloud_count, seed, None, None)
+
+    def label_item(self, pose):
+        x, y, z = (float(v) for v in list(pose)[:3])
+        return (self.mesh.verts, self.mesh.faces, y, x, z)
+
+    def _needs_replan(self):
+        return self.path is not None and self.path_record + 1 > len(self.path)
+
+    def _decide_begin(self, pose_i, cells=None):
+        """Host half of decide, before the goal scores: flush the finished segment (cells: its hindsight cells from the group
+        launch, None: computed here) and start a new path."""
+        if self.experiences:
+            self._flush_experiences(pose_i, cells)
+        self.path_record = 0
+
+    def _decide_end(self, cov, pose, model_input, gt_obs):
+        """Host half of decide, after any replan: keeps the experience; True when the rollout is done (no path)."""
+        if self.path is None or len(self.path) == 0:
+            return True
+        self.experiences.append([cov, model_input, gt_obs, list(pose), int(self.camera.cam_idx[4])])
+        return self.path_record >= len(self.path)
+
+    def _next_idx(self):
+        """Host half of move: the next lattice pose (60 % random heading)."""
+        next_idx = list(self.path[self.path_record])
+        if self.rng.random() <= self.P_RANDOM_HEADING:
+            next_idx[4] = self.rng.randrange(8)
+        return next_idx
+
+    def _move(self, pose_i):
+        """S10-S14: move (4 poses, one raster launch), un-project the supervision frames."""
+        cam, params, st = self.camera, self.params, self.st
+        cam.move_and_capture(self.mesh, self._next_idx())
+        depth, cams = cam.frames_batch([-5, -4, -3, -2])
+        hipops.unproject_append(depth, None, cams, st.cloud, st.cloud_count, params.gathering_factor,
+                                params.sensor_range, seed=self.seed + 11 * pose_i + 5)
+        self.path_record += 1
+
+    def hindsight_xz(self):
+        """(x, z) of the finished segment's poses, fp32 as transform_points_to_n_pieces reads them."""
+        return np.asarray([[e[3][0], e[3][2]] for e in self.experiences], np.float32).reshape(-1, 2)
+
+    def _flush_experiences(self, pose_i, cells=None):
         """Hindsight relabelling (ref :655-693): every later pose of the finished path that falls inside the
-        value map of an earlier one becomes a target pixel (its heading, its cell) with the coverage gained."""
+        value map of an earlier one becomes a target pixel (its heading, its cell) with the coverage gained.
+        cells: host [m,m] int32 from hipops.hindsight_cells_batch (row * V + col, -1 outside); None: per experience here."""
         ex_list = self.experiences
         for a in range(len(ex_list)):
             later = ex_list[a + 1:]
             if not later:
                 continue
-            pts = torch.tensor([list(e[3][:3]) for e in later], dtype=torch.float32, device=self.device)
-            p2d = hu.transform_points_to_n_pieces(pts, ex_list[a][3])
-            cells = hu.get_point_position_in_the_img(p2d.squeeze(0), (self.V, self.V), self.grid_range)
-            cells = cells.reshape(2, -1).cpu().numpy()
+            if cells is None:
+                pts = torch.tensor([list(e[3][:3]) for e in later], dtype=torch.float32, device=self.device)
+                p2d = hu.transform_points_to_n_pieces(pts, ex_list[a][3])
+                rc = hu.get_point_position_in_the_img(p2d.squeeze(0), (self.V, self.V), self.grid_range)
+                rc = rc.reshape(2, -1).cpu().numpy()
+            else:
+                row = cells[a, a + 1:]
+                rc = np.stack([np.where(row >= 0, row // self.V, -1), np.where(row >= 0, row % self.V, -1)])
             pixels, gains = [], []
             for j, e in enumerate(later):
-                r, c = int(cells[0, j]), int(cells[1, j])
+                r, c = int(rc[0, j]), int(rc[1, j])
                 if 0 <= r < self.V and 0 <= c < self.V:
                     d = e[0] - ex_list[a][0]
                     pixels.append([int(e[4]), r, c])
                     gains.append(d * 100 if d > 0 else 0)
             if pixels:
-                store_experience(self.db, {
+                self.put({
                     "current_model_input": ex_list[a][1], "current_gt_2d_layout": ex_list[a][2],
                     "target_value_map_pixel": np.asarray(pixels, np.int64),
                     "actual_coverage_gain": np.asarray(gains, np.float32), "pose_i": pose_i})
                 self.n_stored += 1
         self.experiences = []
 
+    def put(self, data):
+        store_experience(self.db, data)
+
     def _replan(self, pose, model_input):
         """Boltzmann goal sampling + search (ref :695-745).  Returns the path or None."""
-        pl, cam = self.planner, self.camera
+        pl = self.planner
         with torch.no_grad():
             out1, _ = self.nbp(model_input)
         o1 = out1[0]
@@ -419,7 +504,11 @@ class CollectionRollout:
         max_gain = o1.amax(0)
         ok = (cells[0] >= 0) & (cells[0] < self.V) & (cells[1] >= 0) & (cells[1] < self.V)
         vals = max_gain[cells[0].clamp(0, self.V - 1), cells[1].clamp(0, self.V - 1)]
-        ok_h, vals_h, out1_h = ok.cpu().numpy(), vals.cpu().numpy(), o1.cpu().numpy()
+        return self._search(pose, ok.cpu().numpy(), vals.cpu().numpy(), o1.cpu().numpy())
+
+    def _search(self, pose, ok_h, vals_h, out1_h):
+        """Host half of the replan: Boltzmann draw over the in-window candidates, then the search (own rng / generator)."""
+        pl, cam = self.planner, self.camera
         start_id = pl.node_index[tuple(cam.cam_idx[:3])]
         cand = [n for n in range(len(pl.idx3)) if ok_h[n] and n != start_id]
         if not cand:
@@ -446,46 +535,269 @@ class CollectionRollout:
         return None
 
     def run(self, n_poses=100, coverage_after_trajectory=None):
-        cam, params, st = self.camera, self.params, self.st
         for pose_i in range(n_poses):
-            cov = self._observe(pose_i)
-            self.coverage_evolution.append(cov)
-            if coverage_after_trajectory is not None and pose_i == getattr(params, "n_poses_in_trajectory", -1):
-                coverage_after_trajectory.append(cov)
-            if cov > 0.95:
+            done = self._observed(pose_i, self._observe(pose_i))
+            if coverage_after_trajectory is not None and self.coverage_at_trajectory is not None:
+                coverage_after_trajectory.append(self.coverage_at_trajectory)
+                self.coverage_at_trajectory = None
+            if done:
                 break
             pose, model_input, gt_obs = self._inputs(pose_i)
-            if self.path is not None and self.path_record + 1 > len(self.path):
-                if self.experiences:
-                    self._flush_experiences(pose_i)
-                self.path_record = 0
+            if self._needs_replan():
+                self._decide_begin(pose_i)
                 self.path = self._replan(pose, model_input)
-            if self.path is None or len(self.path) == 0:
+            if self._decide_end(self.coverage_evolution[-1], pose, model_input, gt_obs):
                 break
-            self.experiences.append([cov, model_input, gt_obs, list(pose), int(cam.cam_idx[4])])
-            if self.path_record >= len(self.path):
-                break
-            next_idx = list(self.path[self.path_record])
-            if self.rng.random() <= self.P_RANDOM_HEADING:
-                next_idx[4] = self.rng.randrange(8)
-            cam.move_and_capture(self.mesh, next_idx)
-            depth, cams = cam.frames_batch([-5, -4, -3, -2])
-            hipops.unproject_append(depth, None, cams, st.cloud, st.cloud_count, params.gathering_factor,
-                                    params.sensor_range, seed=self.seed + 11 * pose_i + 5)
-            self.path_record += 1
+            self._move(pose_i)
         return self.coverage_evolution
+
+
+class CollectionGroup:
+    """Up to K CollectionRollouts of one rank in lock-step (trajectory_collection(..., rollouts_per_gpu=K)).  Every phase of the
+    step runs once per group step for the live rollouts: coverage (one group launch, one read-back of K counts), the current frame's
+    un-projection, the maps + trajectory channel, the GT label, ONE forward of the replanning rollouts' inputs, their goal scores
+    (one launch, one read-back with the out1 rows), the hindsight cells of the flushing rollouts (one launch, one read-back), the
+    move's render and the supervision frames' un-projection -- each a group launch.  The host halves are CollectionRollout's own
+    (each rollout keeps its random.Random and torch.Generator, so the draws are the serial run's).  A rollout that finishes leaves
+    and its slot takes the rank's next scene.  Records are packed per scene and reach the store in serial order: scene order, then
+    flush order within a scene (the earliest unfinished scene streams its records; later scenes hold theirs until it is done)."""
+
+    def __init__(self, make_rollout, scenes, K, n_poses, device, timing=None):
+        self.make, self.queue, self.K, self.n_poses, self.device = make_rollout, list(scenes), int(K), n_poses, device
+        self.order = list(scenes)                  # commit order
+        self.held = {si: [] for si in self.order}  # packed records not yet in the store
+        self.done = {}                             # si -> finished rollout's (coverage_at_trajectory, n_stored)
+        self.live = []                             # [(si, rollout)]
+        self.t = timing if timing is not None else {}
+        self.n_poses_done = 0
+        self.stored = 0
+        self._buf = None
+
+    def _tick(self, key, t0):
+        t1 = time.perf_counter()
+        self.t[key] = self.t.get(key, 0.0) + (t1 - t0)
+        return t1
+
+    def _refill(self):
+        t0 = time.perf_counter()
+        while len(self.live) < self.K and self.queue:
+            si = self.queue.pop(0)
+            ro = self.make(si)
+            ro.pose_i, ro.frames_appended = 0, 0
+            held = self.held[si]
+            ro.put = lambda data, held=held: held.append(data)       # packed in one place per group step (_pack)
+            self.live.append((si, ro))
+        self._tick("setup_s", t0)
+
+    def _leave(self, si, ro):
+        self.done[si] = (ro.coverage_at_trajectory, ro.n_stored)
+
+    def _commit(self, db, coverage_after_trajectory):
+        """Records into the store in serial order (the first scene of `order` is the only one that may write)."""
+        t0 = time.perf_counter()
+        while self.order:
+            si = self.order[0]
+            for value in self.held[si]:
+                store_packed(db, value)
+            self.held[si].clear()
+            if si not in self.done:
+                break
+            cov_t, n = self.done.pop(si)
+            if coverage_after_trajectory is not None and cov_t is not None:
+                coverage_after_trajectory.append(cov_t)
+            self.stored += n
+            del self.held[si]
+            self.order.pop(0)
+        self._tick("store_put_s", t0)
+
+    def _pack(self):
+        t0 = time.perf_counter()
+        for held in self.held.values():             # in place: the rollouts' put() appends to these lists
+            held[:] = [v if isinstance(v, bytes) else pack_record(v) for v in held]
+        self._tick("pack_s", t0)
+
+    def _buffers(self, n, S):
+        if self._buf is None or self._buf[0].shape[0] < n:
+            K = max(n, self.K)
+            self._buf = (torch.zeros(K, 6, S, S, dtype=torch.float32, device=self.device),
+                         torch.zeros(K, 5, S, S, dtype=torch.float32, device=self.device))
+        return self._buf[0][:n], self._buf[1][:n]
+
+    def run(self, db, coverage_after_trajectory=None):
+        self._refill()
+        while self.live:
+            self.step()
+            self._pack()
+            self._commit(db, coverage_after_trajectory)
+            if len(self.live) < self.K and self.queue:
+                torch.cuda.empty_cache()
+                self._refill()
+        self._commit(db, coverage_after_trajectory)
+        return self.stored
+
+    def _drop(self, keep):
+        keep_ids = {id(ro) for ro in keep}
+        for si, ro in self.live:
+            if id(ro) not in keep_ids:
+                self._leave(si, ro)
+        self.live = [(si, ro) for si, ro in self.live if id(ro) in keep_ids]
+
+    def step(self):
+        t0 = time.perf_counter()
+        grp = [ro for _, ro in self.live]
+        r0 = grp[0]
+        S, V, gr, p0 = r0.S, r0.V, r0.grid_range, r0.params
+        H, W = p0.image_height, p0.image_width
+        # -- observe: coverage in one group launch, one read-back of the counts
+        hipops.coverage_count_batch([ro.coverage_item(ro.pose_i) for ro in grp])
+        counts = torch.stack([ro.st.coverage_counts[ro.pose_i % ro.st.coverage_counts.shape[0], 0] for ro in grp]).cpu().tolist()
+        t0 = self._tick("gpu_step_s", t0)
+        covs = {}
+        alive = []
+        for ro, c in zip(grp, counts):
+            cov = ro._coverage(c)
+            if not ro._observed(ro.pose_i, cov):
+                covs[id(ro)] = cov
+                alive.append(ro)
+        self.n_poses_done += len(grp)
+        self._drop(alive)
+        grp = alive
+        if not grp:
+            return
+        t0 = self._tick("host_search_s", t0)
+        # -- inputs: the current frame, the maps + trajectory channel, the label
+        items = [ro.unproject_item([-1], ro.seed + 11 * ro.pose_i) for ro in grp]
+        if all(it is not None for it in items):
+            hipops.unproject_append_batch(items, H, W, 1, p0.gathering_factor, p0.sensor_range)
+        else:
+            for ro in grp:
+                depth, cams = ro.camera.frames_batch([-1])
+                hipops.unproject_append(depth, None, cams, ro.st.cloud, ro.st.cloud_count, p0.gathering_factor, p0.sensor_range,
+                                        seed=ro.seed + 11 * ro.pose_i)
+        per_frame = int(H * W * p0.gathering_factor) + 1
+        poses, maps = [], []
+        for ro in grp:
+            ro.frames_appended += 1
+            pose, _ = ro.camera.get_pose_from_idx(ro.camera.cam_idx)
+            poses.append(pose)
+            traj_dev, n_old, fresh = ro.camera.trajectory_pending()
+            maps.append((ro.st.cloud, min(ro.st.cloud.shape[0], ro.frames_appended * per_frame), ro.st.cloud_count, pose, ro.y_bins,
+                         traj_dev, n_old, fresh))
+        n = len(grp)
+        maps6, net_in = self._buffers(n, S)
+        hu.step_maps_batch(maps, S, gr, maps6, net_in)
+        label = hipops.slice_obstacle_fig_batch([ro.label_item(pose) for ro, pose in zip(grp, poses)], S, float(gr[1] * 2))
+        rec = torch.empty(n, 6, S, S, dtype=torch.float32, device=self.device)
+        rec[:, :5].copy_(net_in)
+        rec[:, 5].copy_(label)
+        # the records' tensors: one copy per group step (complete before any flush reads them: a flush happens in a later group step,
+        # after that step's blocking read-back of the coverage counts on this stream)
+        rec_h = torch.empty(rec.shape, dtype=torch.float32, pin_memory=True)
+        rec_h.copy_(rec, non_blocking=True)
+        # -- decide: flush the finished segments (hindsight cells in one launch), ONE forward of the replanning rollouts' inputs
+        replan = [i for i, ro in enumerate(grp) if ro._needs_replan()]
+        flush = [i for i in replan if len(grp[i].experiences) > 1]
+        cells_h = {}
+        if flush:
+            xz = [grp[i].hindsight_xz() for i in flush]
+            xz_dev = torch.from_numpy(np.concatenate(xz)).to(self.device)
+            sizes = [len(a) ** 2 for a in xz]
+            cells_dev = torch.empty(sum(sizes), dtype=torch.int32, device=self.device)
+            offs = np.concatenate([[0], np.cumsum([len(a) for a in xz])]).tolist()
+            coffs = np.concatenate([[0], np.cumsum(sizes)]).tolist()
+            hipops.hindsight_cells_batch([(xz_dev[offs[k]:offs[k + 1]], cells_dev[coffs[k]:coffs[k + 1]]) for k in range(len(flush))],
+                                         V, gr)
+            allc = cells_dev.cpu().numpy()
+            for k, i in enumerate(flush):
+                m = len(xz[k])
+                cells_h[i] = allc[coffs[k]:coffs[k + 1]].reshape(m, m)
+        goal = {}
+        if replan:
+            x = net_in if len(replan) == n else net_in[torch.tensor(replan, device=self.device)]
+            with torch.no_grad():
+                out1, _ = grp[0].nbp(x)
+            B = len(replan)
+            P = max(grp[i].planner.pos_dev.shape[0] for i in replan)
+            VV8 = 8 * V * V
+            G = torch.empty(B, 2 * P + VV8, dtype=torch.float32, device=self.device)
+            gitems = []
+            for b, i in enumerate(replan):
+                ro = grp[i]
+                pos = ro.__dict__.get("_pos32")
+                if pos is None:
+                    pos = ro._pos32 = ro.planner.pos_dev.float().contiguous()
+                Pi = pos.shape[0]
+                gitems.append((pos, (float(poses[i][0]), float(poses[i][2])), out1[b].reshape(8, V, V).contiguous(),
+                               G[b, P:P + Pi].view(torch.int32), G[b, :Pi]))
+            hipops.goal_values_batch(gitems, V, gr)
+            G[:, 2 * P:].copy_(out1.reshape(B, VV8))
+            Gh = G.cpu()
+            for b, i in enumerate(replan):
+                Pi = gitems[b][0].shape[0]
+                cell = Gh[b, P:P + Pi].view(torch.int32).numpy()
+                goal[i] = (cell >= 0, Gh[b, :Pi].numpy(), Gh[b, 2 * P:].reshape(8, V, V).numpy())
+        t0 = self._tick("gpu_step_s", t0)
+        alive = []
+        for i, ro in enumerate(grp):
+            model_input, gt_obs = rec_h[i:i + 1, :5], rec_h[i:i + 1, 5:6]
+            if i in goal:
+                ro._decide_begin(ro.pose_i, cells_h.get(i))
+                ro.path = ro._search(poses[i], *goal[i])
+            if not ro._decide_end(covs[id(ro)], poses[i], model_input, gt_obs):
+                alive.append(ro)
+        t0 = self._tick("host_search_s", t0)
+        # -- move: the render in one group launch, the supervision frames' un-projection in one
+        self._drop(alive)
+        grp = alive
+        if not grp:
+            return
+        can_raster = all(ro.camera.deferred_colours(ro.mesh) for ro in grp)
+        pend = []
+        for ro in grp:
+            cams = ro.camera.move_poses(ro._next_idx())
+            if can_raster:
+                out, zf, slot = ro.camera.capture_begin(ro.mesh, cams)
+                pend.append((ro, cams, out, zf, slot))
+            else:
+                ro.camera.capture_images(ro.mesh, cams)
+        t0 = self._tick("host_search_s", t0)
+        if can_raster:
+            hipops.raster_zface_batch([(ro, ro.mesh.verts, ro.mesh.faces, cams, out, zf) for ro, cams, out, zf, _ in pend], H, W,
+                                      len(pend[0][1]))
+            for ro, cams, out, _, slot in pend:
+                ro.camera.capture_commit(out, cams, slot)
+        which = [-5, -4, -3, -2]
+        items = [ro.unproject_item(which, ro.seed + 11 * ro.pose_i + 5) for ro in grp]
+        if all(it is not None for it in items):
+            hipops.unproject_append_batch(items, H, W, 4, p0.gathering_factor, p0.sensor_range)
+        else:
+            for ro in grp:
+                depth, cams = ro.camera.frames_batch(which)
+                hipops.unproject_append(depth, None, cams, ro.st.cloud, ro.st.cloud_count, p0.gathering_factor, p0.sensor_range,
+                                        seed=ro.seed + 11 * ro.pose_i + 5)
+        alive = []
+        for ro in grp:
+            ro.frames_appended += 4
+            ro.path_record += 1
+            ro.pose_i += 1
+            if ro.pose_i < self.n_poses:
+                alive.append(ro)
+        self._drop(alive)
+        self._tick("gpu_step_s", t0)
 
 
 def trajectory_collection(params, current_epoch, dataset, db_env, pc2img_size, value_map_size, prediction_range, nbp,
                           coverage_after_trajectory, memory, device, folder_img_path=None, rank=0, world=1, n_poses=100,
-                          n_gt_points=None):
+                          n_gt_points=None, rollouts_per_gpu=1, timing=None):
     """ref :470-852.  `dataset` is a simulator.scene.SceneDataset; with world > 1 each rank collects the scenes
-    rank, rank + world, ... into its own store (collection is embarrassingly parallel)."""
+    rank, rank + world, ... into its own store (collection is embarrassingly parallel).
+    rollouts_per_gpu = K > 1: up to K of the rank's scenes in lock-step (CollectionGroup); the store receives the same records in
+    the same order as with K = 1.  `timing` (a dict, K > 1) receives the seconds of the group's stages."""
     from ..simulator import scene as sim_scene
     from ..testers.nbp_planning import setup_test_camera
     nbp.eval()
-    stored = 0
-    for si in range(rank, len(dataset), world):
+
+    def make(si):
         sd = dataset[si]
         settings = sim_scene.Settings(sd["settings"], params.scene_scale_factor)
         mesh = sim_scene.load_scene(os.path.join(dataset.data_path, sd["scene_name"], sd["obj_name"]),
@@ -494,8 +806,15 @@ def trajectory_collection(params, current_epoch, dataset, db_env, pc2img_size, v
         seed = 7919 * current_epoch + si
         _, gt_dev = sim_scene.setup_gt_scene(params, settings, mesh, device, 0.05, seed=seed, n_points=n_gt_points)
         camera = setup_test_camera(params, mesh, settings.camera.start_positions[0], settings, device, seed=seed)
-        ro = CollectionRollout(params, nbp, camera, gt_dev, mesh, y_bins, device, db_env, seed,
-                               pc2img_size[0], value_map_size[0], prediction_range)
+        return CollectionRollout(params, nbp, camera, gt_dev, mesh, y_bins, device, db_env, seed,
+                                 pc2img_size[0], value_map_size[0], prediction_range)
+
+    scenes = list(range(rank, len(dataset), world))
+    if int(rollouts_per_gpu) > 1:
+        return CollectionGroup(make, scenes, rollouts_per_gpu, n_poses, device, timing).run(db_env, coverage_after_trajectory)
+    stored = 0
+    for si in scenes:
+        ro = make(si)
         ro.run(n_poses, coverage_after_trajectory)
         stored += ro.n_stored
         del ro
