@@ -240,6 +240,48 @@ int nbp_upconv3x3_split_bn_f32(const float* src, int C, int B, int H, int W, con
                                const float* scale, const float* shift, int relu, float* out, const void* amax_in_or_null,
                                void* amax_out_or_null, int split_k, void* ws, size_t ws_bytes, double* bn_part, int* bn_rows,
                                void* stream);
+/* ---- One-piece ("_h1") forms of the training step's split kernels (NBP.train_precision = "fp16"; nbp_split.hip, template
+ * parameter ONE).  Each takes the arguments of the entry point without the suffix.  Operands are scaled by the same per-tensor power
+ * of two as the split path (max |x| in [2^14, 2^15)) and rounded ONCE to fp16, hi = fp16(s x); every product is one
+ * v_mfma_f32_32x32x16_f16 (exact in the fp32 accumulator) instead of three; the epilogues, scales, amax slots and split-K plans are
+ * the split path's.  Weight planes: [chunk of 16][tap][k half][rows][8] fp16 of the hi pieces alone (half the bytes of the
+ * two-piece planes); the convolutions take only planes from the `_h1` packs. */
+int nbp_pack_conv_weight_split_h1(const float* w_oihw, int N, int C, int ksize, const float* scale_or_null, int c_off,
+                                  int c_total, void* dst_planes, void* wamax_out, void* stream);
+int nbp_pack_conv_weight_split_prezeroed_h1(const float* w_oihw, int N, int C, int ksize, int c_total, void* dst_planes,
+                                            void* wamax_zeroed, void* stream);
+int nbp_pack_conv_weight_split_dgrad_h1(const float* w_oihw, int N, int C, int c_total, void* dst_planes, void* wamax_out, void* stream);
+int nbp_pack_conv_weight_split_dgrad_known_h1(const float* w_oihw, int N, int C, int c_total, void* dst_planes, const void* wamax_known,
+                                              void* stream);
+int nbp_pack_upconv_weight_split_h1(const float* w_oihw, int N, int C, void* dst_planes, void* wamax_out, void* stream);
+int nbp_pack_upconv_weight_split_dgrad_h1(const float* w_oihw, int N, int C, void* dst_planes, void* wamax_out, void* stream);
+int nbp_pack_conv1x1_weight_split_dgrad_h1(const float* w_nc, int N, int C, void* dst_planes, void* wamax_out, void* stream);
+int nbp_prepack_weights_split_h1(const void* descs_dev, int n, void* wamax_words, void* stream);
+int nbp_conv3x3_split_f32_h1(const float* src0, int C0, const float* src1, int C1, int ups, int B, int H, int W,
+                             const void* w_planes, const void* wamax, int N, const float* scale, const float* shift, int relu,
+                             float* out, const void* amax_in_or_null, void* amax_out_or_null, int split_k, void* ws,
+                             size_t ws_bytes, void* stream);
+int nbp_conv3x3_split_bn_f32_h1(const float* src0, int C0, const float* src1, int C1, int ups, int B, int H, int W,
+                                const void* w_planes, const void* wamax, int N, const float* scale, const float* shift, int relu,
+                                float* out, const void* amax_in_or_null, void* amax_out_or_null, int split_k, void* ws,
+                                size_t ws_bytes, double* bn_part, int* bn_rows, void* stream);
+int nbp_upconv3x3_split_f32_h1(const float* src, int C, int B, int H, int W, const void* planes_up, const void* wamax_up, int N,
+                               const float* scale, const float* shift, int relu, float* out, const void* amax_in_or_null,
+                               void* amax_out_or_null, int split_k, void* ws, size_t ws_bytes, void* stream);
+int nbp_upconv3x3_split_bn_f32_h1(const float* src, int C, int B, int H, int W, const void* planes_up, const void* wamax_up, int N,
+                                  const float* scale, const float* shift, int relu, float* out, const void* amax_in_or_null,
+                                  void* amax_out_or_null, int split_k, void* ws, size_t ws_bytes, double* bn_part, int* bn_rows,
+                                  void* stream);
+int nbp_upconv3x3_split_dgrad_f32_h1(const float* dy, int N, int B, int H, int W, const void* planes, const void* wamax, int C,
+                                     const float* scale, const float* shift, float* dx, const void* amax_in, void* amax_out_or_null,
+                                     void* ws, size_t ws_bytes, void* stream);
+int nbp_conv1x1_split_f32_h1(const float* src, int C, long long M, const void* w_planes, const void* wamax, int N,
+                             const float* scale, const float* shift, int relu, float* out, const void* amax_in, void* stream);
+int nbp_upconv_wgrad_split_f32_h1(const float* x, int C, int B, int Hs, int Ws, const float* dy, int N, float* dw,
+                                  const void* amax_x, const void* amax_y, void* ws, size_t ws_bytes, void* stream);
+int nbp_conv_wgrad_split_f32_h1(const float* src0, int C0, const float* src1, int C1, int ups, int B, int H, int W, int ksize,
+                                const float* dy, int N, int c_real, int n_real, float* dw, const void* amax0_or_null,
+                                const void* amax1_or_null, const void* amaxy_or_null, void* ws, size_t ws_bytes, void* stream);
 /* BatchNorm2d training forward from those partial sums (zero_row = C zeros): finalize + normalise, x is read once */
 int nbp_bn_train_forward_part4_f32(const float* x, long long M, int C, const float* gamma, const float* beta, float eps,
                                    float momentum, float* running_mean, float* running_var, int relu, float* mean, float* invstd,

@@ -156,6 +156,13 @@ SIGNATURES["nbp_conv3x3_split_bn_f32"] = (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i,
 SIGNATURES["nbp_upconv3x3_split_bn_f32"] = (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _sz, _vp,
                                                  C.POINTER(_i), _vp])
 SIGNATURES["nbp_bn_train_forward_part4_f32"] = (_i, [_vp, _ll, _i, _vp, _vp, _f, _f, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp])
+# the one-piece ("_h1") forms of the training step's split entry points: the signatures of their two-piece siblings
+for _n in ("nbp_pack_conv_weight_split", "nbp_pack_conv_weight_split_prezeroed", "nbp_pack_conv_weight_split_dgrad",
+           "nbp_pack_conv_weight_split_dgrad_known", "nbp_pack_upconv_weight_split", "nbp_pack_upconv_weight_split_dgrad",
+           "nbp_pack_conv1x1_weight_split_dgrad", "nbp_prepack_weights_split", "nbp_conv3x3_split_f32", "nbp_conv3x3_split_bn_f32",
+           "nbp_upconv3x3_split_f32", "nbp_upconv3x3_split_bn_f32", "nbp_upconv3x3_split_dgrad_f32", "nbp_conv1x1_split_f32",
+           "nbp_upconv_wgrad_split_f32", "nbp_conv_wgrad_split_f32"):
+    SIGNATURES[_n + "_h1"] = SIGNATURES[_n]
 SIGNATURES["nbp_conv_igemm_bf16"] = SIGNATURES["nbp_conv_igemm_f32"]
 SIGNATURES["nbp_conv_igemm_bf16_workspace_bytes"] = SIGNATURES["nbp_conv_igemm_workspace_bytes"]
 SIGNATURES["nbp_pack_conv_weight_bf16"] = SIGNATURES["nbp_pack_conv_weight"]

@@ -58,6 +58,10 @@ __device__ __forceinline__ void split_pair(float x0, float x1, unsigned& h, unsi
     h = __builtin_bit_cast(unsigned, f16x2{h0, h1});
     l = __builtin_bit_cast(unsigned, f16x2{l0, l1});
 }
+// the one-piece form (ONE, training's "fp16" precision): the hi pieces alone, hi = fp16(s x)
+__device__ __forceinline__ unsigned hi_pair(float x0, float x1) {
+    return __builtin_bit_cast(unsigned, f16x2{(_Float16)x0, (_Float16)x1});
+}
 
 // max |x| of a tensor lives in AMAX_WORDS words (float bits; the tensor's max is the max over them): same-address device
 // atomics run at ~0.3 G/s on this part (16 k waves finishing together = 55 us), so writers spread over the words by
@@ -150,7 +154,10 @@ __device__ unsigned nbp_dbg_n;
 // which sets its halo gather (the parity plane, read straight from dout: + py W + px pixels) and the origin of its 2 x 2 taps
 // (1 - py, 1 - px); the filter-row flip r' = 1 - r is baked into the packed planes (pack_upconv_dgrad_h2_kernel).  One workgroup per
 // low-resolution tile, plain output (no parity scatter, no 2 x 2 sum pass).  a.H / a.W = the low-resolution output, a.Hs / a.Ws = dout.
-template <int TW, int TM, int TN, bool PH, bool BS = false, bool P2 = false, bool DG = false>
+// ONE (training's "fp16" precision): one piece per operand, hi = fp16(s x) -- the halo and the weight planes hold hi alone (one plane,
+// [k half][..] without the [hi|lo] level) and every tap-product is ONE MFMA; scales, staging order, split-K and epilogue as above.
+// (ONE leads the parameter list: a kernel symbol ends in the same <..., PH, BS, P2, DG> as before the one-piece form existed)
+template <bool ONE, int TW, int TM, int TN, bool PH, bool BS = false, bool P2 = false, bool DG = false>
 __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv3x3_halo_h2_kernel(SplitArgs a) {
     static_assert(!P2 || PH, "two-parity form: up_conv layers");
     static_assert(!DG || (PH && !BS && !P2), "data gradient of an up_conv layer: the one-parity tap structure");
@@ -166,8 +173,9 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     constexpr int RPB = 32 / TW, TH = 4 * TM * RPB;            // image rows per 32-pixel row block; tile height (16)
     constexpr int HW_ = TW + 2, HPIX = (TH + 2) * HW_;         // 18 x 34 = 612 / 18 x 18 = 324 halo pixels
     constexpr int RS = (HPIX + 7) / 8 * 8 * 16 + 64;           // bytes between (plane, k half) regions (+64: ds_write banks)
-    constexpr int HALO_BYTES = 4 * RS;
-    constexpr int WI = TPR * 4 * NB;                           // weight DMA instructions (64 rows x 16 B) per stage (and parity)
+    constexpr int NPL = ONE ? 1 : 2;                           // fp16 planes per operand (hi | lo, or hi alone)
+    constexpr int HALO_BYTES = 2 * NPL * RS;
+    constexpr int WI = TPR * 2 * NPL * NB;                     // weight DMA instructions (64 rows x 16 B) per stage (and parity)
     constexpr int NPAR = P2 ? 2 : 1;                           // column parities a workgroup computes
     constexpr int WB1 = WI * 1024, WB = NPAR * WB1;
     constexpr int NF = (HPIX * 4 + 255) / 256;                 // float4 pieces of the halo tile per thread
@@ -287,6 +295,10 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
             if ((tid >> 2) + 64 * k >= HPIX) continue;
             f32x4 v = __builtin_bit_cast(f32x4, hreg[k]);
             if constexpr (!PH) { if (gated) v = v * psil[(tid >> 2) + 64 * k]; }
+            if constexpr (ONE) {
+                *reinterpret_cast<u32x2*>(halo + hdst0 + k * 1024) = u32x2{hi_pair(v[0] * sa, v[1] * sa), hi_pair(v[2] * sa, v[3] * sa)};
+                continue;
+            }
             unsigned h0, l0, h1, l1;
             split_pair(v[0] * sa, v[1] * sa, h0, l0);
             split_pair(v[2] * sa, v[3] * sa, h1, l1);
@@ -302,13 +314,14 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
         // PH: the four parities' planes follow each other, each [chunk][4 taps][plane][k half][N][8]
 #pragma unroll
         for (int pq = 0; pq < NPAR; ++pq) {
-            const long long pbase = PHO ? (long long)(py * 2 + (P2 ? pq : px)) * a.chunks_total * TAPS * 4 * a.N : 0;
+            const long long pbase = PHO ? (long long)(py * 2 + (P2 ? pq : px)) * a.chunks_total * TAPS * (2 * NPL) * a.N : 0;
 #pragma unroll
-            for (int k = 0; k < WI / 4; ++k) {
+            for (int k = 0; k < (WI + 3) / 4; ++k) {
                 const int q = wave + 4 * k;
-                const int tt = q / (4 * NB), r = q - tt * (4 * NB);
+                if (WI % 4 != 0 && q >= WI) continue;          // (ONE, three taps x 2 x 64 rows: 6 instructions over 4 waves)
+                const int tt = q / (2 * NPL * NB), r = q - tt * (2 * NPL * NB);
                 const int r4 = r / NB, nb = r - r4 * NB;
-                const unsigned woff = (unsigned)((pbase + (((long long)c * TAPS + row * TPR + tt) * 4 + r4) * a.N + n0 + nb * 64 + lane) * 16);
+                const unsigned woff = (unsigned)((pbase + (((long long)c * TAPS + row * TPR + tt) * (2 * NPL) + r4) * a.N + n0 + nb * 64 + lane) * 16);
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rsw, (lds_ptr_t)(dst + pq * WB1 + q * 1024), 16, woff, 0, 0, 0);
             }
         }
@@ -355,6 +368,27 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
                 constexpr int PW[3] = {0, 1, 0};
 #pragma unroll
                 for (int col = 0; col < 3; ++col) {
+                    if constexpr (ONE) {
+                        u32x4 xh[TM];
+#pragma unroll
+                        for (int i = 0; i < TM; ++i) xh[i] = *reinterpret_cast<const u32x4*>(arow + ((row + py + i * RPB) * HW_ + col) * 16);
+#pragma unroll
+                        for (int pq = 0; pq < 2; ++pq) {
+                            const int tt = col - pq;
+                            if (tt < 0 || tt > 1) continue;
+                            u32x4 wh[TN];
+#pragma unroll
+                            for (int j = 0; j < TN; ++j)
+                                wh[j] = *reinterpret_cast<const u32x4*>(Bt + pq * WB1 + ((tt * 2) * NB + (j >> 1)) * 1024 + (j & 1) * 512);
+#pragma unroll
+                            for (int j = 0; j < TN; ++j)
+#pragma unroll
+                                for (int i = 0; i < TM; ++i)
+                                    accs[pq][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, xh[i]),
+                                                                                            __builtin_bit_cast(f16x8, wh[j]), accs[pq][i][j], 0, 0, 0);
+                        }
+                        continue;
+                    }
                     u32x4 xp[TM][2];
 #pragma unroll
                     for (int i = 0; i < TM; ++i)
@@ -386,6 +420,20 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
             const int pyc = DG ? 1 - ((c / c16_0) >> 1) : py, pxc = DG ? 1 - ((c / c16_0) & 1) : px;
 #pragma unroll
             for (int tt = 0; tt < TPR; ++tt) {
+                if constexpr (ONE) {
+                    u32x4 xh[TM], wh[TN];
+#pragma unroll
+                    for (int i = 0; i < TM; ++i) xh[i] = *reinterpret_cast<const u32x4*>(arow + ((row + pyc + i * RPB) * HW_ + tt + pxc) * 16);
+#pragma unroll
+                    for (int j = 0; j < TN; ++j) wh[j] = *reinterpret_cast<const u32x4*>(Bt + ((tt * 2) * NB + (j >> 1)) * 1024 + (j & 1) * 512);
+#pragma unroll
+                    for (int j = 0; j < TN; ++j)
+#pragma unroll
+                        for (int i = 0; i < TM; ++i)
+                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, xh[i]), __builtin_bit_cast(f16x8, wh[j]),
+                                                                               acc[i][j], 0, 0, 0);
+                    continue;
+                }
                 u32x4 xp[TM][2], wp[TN][2];
 #pragma unroll
                 for (int i = 0; i < TM; ++i)
@@ -597,11 +645,12 @@ struct GateArgs {
     int psi_only;               // PSI form: psi [M] goes to the head of gated[] and the products x * psi are only measured (gated_amax), not written
 };
 
-template <int TN, bool PSI>
+// ONE: the one-piece form (planes [chunk][k half][N][8], one MFMA per product)
+template <bool ONE, int TN, bool PSI>
 __global__ __launch_bounds__(256, 2) void gate1x1_h2_kernel(GateArgs a) {
     const SplitOps& o = a.g[blockIdx.z];
     constexpr int BN = TN * 32;
-    constexpr int WST = 8 * BN * 16;                           // bytes of one weight stage: 2 k steps x 2 planes x 2 k halves x BN rows
+    constexpr int WST = (ONE ? 4 : 8) * BN * 16;               // bytes of one weight stage: 2 k steps x 2 planes x 2 k halves x BN rows
     constexpr int WI = WST / 1024;                             // DMA instructions per stage (64 rows x 16 B each)
     extern __shared__ __attribute__((aligned(16))) char wbuf[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -643,8 +692,8 @@ __global__ __launch_bounds__(256, 2) void gate1x1_h2_kernel(GateArgs a) {
                 constexpr int PER = BN / 64 > 0 ? BN / 64 : 1;  // 64-row blocks per (ks, plane, kh)
                 const int r8 = BN >= 64 ? q / PER : q * 2 + (lane >> 5), nb = BN >= 64 ? q - (q / PER) * PER : 0;
                 const int row = BN >= 64 ? nb * 64 + lane : (lane & 31);
-                const int ks = r8 >> 2, r4 = r8 & 3;
-                const unsigned woff = (unsigned)((((long long)(2 * st + ks) * 4 + r4) * a.N + n0 + row) * 16);
+                const int ks = ONE ? r8 >> 1 : r8 >> 2, r4 = ONE ? r8 & 1 : r8 & 3;
+                const unsigned woff = (unsigned)((((long long)(2 * st + ks) * (ONE ? 2 : 4) + r4) * a.N + n0 + row) * 16);
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rsw, (lds_ptr_t)(dst + q * 1024), 16, woff, 0, 0, 0);
             }
         }
@@ -672,6 +721,16 @@ __global__ __launch_bounds__(256, 2) void gate1x1_h2_kernel(GateArgs a) {
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
                 const f32x4 v0 = __builtin_bit_cast(f32x4, xr[u][ks][0]), v1 = __builtin_bit_cast(f32x4, xr[u][ks][1]);
+                if constexpr (ONE) {
+                    const u32x4 xh = u32x4{hi_pair(v0[0] * sa, v0[1] * sa), hi_pair(v0[2] * sa, v0[3] * sa), hi_pair(v1[0] * sa, v1[1] * sa),
+                                           hi_pair(v1[2] * sa, v1[3] * sa)};
+#pragma unroll
+                    for (int j = 0; j < TN; ++j) {
+                        const u32x4 wh = *reinterpret_cast<const u32x4*>(Bt + (ks * 2) * (BN * 16) + j * 512);
+                        acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, xh), __builtin_bit_cast(f16x8, wh), acc[j], 0, 0, 0);
+                    }
+                    continue;
+                }
                 unsigned h0, l0, h1, l1, h2, l2, h3, l3;
                 split_pair(v0[0] * sa, v0[1] * sa, h0, l0); split_pair(v0[2] * sa, v0[3] * sa, h1, l1);
                 split_pair(v1[0] * sa, v1[1] * sa, h2, l2); split_pair(v1[2] * sa, v1[3] * sa, h3, l3);
@@ -816,13 +875,13 @@ __device__ __forceinline__ f16x8 tr_frag(const char* p) {      // 8 consecutive 
     return __builtin_bit_cast(f16x8, v);
 }
 
-// TW = tile width: 2 x 32 pixels, or 4 x 16 for the 16-pixel-wide level
-template <int TW>
+// TW = tile width: 2 x 32 pixels, or 4 x 16 for the 16-pixel-wide level.  ONE: the one-piece form (hi planes only, one MFMA per step)
+template <int TW, bool ONE = false>
 __global__ __launch_bounds__(256, 2) void wgrad_split_kernel(WgradSplitArgs a) {
     constexpr int TR = 64 / TW, HW_ = TW + 2, HP = (TR + 2) * HW_;      // tile rows; halo pixels of the tile
     constexpr int NX = (HP * 16 + 255) / 256;                          // float4 items of the X halo per thread
     constexpr int XPL = HP * 64, YPL = 64 * 64;                        // bytes of one (plane, channel half) region
-    constexpr int XB = 4 * XPL;                                // X: [plane][half] regions, then dY alike
+    constexpr int XB = (ONE ? 2 : 4) * XPL;                    // X: [plane][half] regions, then dY alike
     extern __shared__ __attribute__((aligned(16))) char wl[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wi = wave >> 1, wj = wave & 1, kh = lane >> 5, ln = lane & 31;
@@ -890,10 +949,14 @@ __global__ __launch_bounds__(256, 2) void wgrad_split_kernel(WgradSplitArgs a) {
             const int hr = (tid + 256 * k) >> 4;
             if (hr >= HP) continue;
             const f32x4 v = __builtin_bit_cast(f32x4, xr[k]);
+            char* d = wl + sdst * XPL + hr * 64 + (c4 & 7) * 8;
+            if constexpr (ONE) {
+                *reinterpret_cast<u32x2*>(d) = u32x2{hi_pair(v[0] * sx, v[1] * sx), hi_pair(v[2] * sx, v[3] * sx)};
+                continue;
+            }
             unsigned h0, l0, h1, l1;
             split_pair(v[0] * sx, v[1] * sx, h0, l0);
             split_pair(v[2] * sx, v[3] * sx, h1, l1);
-            char* d = wl + sdst * XPL + hr * 64 + (c4 & 7) * 8;
             *reinterpret_cast<u32x2*>(d) = u32x2{h0, h1};
             *reinterpret_cast<u32x2*>(d + 2 * XPL) = u32x2{l0, l1};
         }
@@ -901,10 +964,14 @@ __global__ __launch_bounds__(256, 2) void wgrad_split_kernel(WgradSplitArgs a) {
         for (int k = 0; k < 4; ++k) {
             const int pz = (tid + 256 * k) >> 4;
             const f32x4 v = __builtin_bit_cast(f32x4, yr[k]);
+            char* d = wl + XB + sdst * YPL + pz * 64 + (c4 & 7) * 8;
+            if constexpr (ONE) {
+                *reinterpret_cast<u32x2*>(d) = u32x2{hi_pair(v[0] * sy, v[1] * sy), hi_pair(v[2] * sy, v[3] * sy)};
+                continue;
+            }
             unsigned h0, l0, h1, l1;
             split_pair(v[0] * sy, v[1] * sy, h0, l0);
             split_pair(v[2] * sy, v[3] * sy, h1, l1);
-            char* d = wl + XB + sdst * YPL + pz * 64 + (c4 & 7) * 8;
             *reinterpret_cast<u32x2*>(d) = u32x2{h0, h1};
             *reinterpret_cast<u32x2*>(d + 2 * YPL) = u32x2{l0, l1};
         }
@@ -924,7 +991,15 @@ __global__ __launch_bounds__(256, 2) void wgrad_split_kernel(WgradSplitArgs a) {
 #pragma unroll
             for (int s = 0; s < TW / 16; ++s) {
                 const int p0 = r * TW + 16 * s;                               // first of the step's 16 pixels
-                const f16x8 bh = tr_frag(yb_hi + p0 * 64), bl = tr_frag(yb_lo + p0 * 64);
+                const f16x8 bh = tr_frag(yb_hi + p0 * 64);
+                if constexpr (ONE) {
+#pragma unroll
+                    for (int tap = 0; tap < 9; ++tap)
+                        acc[tap] = __builtin_amdgcn_mfma_f32_32x32x16_f16(tr_frag(xa_hi + rofs + ((tap / 3) * HW_ + 16 * s + tap % 3) * 64), bh,
+                                                                          acc[tap], 0, 0, 0);
+                    continue;
+                }
+                const f16x8 bl = tr_frag(yb_lo + p0 * 64);
 #pragma unroll
                 for (int tap = 0; tap < 9; ++tap) {
                     const int hp0 = (tap / 3) * HW_ + 16 * s + tap % 3;       // halo pixel of (row r + dy, column 16 s + dx), less row r
@@ -959,12 +1034,12 @@ __global__ __launch_bounds__(256, 2) void wgrad_split_kernel(WgradSplitArgs a) {
 // [32-channel half][pixel][32 channels]; transpose reads hand both MFMA operands 8 consecutive pixels of one channel per lane.
 // Four accumulator tiles per wave instead of nine: 64 + 44 registers of accumulators and prefetch, no scratch (two or three workgroups
 // per CU measure the same; the bound of two leaves the allocator room).
-template <int TW>
+template <int TW, bool ONE = false>
 __global__ __launch_bounds__(256, 2) void wgrad_up_split_kernel(WgradSplitArgs a) {
     constexpr int TR = 64 / TW, HW_ = TW + 2, HP = (TR + 1) * HW_;     // tile rows; halo pixels ((TR + 1) rows x (TW + 2): TW + 1 are used)
     constexpr int NX = (HP * 16 + 255) / 256;
     constexpr int XPL = HP * 64, YPL = 64 * 64;
-    constexpr int XB = 4 * XPL;
+    constexpr int XB = (ONE ? 2 : 4) * XPL;
     extern __shared__ __attribute__((aligned(16))) char wl[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wi = wave >> 1, wj = wave & 1, kh = lane >> 5, ln = lane & 31;
@@ -1025,10 +1100,14 @@ __global__ __launch_bounds__(256, 2) void wgrad_up_split_kernel(WgradSplitArgs a
             const int hr = (tid + 256 * k) >> 4;
             if (hr >= HP) continue;
             const f32x4 v = __builtin_bit_cast(f32x4, xr[k]);
+            char* d = wl + sdst * XPL + hr * 64 + (c4 & 7) * 8;
+            if constexpr (ONE) {
+                *reinterpret_cast<u32x2*>(d) = u32x2{hi_pair(v[0] * sx, v[1] * sx), hi_pair(v[2] * sx, v[3] * sx)};
+                continue;
+            }
             unsigned h0, l0, h1, l1;
             split_pair(v[0] * sx, v[1] * sx, h0, l0);
             split_pair(v[2] * sx, v[3] * sx, h1, l1);
-            char* d = wl + sdst * XPL + hr * 64 + (c4 & 7) * 8;
             *reinterpret_cast<u32x2*>(d) = u32x2{h0, h1};
             *reinterpret_cast<u32x2*>(d + 2 * XPL) = u32x2{l0, l1};
         }
@@ -1036,10 +1115,14 @@ __global__ __launch_bounds__(256, 2) void wgrad_up_split_kernel(WgradSplitArgs a
         for (int k = 0; k < 4; ++k) {
             const int pz = (tid + 256 * k) >> 4;
             const f32x4 v = __builtin_bit_cast(f32x4, yr[k]);
+            char* d = wl + XB + sdst * YPL + pz * 64 + (c4 & 7) * 8;
+            if constexpr (ONE) {
+                *reinterpret_cast<u32x2*>(d) = u32x2{hi_pair(v[0] * sy, v[1] * sy), hi_pair(v[2] * sy, v[3] * sy)};
+                continue;
+            }
             unsigned h0, l0, h1, l1;
             split_pair(v[0] * sy, v[1] * sy, h0, l0);
             split_pair(v[2] * sy, v[3] * sy, h1, l1);
-            char* d = wl + XB + sdst * YPL + pz * 64 + (c4 & 7) * 8;
             *reinterpret_cast<u32x2*>(d) = u32x2{h0, h1};
             *reinterpret_cast<u32x2*>(d + 2 * YPL) = u32x2{l0, l1};
         }
@@ -1052,7 +1135,15 @@ __global__ __launch_bounds__(256, 2) void wgrad_up_split_kernel(WgradSplitArgs a
 #pragma unroll
             for (int s = 0; s < TW / 16; ++s) {
                 const int p0 = r * TW + 16 * s;
-                const f16x8 bh = tr_frag(yb_hi + p0 * 64), bl = tr_frag(yb_lo + p0 * 64);
+                const f16x8 bh = tr_frag(yb_hi + p0 * 64);
+                if constexpr (ONE) {
+#pragma unroll
+                    for (int tap = 0; tap < 4; ++tap)
+                        acc[tap] = __builtin_amdgcn_mfma_f32_32x32x16_f16(tr_frag(xa_hi + rofs + ((tap >> 1) * HW_ + 16 * s + (tap & 1)) * 64), bh,
+                                                                          acc[tap], 0, 0, 0);
+                    continue;
+                }
+                const f16x8 bl = tr_frag(yb_lo + p0 * 64);
 #pragma unroll
                 for (int tap = 0; tap < 4; ++tap) {
                     const int hp0 = (tap >> 1) * HW_ + 16 * s + (tap & 1);            // halo pixel of (row r + r', column 16 s + t'), less row r
@@ -1081,8 +1172,10 @@ __global__ __launch_bounds__(256, 2) void wgrad_up_split_kernel(WgradSplitArgs a
 // quarter of the HBM rate and needed dY padded from 32 to 64 channels): wgrad_split_kernel without halo or taps.  A workgroup owns a
 // 64 (c) x 64 (n) block -- columns beyond N are zero pixels and are not written -- and walks 64-pixel runs of the [M][.] tensors; one
 // accumulator tile per wave, so four workgroups share a CU and cover each other's loads.
+template <bool ONE = false>
 __global__ __launch_bounds__(256, 4) void wgrad_1x1_split_kernel(WgradSplitArgs a) {
     constexpr int PL = 64 * 64;                // bytes of one (plane, channel half) region: 64 pixels x 64 B
+    constexpr int YB = (ONE ? 2 : 4) * PL;     // dY's regions follow X's
     extern __shared__ __attribute__((aligned(16))) char wl[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wi = wave >> 1, wj = wave & 1, kh = lane >> 5, ln = lane & 31;
@@ -1102,8 +1195,8 @@ __global__ __launch_bounds__(256, 4) void wgrad_1x1_split_kernel(WgradSplitArgs 
     const int loff = (8 * kh + ((lane & 15) >> 2)) * 64 + (16 * ((lane >> 4) & 1) + 4 * (lane & 3)) * 2;
     const char* const xa_hi = wl + (0 * 2 + wi) * PL + loff;
     const char* const xa_lo = wl + (1 * 2 + wi) * PL + loff;
-    const char* const yb_hi = wl + 4 * PL + (0 * 2 + wj) * PL + loff;
-    const char* const yb_lo = wl + 4 * PL + (1 * 2 + wj) * PL + loff;
+    const char* const yb_hi = wl + YB + (0 * 2 + wj) * PL + loff;
+    const char* const yb_lo = wl + YB + (1 * 2 + wj) * PL + loff;
     u32x4 xr[4], yr[4];
     const long long M = (long long)a.H * a.W;  // (pixels; the launcher passes H = M / W)
     auto fetch = [&](int tile) {
@@ -1122,6 +1215,12 @@ __global__ __launch_bounds__(256, 4) void wgrad_1x1_split_kernel(WgradSplitArgs 
         for (int k = 0; k < 4; ++k) {
             const int pz = (tid + 256 * k) >> 4;
             const f32x4 v = __builtin_bit_cast(f32x4, xr[k]), w = __builtin_bit_cast(f32x4, yr[k]);
+            if constexpr (ONE) {
+                char* d = wl + sdst * PL + pz * 64 + (c4 & 7) * 8;
+                *reinterpret_cast<u32x2*>(d) = u32x2{hi_pair(v[0] * sx, v[1] * sx), hi_pair(v[2] * sx, v[3] * sx)};
+                *reinterpret_cast<u32x2*>(d + YB) = u32x2{hi_pair(w[0] * sy, w[1] * sy), hi_pair(w[2] * sy, w[3] * sy)};
+                continue;
+            }
             unsigned h0, l0, h1, l1;
             split_pair(v[0] * sx, v[1] * sx, h0, l0);
             split_pair(v[2] * sx, v[3] * sx, h1, l1);
@@ -1138,6 +1237,10 @@ __global__ __launch_bounds__(256, 4) void wgrad_1x1_split_kernel(WgradSplitArgs 
         if (tile + a.splits < a.n_tiles) fetch(tile + a.splits);
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
+            if constexpr (ONE) {
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(tr_frag(xa_hi + s * 1024), tr_frag(yb_hi + s * 1024), acc, 0, 0, 0);
+                continue;
+            }
             const f16x8 bh = tr_frag(yb_hi + s * 1024), bl = tr_frag(yb_lo + s * 1024);
             const f16x8 ah = tr_frag(xa_hi + s * 1024), al = tr_frag(xa_lo + s * 1024);
             acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc, 0, 0, 0);
@@ -1317,7 +1420,9 @@ __global__ __launch_bounds__(256) void amax_kernel(const float* __restrict__ x, 
 
 // planes [chunk of 16 channels][tap][hi|lo][k half][N][8 fp16] of w[n][c][tap] * (scale ? scale[n] : 1) * 2^(14 - e_w)
 // transposed: the planes of w'[n][c][tap] = w[c][n][taps - 1 - tap] (w is then [C][N][taps]): the data-gradient convolution's
-// weights -- input and output channels swapped, taps reversed -- straight from the layer's own tensor
+// weights -- input and output channels swapped, taps reversed -- straight from the layer's own tensor.
+// ONE: the one-plane layout [chunk][tap][k half][N][8 fp16] of the hi pieces alone
+template <bool ONE = false>
 __global__ void pack_conv_weight_h2_kernel(const float* __restrict__ w, int N, int C, int taps, const float* __restrict__ scale,
                                            int c_off, const unsigned* __restrict__ wamax, unsigned short* __restrict__ dst,
                                            int transposed = 0) {
@@ -1330,6 +1435,12 @@ __global__ void pack_conv_weight_h2_kernel(const float* __restrict__ w, int N, i
         const int n = (int)(t / C);
         float v = transposed ? w[((long long)c * N + n) * taps + (taps - 1 - tap)] : w[i];
         if (scale) v *= scale[n];
+        if constexpr (ONE) {
+            const int cg = c_off + c;
+            const long long base = ((long long)(cg >> 4) * taps + tap) * 2 + ((cg >> 3) & 1);
+            dst[(base * N + n) * 8 + (cg & 7)] = __builtin_bit_cast(unsigned short, (_Float16)(v * sw));
+            continue;
+        }
         unsigned h, l;
         split_pair(v * sw, 0.f, h, l);
         const int cg = c_off + c;
@@ -1352,6 +1463,8 @@ __device__ __forceinline__ double upconv_combined(const double* v, int ph, int r
     return acc;
 }
 // pass 0 (dst == nullptr): max |Wc| into wamax; pass 1: planes [parity][chunk of 16][4 taps][hi|lo][k half][N][8 fp16]
+// (ONE: [parity][chunk of 16][4 taps][k half][N][8], hi alone)
+template <bool ONE = false>
 __global__ __launch_bounds__(256) void pack_upconv_h2_kernel(const float* __restrict__ w, int N, int C, unsigned* __restrict__ wamax,
                                                              unsigned short* __restrict__ dst) {
     const long long NC = (long long)N * C;
@@ -1370,6 +1483,11 @@ __global__ __launch_bounds__(256) void pack_upconv_h2_kernel(const float* __rest
                 if (!dst) { mx = fmaxf(mx, fabsf((float)wc)); continue; }
                 const double ws = wc * sw;
                 const _Float16 h = (_Float16)(float)ws;
+                if constexpr (ONE) {            // (one rounding of the double sum: fp16(s Wc), no intermediate fp32)
+                    const long long base = (((long long)ph * (C >> 4) + (c >> 4)) * 4 + tap) * 2 + ((c >> 3) & 1);
+                    dst[(base * N + n) * 8 + (c & 7)] = __builtin_bit_cast(unsigned short, (_Float16)ws);
+                    continue;
+                }
                 const _Float16 l = (_Float16)(float)(ws - (double)(float)h);
                 const long long base = (((long long)ph * (C >> 4) + (c >> 4)) * 4 + tap) * 4 + ((c >> 3) & 1);
                 dst[((base + 0) * N + n) * 8 + (c & 7)] = __builtin_bit_cast(unsigned short, h);
@@ -1382,7 +1500,8 @@ __global__ __launch_bounds__(256) void pack_upconv_h2_kernel(const float* __rest
 // The same parity filters for the DATA GRADIENT of the layer (conv3x3_halo_h2_kernel<..., DG>): K runs over (parity q, output channel
 // n of the layer), rows over its input channels c, and the tap (r', t') of chunk q holds Wc[q][1 - r'][1 - t'][n][c] (the kernel walks
 // the parity plane with the forward's tap origin mirrored).  pass 0 (dst == nullptr): max |Wc| into wamax; pass 1: planes
-// [q (N / 16) + n / 16][4 taps][hi|lo][k half][C][8 fp16].
+// [q (N / 16) + n / 16][4 taps][hi|lo][k half][C][8 fp16] (ONE: [q (N / 16) + n / 16][4 taps][k half][C][8], hi alone).
+template <bool ONE = false>
 __global__ __launch_bounds__(256) void pack_upconv_dgrad_h2_kernel(const float* __restrict__ w, int N, int C, unsigned* __restrict__ wamax,
                                                                    unsigned short* __restrict__ dst) {
     const long long NC = (long long)N * C;
@@ -1401,6 +1520,11 @@ __global__ __launch_bounds__(256) void pack_upconv_dgrad_h2_kernel(const float* 
                 if (!dst) { mx = fmaxf(mx, fabsf((float)wc)); continue; }
                 const double ws = wc * sw;
                 const _Float16 h = (_Float16)(float)ws;
+                if constexpr (ONE) {            // (one rounding of the double sum, as pack_upconv_h2_kernel<true>)
+                    const long long base = (((long long)q * (N >> 4) + (n >> 4)) * 4 + tap) * 2 + ((n >> 3) & 1);
+                    dst[(base * C + c) * 8 + (n & 7)] = __builtin_bit_cast(unsigned short, (_Float16)ws);
+                    continue;
+                }
                 const _Float16 l = (_Float16)(float)(ws - (double)(float)h);
                 const long long base = (((long long)q * (N >> 4) + (n >> 4)) * 4 + tap) * 4 + ((n >> 3) & 1);
                 dst[((base + 0) * C + c) * 8 + (n & 7)] = __builtin_bit_cast(unsigned short, h);
@@ -1447,9 +1571,28 @@ __global__ __launch_bounds__(256) void prepack_amax_kernel(const PrepackDesc* __
 // One thread packs an 8 x 8 block (rows n, channels c) of one tap: the forward planes take its 8 channels of a row as one 16-byte
 // store, the data gradient's planes its 8 rows of a channel, and the 8 stores of either kind are one 128-byte run (the per-layer pack
 // kernels write 2 bytes at a time; 0.83 ms for the network's weights that way, measured, against 0.2 ms of traffic).
+// ONE: the one-plane layouts ([.. / 16][slot][k half][rows][8]) of the hi pieces (the low halves of hl)
+template <bool ONE = false>
 __device__ __forceinline__ void prepack_store_block(const PrepackDesc& d, const unsigned (&hl)[8][8], int n8, int c8, int slot_f, int slot_t,
                                                     int slots) {
     const int N = d.N, C = d.C, n0 = n8 * 8, c0 = c8 * 8;
+    if constexpr (ONE) {
+        const long long bf = ((long long)(c0 >> 4) * slots + slot_f) * 2 + ((c0 >> 3) & 1);
+        uint4* hf = (uint4*)(d.planes + (bf * N + n0) * 8);
+#pragma unroll
+        for (int nn = 0; nn < 8; ++nn)
+            hf[nn] = uint4{(hl[nn][0] & 0xffffu) | (hl[nn][1] << 16), (hl[nn][2] & 0xffffu) | (hl[nn][3] << 16),
+                           (hl[nn][4] & 0xffffu) | (hl[nn][5] << 16), (hl[nn][6] & 0xffffu) | (hl[nn][7] << 16)};
+        if (slot_t >= 0) {
+            const long long bt = ((long long)(n0 >> 4) * slots + slot_t) * 2 + ((n0 >> 3) & 1);
+            uint4* ht = (uint4*)(d.planes_t + (bt * C + c0) * 8);
+#pragma unroll
+            for (int cc = 0; cc < 8; ++cc)
+                ht[cc] = uint4{(hl[0][cc] & 0xffffu) | (hl[1][cc] << 16), (hl[2][cc] & 0xffffu) | (hl[3][cc] << 16),
+                               (hl[4][cc] & 0xffffu) | (hl[5][cc] << 16), (hl[6][cc] & 0xffffu) | (hl[7][cc] << 16)};
+        }
+        return;
+    }
     {       // forward planes [.. c / 16][slot][hi|lo][k half][N][8]: rows n0..n0+7, one uint4 (8 channels) each
         const long long base = ((long long)(c0 >> 4) * slots + slot_f) * 4 + ((c0 >> 3) & 1);
         uint4* hi = (uint4*)(d.planes + ((base + 0) * N + n0) * 8);
@@ -1479,6 +1622,7 @@ __device__ __forceinline__ void prepack_store_block(const PrepackDesc& d, const 
         }
     }
 }
+template <bool ONE = false>
 __global__ __launch_bounds__(256) void prepack_pack_kernel(const PrepackDesc* __restrict__ descs) {
     const PrepackDesc d = descs[blockIdx.y];
     const int N = d.N, C = d.C, N8 = N >> 3, C8 = C >> 3;
@@ -1505,15 +1649,16 @@ __global__ __launch_bounds__(256) void prepack_pack_kernel(const PrepackDesc* __
                     for (int y = y_lo; y <= y_hi; ++y)
                         for (int x = x_lo; x <= x_hi; ++x) acc += (double)w9[y * 3 + x];
                     const double ws = acc * sw;
-                    const _Float16 h = (_Float16)(float)ws;
+                    const _Float16 h = ONE ? (_Float16)ws : (_Float16)(float)ws;       // (ONE: the per-layer pack's single rounding)
                     const _Float16 l = (_Float16)(float)(ws - (double)(float)h);
                     hl[nn][cc] = (unsigned)__builtin_bit_cast(unsigned short, h) | ((unsigned)__builtin_bit_cast(unsigned short, l) << 16);
                 }
             // forward: chunk index ph (C / 16) + c / 16 -> fold ph into the pointer by offsetting the slot: slots per chunk = 4
             PrepackDesc e = d;
-            e.planes = d.planes + (long long)ph * (C >> 4) * 4 * 4 * N * 8;
-            if (d.planes_t) e.planes_t = d.planes_t + (long long)ph * (N >> 4) * 4 * 4 * C * 8;
-            prepack_store_block(e, hl, n8, c8, tap, d.planes_t ? (1 - r) * 2 + (1 - tt) : -1, 4);
+            constexpr int NPL = ONE ? 1 : 2;
+            e.planes = d.planes + (long long)ph * (C >> 4) * 4 * 2 * NPL * N * 8;
+            if (d.planes_t) e.planes_t = d.planes_t + (long long)ph * (N >> 4) * 4 * 2 * NPL * C * 8;
+            prepack_store_block<ONE>(e, hl, n8, c8, tap, d.planes_t ? (1 - r) * 2 + (1 - tt) : -1, 4);
         }
         return;
     }
@@ -1532,7 +1677,7 @@ __global__ __launch_bounds__(256) void prepack_pack_kernel(const PrepackDesc* __
                 split_pair(d.w[((long long)(n8 * 8 + nn) * C + c8 * 8 + cc) * taps + tap] * swf, 0.f, h, l);
                 hl[nn][cc] = (h & 0xffffu) | (l << 16);
             }
-        prepack_store_block(d, hl, n8, c8, tap, d.planes_t ? taps - 1 - tap : -1, taps);     // data gradient: taps reversed
+        prepack_store_block<ONE>(d, hl, n8, c8, tap, d.planes_t ? taps - 1 - tap : -1, taps);     // data gradient: taps reversed
     }
 }
 
@@ -1544,20 +1689,21 @@ int split_tile_width(int H, int W, int N, int ksize) {
     return 0;
 }
 
-template <int TW, int TM, int TN, bool PH, bool BS = false, bool P2 = false, bool DG = false>
+template <int TW, int TM, int TN, bool PH, bool BS = false, bool P2 = false, bool DG = false, bool ONE = false>
 int launch_h2(const SplitArgs& a, hipStream_t st, int tile) {
     {
         char nm[96];
-        snprintf(nm, sizeof(nm), "conv3x3_halo_h2_kernel<%d, %d, %d, %s, %s, %s, %s>", TW, TM, TN, PH ? "true" : "false", BS ? "true" : "false",
-                 P2 ? "true" : "false", DG ? "true" : "false");
+        snprintf(nm, sizeof(nm), "conv3x3_halo_h2_kernel<%s, %d, %d, %d, %s, %s, %s, %s>", ONE ? "true" : "false", TW, TM, TN, PH ? "true" : "false",
+                 BS ? "true" : "false", P2 ? "true" : "false", DG ? "true" : "false");
         nbp_note_kernel_symbol(tile, nm);
     }
     constexpr int TH = 4 * TM * (32 / TW);
     constexpr int HPIX = (TH + 2) * (TW + 2), RS = (HPIX + 7) / 8 * 8 * 16 + 64, NB = TN / 2;
-    constexpr size_t smem = 4 * (size_t)RS + 2 * (size_t)(PH ? 8 : 12) * NB * 1024 * (P2 ? 2 : 1) + (PH ? 0 : (HPIX * 4 + 15) / 16 * 16);      // (+ psi of the halo pixels)
+    constexpr int NPL = ONE ? 1 : 2;
+    constexpr size_t smem = 2 * NPL * (size_t)RS + 2 * (size_t)(PH ? 4 : 6) * NPL * NB * 1024 * (P2 ? 2 : 1) + (PH ? 0 : (HPIX * 4 + 15) / 16 * 16);      // (+ psi of the halo pixels)
     static bool attr_set = false;
     if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_halo_h2_kernel<TW, TM, TN, PH, BS, P2, DG>),
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_halo_h2_kernel<ONE, TW, TM, TN, PH, BS, P2, DG>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
         if (e != hipSuccess) return (int)e;
         attr_set = true;
@@ -1565,8 +1711,13 @@ int launch_h2(const SplitArgs& a, hipStream_t st, int tile) {
     // PH: tiles of the low-resolution image, four parities in blockIdx.z (fastest); DG: a.M counts the low-resolution output itself
     constexpr bool PHO = PH && !DG;
     dim3 grid((unsigned)(a.M / (PHO ? 4 : 1) / (TH * TW)), (unsigned)(a.N / (TN * 32)), (unsigned)(a.split_k * a.groups * (PHO ? (P2 ? 2 : 4) : 1)));
-    conv3x3_halo_h2_kernel<TW, TM, TN, PH, BS, P2, DG><<<grid, 256, smem, st>>>(a);
+    conv3x3_halo_h2_kernel<ONE, TW, TM, TN, PH, BS, P2, DG><<<grid, 256, smem, st>>>(a);
     return nbp_launch_status();
+}
+// the same instantiation in the two-piece (one == 0) or the one-piece form
+template <int TW, int TM, int TN, bool PH, bool BS = false, bool P2 = false, bool DG = false>
+int launch_h2o(const SplitArgs& a, hipStream_t st, int tile, int one) {
+    return one ? launch_h2<TW, TM, TN, PH, BS, P2, DG, true>(a, st, tile) : launch_h2<TW, TM, TN, PH, BS, P2, DG, false>(a, st, tile);
 }
 
 }  // namespace
@@ -1685,7 +1836,7 @@ int nbp_amax_launch(const float* x, long long n, unsigned* amax_inout, hipStream
 // Returns NBP_E_SHAPE for layers the kernel does not take.
 int nbp_conv_split_launch_g(const ConvOperandsSplit& o, const ConvOperandsSplit* o2, int C0, int C1, int ups, int B, int H, int W,
                             int ksize, int N, int relu, int split_k, void* ws, size_t ws_bytes, hipStream_t st,
-                            float* const* pool_out, int* pooled, const ConvHead* head, int* headed, double* bn_part, int* bn_rows) {
+                            float* const* pool_out, int* pooled, const ConvHead* head, int* headed, double* bn_part, int* bn_rows, int one) {
     const int groups = o2 ? 2 : 1;
     if (bn_rows) *bn_rows = 0;
     NBP_RETURN_IF(!o.src0 || !o.planes || !o.scale || !o.shift || !o.out || !o.amax0 || !o.wamax, NBP_E_ARG);
@@ -1768,25 +1919,25 @@ int nbp_conv_split_launch_g(const ConvOperandsSplit& o, const ConvOperandsSplit*
         *bn_rows = (int)(a.M / (16 * tw));               // pixel tiles (x 4 parities for the up_conv form: the same count)
         if (wide) {                                      // 8 x 32 pixels x 128 channels (see below): twice the pixel tiles
             *bn_rows = (int)(a.M / 256);
-            return launch_h2<32, 2, 4, false, true>(a, st, p.tile);
+            return launch_h2o<32, 2, 4, false, true>(a, st, p.tile, one);
         }
         // (up_conv layers: the two-parity form here too -- the one-parity 16-row form carried 136 B of scratch per lane)
-        return ph ? (tw == 32 ? launch_h2<32, 2, 2, true, true, true>(a, st, p.tile) : launch_h2<16, 2, 4, true, true>(a, st, p.tile))
-                  : (tw == 32 ? launch_h2<32, 4, 2, false, true>(a, st, p.tile) : launch_h2<16, 2, 4, false, true>(a, st, p.tile));
+        return ph ? (tw == 32 ? launch_h2o<32, 2, 2, true, true, true>(a, st, p.tile, one) : launch_h2o<16, 2, 4, true, true>(a, st, p.tile, one))
+                  : (tw == 32 ? launch_h2o<32, 4, 2, false, true>(a, st, p.tile, one) : launch_h2o<16, 2, 4, false, true>(a, st, p.tile, one));
     }
     // up_conv layers on full-height 32-pixel-wide tiles: both column parities in one workgroup of half the height (same workgroup
     // count, one staged halo for two parities).  The 16-pixel-wide levels keep one parity per workgroup (the two-parity form measured
     // 7 % slower per launch there: 619 against 577 us at B = 24); round 3's one-parity 16 x 32 form (120 B of scratch per lane) is gone.
-    int rc = (ph && !r8 && tw == 32) ? launch_h2<32, 2, 2, true, false, true>(a, st, p.tile)
-           : r8 ? (ph ? (tw == 32 ? launch_h2<32, 2, 2, true>(a, st, p.tile) : launch_h2<16, 1, 4, true>(a, st, p.tile))
-                      : (tw == 32 ? launch_h2<32, 2, 2, false>(a, st, p.tile) : launch_h2<16, 1, 4, false>(a, st, p.tile)))
-           : ph ? launch_h2<16, 2, 4, true>(a, st, p.tile)
+    int rc = (ph && !r8 && tw == 32) ? launch_h2o<32, 2, 2, true, false, true>(a, st, p.tile, one)
+           : r8 ? (ph ? (tw == 32 ? launch_h2o<32, 2, 2, true>(a, st, p.tile, one) : launch_h2o<16, 1, 4, true>(a, st, p.tile, one))
+                      : (tw == 32 ? launch_h2o<32, 2, 2, false>(a, st, p.tile, one) : launch_h2o<16, 1, 4, false>(a, st, p.tile, one)))
+           : ph ? launch_h2o<16, 2, 4, true>(a, st, p.tile, one)
                 // 32-pixel-wide levels: 8 x 32 pixels x 128 channels where the layer has them (round 5) -- the same workgroup count, MFMAs
                 // per stage and sums in the same order as 16 x 32 x 64, but a 10 x 34 halo staged per 128 output channels instead of an
                 // 18 x 34 one per 64: 44 % less halo traffic, splitting and LDS writes per output (every N % 128 == 0 layer 1.4 - 2.7 %
                 // faster at B = 24, the forward 9.46 -> 9.38 ms; profiles/r05/tile_8x32x128.txt)
-                : (tw == 32 ? (wide ? launch_h2<32, 2, 4, false>(a, st, p.tile) : launch_h2<32, 4, 2, false>(a, st, p.tile))
-                            : launch_h2<16, 2, 4, false>(a, st, p.tile));
+                : (tw == 32 ? (wide ? launch_h2o<32, 2, 4, false>(a, st, p.tile, one) : launch_h2o<32, 4, 2, false>(a, st, p.tile, one))
+                            : launch_h2o<16, 2, 4, false>(a, st, p.tile, one));
     if (rc) return rc;
     if (p.split_k > 1) {
         const long long MN = a.M * N;
@@ -1879,16 +2030,16 @@ int nbp_gate1x1_split_launch_g(const ConvOperandsSplit& o, const ConvOperandsSpl
     const size_t smem = 2 * (size_t)8 * bn * 16;
     {
         char nm[64];
-        snprintf(nm, sizeof(nm), "gate1x1_h2_kernel<%d, %s>", bn / 32, with_psi ? "true" : "false");
+        snprintf(nm, sizeof(nm), "gate1x1_h2_kernel<false, %d, %s>", bn / 32, with_psi ? "true" : "false");
         nbp_note_kernel_symbol(NBP_TILE_SPLIT_GATE, nm);
     }
     if (with_psi) {
-        if (bn == 128) gate1x1_h2_kernel<4, true><<<grid, 256, smem, st>>>(a);
-        else if (bn == 64) gate1x1_h2_kernel<2, true><<<grid, 256, smem, st>>>(a);
-        else gate1x1_h2_kernel<1, true><<<grid, 256, smem, st>>>(a);
-    } else if (bn == 128) gate1x1_h2_kernel<4, false><<<grid, 256, smem, st>>>(a);
-    else if (bn == 64) gate1x1_h2_kernel<2, false><<<grid, 256, smem, st>>>(a);
-    else gate1x1_h2_kernel<1, false><<<grid, 256, smem, st>>>(a);
+        if (bn == 128) gate1x1_h2_kernel<false, 4, true><<<grid, 256, smem, st>>>(a);
+        else if (bn == 64) gate1x1_h2_kernel<false, 2, true><<<grid, 256, smem, st>>>(a);
+        else gate1x1_h2_kernel<false, 1, true><<<grid, 256, smem, st>>>(a);
+    } else if (bn == 128) gate1x1_h2_kernel<false, 4, false><<<grid, 256, smem, st>>>(a);
+    else if (bn == 64) gate1x1_h2_kernel<false, 2, false><<<grid, 256, smem, st>>>(a);
+    else gate1x1_h2_kernel<false, 1, false><<<grid, 256, smem, st>>>(a);
     return nbp_launch_status();
 }
 
@@ -1897,7 +2048,7 @@ int nbp_gate1x1_split_launch_g(const ConvOperandsSplit& o, const ConvOperandsSpl
 // split_k <= 0: slices by occupancy.  NBP_E_SHAPE when the low-resolution image does not tile.
 int nbp_upconv_dgrad_split_launch(const float* dy, int N, int B, int H, int W, const void* planes, const unsigned* wamax,
                                   const unsigned* amax_in, int C, const float* scale, const float* shift, float* out, unsigned* amax_out,
-                                  int split_k, void* ws, size_t ws_bytes, hipStream_t st) {
+                                  int split_k, void* ws, size_t ws_bytes, hipStream_t st, int one = 0) {
     NBP_RETURN_IF(!dy || !planes || !wamax || !amax_in || !scale || !shift || !out, NBP_E_ARG);
     NBP_RETURN_IF(B < 1 || N < 16 || N % 16 || C < 64 || C % 64, NBP_E_SHAPE);
     const int tw = split_tile_width(H, W, C, 3);
@@ -1925,8 +2076,8 @@ int nbp_upconv_dgrad_split_launch(const float* dy, int N, int B, int H, int W, c
     }
     // (8 x 32-pixel tiles on the 32-pixel-wide levels: the 16-row one-parity form carries 124 B of scratch per lane in its staging
     // section and measured the same, 520.9 against 518-521 maps/s for the training step)
-    int rc = tw == 32 ? launch_h2<32, 2, 2, true, false, false, true>(a, st, NBP_TILE_SPLIT_UP_DGRAD)
-                      : launch_h2<16, 2, 4, true, false, false, true>(a, st, NBP_TILE_SPLIT_UP_DGRAD);
+    int rc = tw == 32 ? launch_h2o<32, 2, 2, true, false, false, true>(a, st, NBP_TILE_SPLIT_UP_DGRAD, one)
+                      : launch_h2o<16, 2, 4, true, false, false, true>(a, st, NBP_TILE_SPLIT_UP_DGRAD, one);
     if (rc) return rc;
     if (a.split_k > 1) {
         const long long MN = a.M * C;
@@ -1943,7 +2094,7 @@ int nbp_upconv_dgrad_split_launch(const float* dy, int N, int B, int H, int W, c
 // on the deep levels, and padded from 32 to 64 output channels on level 2).  planes: nbp_pack_conv_weight_split with ksize = 1
 // ([chunk of 16][hi|lo][k half][N][8]); C % 32 == 0, N % 32 == 0.
 int nbp_conv1x1_split_launch(const float* src, int C, long long M, const void* planes, const unsigned* wamax, const unsigned* amax_in,
-                             int N, const float* scale, const float* shift, int relu, float* out, hipStream_t st) {
+                             int N, const float* scale, const float* shift, int relu, float* out, hipStream_t st, int one = 0) {
     NBP_RETURN_IF(!src || !planes || !wamax || !amax_in || !scale || !shift || !out, NBP_E_ARG);
     NBP_RETURN_IF(C < 32 || C % 32 || N < 32 || N % 32 || M < 1, NBP_E_SHAPE);
     const long long b0 = M * C * 4, bw = (long long)C * N * 4;
@@ -1957,10 +2108,14 @@ int nbp_conv1x1_split_launch(const float* src, int C, long long M, const void* p
     int bn = N % 128 == 0 ? 128 : (N % 64 == 0 ? 64 : 32);
     if (bn == 128 && nbp_cdiv(M, 128) * (N / 128) < 512) bn = 64;
     dim3 grid((unsigned)nbp_cdiv(M, 128), (unsigned)(N / bn), 1u);
-    const size_t smem = 2 * (size_t)8 * bn * 16;
-    if (bn == 128) gate1x1_h2_kernel<4, false><<<grid, 256, smem, st>>>(a);
-    else if (bn == 64) gate1x1_h2_kernel<2, false><<<grid, 256, smem, st>>>(a);
-    else gate1x1_h2_kernel<1, false><<<grid, 256, smem, st>>>(a);
+    const size_t smem = 2 * (size_t)(one ? 4 : 8) * bn * 16;
+    if (one) {
+        if (bn == 128) gate1x1_h2_kernel<true, 4, false><<<grid, 256, smem, st>>>(a);
+        else if (bn == 64) gate1x1_h2_kernel<true, 2, false><<<grid, 256, smem, st>>>(a);
+        else gate1x1_h2_kernel<true, 1, false><<<grid, 256, smem, st>>>(a);
+    } else if (bn == 128) gate1x1_h2_kernel<false, 4, false><<<grid, 256, smem, st>>>(a);
+    else if (bn == 64) gate1x1_h2_kernel<false, 2, false><<<grid, 256, smem, st>>>(a);
+    else gate1x1_h2_kernel<false, 1, false><<<grid, 256, smem, st>>>(a);
     return nbp_launch_status();
 }
 
@@ -1968,7 +2123,7 @@ int nbp_conv1x1_split_launch(const float* src, int C, long long M, const void* p
 // amax3 = 3 x 64 zeroed words of scratch: max |src0|, max |src1|, max |dY| are computed here.
 int nbp_wgrad_split_launch(const float* src0, int C0, const float* src1, int C1, int ups, int B, int H, int W, const float* dy, int N,
                            int n_tiles, int splits, unsigned* amax3, const unsigned* amax0_in, const unsigned* amax1_in,
-                           const unsigned* amaxy_in, float* part, hipStream_t st) {
+                           const unsigned* amaxy_in, float* part, hipStream_t st, int one) {
     const int Hs = ups ? H / 2 : H, Ws = ups ? W / 2 : W;
     const long long b0 = (long long)B * Hs * Ws * C0 * 4, b1 = (long long)B * Hs * Ws * C1 * 4, by = (long long)B * H * W * N * 4;
     NBP_RETURN_IF(b0 >= (1ll << 31) || b1 >= (1ll << 31) || by >= (1ll << 31), NBP_E_SHAPE);
@@ -1986,7 +2141,13 @@ int nbp_wgrad_split_launch(const float* src0, int C0, const float* src1, int C1,
     a.amax0 = amax0_in ? amax0_in : amax3; a.amax1 = amax1_in ? amax1_in : amax3 + AMAX_WORDS;
     a.amaxy = amaxy_in ? amaxy_in : amax3 + 2 * AMAX_WORDS; a.part = part;
     const bool wide = W % 32 == 0 && H % 2 == 0;              // 2 x 32 tiles, else 4 x 16 (nbp_wgrad_split_ok)
-    const int smem = wide ? 4 * (4 * 34 * 64) + 4 * (64 * 64) : 4 * (6 * 18 * 64) + 4 * (64 * 64);
+    const int smem = (one ? 2 : 4) * ((wide ? 4 * 34 * 64 : 6 * 18 * 64) + 64 * 64);
+    dim3 grid((unsigned)(((C0 + C1) / 64) * (N / 64)), (unsigned)splits);
+    if (one) {          // (at most 25.6 KB: below the default limit of dynamic LDS)
+        if (wide) wgrad_split_kernel<32, true><<<grid, 256, smem, st>>>(a);
+        else wgrad_split_kernel<16, true><<<grid, 256, smem, st>>>(a);
+        return nbp_launch_status();
+    }
     static bool attr_set = false;
     if (!attr_set) {
         e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_split_kernel<32>), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1998,7 +2159,6 @@ int nbp_wgrad_split_launch(const float* src0, int C0, const float* src1, int C1,
         if (e != hipSuccess) return (int)e;
         attr_set = true;
     }
-    dim3 grid((unsigned)(((C0 + C1) / 64) * (N / 64)), (unsigned)splits);
     if (wide) wgrad_split_kernel<32><<<grid, 256, smem, st>>>(a);
     else wgrad_split_kernel<16><<<grid, 256, smem, st>>>(a);
     return nbp_launch_status();
@@ -2009,6 +2169,23 @@ extern "C" int nbp_pack_conv_weight_split(const float* w_oihw, int N, int C, int
     NBP_ENTER();
     return nbp_pack_conv_weight_split_launch(w_oihw, N, C, ksize, scale_or_null, c_off, c_total, dst_planes, (unsigned*)wamax_out,
                                              (hipStream_t)stream);
+}
+// ---- the one-piece ("_h1") forms of the packs: the same arguments, the same max |w| word, planes [chunk][tap][k half][rows][8 fp16]
+// of the hi pieces alone (half the bytes of the two-piece planes)
+extern "C" int nbp_pack_conv_weight_split_h1(const float* w_oihw, int N, int C, int ksize, const float* scale_or_null,
+                                             int c_off, int c_total, void* dst_planes, void* wamax_out, void* stream) {
+    NBP_ENTER();
+    NBP_RETURN_IF(!w_oihw || !dst_planes || !wamax_out, NBP_E_ARG);
+    NBP_RETURN_IF(ksize != 1 && ksize != 3, NBP_E_ARG);
+    NBP_RETURN_IF(N < 1 || C < 1 || c_off != 0 || C > c_total || c_total % 32, NBP_E_SHAPE);
+    hipStream_t st = (hipStream_t)stream;
+    const long long total = (long long)N * C * ksize * ksize;
+    hipError_t e = hipMemsetAsync(wamax_out, 0, sizeof(unsigned), st);
+    if (e != hipSuccess) return (int)e;
+    amax_kernel<<<min(nbp_ew_grid(total, 256), 256), 256, 0, st>>>(w_oihw, total, scale_or_null, (long long)C * ksize * ksize, (unsigned*)wamax_out, 1u);
+    pack_conv_weight_h2_kernel<true><<<nbp_ew_grid(total, 256), 256, 0, st>>>(w_oihw, N, C, ksize * ksize, scale_or_null, c_off,
+                                                                             (const unsigned*)wamax_out, (unsigned short*)dst_planes);
+    return nbp_launch_status();
 }
 
 // Planes of the data-gradient convolution of a 3x3 layer with weights w [N][C][3][3]: dx = conv3x3(dy, w') with
@@ -2027,6 +2204,20 @@ extern "C" int nbp_pack_conv_weight_split_dgrad(const float* w_oihw, int N, int 
                                                                        (unsigned short*)dst_planes, 1);
     return nbp_launch_status();
 }
+extern "C" int nbp_pack_conv_weight_split_dgrad_h1(const float* w_oihw, int N, int C, int c_total, void* dst_planes, void* wamax_out,
+                                                   void* stream) {
+    NBP_ENTER();
+    NBP_RETURN_IF(!w_oihw || !dst_planes || !wamax_out, NBP_E_ARG);
+    NBP_RETURN_IF(N < 1 || C < 1 || N > c_total || c_total % 32, NBP_E_SHAPE);
+    hipStream_t st = (hipStream_t)stream;
+    const long long total = (long long)N * C * 9;
+    hipError_t e = hipMemsetAsync(wamax_out, 0, sizeof(unsigned), st);
+    if (e != hipSuccess) return (int)e;
+    amax_kernel<<<min(nbp_ew_grid(total, 256), 256), 256, 0, st>>>(w_oihw, total, nullptr, 9ll * C, (unsigned*)wamax_out, 1u);
+    pack_conv_weight_h2_kernel<true><<<nbp_ew_grid(total, 256), 256, 0, st>>>(w_oihw, C, N, 9, nullptr, 0, (const unsigned*)wamax_out,
+                                                                             (unsigned short*)dst_planes, 1);
+    return nbp_launch_status();
+}
 
 // All weight packs of a training step: descs_dev = n PrepackDesc records on the device (layout in include/nbp_hip.h), wamax words
 // zeroed here.  N % 16 == 0 and C % 16 == 0 for every record (the plane layouts).
@@ -2038,6 +2229,17 @@ extern "C" int nbp_prepack_weights_split(const void* descs_dev, int n, void* wam
     if (e != hipSuccess) return (int)e;
     prepack_amax_kernel<<<dim3(64, (unsigned)n), 256, 0, st>>>((const PrepackDesc*)descs_dev);
     prepack_pack_kernel<<<dim3(256, (unsigned)n), 256, 0, st>>>((const PrepackDesc*)descs_dev);
+    return nbp_launch_status();
+}
+// the same with the one-plane layouts (the planes of the "_h1" pack entry points, bit for bit)
+extern "C" int nbp_prepack_weights_split_h1(const void* descs_dev, int n, void* wamax_words, void* stream) {
+    NBP_ENTER();
+    NBP_RETURN_IF(!descs_dev || !wamax_words || n < 1 || n > 4096, NBP_E_ARG);
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipMemsetAsync(wamax_words, 0, (size_t)n * sizeof(unsigned), st);
+    if (e != hipSuccess) return (int)e;
+    prepack_amax_kernel<<<dim3(64, (unsigned)n), 256, 0, st>>>((const PrepackDesc*)descs_dev);
+    prepack_pack_kernel<true><<<dim3(256, (unsigned)n), 256, 0, st>>>((const PrepackDesc*)descs_dev);
     return nbp_launch_status();
 }
 extern "C" int nbp_prepack_desc_bytes(void) { return (int)sizeof(PrepackDesc); }
@@ -2065,6 +2267,28 @@ extern "C" int nbp_pack_conv_weight_split_dgrad_known(const float* w_oihw, int N
     const long long total = (long long)N * C * 9;
     pack_conv_weight_h2_kernel<<<nbp_ew_grid(total, 256), 256, 0, (hipStream_t)stream>>>(w_oihw, C, N, 9, nullptr, 0, (const unsigned*)wamax_known,
                                                                                         (unsigned short*)dst_planes, 1);
+    return nbp_launch_status();
+}
+extern "C" int nbp_pack_conv_weight_split_prezeroed_h1(const float* w_oihw, int N, int C, int ksize, int c_total, void* dst_planes,
+                                                       void* wamax_zeroed, void* stream) {
+    NBP_ENTER();
+    NBP_RETURN_IF(!w_oihw || !dst_planes || !wamax_zeroed, NBP_E_ARG);
+    NBP_RETURN_IF((ksize != 1 && ksize != 3) || N < 1 || C < 1 || C > c_total || c_total % 32, NBP_E_SHAPE);
+    hipStream_t st = (hipStream_t)stream;
+    const long long total = (long long)N * C * ksize * ksize;
+    amax_kernel<<<min(nbp_ew_grid(total, 256), 256), 256, 0, st>>>(w_oihw, total, nullptr, (long long)C * ksize * ksize, (unsigned*)wamax_zeroed, 1u);
+    pack_conv_weight_h2_kernel<true><<<nbp_ew_grid(total, 256), 256, 0, st>>>(w_oihw, N, C, ksize * ksize, nullptr, 0, (const unsigned*)wamax_zeroed,
+                                                                             (unsigned short*)dst_planes);
+    return nbp_launch_status();
+}
+extern "C" int nbp_pack_conv_weight_split_dgrad_known_h1(const float* w_oihw, int N, int C, int c_total, void* dst_planes,
+                                                         const void* wamax_known, void* stream) {
+    NBP_ENTER();
+    NBP_RETURN_IF(!w_oihw || !dst_planes || !wamax_known, NBP_E_ARG);
+    NBP_RETURN_IF(N < 1 || C < 1 || N > c_total || c_total % 32, NBP_E_SHAPE);
+    const long long total = (long long)N * C * 9;
+    pack_conv_weight_h2_kernel<true><<<nbp_ew_grid(total, 256), 256, 0, (hipStream_t)stream>>>(w_oihw, C, N, 9, nullptr, 0,
+                                                                                              (const unsigned*)wamax_known, (unsigned short*)dst_planes, 1);
     return nbp_launch_status();
 }
 
@@ -2097,7 +2321,7 @@ extern "C" size_t nbp_conv_split_planned_workspace_bytes_k(int B, int H, int W, 
 static int conv3x3_split_impl(const float* src0, int C0, const float* src1, int C1, int ups, int B, int H, int W,
                               const void* w_planes, const void* wamax, int N, const float* scale, const float* shift,
                               int relu, float* out, const void* amax_in_or_null, void* amax_out_or_null, int split_k,
-                              void* ws, size_t ws_bytes, void* stream, double* bn_part, int* bn_rows) {
+                              void* ws, size_t ws_bytes, void* stream, double* bn_part, int* bn_rows, int one = 0) {
     NBP_RETURN_IF(!ws || ws_bytes < 256 || !src0, NBP_E_WS);
     hipStream_t st = (hipStream_t)stream;
     const unsigned* amax = (const unsigned*)amax_in_or_null;
@@ -2114,7 +2338,7 @@ static int conv3x3_split_impl(const float* src0, int C0, const float* src1, int 
     ConvOperandsSplit o{src0, src1, w_planes, scale, shift, out, amax, amax, (const unsigned*)wamax, (unsigned*)amax_out_or_null,
                         nullptr, nullptr};
     return nbp_conv_split_launch_g(o, nullptr, C0, C1, ups, B, H, W, 3, N, relu, split_k, (char*)ws + 256, ws_bytes - 256, st, nullptr,
-                                   nullptr, nullptr, nullptr, bn_part, bn_rows);
+                                   nullptr, nullptr, nullptr, bn_part, bn_rows, one);
 }
 extern "C" int nbp_conv3x3_split_f32(const float* src0, int C0, const float* src1, int C1, int ups, int B, int H, int W,
                                      const void* w_planes, const void* wamax, int N, const float* scale, const float* shift,
@@ -2136,6 +2360,25 @@ extern "C" int nbp_conv3x3_split_bn_f32(const float* src0, int C0, const float* 
     NBP_RETURN_IF(!bn_part || !bn_rows || ((uintptr_t)bn_part & 7), NBP_E_ARG);
     return conv3x3_split_impl(src0, C0, src1, C1, ups, B, H, W, w_planes, wamax, N, scale, shift, relu, out, amax_in_or_null,
                               amax_out_or_null, split_k, ws, ws_bytes, stream, bn_part, bn_rows);
+}
+// ---- the one-piece ("_h1") forms of the training convolutions: the same arguments, planes from the "_h1" packs, one fp16 MFMA per
+// product on hi = fp16(s x) (conv3x3_halo_h2_kernel<true, ...>)
+extern "C" int nbp_conv3x3_split_f32_h1(const float* src0, int C0, const float* src1, int C1, int ups, int B, int H, int W,
+                                        const void* w_planes, const void* wamax, int N, const float* scale, const float* shift,
+                                        int relu, float* out, const void* amax_in_or_null, void* amax_out_or_null, int split_k,
+                                        void* ws, size_t ws_bytes, void* stream) {
+    NBP_ENTER();
+    return conv3x3_split_impl(src0, C0, src1, C1, ups, B, H, W, w_planes, wamax, N, scale, shift, relu, out, amax_in_or_null,
+                              amax_out_or_null, split_k, ws, ws_bytes, stream, nullptr, nullptr, 1);
+}
+extern "C" int nbp_conv3x3_split_bn_f32_h1(const float* src0, int C0, const float* src1, int C1, int ups, int B, int H, int W,
+                                           const void* w_planes, const void* wamax, int N, const float* scale, const float* shift,
+                                           int relu, float* out, const void* amax_in_or_null, void* amax_out_or_null, int split_k,
+                                           void* ws, size_t ws_bytes, double* bn_part, int* bn_rows, void* stream) {
+    NBP_ENTER();
+    NBP_RETURN_IF(!bn_part || !bn_rows || ((uintptr_t)bn_part & 7), NBP_E_ARG);
+    return conv3x3_split_impl(src0, C0, src1, C1, ups, B, H, W, w_planes, wamax, N, scale, shift, relu, out, amax_in_or_null,
+                              amax_out_or_null, split_k, ws, ws_bytes, stream, bn_part, bn_rows, 1);
 }
 
 // ---- weight gradient of an up_conv layer in parity form (training; wgrad_up_split_kernel)
@@ -2159,9 +2402,8 @@ extern "C" size_t nbp_upconv_wgrad_split_workspace_bytes(int B, int Hs, int Ws, 
 }
 // dW [N][C][3][3] of an up_conv layer from its low-resolution input x [B,Hs,Ws,C] and dy [B,2Hs,2Ws,N]; amax_x / amax_y: the tensors'
 // 64-word max-|.| slots (required).  NBP_E_SHAPE when the low-resolution image does not tile (the caller takes nbp_conv_wgrad_split_f32).
-extern "C" int nbp_upconv_wgrad_split_f32(const float* x, int C, int B, int Hs, int Ws, const float* dy, int N, float* dw,
-                                          const void* amax_x, const void* amax_y, void* ws, size_t ws_bytes, void* stream) {
-    NBP_ENTER();
+static int upconv_wgrad_split_impl(const float* x, int C, int B, int Hs, int Ws, const float* dy, int N, float* dw,
+                                   const void* amax_x, const void* amax_y, void* ws, size_t ws_bytes, void* stream, int one) {
     NBP_RETURN_IF(!x || !dy || !dw || !amax_x || !amax_y || !ws || B < 1, NBP_E_ARG);
     NBP_RETURN_IF(!wgrad_up_ok(Hs, Ws, C, N), NBP_E_SHAPE);
     const long long b0 = (long long)B * Hs * Ws * C * 4, by = (long long)B * 4 * Hs * Ws * N * 4;
@@ -2187,18 +2429,31 @@ extern "C" int nbp_upconv_wgrad_split_f32(const float* x, int C, int B, int Hs, 
         attr_set = true;
     }
     dim3 grid((unsigned)((C / 64) * (N / 64)), (unsigned)splits, 4u);
-    if (wide) wgrad_up_split_kernel<32><<<grid, 256, smem32, st>>>(a);
+    if (one) {          // (half the LDS: [hi][k half] regions)
+        if (wide) wgrad_up_split_kernel<32, true><<<grid, 256, smem32 / 2, st>>>(a);
+        else wgrad_up_split_kernel<16, true><<<grid, 256, smem16 / 2, st>>>(a);
+    } else if (wide) wgrad_up_split_kernel<32><<<grid, 256, smem32, st>>>(a);
     else wgrad_up_split_kernel<16><<<grid, 256, smem16, st>>>(a);
     int rc = nbp_launch_status();
     if (rc) return rc;
     wgrad_up_reduce_kernel<<<nbp_ew_grid((long long)N * C * 9, 256), 256, 0, st>>>(a.part, splits, C, N, dw);
     return nbp_launch_status();
 }
+extern "C" int nbp_upconv_wgrad_split_f32(const float* x, int C, int B, int Hs, int Ws, const float* dy, int N, float* dw,
+                                          const void* amax_x, const void* amax_y, void* ws, size_t ws_bytes, void* stream) {
+    NBP_ENTER();
+    return upconv_wgrad_split_impl(x, C, B, Hs, Ws, dy, N, dw, amax_x, amax_y, ws, ws_bytes, stream, 0);
+}
+extern "C" int nbp_upconv_wgrad_split_f32_h1(const float* x, int C, int B, int Hs, int Ws, const float* dy, int N, float* dw,
+                                             const void* amax_x, const void* amax_y, void* ws, size_t ws_bytes, void* stream) {
+    NBP_ENTER();
+    return upconv_wgrad_split_impl(x, C, B, Hs, Ws, dy, N, dw, amax_x, amax_y, ws, ws_bytes, stream, 1);
+}
 
 // ---- weight gradient of a 1x1 layer on the split scheme (wgrad_1x1_split_kernel): partial sums [splits][C][N] into `part`;
 // the caller reduces them (nbp_train.hip).  C % 64 == 0, N % 4 == 0.
 int nbp_wgrad_1x1_split_launch(const float* x, int C, long long M, const float* dy, int N, int n_tiles, int splits, const unsigned* amax_x,
-                               const unsigned* amax_y, float* part, hipStream_t st) {
+                               const unsigned* amax_y, float* part, hipStream_t st, int one) {
     NBP_RETURN_IF(M * C * 4 >= (1ll << 31) || M * N * 4 >= (1ll << 31), NBP_E_SHAPE);
     WgradSplitArgs a;
     NBP_RETURN_IF(M % 64 != 0, NBP_E_SHAPE);                       // (every level of the network; the kernel counts pixels as H x 64)
@@ -2207,7 +2462,8 @@ int nbp_wgrad_1x1_split_launch(const float* x, int C, long long M, const float* 
     a.co_tiles = (N + 63) / 64; a.n_tiles = n_tiles; a.splits = splits;
     a.amax0 = amax_x; a.amax1 = amax_x; a.amaxy = amax_y; a.part = part;
     dim3 grid((unsigned)((C / 64) * a.co_tiles), (unsigned)splits);
-    wgrad_1x1_split_kernel<<<grid, 256, 8 * 64 * 64, st>>>(a);
+    if (one) wgrad_1x1_split_kernel<true><<<grid, 256, 4 * 64 * 64, st>>>(a);
+    else wgrad_1x1_split_kernel<<<grid, 256, 8 * 64 * 64, st>>>(a);
     return nbp_launch_status();
 }
 
@@ -2245,6 +2501,14 @@ extern "C" int nbp_upconv3x3_split_dgrad_f32(const float* dy, int N, int B, int 
                                          (unsigned*)amax_out_or_null, 0, ws ? (char*)ws + 256 : nullptr, ws_bytes >= 256 ? ws_bytes - 256 : 0,
                                          (hipStream_t)stream);
 }
+extern "C" int nbp_upconv3x3_split_dgrad_f32_h1(const float* dy, int N, int B, int H, int W, const void* planes, const void* wamax, int C,
+                                                const float* scale, const float* shift, float* dx, const void* amax_in, void* amax_out_or_null,
+                                                void* ws, size_t ws_bytes, void* stream) {
+    NBP_ENTER();
+    return nbp_upconv_dgrad_split_launch(dy, N, B, H, W, planes, (const unsigned*)wamax, (const unsigned*)amax_in, C, scale, shift, dx,
+                                         (unsigned*)amax_out_or_null, 0, ws ? (char*)ws + 256 : nullptr, ws_bytes >= 256 ? ws_bytes - 256 : 0,
+                                         (hipStream_t)stream, 1);
+}
 
 // out [M][N] = src [M][C] (1x1 convolution) on the split scheme; w_planes / wamax from nbp_pack_conv_weight_split(ksize = 1),
 // or from nbp_pack_conv1x1_weight_split_dgrad for the data gradient (dx = dy W^T); amax_in: the 64-word max-|src| slot (required).
@@ -2253,6 +2517,13 @@ extern "C" int nbp_conv1x1_split_f32(const float* src, int C, long long M, const
     NBP_ENTER();
     return nbp_conv1x1_split_launch(src, C, M, w_planes, (const unsigned*)wamax, (const unsigned*)amax_in, N, scale, shift, relu, out,
                                     (hipStream_t)stream);
+}
+// planes: nbp_pack_conv_weight_split_h1 (ksize = 1) or nbp_pack_conv1x1_weight_split_dgrad_h1
+extern "C" int nbp_conv1x1_split_f32_h1(const float* src, int C, long long M, const void* w_planes, const void* wamax, int N,
+                                        const float* scale, const float* shift, int relu, float* out, const void* amax_in, void* stream) {
+    NBP_ENTER();
+    return nbp_conv1x1_split_launch(src, C, M, w_planes, (const unsigned*)wamax, (const unsigned*)amax_in, N, scale, shift, relu, out,
+                                    (hipStream_t)stream, 1);
 }
 // planes of w^T for the data gradient of a 1x1 layer w [N][C]: a 1x1 convolution from N (dy's channels) to C
 extern "C" int nbp_pack_conv1x1_weight_split_dgrad(const float* w_nc, int N, int C, void* dst_planes, void* wamax_out, void* stream) {
@@ -2269,16 +2540,53 @@ extern "C" int nbp_pack_conv1x1_weight_split_dgrad(const float* w_nc, int N, int
                                                                        (unsigned short*)dst_planes, 1);
     return nbp_launch_status();
 }
+extern "C" int nbp_pack_conv1x1_weight_split_dgrad_h1(const float* w_nc, int N, int C, void* dst_planes, void* wamax_out, void* stream) {
+    NBP_ENTER();
+    NBP_RETURN_IF(!w_nc || !dst_planes || !wamax_out, NBP_E_ARG);
+    NBP_RETURN_IF(N < 32 || N % 32 || C < 32 || C % 32, NBP_E_SHAPE);
+    hipStream_t st = (hipStream_t)stream;
+    const long long total = (long long)N * C;
+    hipError_t e = hipMemsetAsync(wamax_out, 0, sizeof(unsigned), st);
+    if (e != hipSuccess) return (int)e;
+    amax_kernel<<<min(nbp_ew_grid(total, 256), 256), 256, 0, st>>>(w_nc, total, nullptr, C, (unsigned*)wamax_out, 1u);
+    pack_conv_weight_h2_kernel<true><<<nbp_ew_grid(total, 256), 256, 0, st>>>(w_nc, C, N, 1, nullptr, 0, (const unsigned*)wamax_out,
+                                                                             (unsigned short*)dst_planes, 1);
+    return nbp_launch_status();
+}
 
 extern "C" int nbp_pack_upconv_weight_split(const float* w_oihw, int N, int C, void* dst_planes, void* wamax_out, void* stream) {
     NBP_ENTER();
     return nbp_pack_upconv_weight_split_launch(w_oihw, N, C, dst_planes, (unsigned*)wamax_out, (hipStream_t)stream);
 }
+extern "C" int nbp_pack_upconv_weight_split_h1(const float* w_oihw, int N, int C, void* dst_planes, void* wamax_out, void* stream) {
+    NBP_ENTER();
+    NBP_RETURN_IF(!w_oihw || !dst_planes || !wamax_out, NBP_E_ARG);
+    NBP_RETURN_IF(N < 1 || C < 16 || C % 16, NBP_E_SHAPE);
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipMemsetAsync(wamax_out, 0, sizeof(unsigned), st);
+    if (e != hipSuccess) return (int)e;
+    const long long NC = (long long)N * C;
+    pack_upconv_h2_kernel<true><<<min(nbp_ew_grid(NC, 256), 256), 256, 0, st>>>(w_oihw, N, C, (unsigned*)wamax_out, nullptr);
+    pack_upconv_h2_kernel<true><<<nbp_ew_grid(NC, 256), 256, 0, st>>>(w_oihw, N, C, (unsigned*)wamax_out, (unsigned short*)dst_planes);
+    return nbp_launch_status();
+}
+extern "C" int nbp_pack_upconv_weight_split_dgrad_h1(const float* w_oihw, int N, int C, void* dst_planes, void* wamax_out, void* stream) {
+    NBP_ENTER();
+    NBP_RETURN_IF(!w_oihw || !dst_planes || !wamax_out, NBP_E_ARG);
+    NBP_RETURN_IF(N < 16 || N % 16 || C < 1, NBP_E_SHAPE);
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipMemsetAsync(wamax_out, 0, sizeof(unsigned), st);
+    if (e != hipSuccess) return (int)e;
+    const long long NC = (long long)N * C;
+    pack_upconv_dgrad_h2_kernel<true><<<min(nbp_ew_grid(NC, 256), 256), 256, 0, st>>>(w_oihw, N, C, (unsigned*)wamax_out, nullptr);
+    pack_upconv_dgrad_h2_kernel<true><<<nbp_ew_grid(NC, 256), 256, 0, st>>>(w_oihw, N, C, (unsigned*)wamax_out, (unsigned short*)dst_planes);
+    return nbp_launch_status();
+}
 
 static int upconv3x3_split_impl(const float* src, int C, int B, int H, int W, const void* planes_up, const void* wamax_up,
                                 int N, const float* scale, const float* shift, int relu, float* out,
                                 const void* amax_in_or_null, void* amax_out_or_null, int split_k, void* ws, size_t ws_bytes,
-                                void* stream, double* bn_part, int* bn_rows) {
+                                void* stream, double* bn_part, int* bn_rows, int one = 0) {
     NBP_RETURN_IF(!ws || ws_bytes < 256 || !src || !planes_up || !wamax_up, NBP_E_WS);
     NBP_RETURN_IF((H | W) & 1, NBP_E_SHAPE);
     hipStream_t st = (hipStream_t)stream;
@@ -2299,7 +2607,7 @@ static int upconv3x3_split_impl(const float* src, int C, int B, int H, int W, co
     ConvOperandsSplit o{src, nullptr, planes_up, scale, shift, out, amax, amax, (const unsigned*)wamax_up, (unsigned*)amax_out_or_null,
                         planes_up, (const unsigned*)wamax_up};
     return nbp_conv_split_launch_g(o, nullptr, C, 0, 1, B, H, W, 3, N, relu, split_k, (char*)ws + 256, ws_bytes - 256, st, nullptr, nullptr,
-                                   nullptr, nullptr, bn_part, bn_rows);
+                                   nullptr, nullptr, bn_part, bn_rows, one);
 }
 extern "C" int nbp_upconv3x3_split_f32(const float* src, int C, int B, int H, int W, const void* planes_up, const void* wamax_up,
                                        int N, const float* scale, const float* shift, int relu, float* out,
@@ -2317,4 +2625,21 @@ extern "C" int nbp_upconv3x3_split_bn_f32(const float* src, int C, int B, int H,
     NBP_RETURN_IF(!bn_part || !bn_rows || ((uintptr_t)bn_part & 7), NBP_E_ARG);
     return upconv3x3_split_impl(src, C, B, H, W, planes_up, wamax_up, N, scale, shift, relu, out, amax_in_or_null, amax_out_or_null, split_k,
                                 ws, ws_bytes, stream, bn_part, bn_rows);
+}
+extern "C" int nbp_upconv3x3_split_f32_h1(const float* src, int C, int B, int H, int W, const void* planes_up, const void* wamax_up,
+                                          int N, const float* scale, const float* shift, int relu, float* out,
+                                          const void* amax_in_or_null, void* amax_out_or_null, int split_k, void* ws, size_t ws_bytes,
+                                          void* stream) {
+    NBP_ENTER();
+    return upconv3x3_split_impl(src, C, B, H, W, planes_up, wamax_up, N, scale, shift, relu, out, amax_in_or_null, amax_out_or_null, split_k,
+                                ws, ws_bytes, stream, nullptr, nullptr, 1);
+}
+extern "C" int nbp_upconv3x3_split_bn_f32_h1(const float* src, int C, int B, int H, int W, const void* planes_up, const void* wamax_up,
+                                             int N, const float* scale, const float* shift, int relu, float* out,
+                                             const void* amax_in_or_null, void* amax_out_or_null, int split_k, void* ws, size_t ws_bytes,
+                                             double* bn_part, int* bn_rows, void* stream) {
+    NBP_ENTER();
+    NBP_RETURN_IF(!bn_part || !bn_rows || ((uintptr_t)bn_part & 7), NBP_E_ARG);
+    return upconv3x3_split_impl(src, C, B, H, W, planes_up, wamax_up, N, scale, shift, relu, out, amax_in_or_null, amax_out_or_null, split_k,
+                                ws, ws_bytes, stream, bn_part, bn_rows, 1);
 }

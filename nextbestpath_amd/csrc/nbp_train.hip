@@ -1964,18 +1964,18 @@ extern "C" int nbp_conv_first_wgrad_f32(const float* x_nchw, int B, int H, int W
 
 // (nbp_split.hip)
 int nbp_wgrad_1x1_split_launch(const float* x, int C, long long M, const float* dy, int N, int n_tiles, int splits, const unsigned* amax_x,
-                               const unsigned* amax_y, float* part, hipStream_t st);
+                               const unsigned* amax_y, float* part, hipStream_t st, int one);
 int nbp_wgrad_split_launch(const float* src0, int C0, const float* src1, int C1, int ups, int B, int H, int W, const float* dy, int N,
                            int n_tiles, int splits, unsigned* amax3, const unsigned* amax0_in, const unsigned* amax1_in,
-                           const unsigned* amaxy_in, float* part, hipStream_t st);
+                           const unsigned* amaxy_in, float* part, hipStream_t st, int one);
 
 // The same gradient with the products on the fp16 matrix pipe (two-piece operands, three exact MFMAs per product, fp32
 // accumulation; nbp_split.hip: wgrad_split_kernel) for the 3x3 layers the halo-tile form takes; everything else falls through
 // to nbp_conv_wgrad_f32.  Workspace: nbp_conv_wgrad_workspace_bytes (it includes the 768 B of max-|.| scratch).
-extern "C" int nbp_conv_wgrad_split_f32(const float* src0, int C0, const float* src1, int C1, int ups, int B, int H, int W,
-                                        int ksize, const float* dy, int N, int c_real, int n_real, float* dw,
-                                        const void* amax0_or_null, const void* amax1_or_null, const void* amaxy_or_null, void* ws,
-                                        size_t ws_bytes, void* stream) {
+static int conv_wgrad_split_impl(const float* src0, int C0, const float* src1, int C1, int ups, int B, int H, int W,
+                                 int ksize, const float* dy, int N, int c_real, int n_real, float* dw,
+                                 const void* amax0_or_null, const void* amax1_or_null, const void* amaxy_or_null, void* ws,
+                                 size_t ws_bytes, void* stream, int one) {
     const bool wide = wgrad_halo_ok(H, W, ksize), narrow = !wide && ksize == 3 && H >= 4 && W >= 16 && !(H & 3) && !(W & 15);
     const bool take = ksize == 3 && (wide || narrow) && (long long)B * H * W * N * 4 < (1ll << 31) && src0 && dy && dw &&
                       ws && B >= 1 && C0 >= 64 && C0 % 64 == 0 && C1 >= 0 && C1 % 64 == 0 && N >= 64 && N % 64 == 0 &&
@@ -1994,13 +1994,12 @@ extern "C" int nbp_conv_wgrad_split_f32(const float* src0, int C0, const float* 
             float* part = (float*)(((uintptr_t)ws + 255) / 256 * 256);
             hipStream_t st1 = (hipStream_t)stream;
             int rc = nbp_wgrad_1x1_split_launch(src0, C0, M1, dy, N, n_tiles, (int)sp, (const unsigned*)amax0_or_null,
-                                                (const unsigned*)amaxy_or_null, part, st1);
+                                                (const unsigned*)amaxy_or_null, part, st1, one);
             if (rc) return rc;
             return wgrad_reduce_launch(part, (int)sp, 1, C0, N, c_real, n_real, dw, part + (size_t)sp * C0 * N, st1);
         }
     }
     if (!take) return nbp_conv_wgrad_f32(src0, C0, src1, C1, ups, B, H, W, ksize, dy, N, c_real, n_real, dw, ws, ws_bytes, stream);
-    NBP_ENTER();
     NBP_RETURN_IF(c_real < 1 || c_real > C0 + C1 || n_real < 1 || n_real > N, NBP_E_ARG);
     int n_tiles, splits;
     wgrad_halo_plan(B, wide ? H : H / 2, wide ? W : W * 2, C0 + C1, N, &n_tiles, &splits);      // 64-pixel tiles either way
@@ -2009,11 +2008,29 @@ extern "C" int nbp_conv_wgrad_split_f32(const float* src0, int C0, const float* 
     unsigned* amax3 = (unsigned*)(((uintptr_t)ws + 255) / 256 * 256);
     float* part = (float*)((char*)amax3 + 1024);
     int rc = nbp_wgrad_split_launch(src0, C0, src1, C1, ups, B, H, W, dy, N, n_tiles, splits, amax3, (const unsigned*)amax0_or_null,
-                                    (const unsigned*)amax1_or_null, (const unsigned*)amaxy_or_null, part, st);
+                                    (const unsigned*)amax1_or_null, (const unsigned*)amaxy_or_null, part, st, one);
     if (rc) return rc;
     float* tmp = part + (size_t)splits * 9 * (C0 + C1) * N;
     const bool room = ws_bytes >= (size_t)(splits + WGRAD_REDUCE_GROUPS) * 9 * (C0 + C1) * N * sizeof(float) + 256 + 1024;
     return wgrad_reduce_launch(part, splits, 9, C0 + C1, N, c_real, n_real, dw, room ? tmp : nullptr, st);
+}
+extern "C" int nbp_conv_wgrad_split_f32(const float* src0, int C0, const float* src1, int C1, int ups, int B, int H, int W,
+                                        int ksize, const float* dy, int N, int c_real, int n_real, float* dw,
+                                        const void* amax0_or_null, const void* amax1_or_null, const void* amaxy_or_null, void* ws,
+                                        size_t ws_bytes, void* stream) {
+    NBP_ENTER();
+    return conv_wgrad_split_impl(src0, C0, src1, C1, ups, B, H, W, ksize, dy, N, c_real, n_real, dw, amax0_or_null, amax1_or_null,
+                                 amaxy_or_null, ws, ws_bytes, stream, 0);
+}
+// The one-piece form (wgrad_split_kernel / wgrad_1x1_split_kernel with ONE: hi = fp16(s x) alone, one MFMA per product) of the
+// layers the split kernels take; the rest falls through to nbp_conv_wgrad_f32 exactly as above.
+extern "C" int nbp_conv_wgrad_split_f32_h1(const float* src0, int C0, const float* src1, int C1, int ups, int B, int H, int W,
+                                           int ksize, const float* dy, int N, int c_real, int n_real, float* dw,
+                                           const void* amax0_or_null, const void* amax1_or_null, const void* amaxy_or_null, void* ws,
+                                           size_t ws_bytes, void* stream) {
+    NBP_ENTER();
+    return conv_wgrad_split_impl(src0, C0, src1, C1, ups, B, H, W, ksize, dy, N, c_real, n_real, dw, amax0_or_null, amax1_or_null,
+                                 amaxy_or_null, ws, ws_bytes, stream, 1);
 }
 
 extern "C" int nbp_gather_values_f32(const float* out1_nchw, const long long* coords_bcxy, int K, int C, int H, int W, float* pred,

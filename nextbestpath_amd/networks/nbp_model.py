@@ -115,6 +115,12 @@ class NBP(nn.Module):
         #   "bf16"       bf16 activations and weights (BASELINE configs[4]).
         # All but "bf16" meet the 1e-4 parity bar.  NBP_TUNING=1 NBP_CONV_PRECISION=... overrides the default (A/B measurements).
         self.conv_precision = _lib.tune("NBP_CONV_PRECISION", "fp32_split")
+        # train-mode arithmetic of the convolutions the split kernels take (networks/training.py, read once per training forward):
+        #   "fp32_split" (default) the eval path's three exact fp16 MFMAs per fp32 product;
+        #   "fp16"       scaled fp16 mixed precision: each operand scaled by its tensor's power of two (max |x| in [2^14, 2^15))
+        #                and rounded once to fp16, ONE MFMA per product, fp32 accumulation, fp32 epilogues / master weights / AdamW.
+        # Eval mode (conv_precision) is not affected.
+        self.train_precision = "fp32_split"
 
     # ------------------------------------------------------------------ packing
     def _state_key(self):

@@ -83,12 +83,24 @@ def _igemm(src0, src1, ups, wpk, N, ksize, scale, shift, relu):
 _SPLIT = _lib.tune("NBP_TRAIN_SPLIT", "1") != "0"
 _WGRAD_SPLIT = _lib.tune("NBP_TRAIN_WGRAD_SPLIT", "1") == "1"      # A/B: weight gradients on the fp32 pipe
 
+# Training arithmetic of the layers the split kernels take (NBP.train_precision, read once per forward_train and carried in every
+# ConvFn's context): "fp32_split" = two fp16 pieces per operand, three exact MFMAs per product; "fp16" = the one-piece forms
+# (csrc/nbp_split.hip, ONE; the "_h1" entry points): hi = fp16(s x) with the same per-tensor power-of-two scale, ONE MFMA per product,
+# fp32 accumulation, fp32 epilogues -- scaled-fp16 mixed precision.  Every other layer (Conv1.conv.0, Final1, the psi / Final2 row
+# dots, BatchNorm, loss, AdamW) keeps its fp32 arithmetic in both modes.
+TRAIN_PRECISIONS = ("fp32_split", "fp16")
+
+
+def _fn(name, one):
+    """Entry point `name` of the library, or its one-piece ("_h1") form."""
+    return getattr(_lib.lib(), name + "_h1" if one else name)
+
 
 def _split_ok(H, W, N, ksize):
     return _SPLIT and ksize == 3 and H % 16 == 0 and ((W % 32 == 0 and N % 64 == 0) or (W % 16 == 0 and N % 128 == 0))
 
 
-def _pack_split(w_oihw, n_pad, c_total):
+def _pack_split(w_oihw, n_pad, c_total, one=False):
     """OIHW fp32 [N, C, 3, 3] -> (hi/lo fp16 planes for N padded to n_pad rows and C to c_total channels, max |w| word)."""
     N, C, k, _ = w_oihw.shape
     # the pack kernel writes every plane entry of the channels it is given: only padded channels need the zero fill
@@ -100,8 +112,8 @@ def _pack_split(w_oihw, n_pad, c_total):
         wp = torch.zeros(n_pad, C, k, k, dtype=torch.float32, device=w_oihw.device)
         wp[:N] = w_oihw
         w_oihw = wp
-    _chk(_lib.lib().nbp_pack_conv_weight_split_prezeroed(_lib.ptr(w_oihw), n_pad, C, 3, c_total, _lib.ptr(planes), _lib.ptr(wamax),
-                                                         _st()), "pack_split")
+    _chk(_fn("nbp_pack_conv_weight_split_prezeroed", one)(_lib.ptr(w_oihw), n_pad, C, 3, c_total, _lib.ptr(planes), _lib.ptr(wamax),
+                                                          _st()), "pack_split")
     return planes, wamax
 
 
@@ -193,7 +205,7 @@ def _bn_part(out):
     return torch.empty(_lib.lib().nbp_conv_bn_part_rows(B, H, W) * 2 * N, dtype=torch.float64, device=out.device), ctypes.c_int(0)
 
 
-def _conv_split(src0, src1, ups, packed, N, scale, shift, relu, amax=None, bn=False):
+def _conv_split(src0, src1, ups, packed, N, scale, shift, relu, amax=None, bn=False, one=False):
     L = _lib.lib()
     planes, wamax = packed
     B, Hs, Ws, C0 = src0.shape
@@ -204,13 +216,13 @@ def _conv_split(src0, src1, ups, packed, N, scale, shift, relu, amax=None, bn=Fa
     # max |x| of the inputs: the caller's slot, else taken inside the call (autograd hands tensors over without their history)
     if bn:      # the BatchNorm behind this layer gets the column sums of the output from the epilogue (when the launch has them)
         part, rows = _bn_part(out)
-        _chk(L.nbp_conv3x3_split_bn_f32(_lib.ptr(src0), C0, _lib.ptr(src1), C1, int(ups), B, H, W, _lib.ptr(planes), _lib.ptr(wamax), N,
+        _chk(_fn("nbp_conv3x3_split_bn_f32", one)(_lib.ptr(src0), C0, _lib.ptr(src1), C1, int(ups), B, H, W, _lib.ptr(planes), _lib.ptr(wamax), N,
                                         _lib.ptr(scale), _lib.ptr(shift), int(relu), _lib.ptr(out), _lib.ptr(amax), None, _TRAIN_SK, _lib.ptr(ws),
                                         ws.numel(), _lib.ptr(part), ctypes.byref(rows), _st()), "conv3x3_split_bn")
         if rows.value > 0:
             _note(out, bnpart=(part, rows.value))
         return out
-    _chk(L.nbp_conv3x3_split_f32(_lib.ptr(src0), C0, _lib.ptr(src1), C1, int(ups), B, H, W, _lib.ptr(planes), _lib.ptr(wamax), N,
+    _chk(_fn("nbp_conv3x3_split_f32", one)(_lib.ptr(src0), C0, _lib.ptr(src1), C1, int(ups), B, H, W, _lib.ptr(planes), _lib.ptr(wamax), N,
                                  _lib.ptr(scale), _lib.ptr(shift), int(relu), _lib.ptr(out), _lib.ptr(amax), None, _TRAIN_SK, _lib.ptr(ws),
                                  ws.numel(), _st()), "conv3x3_split")
     return out
@@ -226,11 +238,11 @@ def _conv1x1_ok(M, C, N, c_real):
     return _SPLIT and _SPLIT_1X1 and C % 32 == 0 and N % 32 == 0 and c_real == C and M * C * 4 < 2 ** 31 and N * C * 4 < 2 ** 31
 
 
-def _conv1x1_split(x, planes, wamax, N, scale, shift, amax):
+def _conv1x1_split(x, planes, wamax, N, scale, shift, amax, one=False):
     """x [B,H,W,C] -> [B,H,W,N] through the 1x1 split kernel; amax = the 64-word max-|x| slot."""
     B, H, W, C = x.shape
     out = torch.empty(B, H, W, N, dtype=torch.float32, device=x.device)
-    _chk(_lib.lib().nbp_conv1x1_split_f32(_lib.ptr(x), C, B * H * W, _lib.ptr(planes), _lib.ptr(wamax), N, _lib.ptr(scale),
+    _chk(_fn("nbp_conv1x1_split_f32", one)(_lib.ptr(x), C, B * H * W, _lib.ptr(planes), _lib.ptr(wamax), N, _lib.ptr(scale),
                                           _lib.ptr(shift), 0, _lib.ptr(out), _lib.ptr(amax), _st()), "conv1x1_split")
     return out
 
@@ -247,7 +259,7 @@ def _upconv_ok(Hs, Ws, N):
     return _SPLIT and Hs % 16 == 0 and ((Ws % 32 == 0 and N % 64 == 0) or (Ws % 16 == 0 and N % 128 == 0))
 
 
-def _upconv_split(src, w_oihw, n_pad, scale, shift, amax=None, bn=False, pre=None):
+def _upconv_split(src, w_oihw, n_pad, scale, shift, amax=None, bn=False, pre=None, one=False):
     L = _lib.lib()
     N, C, _, _ = w_oihw.shape
     B, Hs, Ws, C0 = src.shape
@@ -260,19 +272,19 @@ def _upconv_split(src, w_oihw, n_pad, scale, shift, amax=None, bn=False, pre=Non
             w_oihw = wp
         planes = torch.empty(4 * (C0 // 16) * 4 * 4 * n_pad * 8, dtype=torch.int16, device=src.device)
         wamax = torch.empty(1, dtype=torch.int32, device=src.device)             # zeroed by the pack launch itself
-        _chk(L.nbp_pack_upconv_weight_split(_lib.ptr(w_oihw), n_pad, C0, _lib.ptr(planes), _lib.ptr(wamax), _st()), "pack_upconv")
+        _chk(_fn("nbp_pack_upconv_weight_split", one)(_lib.ptr(w_oihw), n_pad, C0, _lib.ptr(planes), _lib.ptr(wamax), _st()), "pack_upconv")
     H, W = 2 * Hs, 2 * Ws
     out = torch.empty(B, H, W, n_pad, dtype=torch.float32, device=src.device)
     ws = _ws(L.nbp_conv_split_planned_workspace_bytes_k(B, H, W, C0, n_pad, 1, _TRAIN_SK, None), src.device)
     if bn:
         part, rows = _bn_part(out)
-        _chk(L.nbp_upconv3x3_split_bn_f32(_lib.ptr(src), C0, B, H, W, _lib.ptr(planes), _lib.ptr(wamax), n_pad, _lib.ptr(scale),
+        _chk(_fn("nbp_upconv3x3_split_bn_f32", one)(_lib.ptr(src), C0, B, H, W, _lib.ptr(planes), _lib.ptr(wamax), n_pad, _lib.ptr(scale),
                                           _lib.ptr(shift), 0, _lib.ptr(out), _lib.ptr(amax), None, _TRAIN_SK, _lib.ptr(ws), ws.numel(),
                                           _lib.ptr(part), ctypes.byref(rows), _st()), "upconv3x3_split_bn")
         if rows.value > 0:
             _note(out, bnpart=(part, rows.value))
         return out
-    _chk(L.nbp_upconv3x3_split_f32(_lib.ptr(src), C0, B, H, W, _lib.ptr(planes), _lib.ptr(wamax), n_pad, _lib.ptr(scale),
+    _chk(_fn("nbp_upconv3x3_split_f32", one)(_lib.ptr(src), C0, B, H, W, _lib.ptr(planes), _lib.ptr(wamax), n_pad, _lib.ptr(scale),
                                    _lib.ptr(shift), 0, _lib.ptr(out), _lib.ptr(amax), None, _TRAIN_SK, _lib.ptr(ws), ws.numel(), _st()), "upconv3x3_split")
     return out
 
@@ -302,8 +314,9 @@ def _prepack_layers(net):
     return out
 
 
-def _prepack_run(net, dev):
-    """Packs every layer's weights for this step; returns the lookup table (None: switched off / nothing to pack)."""
+def _prepack_run(net, dev, one=False):
+    """Packs every layer's weights for this step (one: the one-plane layouts of the "fp16" mode); returns the lookup table (None:
+    switched off / nothing to pack)."""
     import numpy as np
     if not (_PREPACK and _SPLIT):
         return None
@@ -315,7 +328,7 @@ def _prepack_run(net, dev):
     # parameter whose storage was replaced and later landed on the same address with another shape must not reuse stale N / C;
     # ADVICE r05).  Assumptions documented beside ctx.pre: one stream, and weights unchanged between a forward and ITS backward
     # (an optimizer step comes after the backward; the next forward re-packs into the same persistent planes).
-    key = (str(dev),) + tuple((w.data_ptr(), tuple(w.shape), str(w.dtype), w.untyped_storage().data_ptr(), w.numel()) for w, *_ in layers)
+    key = (str(dev), bool(one)) + tuple((w.data_ptr(), tuple(w.shape), str(w.dtype), w.untyped_storage().data_ptr(), w.numel()) for w, *_ in layers)
     tab = _PRE_CACHE.get(key)
     if tab is None:
         while len(_PRE_CACHE) >= 2:                    # (two networks at most -- e.g. a trained and a frozen copy: the buffers are
@@ -335,7 +348,7 @@ def _prepack_run(net, dev):
             keep.append((w, w.untyped_storage()))      # the storages themselves, not only the Parameter objects
         descs = torch.from_numpy(rec.view(np.uint8).copy()).to(dev)
         tab = _PRE_CACHE[key] = {"descs": descs, "wamax": wamax, "look": look, "n": n, "keep": keep}
-    _chk(L.nbp_prepack_weights_split(_lib.ptr(tab["descs"]), tab["n"], _lib.ptr(tab["wamax"]), _st()), "prepack")
+    _chk(_fn("nbp_prepack_weights_split", one)(_lib.ptr(tab["descs"]), tab["n"], _lib.ptr(tab["wamax"]), _st()), "prepack")
     return tab["look"]
 
 
@@ -349,10 +362,11 @@ def _prepacked(w, kind, N, C):
 
 class ConvFn(torch.autograd.Function):
     """y = conv_k(cat(x0, x1) [x2 nearest-upsampled]) + bias; weight OIHW [N, c_real, k, k].
-    x0 / x1 channel counts are multiples of 64 (c_real < C0 only for the zero-padded network input)."""
+    x0 / x1 channel counts are multiples of 64 (c_real < C0 only for the zero-padded network input).
+    one: the one-piece ("fp16") forms of the split kernels, for this layer's forward and backward alike."""
 
     @staticmethod
-    def forward(ctx, x0, x1, weight, bias, ups, bn_next=False):
+    def forward(ctx, x0, x1, weight, bias, ups, bn_next=False, one=False):
         L = _lib.lib()
         N, c_real, k, _ = weight.shape
         C0 = x0.shape[3]
@@ -383,13 +397,13 @@ class ConvFn(torch.autograd.Function):
         if ups and k == 3 and x1 is None and _upconv_ok(x0.shape[1], x0.shape[2], Np):
             xmax = _amax_slot(x0)
             pre = _prepacked(w, 2, N, c_real) if (N == Np and c_real == C0) else None
-            y = _upconv_split(x0, w, Np, scale, shift, xmax, bn, pre)
+            y = _upconv_split(x0, w, Np, scale, shift, xmax, bn, pre, one)
         elif _split_ok(H, W, Np, k):
             xmax = _amax_slot(x0, x1)
             pre = _prepacked(w, 0, N, c_real) if (N == Np and c_real == Ctot) else None
-            packed = (pre[3], pre[5]) if pre is not None else _pack_split(w, Np, Ctot)
+            packed = (pre[3], pre[5]) if pre is not None else _pack_split(w, Np, Ctot, one)
             wmax_fwd = packed[1]                       # max |w|: the data gradient's planes hold the same values
-            y = _conv_split(x0, x1, ups, packed, Np, scale, shift, False, xmax, bn)
+            y = _conv_split(x0, x1, ups, packed, Np, scale, shift, False, xmax, bn, one)
         elif one_by_one:
             xmax = _amax_slot(x0)
             pre = _prepacked(w, 1, N, C0)
@@ -398,8 +412,9 @@ class ConvFn(torch.autograd.Function):
             else:
                 planes = torch.empty(C0 // 16 * 4 * N * 8, dtype=torch.int16, device=dev)
                 wamax = torch.empty(1, dtype=torch.int32, device=dev)
-                _chk(L.nbp_pack_conv_weight_split(_lib.ptr(w), N, C0, 1, None, 0, C0, _lib.ptr(planes), _lib.ptr(wamax), _st()), "pack_split_1x1")
-            y = _conv1x1_split(x0, planes, wamax, N, scale, shift, xmax)
+                _chk(_fn("nbp_pack_conv_weight_split", one)(_lib.ptr(w), N, C0, 1, None, 0, C0, _lib.ptr(planes), _lib.ptr(wamax), _st()),
+                     "pack_split_1x1")
+            y = _conv1x1_split(x0, planes, wamax, N, scale, shift, xmax, one)
         else:
             wpk = torch.empty(Ctot // 32 * k * k * Np * 32, dtype=torch.float32, device=dev)
             _chk(L.nbp_pack_conv_weight_padded(_lib.ptr(w), N, c_real, k, Ctot, Np, _lib.ptr(wpk), _st()), "pack_fwd")
@@ -408,6 +423,7 @@ class ConvFn(torch.autograd.Function):
         ctx.xmax = xmax
         ctx.wmax_fwd = wmax_fwd
         ctx.pre = pre
+        ctx.one = bool(one)
         ctx.meta = (N, c_real, k, C0, C1, Np, bool(ups), x1 is not None, one_by_one)
         return _slice_channels(y, 0, N)
 
@@ -417,6 +433,7 @@ class ConvFn(torch.autograd.Function):
         x0, x1, w = ctx.saved_tensors
         N, c_real, k, C0, C1, Np, ups, has1, one_by_one = ctx.meta
         x1 = x1 if has1 else None
+        one = ctx.one
         dev = dy.device
         info = _noted(dy, "colsum") if dy.is_contiguous() else None       # (max-|dy| slot, column sums): this very tensor's
         dy_note = getattr(dy, "_nbp_note", None)
@@ -444,13 +461,13 @@ class ConvFn(torch.autograd.Function):
         if wsu:
             dymax = info[0] if info is not None else _amax_slot(dy)
             wsb = _ws(wsu, dev)
-            _chk(L.nbp_upconv_wgrad_split_f32(_lib.ptr(x0), C0, B, H // 2, W // 2, _lib.ptr(dy), Np, _lib.ptr(dw), _lib.ptr(ctx.xmax),
+            _chk(_fn("nbp_upconv_wgrad_split_f32", one)(_lib.ptr(x0), C0, B, H // 2, W // 2, _lib.ptr(dy), Np, _lib.ptr(dw), _lib.ptr(ctx.xmax),
                                               _lib.ptr(dymax), _lib.ptr(wsb), wsb.numel(), _st()), "upconv_wgrad_split")
         elif _SPLIT and _WGRAD_SPLIT:
             # max |dy|: shared with the data gradient below; measured by the BatchNorm backward when dy came from one (padding
             # channels are zeros: same maximum)
             dymax = (info[0] if info is not None else _amax_slot(dy)) if (k == 3 or one_by_one) else None
-            _chk(L.nbp_conv_wgrad_split_f32(_lib.ptr(x0), C0, _lib.ptr(x1), C1, int(ups), B, H, W, k, _lib.ptr(dyw), Nw, c_real, N,
+            _chk(_fn("nbp_conv_wgrad_split_f32", one)(_lib.ptr(x0), C0, _lib.ptr(x1), C1, int(ups), B, H, W, k, _lib.ptr(dyw), Nw, c_real, N,
                                             _lib.ptr(dw), _lib.ptr(ctx.xmax), _lib.ptr(ctx.xmax), _lib.ptr(dymax), _lib.ptr(ws),
                                             ws.numel(), _st()), "conv_wgrad_split")
         else:
@@ -459,7 +476,7 @@ class ConvFn(torch.autograd.Function):
         dx0 = dx1 = None
         if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
             Ctot = C0 + C1
-            one, zero = _const(1.0, Ctot, dev), _const(0.0, Ctot, dev)
+            ones, zero = _const(1.0, Ctot, dev), _const(0.0, Ctot, dev)
             if (ups and k == 3 and not has1 and _UP_DGRAD and N == Np and c_real == C0 and _upconv_ok(H // 2, W // 2, C0)
                     and B * H * W * Np * 4 < 2 ** 31):
                 pre = getattr(ctx, "pre", None)
@@ -468,15 +485,15 @@ class ConvFn(torch.autograd.Function):
                 else:
                     planes = torch.empty(32 * Np * C0, dtype=torch.int16, device=dev)
                     wamax = torch.empty(1, dtype=torch.int32, device=dev)
-                    _chk(L.nbp_pack_upconv_weight_split_dgrad(_lib.ptr(w), Np, C0, _lib.ptr(planes), _lib.ptr(wamax), _st()), "pack_upconv_dgrad")
+                    _chk(_fn("nbp_pack_upconv_weight_split_dgrad", one)(_lib.ptr(w), Np, C0, _lib.ptr(planes), _lib.ptr(wamax), _st()), "pack_upconv_dgrad")
                 if dymax is None:
                     dymax = info[0] if info is not None else _amax_slot(dy)
                 dxl = torch.empty(B, H // 2, W // 2, C0, dtype=torch.float32, device=dev)
                 wsd = _ws(L.nbp_upconv_split_dgrad_workspace_bytes(B, H // 2, W // 2, Np, C0), dev)
-                _chk(L.nbp_upconv3x3_split_dgrad_f32(_lib.ptr(dy), Np, B, H // 2, W // 2, _lib.ptr(planes), _lib.ptr(wamax), C0,
-                                                     _lib.ptr(one), _lib.ptr(zero), _lib.ptr(dxl), _lib.ptr(dymax), None, _lib.ptr(wsd),
+                _chk(_fn("nbp_upconv3x3_split_dgrad_f32", one)(_lib.ptr(dy), Np, B, H // 2, W // 2, _lib.ptr(planes), _lib.ptr(wamax), C0,
+                                                     _lib.ptr(ones), _lib.ptr(zero), _lib.ptr(dxl), _lib.ptr(dymax), None, _lib.ptr(wsd),
                                                      wsd.numel(), _st()), "upconv_dgrad_split")
-                return dxl, None, dw, db, None, None
+                return dxl, None, dw, db, None, None, None
             if one_by_one:
                 # dx = dy W^T: a 1x1 convolution from N to C0 channels on the same kernel
                 pre = getattr(ctx, "pre", None)
@@ -485,10 +502,10 @@ class ConvFn(torch.autograd.Function):
                 else:
                     planes = torch.empty(N // 16 * 4 * C0 * 8, dtype=torch.int16, device=dev)
                     wamax = torch.empty(1, dtype=torch.int32, device=dev)
-                    _chk(L.nbp_pack_conv1x1_weight_split_dgrad(_lib.ptr(w), N, C0, _lib.ptr(planes), _lib.ptr(wamax), _st()), "pack_dgrad_1x1")
+                    _chk(_fn("nbp_pack_conv1x1_weight_split_dgrad", one)(_lib.ptr(w), N, C0, _lib.ptr(planes), _lib.ptr(wamax), _st()), "pack_dgrad_1x1")
                 if dymax is None:
                     dymax = info[0] if info is not None else _amax_slot(dy)
-                dx = _conv1x1_split(dy, planes, wamax, C0, one, zero, dymax)
+                dx = _conv1x1_split(dy, planes, wamax, C0, ones, zero, dymax, one)
             elif _split_ok(H, W, Ctot, k):
                 # dx = conv3x3(dy, w^T with the taps reversed): output channels = the (padded) input channels
                 if c_real == Ctot and N == Np:
@@ -499,20 +516,20 @@ class ConvFn(torch.autograd.Function):
                         wamax = pre[5]
                     elif getattr(ctx, "wmax_fwd", None) is not None:      # the forward's pack of the same weights measured max |w|
                         wamax = ctx.wmax_fwd
-                        _chk(L.nbp_pack_conv_weight_split_dgrad_known(_lib.ptr(w), N, c_real, Np, _lib.ptr(planes), _lib.ptr(wamax), _st()),
+                        _chk(_fn("nbp_pack_conv_weight_split_dgrad_known", one)(_lib.ptr(w), N, c_real, Np, _lib.ptr(planes), _lib.ptr(wamax), _st()),
                              "pack_dgrad_split")
                     else:
                         wamax = torch.empty(1, dtype=torch.int32, device=dev)
-                        _chk(L.nbp_pack_conv_weight_split_dgrad(_lib.ptr(w), N, c_real, Np, _lib.ptr(planes), _lib.ptr(wamax), _st()), "pack_dgrad_split")
+                        _chk(_fn("nbp_pack_conv_weight_split_dgrad", one)(_lib.ptr(w), N, c_real, Np, _lib.ptr(planes), _lib.ptr(wamax), _st()), "pack_dgrad_split")
                     packed = (planes, wamax)
                 else:
                     wt = w.flip(2, 3).permute(1, 0, 2, 3).contiguous()            # [c_real, N, 3, 3]
-                    packed = _pack_split(wt, Ctot, Np)
-                dx = _conv_split(dy, None, False, packed, Ctot, one, zero, False, dymax)
+                    packed = _pack_split(wt, Ctot, Np, one)
+                dx = _conv_split(dy, None, False, packed, Ctot, ones, zero, False, dymax, one=one)
             else:
                 wt = torch.empty(Np // 32 * k * k * Ctot * 32, dtype=torch.float32, device=dev)
                 _chk(L.nbp_pack_conv_weight_dgrad(_lib.ptr(w), N, c_real, k, Ctot, Np, _lib.ptr(wt), _st()), "pack_dgrad")
-                dx = _igemm(dy, None, False, wt, Ctot, k, one, zero, False)        # [B,H,W,Ctot] at output resolution
+                dx = _igemm(dy, None, False, wt, Ctot, k, ones, zero, False)       # [B,H,W,Ctot] at output resolution
             if ups:
                 low = torch.empty(B, H // 2, W // 2, Ctot, dtype=torch.float32, device=dev)
                 _chk(L.nbp_sum2x2_f32(_lib.ptr(dx), B, H // 2, W // 2, Ctot, _lib.ptr(low), _st()), "sum2x2")
@@ -525,7 +542,7 @@ class ConvFn(torch.autograd.Function):
                 dx0, dx1 = _slice_channels(dx, 0, C0), _slice_channels(dx, C0, C1)
             else:
                 dx0 = dx
-        return dx0, dx1, dw, db, None, None
+        return dx0, dx1, dw, db, None, None, None
 
 
 # Conv1.conv.0 straight from the NCHW network input (csrc/nbp_first_conv.h forward, wgrad_first_kernel backward) instead of a
@@ -983,6 +1000,7 @@ def _t(name, y):
 
 
 _NBT = None          # inside forward_train: the BatchNorm layers' num_batches_tracked tensors seen so far
+_ONE = False         # inside forward_train: the net's train_precision is "fp16" (the one-piece kernels)
 
 
 def _bn(mod, x, relu, name=None):
@@ -997,22 +1015,22 @@ def _bn(mod, x, relu, name=None):
 
 def _block(seq, x0, x1=None, name=""):
     """conv_block (ref :8-21): (conv3x3 -> BN -> ReLU) x 2 on cat(x0, x1)."""
-    y = _t(name + ".conv.0", ConvFn.apply(x0, x1, seq[0].weight, seq[0].bias, False, True))
+    y = _t(name + ".conv.0", ConvFn.apply(x0, x1, seq[0].weight, seq[0].bias, False, True, _ONE))
     y = _bn(seq[1], y, True, name + ".conv.1")
-    y = _t(name + ".conv.3", ConvFn.apply(y, None, seq[3].weight, seq[3].bias, False, True))
+    y = _t(name + ".conv.3", ConvFn.apply(y, None, seq[3].weight, seq[3].bias, False, True, _ONE))
     return _bn(seq[4], y, True, name + ".conv.4")
 
 
 def _up_conv(seq, x, name=""):
     """up_conv (ref :23-34): nearest x2 -> conv3x3 -> BN -> ReLU (the upsample is fused in the conv gather)."""
-    y = _t(name + ".up.1", ConvFn.apply(x, None, seq[1].weight, seq[1].bias, True, True))
+    y = _t(name + ".up.1", ConvFn.apply(x, None, seq[1].weight, seq[1].bias, True, True, _ONE))
     return _bn(seq[2], y, True, name + ".up.2")
 
 
 def _gate(att, g, x, name="", x_scale=None):
     """Attention_block (ref :36-62).  x_scale: the alias of x the final x * psi reads (FanOutFn), x itself when None."""
-    gp = _t(name + ".W_g.0", ConvFn.apply(g, None, att.W_g[0].weight, att.W_g[0].bias, False))
-    xp = _t(name + ".W_x.0", ConvFn.apply(x, None, att.W_x[0].weight, att.W_x[0].bias, False))
+    gp = _t(name + ".W_g.0", ConvFn.apply(g, None, att.W_g[0].weight, att.W_g[0].bias, False, False, _ONE))
+    xp = _t(name + ".W_x.0", ConvFn.apply(x, None, att.W_x[0].weight, att.W_x[0].bias, False, False, _ONE))
     if _gate_mid_ok(gp, xp):
         bg, bx = att.W_g[1], att.W_x[1]
         p = GateMidFn.apply(gp, xp, bg.weight, bg.bias, bg.running_mean, bg.running_var, bg.eps, bg.momentum, bx.weight, bx.bias,
@@ -1032,15 +1050,28 @@ def _gate(att, g, x, name="", x_scale=None):
     return _t(name + ".out", RowScaleFn.apply(x if x_scale is None else x_scale, psi))
 
 
+def train_precision_one(net):
+    """True when net.train_precision selects the one-piece kernels ("fp16"), False for "fp32_split"; ValueError otherwise."""
+    prec = getattr(net, "train_precision", "fp32_split")
+    if prec not in TRAIN_PRECISIONS:
+        raise ValueError(f"NBP.train_precision must be one of {TRAIN_PRECISIONS}, got {prec!r}")
+    if prec == "fp16" and not (_SPLIT and _WGRAD_SPLIT):
+        # the A/B switches put the convolutions on the fp32 pipe: "fp16" would silently train in fp32
+        raise RuntimeError('train_precision "fp16" needs the split kernels (NBP_TRAIN_SPLIT / NBP_TRAIN_WGRAD_SPLIT are switched off)')
+    return prec == "fp16"
+
+
 def forward_train(net, x):
     """NBP.forward in train mode (ref :110-160) -> (out1 [B,8,S/4,S/4], out2 [B,1,S,S]) with autograd."""
     L = _lib.lib()
     B, _, S, _ = x.shape
     dev = x.device
+    one = train_precision_one(net)             # (once per forward; every ConvFn carries it to its backward)
     _reset_arena(dev)
-    global _NBT, _PRE
+    global _NBT, _PRE, _ONE
     _NBT = []
-    _PRE = _prepack_run(net, dev) if _observer is None else None
+    _ONE = one
+    _PRE = _prepack_run(net, dev, one) if _observer is None else None
     try:
         return _forward_train(net, x, L, B, S, dev)
     finally:
@@ -1048,6 +1079,7 @@ def forward_train(net, x):
             with torch.no_grad():
                 torch._foreach_add_(_NBT, 1)       # nn.BatchNorm2d's num_batches_tracked += 1 (46 one-element kernels otherwise)
         _NBT = None
+        _ONE = False
         _PRE = None                                # (each layer's context holds its planes for the backward)
 
 
@@ -1057,7 +1089,7 @@ def _forward_train(net, x, L, B, S, dev):
         # the first layer reads the NCHW input itself; the rest of the block as _block
         y = _t("Conv1.conv.0", FirstConvFn.apply(x.contiguous().float(), seq[0].weight, seq[0].bias))
         y = _bn(seq[1], y, True, "Conv1.conv.1")
-        y = _t("Conv1.conv.3", ConvFn.apply(y, None, seq[3].weight, seq[3].bias, False, True))
+        y = _t("Conv1.conv.3", ConvFn.apply(y, None, seq[3].weight, seq[3].bias, False, True, _ONE))
         x1 = _bn(seq[4], y, True, "Conv1.conv.4")
     else:
         xh = torch.empty(B, S, S, 5, dtype=torch.float32, device=dev)

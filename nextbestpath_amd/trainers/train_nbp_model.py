@@ -225,7 +225,8 @@ def _mean_over_ranks(x: float, device) -> float:
 
 
 def train_experience_data(training_set_db, params, optimizer, nbp, device, current_epoch):
-    """ref nbp_utils.py:340-395 (GradScaler without autocast is the identity scale for fp32; omitted).  As in the
+    """ref nbp_utils.py:340-395 (GradScaler without autocast is the identity scale for fp32; omitted -- the "fp16"
+    train_precision scales every fp16 operand per tensor instead, NBP.train_precision).  As in the
     reference the early poses (pose_i <= 10) are dropped INSIDE each batch during epoch 1 (:348-362), a batch left empty
     is skipped before the optimiser-step test (:364-365), and the step fires every 8 non-empty batches or on the batch
     that reaches the end of the set (:385).  Under torchrun the ranks agree on "empty" and on the batch count, because
@@ -352,6 +353,9 @@ def run_training_nbp(params):
     torch.cuda.set_device(device)
     random.seed(params.random_seed + rank); np.random.seed(params.random_seed + rank); torch.manual_seed(params.torch_seed)
     nbp = NBP().to(device)
+    # the training step's arithmetic (NBP.train_precision): "fp32_split" or "fp16" (scaled fp16 mixed precision); the
+    # checkpoints are fp32 state_dicts either way
+    nbp.train_precision = getattr(params, "train_precision", "fp32_split")
     nbp, optimizer, best_loss, _ = initialize_nbp(params, nbp, params.torch_seed)
     S = getattr(params, "grid_size", 256)
     os.makedirs(params.output_dir, exist_ok=True)

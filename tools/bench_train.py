@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Config 3 of BASELINE.json: NBP fwd + bwd + AdamW step, batch of 256x256 maps, fp32, 1 MI355X.
-    python tools/bench_train.py [--batch 32] [--steps 5] [--size 256]
+    python tools/bench_train.py [--batch 32] [--steps 5] [--size 256] [--precision fp32_split|fp16]
 Prints one JSON line: train maps/s, TFLOP/s against 546.9 GFLOP/map, and the torch-CPU baseline
 (stock autograd on the same weights = the reference's arithmetic) on a bounded sample."""
 import argparse
@@ -24,10 +24,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--cpu-batch", type=int, default=2)
+    ap.add_argument("--precision", choices=tr.TRAIN_PRECISIONS, default="fp32_split",
+                    help="NBP.train_precision: the split path (default) or scaled fp16 mixed precision")
     a = ap.parse_args()
     dev = torch.device("cuda")
     torch.manual_seed(9)
     net = NBP().to(dev).train()
+    net.train_precision = a.precision
     opt = make_optimizer(net)
     db = make_synthetic_experiences(a.batch, a.size, seed=3)
     xs, gt, coords, gains, bidx = _collate(db, dev)
@@ -69,8 +72,9 @@ def main():
         cpu = {"value": round(nb / cpu_dt, 4), "unit": "maps/s", "cores": torch.get_num_threads(), "kind": "port",
                "sample": f"one fwd+bwd of {nb} maps with torch CPU autograd ({cpu_dt:.1f} s)"}
     print(json.dumps({
-        "metric": "NBP training maps/s (fwd+bwd+AdamW, fp32)", "value": round(a.batch / dt, 3), "unit": "maps/s",
+        "metric": f"NBP training maps/s (fwd+bwd+AdamW, {a.precision})", "value": round(a.batch / dt, 3), "unit": "maps/s",
         "n_gpus": 1, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(dt * 1e3, 2), "dtype": "f32",
+        "train_precision": a.precision,
         "data": "synthetic", "config": {"workload": f"configs[2]: train step, batch {a.batch} x {a.size}x{a.size}"},
         "tflops_reference_formulation": round(a.batch * flop_map / dt / 1e12, 2), "frac_of_split_ceiling_reference_formulation": round(a.batch * flop_map / dt / (2500e12 / 3), 4),
         "loss": float(loss.item()), "producer_notes": dict(tr.HANDOFF_STATS),
