@@ -271,16 +271,9 @@ def ptr(t) -> int:
 _knobs = {}
 # switches that change the ARITHMETIC (results differ beyond reordering): a benchmark line measured with one of them set is
 # not the headline configuration (bench.py refuses to call it `value`)
-NUMERICS_KNOBS = {"NBP_CONV_PRECISION", "NBP_TRAIN_SPLIT", "NBP_TRAIN_WGRAD_SPLIT", "NBP_SPLIT_MAX_K", "NBP_SPLIT_MAX_K_SMALL", "NBP_GATE_PSI",
-                  "NBP_CONV_HEAD", "NBP_BF16_PSI", "NBP_BF16_FUSE", "NBP_TRAIN_FUSE", "NBP_TRAIN_SPLIT_1X1", "NBP_TRAIN_CHAIN_BOUND",
-                  "NBP_TRAIN_UP_DGRAD", "NBP_TRAIN_UP_WGRAD",
-                  #  Conv1.conv.0 on the fp32 MFMA pipe instead of the split scheme -- it flipped a ReLU mask in
-                  # test_full_network_training_step_vs_oracle; the fused AdamW rounds in another order than the foreach form
-                  "NBP_TRAIN_FIRST_CONV", "NBP_TRAIN_FUSED_ADAMW",
-                  # (round 6) the n-ary gradient sums add in another order than autograd's pairwise adds (the fused gate middle,
-                  # NBP_TRAIN_GATE_FUSE, is bit-identical to the separate Functions: not listed)
-                  "NBP_TRAIN_FANOUT"}
-# bit-identical switches (NBP_TRAIN_PREPACK, NBP_STEP_OVERLAP, ...) are not listed here; effective_knobs() reports every switch
+NUMERICS_KNOBS = {"NBP_CONV_PRECISION", "NBP_SPLIT_MAX_K", "NBP_SPLIT_MAX_K_SMALL", "NBP_GATE_PSI", "NBP_CONV_HEAD", "NBP_BF16_PSI",
+                  "NBP_BF16_FUSE"}
+# bit-identical switches (NBP_STEP_OVERLAP, ...) are not listed here; effective_knobs() reports every switch
 # that is off its default, numerics-affecting or not
 
 

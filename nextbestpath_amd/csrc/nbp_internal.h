@@ -74,7 +74,7 @@ struct ConvOperandsSplit {
     const float* psi0 = nullptr;
 };
 ConvPlan nbp_plan_conv_split(long long M, int N, int chunks_total, int split_k, int groups, int H, int W, int ksize, int ups = 0);
-int nbp_pack_upconv_weight_split_launch(const float* w_oihw, int N, int C, void* dst, unsigned* wamax_out, hipStream_t st);
+int nbp_pack_upconv_weight_split_launch(const float* w_oihw, int N, int C, void* dst, unsigned* wamax_out, hipStream_t st, int one = 0);
 // head != null offers the one-channel sigmoid head that alone consumes a 64-channel layer: out1[m] = sigmoid((out[m,:] . w) * scale[0]
 // + shift[0]); *headed tells whether the launch wrote it INSTEAD of `out` -- if not, the caller runs nbp_final_1x1_f32 as before
 struct ConvHead { const float* w; const float* scale; const float* shift; float* out; };
@@ -84,8 +84,9 @@ int nbp_conv_split_launch_g(const ConvOperandsSplit& o, const ConvOperandsSplit*
                             int ksize, int N, int relu, int split_k, void* ws, size_t ws_bytes, hipStream_t st,
                             float* const* pool_out = nullptr, int* pooled = nullptr, const struct ConvHead* head = nullptr,
                             int* headed = nullptr, double* bn_part = nullptr, int* bn_rows = nullptr, int one = 0);
+// one: the one-plane ("_h1") layouts of the training's "fp16" mode
 int nbp_pack_conv_weight_split_launch(const float* w_oihw, int N, int C, int ksize, const float* scale_or_null, int c_off,
-                                      int c_total, void* dst, unsigned* wamax_out, hipStream_t st);
+                                      int c_total, void* dst, unsigned* wamax_out, hipStream_t st, int one = 0);
 int nbp_amax_launch(const float* x, long long n, unsigned* amax_inout, hipStream_t st);
 // 3x3 weight gradient on the split scheme: partial sums [splits][9][C0 + C1][N]; amax3 = 3 x 64 words of scratch
 int nbp_wgrad_split_launch(const float* src0, int C0, const float* src1, int C1, int ups, int B, int H, int W, const float* dy, int N,

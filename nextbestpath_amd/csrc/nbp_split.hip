@@ -1955,7 +1955,7 @@ int nbp_conv_split_launch_g(const ConvOperandsSplit& o, const ConvOperandsSplit*
 
 // wamax_out: device word that receives max |w * scale| (float bits); the planes are scaled by 2^(14 - floor(log2 max))
 int nbp_pack_conv_weight_split_launch(const float* w_oihw, int N, int C, int ksize, const float* scale_or_null, int c_off,
-                                      int c_total, void* dst, unsigned* wamax_out, hipStream_t st) {
+                                      int c_total, void* dst, unsigned* wamax_out, hipStream_t st, int one) {
     NBP_RETURN_IF(!w_oihw || !dst || !wamax_out, NBP_E_ARG);
     NBP_RETURN_IF(ksize != 1 && ksize != 3, NBP_E_ARG);
     NBP_RETURN_IF(N < 1 || C < 1 || c_off != 0 || C > c_total || c_total % 32, NBP_E_SHAPE);   // one scale per layer: one call
@@ -1963,20 +1963,27 @@ int nbp_pack_conv_weight_split_launch(const float* w_oihw, int N, int C, int ksi
     hipError_t e = hipMemsetAsync(wamax_out, 0, sizeof(unsigned), st);
     if (e != hipSuccess) return (int)e;
     amax_kernel<<<min(nbp_ew_grid(total, 256), 256), 256, 0, st>>>(w_oihw, total, scale_or_null, (long long)C * ksize * ksize, wamax_out, 1u);
-    pack_conv_weight_h2_kernel<<<nbp_ew_grid(total, 256), 256, 0, st>>>(w_oihw, N, C, ksize * ksize, scale_or_null, c_off, wamax_out,
-                                                                       (unsigned short*)dst);
+    const int grid = nbp_ew_grid(total, 256);
+    if (one) pack_conv_weight_h2_kernel<true><<<grid, 256, 0, st>>>(w_oihw, N, C, ksize * ksize, scale_or_null, c_off, wamax_out, (unsigned short*)dst);
+    else pack_conv_weight_h2_kernel<<<grid, 256, 0, st>>>(w_oihw, N, C, ksize * ksize, scale_or_null, c_off, wamax_out, (unsigned short*)dst);
     return nbp_launch_status();
 }
 
 // Planes of the four parity filters of an up_conv layer: [parity][chunk][4 taps][plane][k half][N][8 fp16], one max |w| for all.
-int nbp_pack_upconv_weight_split_launch(const float* w_oihw, int N, int C, void* dst, unsigned* wamax_out, hipStream_t st) {
+int nbp_pack_upconv_weight_split_launch(const float* w_oihw, int N, int C, void* dst, unsigned* wamax_out, hipStream_t st, int one) {
     NBP_RETURN_IF(!w_oihw || !dst || !wamax_out, NBP_E_ARG);
     NBP_RETURN_IF(N < 1 || C < 16 || C % 16, NBP_E_SHAPE);
     hipError_t e = hipMemsetAsync(wamax_out, 0, sizeof(unsigned), st);
     if (e != hipSuccess) return (int)e;
     const long long NC = (long long)N * C;
-    pack_upconv_h2_kernel<<<min(nbp_ew_grid(NC, 256), 256), 256, 0, st>>>(w_oihw, N, C, wamax_out, nullptr);
-    pack_upconv_h2_kernel<<<nbp_ew_grid(NC, 256), 256, 0, st>>>(w_oihw, N, C, wamax_out, (unsigned short*)dst);
+    const int grid = nbp_ew_grid(NC, 256);
+    if (one) {
+        pack_upconv_h2_kernel<true><<<min(grid, 256), 256, 0, st>>>(w_oihw, N, C, wamax_out, nullptr);
+        pack_upconv_h2_kernel<true><<<grid, 256, 0, st>>>(w_oihw, N, C, wamax_out, (unsigned short*)dst);
+    } else {
+        pack_upconv_h2_kernel<<<min(grid, 256), 256, 0, st>>>(w_oihw, N, C, wamax_out, nullptr);
+        pack_upconv_h2_kernel<<<grid, 256, 0, st>>>(w_oihw, N, C, wamax_out, (unsigned short*)dst);
+    }
     return nbp_launch_status();
 }
 
@@ -2175,24 +2182,15 @@ extern "C" int nbp_pack_conv_weight_split(const float* w_oihw, int N, int C, int
 extern "C" int nbp_pack_conv_weight_split_h1(const float* w_oihw, int N, int C, int ksize, const float* scale_or_null,
                                              int c_off, int c_total, void* dst_planes, void* wamax_out, void* stream) {
     NBP_ENTER();
-    NBP_RETURN_IF(!w_oihw || !dst_planes || !wamax_out, NBP_E_ARG);
-    NBP_RETURN_IF(ksize != 1 && ksize != 3, NBP_E_ARG);
-    NBP_RETURN_IF(N < 1 || C < 1 || c_off != 0 || C > c_total || c_total % 32, NBP_E_SHAPE);
-    hipStream_t st = (hipStream_t)stream;
-    const long long total = (long long)N * C * ksize * ksize;
-    hipError_t e = hipMemsetAsync(wamax_out, 0, sizeof(unsigned), st);
-    if (e != hipSuccess) return (int)e;
-    amax_kernel<<<min(nbp_ew_grid(total, 256), 256), 256, 0, st>>>(w_oihw, total, scale_or_null, (long long)C * ksize * ksize, (unsigned*)wamax_out, 1u);
-    pack_conv_weight_h2_kernel<true><<<nbp_ew_grid(total, 256), 256, 0, st>>>(w_oihw, N, C, ksize * ksize, scale_or_null, c_off,
-                                                                             (const unsigned*)wamax_out, (unsigned short*)dst_planes);
-    return nbp_launch_status();
+    return nbp_pack_conv_weight_split_launch(w_oihw, N, C, ksize, scale_or_null, c_off, c_total, dst_planes, (unsigned*)wamax_out,
+                                             (hipStream_t)stream, 1);
 }
 
 // Planes of the data-gradient convolution of a 3x3 layer with weights w [N][C][3][3]: dx = conv3x3(dy, w') with
 // w'[c][n][tap] = w[n][c][8 - tap] -- C output rows, N input channels padded to c_total (flip + permute + pack in one launch).
-extern "C" int nbp_pack_conv_weight_split_dgrad(const float* w_oihw, int N, int C, int c_total, void* dst_planes, void* wamax_out,
-                                                void* stream) {
-    NBP_ENTER();
+template <bool ONE>
+static int pack_conv_weight_split_dgrad_impl(const float* w_oihw, int N, int C, int c_total, void* dst_planes, void* wamax_out,
+                                             void* stream) {
     NBP_RETURN_IF(!w_oihw || !dst_planes || !wamax_out, NBP_E_ARG);
     NBP_RETURN_IF(N < 1 || C < 1 || N > c_total || c_total % 32, NBP_E_SHAPE);
     hipStream_t st = (hipStream_t)stream;
@@ -2200,98 +2198,89 @@ extern "C" int nbp_pack_conv_weight_split_dgrad(const float* w_oihw, int N, int 
     hipError_t e = hipMemsetAsync(wamax_out, 0, sizeof(unsigned), st);
     if (e != hipSuccess) return (int)e;
     amax_kernel<<<min(nbp_ew_grid(total, 256), 256), 256, 0, st>>>(w_oihw, total, nullptr, 9ll * C, (unsigned*)wamax_out, 1u);
-    pack_conv_weight_h2_kernel<<<nbp_ew_grid(total, 256), 256, 0, st>>>(w_oihw, C, N, 9, nullptr, 0, (const unsigned*)wamax_out,
-                                                                       (unsigned short*)dst_planes, 1);
+    pack_conv_weight_h2_kernel<ONE><<<nbp_ew_grid(total, 256), 256, 0, st>>>(w_oihw, C, N, 9, nullptr, 0, (const unsigned*)wamax_out,
+                                                                            (unsigned short*)dst_planes, 1);
     return nbp_launch_status();
+}
+extern "C" int nbp_pack_conv_weight_split_dgrad(const float* w_oihw, int N, int C, int c_total, void* dst_planes, void* wamax_out,
+                                                void* stream) {
+    NBP_ENTER();
+    return pack_conv_weight_split_dgrad_impl<false>(w_oihw, N, C, c_total, dst_planes, wamax_out, stream);
 }
 extern "C" int nbp_pack_conv_weight_split_dgrad_h1(const float* w_oihw, int N, int C, int c_total, void* dst_planes, void* wamax_out,
                                                    void* stream) {
     NBP_ENTER();
-    NBP_RETURN_IF(!w_oihw || !dst_planes || !wamax_out, NBP_E_ARG);
-    NBP_RETURN_IF(N < 1 || C < 1 || N > c_total || c_total % 32, NBP_E_SHAPE);
-    hipStream_t st = (hipStream_t)stream;
-    const long long total = (long long)N * C * 9;
-    hipError_t e = hipMemsetAsync(wamax_out, 0, sizeof(unsigned), st);
-    if (e != hipSuccess) return (int)e;
-    amax_kernel<<<min(nbp_ew_grid(total, 256), 256), 256, 0, st>>>(w_oihw, total, nullptr, 9ll * C, (unsigned*)wamax_out, 1u);
-    pack_conv_weight_h2_kernel<true><<<nbp_ew_grid(total, 256), 256, 0, st>>>(w_oihw, C, N, 9, nullptr, 0, (const unsigned*)wamax_out,
-                                                                             (unsigned short*)dst_planes, 1);
-    return nbp_launch_status();
+    return pack_conv_weight_split_dgrad_impl<true>(w_oihw, N, C, c_total, dst_planes, wamax_out, stream);
 }
 
 // All weight packs of a training step: descs_dev = n PrepackDesc records on the device (layout in include/nbp_hip.h), wamax words
-// zeroed here.  N % 16 == 0 and C % 16 == 0 for every record (the plane layouts).
-extern "C" int nbp_prepack_weights_split(const void* descs_dev, int n, void* wamax_words, void* stream) {
-    NBP_ENTER();
+// zeroed here.  N % 16 == 0 and C % 16 == 0 for every record (the plane layouts).  ONE: the one-plane layouts (the planes of the
+// "_h1" pack entry points, bit for bit).
+template <bool ONE>
+static int prepack_weights_split_impl(const void* descs_dev, int n, void* wamax_words, void* stream) {
     NBP_RETURN_IF(!descs_dev || !wamax_words || n < 1 || n > 4096, NBP_E_ARG);
     hipStream_t st = (hipStream_t)stream;
     hipError_t e = hipMemsetAsync(wamax_words, 0, (size_t)n * sizeof(unsigned), st);
     if (e != hipSuccess) return (int)e;
     prepack_amax_kernel<<<dim3(64, (unsigned)n), 256, 0, st>>>((const PrepackDesc*)descs_dev);
-    prepack_pack_kernel<<<dim3(256, (unsigned)n), 256, 0, st>>>((const PrepackDesc*)descs_dev);
+    prepack_pack_kernel<ONE><<<dim3(256, (unsigned)n), 256, 0, st>>>((const PrepackDesc*)descs_dev);
     return nbp_launch_status();
 }
-// the same with the one-plane layouts (the planes of the "_h1" pack entry points, bit for bit)
+extern "C" int nbp_prepack_weights_split(const void* descs_dev, int n, void* wamax_words, void* stream) {
+    NBP_ENTER();
+    return prepack_weights_split_impl<false>(descs_dev, n, wamax_words, stream);
+}
 extern "C" int nbp_prepack_weights_split_h1(const void* descs_dev, int n, void* wamax_words, void* stream) {
     NBP_ENTER();
-    NBP_RETURN_IF(!descs_dev || !wamax_words || n < 1 || n > 4096, NBP_E_ARG);
-    hipStream_t st = (hipStream_t)stream;
-    hipError_t e = hipMemsetAsync(wamax_words, 0, (size_t)n * sizeof(unsigned), st);
-    if (e != hipSuccess) return (int)e;
-    prepack_amax_kernel<<<dim3(64, (unsigned)n), 256, 0, st>>>((const PrepackDesc*)descs_dev);
-    prepack_pack_kernel<true><<<dim3(256, (unsigned)n), 256, 0, st>>>((const PrepackDesc*)descs_dev);
-    return nbp_launch_status();
+    return prepack_weights_split_impl<true>(descs_dev, n, wamax_words, stream);
 }
 extern "C" int nbp_prepack_desc_bytes(void) { return (int)sizeof(PrepackDesc); }
 
 // The training step's forms of the two packs above (round 5: a 3x3 layer cost six launches per step for its weights -- memset, max,
 // pack, twice): `_prezeroed` takes a max-|w| word the caller has already zeroed (one fill per forward for all layers) and
 // `_dgrad_known` the word the forward's pack of the same weights left, since the data-gradient planes hold the same values.
-extern "C" int nbp_pack_conv_weight_split_prezeroed(const float* w_oihw, int N, int C, int ksize, int c_total, void* dst_planes,
-                                                    void* wamax_zeroed, void* stream) {
-    NBP_ENTER();
+template <bool ONE>
+static int pack_conv_weight_split_prezeroed_impl(const float* w_oihw, int N, int C, int ksize, int c_total, void* dst_planes,
+                                                 void* wamax_zeroed, void* stream) {
     NBP_RETURN_IF(!w_oihw || !dst_planes || !wamax_zeroed, NBP_E_ARG);
     NBP_RETURN_IF((ksize != 1 && ksize != 3) || N < 1 || C < 1 || C > c_total || c_total % 32, NBP_E_SHAPE);
     hipStream_t st = (hipStream_t)stream;
     const long long total = (long long)N * C * ksize * ksize;
     amax_kernel<<<min(nbp_ew_grid(total, 256), 256), 256, 0, st>>>(w_oihw, total, nullptr, (long long)C * ksize * ksize, (unsigned*)wamax_zeroed, 1u);
-    pack_conv_weight_h2_kernel<<<nbp_ew_grid(total, 256), 256, 0, st>>>(w_oihw, N, C, ksize * ksize, nullptr, 0, (const unsigned*)wamax_zeroed,
-                                                                       (unsigned short*)dst_planes);
+    pack_conv_weight_h2_kernel<ONE><<<nbp_ew_grid(total, 256), 256, 0, st>>>(w_oihw, N, C, ksize * ksize, nullptr, 0, (const unsigned*)wamax_zeroed,
+                                                                            (unsigned short*)dst_planes);
     return nbp_launch_status();
+}
+template <bool ONE>
+static int pack_conv_weight_split_dgrad_known_impl(const float* w_oihw, int N, int C, int c_total, void* dst_planes,
+                                                   const void* wamax_known, void* stream) {
+    NBP_RETURN_IF(!w_oihw || !dst_planes || !wamax_known, NBP_E_ARG);
+    NBP_RETURN_IF(N < 1 || C < 1 || N > c_total || c_total % 32, NBP_E_SHAPE);
+    const long long total = (long long)N * C * 9;
+    pack_conv_weight_h2_kernel<ONE><<<nbp_ew_grid(total, 256), 256, 0, (hipStream_t)stream>>>(w_oihw, C, N, 9, nullptr, 0, (const unsigned*)wamax_known,
+                                                                                             (unsigned short*)dst_planes, 1);
+    return nbp_launch_status();
+}
+extern "C" int nbp_pack_conv_weight_split_prezeroed(const float* w_oihw, int N, int C, int ksize, int c_total, void* dst_planes,
+                                                    void* wamax_zeroed, void* stream) {
+    NBP_ENTER();
+    return pack_conv_weight_split_prezeroed_impl<false>(w_oihw, N, C, ksize, c_total, dst_planes, wamax_zeroed, stream);
 }
 extern "C" int nbp_pack_conv_weight_split_dgrad_known(const float* w_oihw, int N, int C, int c_total, void* dst_planes,
                                                       const void* wamax_known, void* stream) {
     NBP_ENTER();
-    NBP_RETURN_IF(!w_oihw || !dst_planes || !wamax_known, NBP_E_ARG);
-    NBP_RETURN_IF(N < 1 || C < 1 || N > c_total || c_total % 32, NBP_E_SHAPE);
-    const long long total = (long long)N * C * 9;
-    pack_conv_weight_h2_kernel<<<nbp_ew_grid(total, 256), 256, 0, (hipStream_t)stream>>>(w_oihw, C, N, 9, nullptr, 0, (const unsigned*)wamax_known,
-                                                                                        (unsigned short*)dst_planes, 1);
-    return nbp_launch_status();
+    return pack_conv_weight_split_dgrad_known_impl<false>(w_oihw, N, C, c_total, dst_planes, wamax_known, stream);
 }
 extern "C" int nbp_pack_conv_weight_split_prezeroed_h1(const float* w_oihw, int N, int C, int ksize, int c_total, void* dst_planes,
                                                        void* wamax_zeroed, void* stream) {
     NBP_ENTER();
-    NBP_RETURN_IF(!w_oihw || !dst_planes || !wamax_zeroed, NBP_E_ARG);
-    NBP_RETURN_IF((ksize != 1 && ksize != 3) || N < 1 || C < 1 || C > c_total || c_total % 32, NBP_E_SHAPE);
-    hipStream_t st = (hipStream_t)stream;
-    const long long total = (long long)N * C * ksize * ksize;
-    amax_kernel<<<min(nbp_ew_grid(total, 256), 256), 256, 0, st>>>(w_oihw, total, nullptr, (long long)C * ksize * ksize, (unsigned*)wamax_zeroed, 1u);
-    pack_conv_weight_h2_kernel<true><<<nbp_ew_grid(total, 256), 256, 0, st>>>(w_oihw, N, C, ksize * ksize, nullptr, 0, (const unsigned*)wamax_zeroed,
-                                                                             (unsigned short*)dst_planes);
-    return nbp_launch_status();
+    return pack_conv_weight_split_prezeroed_impl<true>(w_oihw, N, C, ksize, c_total, dst_planes, wamax_zeroed, stream);
 }
 extern "C" int nbp_pack_conv_weight_split_dgrad_known_h1(const float* w_oihw, int N, int C, int c_total, void* dst_planes,
                                                          const void* wamax_known, void* stream) {
     NBP_ENTER();
-    NBP_RETURN_IF(!w_oihw || !dst_planes || !wamax_known, NBP_E_ARG);
-    NBP_RETURN_IF(N < 1 || C < 1 || N > c_total || c_total % 32, NBP_E_SHAPE);
-    const long long total = (long long)N * C * 9;
-    pack_conv_weight_h2_kernel<true><<<nbp_ew_grid(total, 256), 256, 0, (hipStream_t)stream>>>(w_oihw, C, N, 9, nullptr, 0,
-                                                                                              (const unsigned*)wamax_known, (unsigned short*)dst_planes, 1);
-    return nbp_launch_status();
+    return pack_conv_weight_split_dgrad_known_impl<true>(w_oihw, N, C, c_total, dst_planes, wamax_known, stream);
 }
-
 extern "C" int nbp_amax_f32(const float* x, long long n, void* amax_inout, void* stream) {
     NBP_ENTER();
     NBP_RETURN_IF(!x || !amax_inout || n < 0, NBP_E_ARG);
@@ -2469,17 +2458,21 @@ int nbp_wgrad_1x1_split_launch(const float* x, int C, long long M, const float* 
 
 // ---- data gradient of an up_conv layer in parity form (training; conv3x3_halo_h2_kernel<..., DG>)
 // planes: 32 N C fp16 ([4 parities x N / 16 chunks][4 taps][hi|lo][k half][C][8]) from the layer's own weight [N][C][3][3]
-extern "C" int nbp_pack_upconv_weight_split_dgrad(const float* w_oihw, int N, int C, void* dst_planes, void* wamax_out, void* stream) {
-    NBP_ENTER();
+template <bool ONE>
+static int pack_upconv_weight_split_dgrad_impl(const float* w_oihw, int N, int C, void* dst_planes, void* wamax_out, void* stream) {
     NBP_RETURN_IF(!w_oihw || !dst_planes || !wamax_out, NBP_E_ARG);
     NBP_RETURN_IF(N < 16 || N % 16 || C < 1, NBP_E_SHAPE);
     hipStream_t st = (hipStream_t)stream;
     hipError_t e = hipMemsetAsync(wamax_out, 0, sizeof(unsigned), st);
     if (e != hipSuccess) return (int)e;
     const long long NC = (long long)N * C;
-    pack_upconv_dgrad_h2_kernel<<<min(nbp_ew_grid(NC, 256), 256), 256, 0, st>>>(w_oihw, N, C, (unsigned*)wamax_out, nullptr);
-    pack_upconv_dgrad_h2_kernel<<<nbp_ew_grid(NC, 256), 256, 0, st>>>(w_oihw, N, C, (unsigned*)wamax_out, (unsigned short*)dst_planes);
+    pack_upconv_dgrad_h2_kernel<ONE><<<min(nbp_ew_grid(NC, 256), 256), 256, 0, st>>>(w_oihw, N, C, (unsigned*)wamax_out, nullptr);
+    pack_upconv_dgrad_h2_kernel<ONE><<<nbp_ew_grid(NC, 256), 256, 0, st>>>(w_oihw, N, C, (unsigned*)wamax_out, (unsigned short*)dst_planes);
     return nbp_launch_status();
+}
+extern "C" int nbp_pack_upconv_weight_split_dgrad(const float* w_oihw, int N, int C, void* dst_planes, void* wamax_out, void* stream) {
+    NBP_ENTER();
+    return pack_upconv_weight_split_dgrad_impl<false>(w_oihw, N, C, dst_planes, wamax_out, stream);
 }
 // workspace of nbp_upconv3x3_split_dgrad_f32 (its split-K slices, by occupancy)
 extern "C" size_t nbp_upconv_split_dgrad_workspace_bytes(int B, int H, int W, int N, int C) {
@@ -2526,8 +2519,8 @@ extern "C" int nbp_conv1x1_split_f32_h1(const float* src, int C, long long M, co
                                     (hipStream_t)stream, 1);
 }
 // planes of w^T for the data gradient of a 1x1 layer w [N][C]: a 1x1 convolution from N (dy's channels) to C
-extern "C" int nbp_pack_conv1x1_weight_split_dgrad(const float* w_nc, int N, int C, void* dst_planes, void* wamax_out, void* stream) {
-    NBP_ENTER();
+template <bool ONE>
+static int pack_conv1x1_weight_split_dgrad_impl(const float* w_nc, int N, int C, void* dst_planes, void* wamax_out, void* stream) {
     NBP_RETURN_IF(!w_nc || !dst_planes || !wamax_out, NBP_E_ARG);
     NBP_RETURN_IF(N < 32 || N % 32 || C < 32 || C % 32, NBP_E_SHAPE);
     hipStream_t st = (hipStream_t)stream;
@@ -2536,22 +2529,17 @@ extern "C" int nbp_pack_conv1x1_weight_split_dgrad(const float* w_nc, int N, int
     if (e != hipSuccess) return (int)e;
     amax_kernel<<<min(nbp_ew_grid(total, 256), 256), 256, 0, st>>>(w_nc, total, nullptr, C, (unsigned*)wamax_out, 1u);
     // (transposed form of the pack: rows = C output channels, K = N input channels, w'[c][n] = w[n][c])
-    pack_conv_weight_h2_kernel<<<nbp_ew_grid(total, 256), 256, 0, st>>>(w_nc, C, N, 1, nullptr, 0, (const unsigned*)wamax_out,
-                                                                       (unsigned short*)dst_planes, 1);
+    pack_conv_weight_h2_kernel<ONE><<<nbp_ew_grid(total, 256), 256, 0, st>>>(w_nc, C, N, 1, nullptr, 0, (const unsigned*)wamax_out,
+                                                                            (unsigned short*)dst_planes, 1);
     return nbp_launch_status();
+}
+extern "C" int nbp_pack_conv1x1_weight_split_dgrad(const float* w_nc, int N, int C, void* dst_planes, void* wamax_out, void* stream) {
+    NBP_ENTER();
+    return pack_conv1x1_weight_split_dgrad_impl<false>(w_nc, N, C, dst_planes, wamax_out, stream);
 }
 extern "C" int nbp_pack_conv1x1_weight_split_dgrad_h1(const float* w_nc, int N, int C, void* dst_planes, void* wamax_out, void* stream) {
     NBP_ENTER();
-    NBP_RETURN_IF(!w_nc || !dst_planes || !wamax_out, NBP_E_ARG);
-    NBP_RETURN_IF(N < 32 || N % 32 || C < 32 || C % 32, NBP_E_SHAPE);
-    hipStream_t st = (hipStream_t)stream;
-    const long long total = (long long)N * C;
-    hipError_t e = hipMemsetAsync(wamax_out, 0, sizeof(unsigned), st);
-    if (e != hipSuccess) return (int)e;
-    amax_kernel<<<min(nbp_ew_grid(total, 256), 256), 256, 0, st>>>(w_nc, total, nullptr, C, (unsigned*)wamax_out, 1u);
-    pack_conv_weight_h2_kernel<true><<<nbp_ew_grid(total, 256), 256, 0, st>>>(w_nc, C, N, 1, nullptr, 0, (const unsigned*)wamax_out,
-                                                                             (unsigned short*)dst_planes, 1);
-    return nbp_launch_status();
+    return pack_conv1x1_weight_split_dgrad_impl<true>(w_nc, N, C, dst_planes, wamax_out, stream);
 }
 
 extern "C" int nbp_pack_upconv_weight_split(const float* w_oihw, int N, int C, void* dst_planes, void* wamax_out, void* stream) {
@@ -2560,27 +2548,11 @@ extern "C" int nbp_pack_upconv_weight_split(const float* w_oihw, int N, int C, v
 }
 extern "C" int nbp_pack_upconv_weight_split_h1(const float* w_oihw, int N, int C, void* dst_planes, void* wamax_out, void* stream) {
     NBP_ENTER();
-    NBP_RETURN_IF(!w_oihw || !dst_planes || !wamax_out, NBP_E_ARG);
-    NBP_RETURN_IF(N < 1 || C < 16 || C % 16, NBP_E_SHAPE);
-    hipStream_t st = (hipStream_t)stream;
-    hipError_t e = hipMemsetAsync(wamax_out, 0, sizeof(unsigned), st);
-    if (e != hipSuccess) return (int)e;
-    const long long NC = (long long)N * C;
-    pack_upconv_h2_kernel<true><<<min(nbp_ew_grid(NC, 256), 256), 256, 0, st>>>(w_oihw, N, C, (unsigned*)wamax_out, nullptr);
-    pack_upconv_h2_kernel<true><<<nbp_ew_grid(NC, 256), 256, 0, st>>>(w_oihw, N, C, (unsigned*)wamax_out, (unsigned short*)dst_planes);
-    return nbp_launch_status();
+    return nbp_pack_upconv_weight_split_launch(w_oihw, N, C, dst_planes, (unsigned*)wamax_out, (hipStream_t)stream, 1);
 }
 extern "C" int nbp_pack_upconv_weight_split_dgrad_h1(const float* w_oihw, int N, int C, void* dst_planes, void* wamax_out, void* stream) {
     NBP_ENTER();
-    NBP_RETURN_IF(!w_oihw || !dst_planes || !wamax_out, NBP_E_ARG);
-    NBP_RETURN_IF(N < 16 || N % 16 || C < 1, NBP_E_SHAPE);
-    hipStream_t st = (hipStream_t)stream;
-    hipError_t e = hipMemsetAsync(wamax_out, 0, sizeof(unsigned), st);
-    if (e != hipSuccess) return (int)e;
-    const long long NC = (long long)N * C;
-    pack_upconv_dgrad_h2_kernel<true><<<min(nbp_ew_grid(NC, 256), 256), 256, 0, st>>>(w_oihw, N, C, (unsigned*)wamax_out, nullptr);
-    pack_upconv_dgrad_h2_kernel<true><<<nbp_ew_grid(NC, 256), 256, 0, st>>>(w_oihw, N, C, (unsigned*)wamax_out, (unsigned short*)dst_planes);
-    return nbp_launch_status();
+    return pack_upconv_weight_split_dgrad_impl<true>(w_oihw, N, C, dst_planes, wamax_out, stream);
 }
 
 static int upconv3x3_split_impl(const float* src, int C, int B, int H, int W, const void* planes_up, const void* wamax_up,

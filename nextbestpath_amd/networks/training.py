@@ -13,8 +13,6 @@ the parameter gradients have the reference's shapes.
 """
 from __future__ import annotations
 
-import os
-
 import ctypes
 
 import torch
@@ -79,9 +77,7 @@ def _igemm(src0, src1, ups, wpk, N, ksize, scale, shift, relu):
 
 
 # 3x3 convolutions of the forward and of the data gradient on the fp16 matrix pipe through two-piece operand splitting
-# (csrc/nbp_split.hip: the fp32 pipe's accuracy at 5.3x its matrix rate); NBP_TRAIN_SPLIT=0 keeps the fp32 MFMA pipe.
-_SPLIT = _lib.tune("NBP_TRAIN_SPLIT", "1") != "0"
-_WGRAD_SPLIT = _lib.tune("NBP_TRAIN_WGRAD_SPLIT", "1") == "1"      # A/B: weight gradients on the fp32 pipe
+# (csrc/nbp_split.hip: the fp32 pipe's accuracy at 5.3x its matrix rate); the implicit GEMM on the fp32 pipe takes what they do not tile.
 
 # Training arithmetic of the layers the split kernels take (NBP.train_precision, read once per forward_train and carried in every
 # ConvFn's context): "fp32_split" = two fp16 pieces per operand, three exact MFMAs per product; "fp16" = the one-piece forms
@@ -97,7 +93,7 @@ def _fn(name, one):
 
 
 def _split_ok(H, W, N, ksize):
-    return _SPLIT and ksize == 3 and H % 16 == 0 and ((W % 32 == 0 and N % 64 == 0) or (W % 16 == 0 and N % 128 == 0))
+    return ksize == 3 and H % 16 == 0 and ((W % 32 == 0 and N % 64 == 0) or (W % 16 == 0 and N % 128 == 0))
 
 
 def _pack_split(w_oihw, n_pad, c_total, one=False):
@@ -119,8 +115,8 @@ def _pack_split(w_oihw, n_pad, c_total, one=False):
 
 # split-K request of the training convolutions: -1 = slices by occupancy only (csrc/nbp_split.hip: nbp_plan_conv_split; the
 # accuracy-driven chain bound of the eval forward costs the step partial sums, ~25 reduce launches and the BatchNorm statistics of
-# every layer it splits); NBP_TRAIN_CHAIN_BOUND=1: 0 = the eval forward's plan
-_TRAIN_SK = 0 if _lib.tune("NBP_TRAIN_CHAIN_BOUND", "0") == "1" else -1
+# every layer it splits)
+_TRAIN_SK = -1
 _CONST = {}
 
 
@@ -137,18 +133,17 @@ def _const(value, n, device):
 # tensor object (a Python attribute: it lives and dies with the tensor, and a different tensor that happens to reuse the address
 # -- a forward under no_grad, recompute, two forwards before one backward -- can never pick it up; round 3 keyed process-global
 # dicts by data_ptr()).  A consumer that gets a tensor without a note (autograd summed two gradients, a slice, a copy) takes its
-# own pass.  NBP_TRAIN_FUSE=0 switches the hand-off off altogether.
-_FUSE = _lib.tune("NBP_TRAIN_FUSE", "1") == "1"
-_BN_EPILOGUE = _lib.tune("NBP_TRAIN_BN_EPILOGUE", "1") == "1"      # BatchNorm statistics from the producing convolution's epilogue (0 = its own pass)
-_SLICE_VIEWS = _lib.tune("NBP_TRAIN_SLICE_VIEWS", "1") == "1"      # two-source convolutions return channel-slice VIEWS of dx (0 = copies)
-_MASK_FROM_X = _lib.tune("NBP_TRAIN_MASK_FROM_X", "1") == "1"      # BatchNorm backward: ReLU mask rebuilt from x (0 = read y, as round 3)
+# own pass.
+# Module flags (default True) that the tests set to False to run the reference form a path is compared against -- forms an observer
+# or a shape the fast path does not take reaches anyway:
+_BN_EPILOGUE = True      # BatchNorm statistics from the producing convolution's epilogue (False: the BatchNorm's own pass)
+_MASK_FROM_X = True      # BatchNorm backward: ReLU mask rebuilt from x (False: read y)
 _ARENA = {}
 
 
 def _note(t, **kw):
     """Attach producer knowledge to tensor t: amax = 64-word max-|t| slot; colsum = column sums of t (with its max slot)."""
-    if _FUSE:
-        t._nbp_note = kw
+    t._nbp_note = kw
     return t
 
 
@@ -156,7 +151,7 @@ HANDOFF_STATS = {"hit": 0, "miss": 0}      # notes found / not found by consumer
 
 
 def _noted(t, key):
-    n = getattr(t, "_nbp_note", None) if _FUSE and t is not None else None
+    n = getattr(t, "_nbp_note", None) if t is not None else None
     v = None if n is None else n.get(key)
     HANDOFF_STATS["hit" if v is not None else "miss"] += 1
     return v
@@ -184,7 +179,7 @@ def _amax_slot(*tensors):
     """64-word max-|.| slot (csrc/nbp_split.hip) over the given tensors: one streaming pass each, shared by every kernel that
     scales them (forward + weight gradient for a layer's inputs; data + weight gradient for its output gradient)."""
     live = [t for t in tensors if t is not None and t.numel()]
-    if _FUSE and len(live) == 1:
+    if len(live) == 1:
         known = _noted(live[0], "amax")
         if known is not None:
             return known                       # the producer (BatchNorm apply) measured it while writing the tensor
@@ -230,12 +225,11 @@ def _conv_split(src0, src1, ups, packed, N, scale, shift, relu, amax=None, bn=Fa
 
 # 1x1 layers (the attention gates' W_g / W_x) and their data gradients on the split scheme through the gates' kernel with one source
 # (csrc/nbp_split.hip: nbp_conv1x1_split_f32) instead of the fp32 pipe's implicit GEMM: no padding of 32 output channels to 64,
-# memory-bound on every level.  NBP_TRAIN_SPLIT_1X1=0: the implicit GEMM.
-_SPLIT_1X1 = _lib.tune("NBP_TRAIN_SPLIT_1X1", "1") == "1"
+# memory-bound on every level.
 
 
 def _conv1x1_ok(M, C, N, c_real):
-    return _SPLIT and _SPLIT_1X1 and C % 32 == 0 and N % 32 == 0 and c_real == C and M * C * 4 < 2 ** 31 and N * C * 4 < 2 ** 31
+    return C % 32 == 0 and N % 32 == 0 and c_real == C and M * C * 4 < 2 ** 31 and N * C * 4 < 2 ** 31
 
 
 def _conv1x1_split(x, planes, wamax, N, scale, shift, amax, one=False):
@@ -247,32 +241,23 @@ def _conv1x1_split(x, planes, wamax, N, scale, shift, amax, one=False):
     return out
 
 
-# data gradient of the up_conv layers in parity form (csrc/nbp_split.hip: conv3x3_halo_h2_kernel<..., DG>): dx at the low resolution
-# straight from dy, 16 tap-products per low-resolution pixel instead of 36 + a 2x2 sum pass.  NBP_TRAIN_UP_DGRAD=0: round 4's form.
-_UP_DGRAD = _lib.tune("NBP_TRAIN_UP_DGRAD", "1") == "1"
-# ... and their weight gradient (wgrad_up_split_kernel: 16 tap-GEMMs over M / 4 pixels instead of 9 over M).  NBP_TRAIN_UP_WGRAD=0: the 3x3 form.
-_UP_WGRAD = _lib.tune("NBP_TRAIN_UP_WGRAD", "1") == "1"
+# The up_conv layers' gradients take the parity form too where it tiles: the data gradient (csrc/nbp_split.hip:
+# conv3x3_halo_h2_kernel<..., DG>) at the low resolution straight from dy, 16 tap-products per low-resolution pixel instead of 36 + a
+# 2x2 sum pass; the weight gradient (wgrad_up_split_kernel) as 16 tap-GEMMs over M / 4 pixels instead of 9 over M.  False (tests):
+# the full-resolution 3x3 forms, which layers that do not tile take anyway.
+_UP_DGRAD = True
+_UP_WGRAD = True
 
 
 def _upconv_ok(Hs, Ws, N):
     """up_conv layers (x2 nearest upsample + 3x3): four 2x2 parity convolutions of the low-resolution input when it tiles."""
-    return _SPLIT and Hs % 16 == 0 and ((Ws % 32 == 0 and N % 64 == 0) or (Ws % 16 == 0 and N % 128 == 0))
+    return Hs % 16 == 0 and ((Ws % 32 == 0 and N % 64 == 0) or (Ws % 16 == 0 and N % 128 == 0))
 
 
-def _upconv_split(src, w_oihw, n_pad, scale, shift, amax=None, bn=False, pre=None, one=False):
+def _upconv_split(src, packed, n_pad, scale, shift, amax=None, bn=False, one=False):
     L = _lib.lib()
-    N, C, _, _ = w_oihw.shape
+    planes, wamax = packed
     B, Hs, Ws, C0 = src.shape
-    if pre is not None and N == n_pad and C == C0:
-        planes, wamax = pre[3], pre[5]              # packed at the start of the forward (_prepack_run)
-    else:
-        if N != n_pad or C != C0:       # zero rows / channels up to the padded counts
-            wp = torch.zeros(n_pad, C0, 3, 3, dtype=torch.float32, device=w_oihw.device)
-            wp[:N, :C] = w_oihw
-            w_oihw = wp
-        planes = torch.empty(4 * (C0 // 16) * 4 * 4 * n_pad * 8, dtype=torch.int16, device=src.device)
-        wamax = torch.empty(1, dtype=torch.int32, device=src.device)             # zeroed by the pack launch itself
-        _chk(_fn("nbp_pack_upconv_weight_split", one)(_lib.ptr(w_oihw), n_pad, C0, _lib.ptr(planes), _lib.ptr(wamax), _st()), "pack_upconv")
     H, W = 2 * Hs, 2 * Ws
     out = torch.empty(B, H, W, n_pad, dtype=torch.float32, device=src.device)
     ws = _ws(L.nbp_conv_split_planned_workspace_bytes_k(B, H, W, C0, n_pad, 1, _TRAIN_SK, None), src.device)
@@ -292,8 +277,9 @@ def _upconv_split(src, w_oihw, n_pad, scale, shift, amax=None, bn=False, pre=Non
 # ---- all weight packs of a step in two launches (csrc/nbp_split.hip: nbp_prepack_weights_split).  forward_train builds (once per set of
 # parameter storages) a device table of the layers the split kernels take -- 3x3, up_conv and the gates' 1x1 layers -- with persistent
 # plane buffers, runs the two launches at the start of every forward, and the layers look their planes up by the weight's address;
-# a layer called outside forward_train (tests) packs for itself as before.  NBP_TRAIN_PREPACK=0: every layer packs for itself.
-_PREPACK = _lib.tune("NBP_TRAIN_PREPACK", "1") == "1"
+# a layer called outside forward_train (tests) packs for itself as before.  False: every layer packs for itself (the reference of
+# the bit-identity tests).
+_PREPACK = True
 _PRE_CACHE = {}          # key (device, parameter addresses) -> table
 _PRE = None              # the current step's {weight address: (kind, N, C, planes, planes_t, wamax)}
 
@@ -318,7 +304,7 @@ def _prepack_run(net, dev, one=False):
     """Packs every layer's weights for this step (one: the one-plane layouts of the "fp16" mode); returns the lookup table (None:
     switched off / nothing to pack)."""
     import numpy as np
-    if not (_PREPACK and _SPLIT):
+    if not _PREPACK:
         return None
     L = _lib.lib()
     layers = _prepack_layers(net)
@@ -360,10 +346,55 @@ def _prepacked(w, kind, N, C):
     return e if (e is not None and e[0] == kind and e[1] == N and e[2] == C) else None
 
 
+def _weight_planes(w, kind, dgrad, one, rows, chans, pre=None, wmax=None):
+    """(planes, max-|w| word) of layer weight w [N, C, k, k] for a split kernel: the planes of the layer's forward convolution (rows =
+    the padded N, chans = its input channels) or of its data gradient (dgrad: rows = the input channels, chans = the padded N), in
+    the one-piece layout when `one`.  kind as in the prepack table: 0 = 3x3, 1 = 1x1, 2 = up_conv (the four parity filters).
+    pre: this step's prepacked entry of the layer (_prepacked, ctx.pre), taken when it holds this kind; else the weights are packed
+    here.  wmax: the word the forward's 3x3 pack measured (the data-gradient planes hold the same values: no second max pass)."""
+    if pre is not None and pre[0] == kind:
+        return pre[4 if dgrad else 3], pre[5]
+    N, C = w.shape[:2]
+    if kind == 0 and (not dgrad or (C, N) != (rows, chans)):
+        # the forward (its max word out of the arena, zeroed already); the data gradient of a padded layer as the same pack of the
+        # flipped, transposed weights
+        return _pack_split(w.flip(2, 3).permute(1, 0, 2, 3).contiguous() if dgrad else w, rows, chans, one)
+    if kind == 2 and not dgrad and (N, C) != (rows, chans):       # zero rows / channels up to the padded counts
+        wp = torch.zeros(rows, chans, 3, 3, dtype=torch.float32, device=w.device)
+        wp[:N, :C] = w
+        w, N, C = wp, rows, chans
+    planes = torch.empty(chans // 16 * (9, 1, 16)[kind] * 4 * rows * 8, dtype=torch.int16, device=w.device)
+    if kind == 0:                     # (the data gradient of an unpadded layer)
+        name, dims = "nbp_pack_conv_weight_split_dgrad", (N, C, chans)
+    elif kind == 1:
+        name, dims = ("nbp_pack_conv1x1_weight_split_dgrad", (N, C)) if dgrad else ("nbp_pack_conv_weight_split", (N, C, 1, None, 0, C))
+    else:
+        name, dims = "nbp_pack_upconv_weight_split" + ("_dgrad" if dgrad else ""), (N, C)
+    if kind == 0 and wmax is not None:
+        name, wamax = name + "_known", wmax
+    else:
+        wamax = torch.empty(1, dtype=torch.int32, device=w.device)         # zeroed by the pack launch itself
+    _chk(_fn(name, one)(_lib.ptr(w), *dims, _lib.ptr(planes), _lib.ptr(wamax), _st()), name)
+    return planes, wamax
+
+
 class ConvFn(torch.autograd.Function):
     """y = conv_k(cat(x0, x1) [x2 nearest-upsampled]) + bias; weight OIHW [N, c_real, k, k].
     x0 / x1 channel counts are multiples of 64 (c_real < C0 only for the zero-padded network input).
-    one: the one-piece ("fp16") forms of the split kernels, for this layer's forward and backward alike."""
+    one: the one-piece ("fp16") forms of the split kernels, for this layer's forward and backward alike.
+
+    Kernels, first rule that holds (Np = N padded to 64; H, W = the output resolution; Ctot = C0 + C1 -- the data gradient's
+    output channels, which is why its rules differ from the forward's):
+      forward    up_conv parity form  ups, k = 3, one source, _upconv_ok(H / 2, W / 2, Np)
+                 3x3 split            _split_ok(H, W, Np, k)
+                 1x1 split            k = 1, no ups, one source, _conv1x1_ok (Np = N)
+                 implicit GEMM        the rest
+      dw         up_conv parity form  _UP_WGRAD, ups, k = 3, one source, N = Np, c_real = C0, forward on a split kernel, M Np < 2^29
+                 split entry point    the rest (it falls through to the fp32 pipe for the shapes it does not take)
+      dx         up_conv parity form  _UP_DGRAD, ups, k = 3, one source, N = Np, c_real = C0, _upconv_ok(H / 2, W / 2, C0), M Np < 2^29
+                 1x1 split            the forward's 1x1 rule, N -> C0 channels
+                 3x3 split            _split_ok(H, W, Ctot, k), then a 2x2 sum when ups
+                 implicit GEMM        the rest, then a 2x2 sum when ups"""
 
     @staticmethod
     def forward(ctx, x0, x1, weight, bias, ups, bn_next=False, one=False):
@@ -385,40 +416,34 @@ class ConvFn(torch.autograd.Function):
             shift = torch.zeros(Np, dtype=torch.float32, device=dev)
             shift[:N] = bias.detach()
         H, W = (x0.shape[1] * 2, x0.shape[2] * 2) if ups else (x0.shape[1], x0.shape[2])
-        xmax = None                      # joint max-|.| slot of the inputs: taken once, reused by the weight gradient
-        wmax_fwd = None
         # bn_next: a BatchNorm consumes this output -- its statistics' partial sums come out of the epilogue (not for padded
         # channel counts, whose output is sliced; not under an observer, which may rewrite the output)
         bn = bool(bn_next) and _BN_EPILOGUE and N == Np and _observer is None
-        # this step's prepacked planes of the layer (kind, N, C, planes, planes_t, wamax).  They live in ONE persistent buffer per
-        # layer that every forward_train() of this network overwrites: backward(t) after a LATER forward_train() is only right while
-        # the weights are unchanged in between and everything runs on one stream (true of the trainer: forward, backward, step)
-        pre = None
         if ups and k == 3 and x1 is None and _upconv_ok(x0.shape[1], x0.shape[2], Np):
-            xmax = _amax_slot(x0)
-            pre = _prepacked(w, 2, N, c_real) if (N == Np and c_real == C0) else None
-            y = _upconv_split(x0, w, Np, scale, shift, xmax, bn, pre, one)
+            kind = 2
         elif _split_ok(H, W, Np, k):
-            xmax = _amax_slot(x0, x1)
-            pre = _prepacked(w, 0, N, c_real) if (N == Np and c_real == Ctot) else None
-            packed = (pre[3], pre[5]) if pre is not None else _pack_split(w, Np, Ctot, one)
-            wmax_fwd = packed[1]                       # max |w|: the data gradient's planes hold the same values
-            y = _conv_split(x0, x1, ups, packed, Np, scale, shift, False, xmax, bn, one)
-        elif one_by_one:
-            xmax = _amax_slot(x0)
-            pre = _prepacked(w, 1, N, C0)
-            if pre is not None:
-                planes, wamax = pre[3], pre[5]
-            else:
-                planes = torch.empty(C0 // 16 * 4 * N * 8, dtype=torch.int16, device=dev)
-                wamax = torch.empty(1, dtype=torch.int32, device=dev)
-                _chk(_fn("nbp_pack_conv_weight_split", one)(_lib.ptr(w), N, C0, 1, None, 0, C0, _lib.ptr(planes), _lib.ptr(wamax), _st()),
-                     "pack_split_1x1")
-            y = _conv1x1_split(x0, planes, wamax, N, scale, shift, xmax, one)
+            kind = 0
         else:
+            kind = 1 if one_by_one else None
+        xmax = wmax_fwd = pre = None
+        if kind is None:
             wpk = torch.empty(Ctot // 32 * k * k * Np * 32, dtype=torch.float32, device=dev)
             _chk(L.nbp_pack_conv_weight_padded(_lib.ptr(w), N, c_real, k, Ctot, Np, _lib.ptr(wpk), _st()), "pack_fwd")
             y = _igemm(x0, x1, ups, wpk, Np, k, scale, shift, False)
+        else:
+            xmax = _amax_slot(x0, x1)      # joint max-|.| slot of the inputs: taken once, reused by the weight gradient
+            # this step's prepacked planes of the layer (kind, N, C, planes, planes_t, wamax).  They live in ONE persistent buffer per
+            # layer that every forward_train() of this network overwrites: backward(t) after a LATER forward_train() is only right while
+            # the weights are unchanged in between and everything runs on one stream (true of the trainer: forward, backward, step)
+            pre = _prepacked(w, kind, N, c_real) if (N == Np and c_real == Ctot) else None
+            packed = _weight_planes(w, kind, False, one, Np, Ctot, pre)
+            if kind == 2:
+                y = _upconv_split(x0, packed, Np, scale, shift, xmax, bn, one)
+            elif kind == 0:
+                wmax_fwd = packed[1]       # max |w|: the data gradient's planes hold the same values
+                y = _conv_split(x0, x1, ups, packed, Np, scale, shift, False, xmax, bn, one)
+            else:
+                y = _conv1x1_split(x0, *packed, N, scale, shift, xmax, one)
         ctx.save_for_backward(x0, x1 if x1 is not None else torch.empty(0, device=dev), w)
         ctx.xmax = xmax
         ctx.wmax_fwd = wmax_fwd
@@ -450,44 +475,28 @@ class ConvFn(torch.autograd.Function):
         dw = torch.empty(N, c_real, k, k, dtype=torch.float32, device=dev)
         # (the fp32-pipe weight-gradient kernels of the 1x1 layers take 64-column blocks of dy: a 32-channel gate pads here only)
         # ... unless the 1x1 split form takes the layer (few input channels, many pixels: it masks the missing columns itself)
-        own_1x1 = one_by_one and _SPLIT and _WGRAD_SPLIT and C0 % 64 == 0 and C0 <= 128 and (B * H * W) % 64 == 0
+        own_1x1 = one_by_one and C0 % 64 == 0 and C0 <= 128 and M % 64 == 0
         dyw, Nw = (dy, Np) if (Np % 64 == 0 or own_1x1) else (_pad_channels(dy, _up(Np)), _up(Np))
-        ws = _ws(L.nbp_conv_wgrad_workspace_bytes(B, H, W, C0, C1, Nw, k), dev)
-        # the 3x3 weight gradients take the split scheme too (the entry point falls through to the fp32 pipe for the rest)
-        dymax = None
-        up_parity = (ups and k == 3 and not has1 and N == Np and c_real == C0 and _SPLIT and _WGRAD_SPLIT and ctx.xmax is not None
-                     and B * H * W * Np * 4 < 2 ** 31)
-        wsu = L.nbp_upconv_wgrad_split_workspace_bytes(B, H // 2, W // 2, C0, Np) if (up_parity and _UP_WGRAD) else 0
+        # max |dy|: shared by the weight and the data gradient; measured by the BatchNorm backward when dy came from one (padding
+        # channels are zeros: same maximum)
+        dymax = (info[0] if info is not None else _amax_slot(dy)) if (k == 3 or one_by_one) else None
+        up_tiles = ups and k == 3 and not has1 and N == Np and c_real == C0 and M * Np * 4 < 2 ** 31
+        wsu = L.nbp_upconv_wgrad_split_workspace_bytes(B, H // 2, W // 2, C0, Np) if (up_tiles and _UP_WGRAD and ctx.xmax is not None) else 0
         if wsu:
-            dymax = info[0] if info is not None else _amax_slot(dy)
             wsb = _ws(wsu, dev)
             _chk(_fn("nbp_upconv_wgrad_split_f32", one)(_lib.ptr(x0), C0, B, H // 2, W // 2, _lib.ptr(dy), Np, _lib.ptr(dw), _lib.ptr(ctx.xmax),
                                               _lib.ptr(dymax), _lib.ptr(wsb), wsb.numel(), _st()), "upconv_wgrad_split")
-        elif _SPLIT and _WGRAD_SPLIT:
-            # max |dy|: shared with the data gradient below; measured by the BatchNorm backward when dy came from one (padding
-            # channels are zeros: same maximum)
-            dymax = (info[0] if info is not None else _amax_slot(dy)) if (k == 3 or one_by_one) else None
+        else:
+            ws = _ws(L.nbp_conv_wgrad_workspace_bytes(B, H, W, C0, C1, Nw, k), dev)
             _chk(_fn("nbp_conv_wgrad_split_f32", one)(_lib.ptr(x0), C0, _lib.ptr(x1), C1, int(ups), B, H, W, k, _lib.ptr(dyw), Nw, c_real, N,
                                             _lib.ptr(dw), _lib.ptr(ctx.xmax), _lib.ptr(ctx.xmax), _lib.ptr(dymax), _lib.ptr(ws),
                                             ws.numel(), _st()), "conv_wgrad_split")
-        else:
-            _chk(L.nbp_conv_wgrad_f32(_lib.ptr(x0), C0, _lib.ptr(x1), C1, int(ups), B, H, W, k, _lib.ptr(dyw), Nw, c_real, N,
-                                      _lib.ptr(dw), _lib.ptr(ws), ws.numel(), _st()), "conv_wgrad")
         dx0 = dx1 = None
         if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
             Ctot = C0 + C1
             ones, zero = _const(1.0, Ctot, dev), _const(0.0, Ctot, dev)
-            if (ups and k == 3 and not has1 and _UP_DGRAD and N == Np and c_real == C0 and _upconv_ok(H // 2, W // 2, C0)
-                    and B * H * W * Np * 4 < 2 ** 31):
-                pre = getattr(ctx, "pre", None)
-                if pre is not None and pre[0] == 2:
-                    planes, wamax = pre[4], pre[5]
-                else:
-                    planes = torch.empty(32 * Np * C0, dtype=torch.int16, device=dev)
-                    wamax = torch.empty(1, dtype=torch.int32, device=dev)
-                    _chk(_fn("nbp_pack_upconv_weight_split_dgrad", one)(_lib.ptr(w), Np, C0, _lib.ptr(planes), _lib.ptr(wamax), _st()), "pack_upconv_dgrad")
-                if dymax is None:
-                    dymax = info[0] if info is not None else _amax_slot(dy)
+            if up_tiles and _UP_DGRAD and _upconv_ok(H // 2, W // 2, C0):
+                planes, wamax = _weight_planes(w, 2, True, one, C0, Np, ctx.pre)
                 dxl = torch.empty(B, H // 2, W // 2, C0, dtype=torch.float32, device=dev)
                 wsd = _ws(L.nbp_upconv_split_dgrad_workspace_bytes(B, H // 2, W // 2, Np, C0), dev)
                 _chk(_fn("nbp_upconv3x3_split_dgrad_f32", one)(_lib.ptr(dy), Np, B, H // 2, W // 2, _lib.ptr(planes), _lib.ptr(wamax), C0,
@@ -496,35 +505,10 @@ class ConvFn(torch.autograd.Function):
                 return dxl, None, dw, db, None, None, None
             if one_by_one:
                 # dx = dy W^T: a 1x1 convolution from N to C0 channels on the same kernel
-                pre = getattr(ctx, "pre", None)
-                if pre is not None and pre[0] == 1:
-                    planes, wamax = pre[4], pre[5]
-                else:
-                    planes = torch.empty(N // 16 * 4 * C0 * 8, dtype=torch.int16, device=dev)
-                    wamax = torch.empty(1, dtype=torch.int32, device=dev)
-                    _chk(_fn("nbp_pack_conv1x1_weight_split_dgrad", one)(_lib.ptr(w), N, C0, _lib.ptr(planes), _lib.ptr(wamax), _st()), "pack_dgrad_1x1")
-                if dymax is None:
-                    dymax = info[0] if info is not None else _amax_slot(dy)
-                dx = _conv1x1_split(dy, planes, wamax, C0, ones, zero, dymax, one)
+                dx = _conv1x1_split(dy, *_weight_planes(w, 1, True, one, C0, N, ctx.pre), C0, ones, zero, dymax, one)
             elif _split_ok(H, W, Ctot, k):
                 # dx = conv3x3(dy, w^T with the taps reversed): output channels = the (padded) input channels
-                if c_real == Ctot and N == Np:
-                    # flip + permute + pack in one launch (they were an ATen flip, a strided copy and the pack)
-                    pre = getattr(ctx, "pre", None)
-                    planes = pre[4] if (pre is not None and pre[0] == 0) else torch.empty(Np // 16 * 9 * 4 * Ctot * 8, dtype=torch.int16, device=dev)
-                    if pre is not None and pre[0] == 0:
-                        wamax = pre[5]
-                    elif getattr(ctx, "wmax_fwd", None) is not None:      # the forward's pack of the same weights measured max |w|
-                        wamax = ctx.wmax_fwd
-                        _chk(_fn("nbp_pack_conv_weight_split_dgrad_known", one)(_lib.ptr(w), N, c_real, Np, _lib.ptr(planes), _lib.ptr(wamax), _st()),
-                             "pack_dgrad_split")
-                    else:
-                        wamax = torch.empty(1, dtype=torch.int32, device=dev)
-                        _chk(_fn("nbp_pack_conv_weight_split_dgrad", one)(_lib.ptr(w), N, c_real, Np, _lib.ptr(planes), _lib.ptr(wamax), _st()), "pack_dgrad_split")
-                    packed = (planes, wamax)
-                else:
-                    wt = w.flip(2, 3).permute(1, 0, 2, 3).contiguous()            # [c_real, N, 3, 3]
-                    packed = _pack_split(wt, Ctot, Np, one)
+                packed = _weight_planes(w, 0, True, one, Ctot, Np, ctx.pre, ctx.wmax_fwd)
                 dx = _conv_split(dy, None, False, packed, Ctot, ones, zero, False, dymax, one=one)
             else:
                 wt = torch.empty(Np // 32 * k * k * Ctot * 32, dtype=torch.float32, device=dev)
@@ -534,24 +518,19 @@ class ConvFn(torch.autograd.Function):
                 low = torch.empty(B, H // 2, W // 2, Ctot, dtype=torch.float32, device=dev)
                 _chk(L.nbp_sum2x2_f32(_lib.ptr(dx), B, H // 2, W // 2, Ctot, _lib.ptr(low), _st()), "sum2x2")
                 dx = low
-            if has1 and _SLICE_VIEWS:
+            if has1:
                 # views of the joint gradient: the attention gate's RowScaleFn reads its slice in place, autograd's sum of dd's two
                 # gradients reads the other (the two slice copies were 2 x (C0 + C1) x M x 4 bytes per decoder level)
                 dx0, dx1 = dx[..., :C0], dx[..., C0:]
-            elif has1:
-                dx0, dx1 = _slice_channels(dx, 0, C0), _slice_channels(dx, C0, C1)
             else:
                 dx0 = dx
         return dx0, dx1, dw, db, None, None, None
 
 
-# Conv1.conv.0 straight from the NCHW network input (csrc/nbp_first_conv.h forward, wgrad_first_kernel backward) instead of a
-# 64-channel padded copy through the 64 -> 64 kernels.  NBP_TRAIN_FIRST_CONV=0: round 4's form.
-_FIRST_CONV = _lib.tune("NBP_TRAIN_FIRST_CONV", "1") == "1"
-
-
 class FirstConvFn(torch.autograd.Function):
-    """y [B,S,S,64] (NHWC) = conv3x3(x [B,5,S,S] NCHW) + bias (nbp_model.py:66); the network input takes no gradient."""
+    """y [B,S,S,64] (NHWC) = conv3x3(x [B,5,S,S] NCHW) + bias (nbp_model.py:66); the network input takes no gradient.  Conv1.conv.0
+    straight from the NCHW input (csrc/nbp_first_conv.h forward, wgrad_first_kernel backward) instead of a 64-channel padded copy
+    through the 64 -> 64 kernels (which _forward_train keeps for S % 32 != 0)."""
 
     @staticmethod
     def forward(ctx, x, weight, bias):
@@ -596,7 +575,7 @@ class BNFn(torch.autograd.Function):
         y = torch.empty_like(x)
         ws = _ws(L.nbp_colreduce_workspace_bytes(M, C), dev)
         g, b = gamma.detach().contiguous(), beta.detach().contiguous()
-        slot = _fresh_slots(dev) if _FUSE and C % 4 == 0 else None
+        slot = _fresh_slots(dev) if C % 4 == 0 else None
         # the backward rebuilds the ReLU mask from x through the unrounded statistics (two tensor reads less per BatchNorm): not
         # when an observer may rewrite y after the fact (its mask is then y's, and y is what gets saved)
         stat = torch.empty(4 * C, dtype=torch.float64, device=dev) if (_MASK_FROM_X and relu and C % 4 == 0 and _observer is None) else None       # mean | invstd | mask bounds lo | hi
@@ -641,7 +620,7 @@ class BNFn(torch.autograd.Function):
         dg = torch.empty(C, dtype=torch.float32, device=dev)
         db = torch.empty(C, dtype=torch.float32, device=dev)
         ws = _ws(L.nbp_colreduce_workspace_bytes(M, C), dev)
-        fuse = _FUSE and C % 4 == 0
+        fuse = C % 4 == 0
         slot = _fresh_slots(dev) if fuse else None
         csum = torch.empty(C, dtype=torch.float32, device=dev) if fuse else None
         if ctx.mask_from_x:
@@ -660,8 +639,6 @@ class BNFn(torch.autograd.Function):
 # An activation with several consumers (the encoder skips: max-pool + two uses per attention gate; x5 and every up_conv output: two)
 # goes through FanOutFn: n aliases forward, and the consumers' gradients meet in ONE n-ary sum launch (csrc/nbp_train.hip:
 # sum_n4_kernel, n reads + 1 write) instead of autograd's n - 1 binary adds (3 (n - 1) tensor passes; 19 ATen launches per step).
-# NBP_TRAIN_FANOUT=0: autograd sums (round 5).
-_FANOUT = _lib.tune("NBP_TRAIN_FANOUT", "1") == "1"
 
 
 class FanOutFn(torch.autograd.Function):
@@ -706,7 +683,7 @@ class FanOutFn(torch.autograd.Function):
 
 def _fan(x, n):
     """n aliases of x for its n consumers (each keeps what the producer noted about x)."""
-    if not (_FANOUT and n > 1 and torch.is_grad_enabled() and x.requires_grad):
+    if not (n > 1 and torch.is_grad_enabled() and x.requires_grad):
         return (x,) * n
     outs = FanOutFn.apply(x, n)
     note = getattr(x, "_nbp_note", None)
@@ -811,7 +788,7 @@ class RowScaleFn(torch.autograd.Function):
         B, H, W, C = x.shape
         x, s = x.contiguous(), s.contiguous()
         out = torch.empty_like(x)
-        if _FUSE and C % 4 == 0 and x.data_ptr() % 16 == 0 and out.data_ptr() % 16 == 0:
+        if C % 4 == 0 and x.data_ptr() % 16 == 0 and out.data_ptr() % 16 == 0:
             slot = _fresh_slots(x.device)              # max |x psi| for the convolution that consumes the gated tensor
             _chk(_lib.lib().nbp_rowscale_amax_f32(_lib.ptr(x), _lib.ptr(s), B * H * W, C, _lib.ptr(out), _lib.ptr(slot), _st()), "rowscale_amax")
             _note(out, amax=slot)
@@ -845,8 +822,8 @@ class RowScaleFn(torch.autograd.Function):
 
 # The attention gate's element-wise middle as ONE Function (csrc/nbp_train.hip: gate_mid_*): BN_g, BN_x, add-relu and the psi row-dot in one
 # pass over the two 1x1 convolutions' outputs, and the whole of its backward in a reduce + an apply pass -- every output bit-identical to
-# the separate Functions' (BNFn x 2, AddReluFn, PsiConvFn: rounds 3-5), which NBP_TRAIN_GATE_FUSE=0 brings back.
-_GATE_FUSE = _lib.tune("NBP_TRAIN_GATE_FUSE", "1") == "1"
+# the separate Functions' (BNFn x 2, AddReluFn, PsiConvFn: rounds 3-5), which an observer or False here brings back.
+_GATE_FUSE = True
 
 
 def _gate_mid_ok(gp, xp):
@@ -895,17 +872,17 @@ class GateMidFn(torch.autograd.Function):
         f32 = lambda n: torch.empty(n, dtype=torch.float32, device=dev)
         dgp, dxp = torch.empty_like(gp), torch.empty_like(xp)
         dgam_g, dbet_g, dgam_x, dbet_x, dw, cs_g, cs_x = f32(F), f32(F), f32(F), f32(F), f32(F), f32(F), f32(F)
-        slots = _fresh_slots(dev, 2) if _FUSE else None
-        sl_g, sl_x = (slots[:64], slots[64:]) if slots is not None else (None, None)
+        slots = _fresh_slots(dev, 2)
+        sl_g, sl_x = slots[:64], slots[64:]
         ws = _ws(L.nbp_gate_mid_workspace_bytes(M, F), dev)
         _chk(L.nbp_gate_mid_backward_f32(_lib.ptr(dp), _lib.ptr(w), _lib.ptr(q), _lib.ptr(gp), _lib.ptr(xp), M, F, _lib.ptr(mean_g),
                                          _lib.ptr(inv_g), _lib.ptr(gg), _lib.ptr(mean_x), _lib.ptr(inv_x), _lib.ptr(gx), _lib.ptr(dgp),
                                          _lib.ptr(dxp), _lib.ptr(dgam_g), _lib.ptr(dbet_g), _lib.ptr(dgam_x), _lib.ptr(dbet_x), _lib.ptr(dw),
                                          _lib.ptr(cs_g), _lib.ptr(cs_x), _lib.ptr(sl_g), _lib.ptr(sl_x), _lib.ptr(ws), ws.numel(), _st()),
              "gate_mid_backward")
-        if _FUSE:        # what BNFn.backward hands the 1x1 convolutions in front: max |.| slot and column sums of their dy
-            _note(dgp, colsum=(sl_g, cs_g))
-            _note(dxp, colsum=(sl_x, cs_x))
+        # what BNFn.backward hands the 1x1 convolutions in front: max |.| slot and column sums of their dy
+        _note(dgp, colsum=(sl_g, cs_g))
+        _note(dxp, colsum=(sl_x, cs_x))
         db = _colsum(dp.view(M, 1))
         return dgp, dxp, dgam_g, dbet_g, None, None, None, None, dgam_x, dbet_x, None, None, None, None, dw.view(ctx.wshape), db
 
@@ -1055,9 +1032,6 @@ def train_precision_one(net):
     prec = getattr(net, "train_precision", "fp32_split")
     if prec not in TRAIN_PRECISIONS:
         raise ValueError(f"NBP.train_precision must be one of {TRAIN_PRECISIONS}, got {prec!r}")
-    if prec == "fp16" and not (_SPLIT and _WGRAD_SPLIT):
-        # the A/B switches put the convolutions on the fp32 pipe: "fp16" would silently train in fp32
-        raise RuntimeError('train_precision "fp16" needs the split kernels (NBP_TRAIN_SPLIT / NBP_TRAIN_WGRAD_SPLIT are switched off)')
     return prec == "fp16"
 
 
@@ -1085,7 +1059,7 @@ def forward_train(net, x):
 
 def _forward_train(net, x, L, B, S, dev):
     seq = net.Conv1.conv
-    if (_FIRST_CONV and S % 32 == 0 and tuple(seq[0].weight.shape) == (64, 5, 3, 3) and B * S * S * 64 * 4 < 2 ** 31):
+    if (S % 32 == 0 and tuple(seq[0].weight.shape) == (64, 5, 3, 3) and B * S * S * 64 * 4 < 2 ** 31):
         # the first layer reads the NCHW input itself; the rest of the block as _block
         y = _t("Conv1.conv.0", FirstConvFn.apply(x.contiguous().float(), seq[0].weight, seq[0].bias))
         y = _bn(seq[1], y, True, "Conv1.conv.1")

@@ -18,7 +18,6 @@ import random
 import numpy as np
 import torch
 
-from .. import _lib
 from ..networks import training as tr
 from ..networks.nbp_model import NBP
 
@@ -29,7 +28,7 @@ def make_optimizer(nbp, lr=0.001):
     element-wise passes of the default `foreach` form: 3 % of a B = 32 training step); same update rule."""
     kw = dict(lr=lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01)
     params = list(nbp.parameters())
-    if params and all(p.is_cuda for p in params) and _lib.tune("NBP_TRAIN_FUSED_ADAMW", "1") == "1":
+    if params and all(p.is_cuda for p in params):
         try:
             return torch.optim.AdamW(params, fused=True, **kw)
         except (RuntimeError, TypeError, ValueError):     # a torch build without the fused kernel
@@ -60,7 +59,7 @@ def make_synthetic_experiences(n, S=256, seed=0):
     return out
 
 
-_STAGE_BATCHES = _lib.tune("NBP_TRAIN_STAGE_BATCHES", "1") == "1"      # 0: every batch through _collate's synchronous copies
+_STAGE_BATCHES = True      # False: every batch through _collate's synchronous copies (the bit-identity tests' reference)
 
 
 def _collate(batch_data, device):

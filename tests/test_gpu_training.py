@@ -636,8 +636,8 @@ def test_training_step_vs_reference_golden_well_conditioned(hip, nbp_weights, go
     # handful of flipped elements: bounded by an order of magnitude around torch's own error instead of 3x
     bad = [(h, t) for h, t in zip(e_hip, e_t32) if h > (max(3.0 * t, 3e-2) if t < 3e-2 else 10.0 * t)]
     assert not bad, bad[:8]
-    # typical tensor: at the chaos level (the fp32-pipe variant, NBP_TRAIN_SPLIT=0, sits at 7e-3 where torch shows 1.3e-3 and
-    # the default split path 2e-3: two flipped elements under the value head, see above)
+    # typical tensor: at the chaos level (a since-retired fp32-pipe variant of the training convolutions sat at 7e-3 where torch
+    # shows 1.3e-3 and the default split path 2e-3: two flipped elements under the value head, see above)
     assert float(np.median(e_hip)) <= max(3.0 * float(np.median(e_t32)), 1e-2), (np.median(e_hip), np.median(e_t32))
 
 

@@ -1,6 +1,6 @@
 """Diagnostic (GPU box): train_experience_data (the trainer's epoch loop: collation, host-to-device copies, forward, backward, an AdamW step every
 8 batches) on host-resident replay records, batch 32 x 256 x 256 -- maps/s with the batches staged on a copy stream and the losses kept on the device
-until the optimizer step (NBP_TRAIN_STAGE_BATCHES=1, default) against the reference's loop shape (0: synchronous copies; and, for the record, its
+until the optimizer step (_STAGE_BATCHES = True, default) against the reference's loop shape (False: synchronous copies; and, for the record, its
 per-batch loss.item(), which round 6 removed in both modes)."""
 import os, sys, time, types, random
 import numpy as np, torch
