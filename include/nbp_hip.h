@@ -865,6 +865,19 @@ int nbp_scatter_values_f32(const float* dpred, const long long* coords_bcxy, int
  * double); dp (optional) = grad_coef * d(mean loss)/dp. */
 int nbp_loss_f32(int mode, const float* p, const float* t, long long n, float grad_coef, double* sum_out,
                  float* dp_or_null, void* ws, size_t ws_bytes, void* stream);
+/* Exact D4 symmetry augmentation of a training batch (csrc/nbp_augment.hip).  The reference defines augment_data
+ * (next_best_path/utility/nbp_utils.py:267-289: flips and 90-degree rotations of the images, p = 0.4) and never calls it; as
+ * written it turns only the images (the sparse targets stay where they were) and an array flip i -> S-1-i moves the input by one
+ * pixel but the value map by one cell.  Here the planes move about the CAMERA: pixel index i = rint((v + 40) S / 80) puts the camera
+ * at S/2, so the reflection v -> -v is i -> S - i.  ops_dev: B op codes on the device, bit 0 = transpose (rows <-> cols), bit 1 =
+ * reflect rows, bit 2 = reflect cols, applied in that order:
+ *     transpose     out[r][c] = in[c][r]
+ *     reflect rows  out[r][c] = in[S - r][c] for r >= 1, out[0][c] = 0 (the mirror image of index 0 is index S, outside the array)
+ * x [B,5,S,S] and gt [B,1,S,S] NCHW fp32 -> x_out, gt_out (out of place, nothing may alias), all 6 B planes in one launch; bit-exact
+ * moves.  The targets' cells and heading channels are remapped on the host (utility/augment.py).  NBP_E_ARG: null pointer, B < 1,
+ * aliasing buffers; NBP_E_SHAPE: S % 16 != 0, 6 B > 65535, a pointer off the 16-byte grid; nothing is written on an error. */
+int nbp_augment_batch_f32(const float* x, const float* gt, const int* ops_dev, int B, int S, float* x_out, float* gt_out,
+                          void* stream);
 
 /* ---- The replay store's container in LMDB's on-disk format (csrc/nbp_mdb.cpp; host only).  The reference keeps its experience
  * records in an LMDB environment (next_best_path/trainers/train_nbp_model.py:61-63 lmdb.open(path, map_size);

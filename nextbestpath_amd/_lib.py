@@ -95,6 +95,7 @@ SIGNATURES = {
     "nbp_gather_values_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "nbp_scatter_values_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "nbp_loss_f32": (_i, [_i, _vp, _vp, _ll, _f, _vp, _vp, _vp, _sz, _vp]),
+    "nbp_augment_batch_f32": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
     "nbp_fuse_obstacle_f32": (_i, [_vp, _vp, _vp, _f, _i, _vp, _vp, _vp]),
     "nbp_score_candidates_f32": (_i, [_vp, _i, _f, _f, _vp, _i, _vp, _i, _f, _f, _vp, _vp, _vp, _vp, _vp]),
     "nbp_edges_blocked_u8": (_i, [_vp, _i, _f, _f, _f, _f, _vp, _vp, _i, _vp, _vp]),

@@ -20,6 +20,7 @@ import torch
 
 from ..networks import training as tr
 from ..networks.nbp_model import NBP
+from ..utility import augment, hipops
 
 
 def make_optimizer(nbp, lr=0.001):
@@ -128,8 +129,9 @@ class _BatchStager:
         return out, ev
 
 
-def _collate_staged(batch_data, device, stager):
-    """_collate with the copies on the stager's stream: returns the same five tensors; the CURRENT stream waits for them."""
+def _collate_staged(batch_data, device, stager, ops=None):
+    """_collate with the copies on the stager's stream: returns the same five tensors; the CURRENT stream waits for them.
+    `ops` (augmentation op codes, int32 [n]; None without augmentation) ride along as a sixth tensor."""
     n = len(batch_data)
     x0 = batch_data[0]["current_model_input"]
     S = x0.shape[-1]
@@ -145,6 +147,8 @@ def _collate_staged(batch_data, device, stager):
     cd = stager.buffer("coords", (K, 3), torch.int64).numpy()
     gn = stager.buffer("gains", (K,), torch.float32).numpy()
     bi = stager.buffer("bidx", (K,), torch.int64).numpy()
+    if ops is not None:
+        stager.buffer("ops", (n,), torch.int32).numpy()[:] = ops
     k = 0
     for i, (d, c) in enumerate(zip(batch_data, coords)):
         xs[i] = d["current_model_input"][0]
@@ -155,15 +159,18 @@ def _collate_staged(batch_data, device, stager):
         bi[k:k + m] = i
         k += m
     dev, ev = stager.commit()
-    return (dev["xs"], dev["gt"], dev["coords"], dev["gains"], dev["bidx"]), ev
+    out = (dev["xs"], dev["gt"], dev["coords"], dev["gains"], dev["bidx"])
+    return (out if ops is None else out + (dev["ops"],)), ev
 
 
-def _collate_any(batch_data, device, stager):
+def _collate_any(batch_data, device, stager, ops=None):
     """Staged collation for records of the replay store's shape (one map per record); anything else through _collate."""
     if all(d["current_model_input"].shape[0] == 1 and d["current_gt_2d_layout"].shape[0] == 1 for d in batch_data):
-        return _collate_staged(batch_data, device, stager)
+        return _collate_staged(batch_data, device, stager, ops)
     ev = torch.cuda.Event()
     out = _collate(batch_data, device)
+    if ops is not None:
+        out = out + (torch.from_numpy(np.asarray(ops, dtype=np.int32)).to(device),)
     ev.record(torch.cuda.current_stream(device))
     return out, ev
 
@@ -223,14 +230,38 @@ def _mean_over_ranks(x: float, device) -> float:
     return float(t.item()) / dist.get_world_size()
 
 
+def _augment_rng(params):
+    """The trainer's own generator for the augmentation draws: one per params object, so that it runs on across the inner epochs
+    and never touches the global `random` (which shuffles the replay set).  Seed: `augment_seed`, else random_seed + rank."""
+    rng = getattr(params, "_augment_rng", None)
+    if rng is None:
+        seed = getattr(params, "augment_seed", None)
+        if seed is None:
+            dist = _dist()
+            seed = int(getattr(params, "random_seed", 0)) + (dist.get_rank() if dist is not None else 0)
+        rng = random.Random(f"nbp-augment-{int(seed)}")
+        params._augment_rng = rng
+    return rng
+
+
 def train_experience_data(training_set_db, params, optimizer, nbp, device, current_epoch):
     """ref nbp_utils.py:340-395 (GradScaler without autocast is the identity scale for fp32; omitted -- the "fp16"
     train_precision scales every fp16 operand per tensor instead, NBP.train_precision).  As in the
     reference the early poses (pose_i <= 10) are dropped INSIDE each batch during epoch 1 (:348-362), a batch left empty
     is skipped before the optimiser-step test (:364-365), and the step fires every 8 non-empty batches or on the batch
     that reaches the end of the set (:385).  Under torchrun the ranks agree on "empty" and on the batch count, because
-    the step contains the gradient all-reduce."""
+    the step contains the gradient all-reduce.
+
+    Not in the reference's loop (its augment_data, nbp_utils.py:267-289, is never called): with params.augment_probability = p > 0
+    every sample is moved, with probability p, by one of the seven non-identity symmetries of the square about the camera
+    (utility/augment.py) -- the targets' cells and heading channels on the host before collation, on shallow copies of the records,
+    the six planes on the device behind the staged copy (one launch, hipops.augment_batch).  p = 0 (the default) draws nothing and
+    launches nothing."""
     random.shuffle(training_set_db)
+    aug_p = float(getattr(params, "augment_probability", 0.0) or 0.0)
+    if not 0.0 <= aug_p <= 1.0:
+        raise ValueError(f"augment_probability {aug_p} outside [0, 1]")
+    aug_rng = _augment_rng(params) if aug_p > 0 else None
     # the batch losses of an accumulation window stay on the device until its optimizer step (the reference's `batch_loss.item()`
     # per batch, nbp_utils.py:384, is a device synchronisation per batch: the GPU then idles through the next batch's collation and
     # host-to-device copy).  Same numbers: the same fp32 losses, converted and added as Python floats in the same order.
@@ -247,6 +278,13 @@ def train_experience_data(training_set_db, params, optimizer, nbp, device, curre
             batch = [d for d in batch if d["pose_i"] > 10]
         return batch
 
+    def augmented(batch):
+        """-> (records with their targets moved, op codes) -- (batch, None) without augmentation"""
+        if aug_rng is None:
+            return batch, None
+        ops = augment.draw_ops(aug_rng, len(batch), aug_p)
+        return augment.augment_records(batch, ops, batch[0]["current_model_input"].shape[-1] // 4), ops
+
     staged = None            # (batch index, tensors, event) of the batch whose copies were started under the previous one's compute
     for bi in range(n_batches):
         batch = batch_of(bi)
@@ -256,14 +294,22 @@ def train_experience_data(training_set_db, params, optimizer, nbp, device, curre
         if not have:
             continue
         if stager is None:
+            batch, ops = augmented(batch)
             xs, gt, coords, gains, bidx = _collate(batch, device)
+            if ops is not None:
+                ops = torch.from_numpy(ops).to(device)
         else:
             if staged is None or staged[0] != bi:
-                staged = (bi,) + _collate_any(batch, device, stager)
-            (xs, gt, coords, gains, bidx), ev = staged[1], staged[2]
+                batch, ops = augmented(batch)
+                staged = (bi,) + _collate_any(batch, device, stager, ops)
+            tensors, ev = staged[1], staged[2]
             torch.cuda.current_stream(device).wait_event(ev)
-            for t in (xs, gt, coords, gains, bidx):
+            for t in tensors:
                 t.record_stream(torch.cuda.current_stream(device))
+            xs, gt, coords, gains, bidx = tensors[:5]
+            ops = tensors[5] if len(tensors) > 5 else None
+        if ops is not None:
+            xs, gt = hipops.augment_batch(xs, gt, ops)
         out1, out2 = nbp(xs)
         pred = tr.gather_values(out1, bidx, coords)
         loss = nbp.loss(pred, gains, out2, gt)
@@ -272,7 +318,11 @@ def train_experience_data(training_set_db, params, optimizer, nbp, device, curre
         updates += 1
         if stager is not None and bi + 1 < n_batches:       # the next batch's collation and copies, under this batch's kernels
             nb = batch_of(bi + 1)
-            staged = ((bi + 1,) + _collate_any(nb, device, stager)) if nb else None
+            if nb:
+                nb, nops = augmented(nb)
+                staged = (bi + 1,) + _collate_any(nb, device, stager, nops)
+            else:
+                staged = None
         if updates % accumulation_steps == 0 or bi + 1 == n_batches:
             allreduce_gradients(nbp)
             optimizer.step()

@@ -649,3 +649,20 @@ def append_points(dst, offset, pts_host):
     a = np.ascontiguousarray(np.asarray(pts_host, np.float32).reshape(-1, 3))
     rc = _lib.lib().nbp_append_points_f32(_lib.ptr(dst), int(offset), a.ctypes.data_as(C.POINTER(C.c_float)), a.shape[0], _st())
     _lib.check(rc, "nbp_append_points_f32")
+
+
+def augment_batch(x, gt, ops):
+    """x [B,5,S,S], gt [B,1,S,S] fp32 and ops int32 [B] (op codes of utility/augment.py), all on the device -> (x', gt'): every
+    sample's six planes moved by its element of D4 about the camera, one launch (nbp_augment_batch_f32), out of place."""
+    for name, t in (("x", x), ("gt", gt), ("ops", ops)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError(f"augment_batch: the HIP path needs a cuda tensor for {name} (no CPU fallback)")
+    B, S = x.shape[0], x.shape[-1]
+    if (x.dtype != torch.float32 or gt.dtype != torch.float32 or ops.dtype != torch.int32 or tuple(x.shape) != (B, 5, S, S)
+            or tuple(gt.shape) != (B, 1, S, S) or tuple(ops.shape) != (B,)):
+        raise ValueError("augment_batch: x [B,5,S,S] fp32, gt [B,1,S,S] fp32 and ops [B] int32 expected")
+    x_out, gt_out = torch.empty_like(x), torch.empty_like(gt)
+    with torch.cuda.device(x.device):
+        rc = _lib.lib().nbp_augment_batch_f32(_lib.ptr(x), _lib.ptr(gt), _lib.ptr(ops), B, S, _lib.ptr(x_out), _lib.ptr(gt_out), _st())
+    _lib.check(rc, "nbp_augment_batch_f32")
+    return x_out, gt_out

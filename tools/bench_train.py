@@ -1,20 +1,23 @@
 #!/usr/bin/env python
 """Config 3 of BASELINE.json: NBP fwd + bwd + AdamW step, batch of 256x256 maps, fp32, 1 MI355X.
-    python tools/bench_train.py [--batch 32] [--steps 5] [--size 256] [--precision fp32_split|fp16]
+    python tools/bench_train.py [--batch 32] [--steps 5] [--size 256] [--precision fp32_split|fp16] [--augment P]
 Prints one JSON line: train maps/s, TFLOP/s against 546.9 GFLOP/map, and the torch-CPU baseline
 (stock autograd on the same weights = the reference's arithmetic) on a bounded sample."""
 import argparse
 import json
 import os
+import random
 import sys
 import time
 
+import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from nextbestpath_amd.networks import training as tr  # noqa: E402
 from nextbestpath_amd.networks.nbp_model import NBP  # noqa: E402
 from nextbestpath_amd.trainers.train_nbp_model import _collate, make_optimizer, make_synthetic_experiences  # noqa: E402
+from nextbestpath_amd.utility import augment, hipops  # noqa: E402
 
 
 def main():
@@ -26,6 +29,9 @@ def main():
     ap.add_argument("--cpu-batch", type=int, default=2)
     ap.add_argument("--precision", choices=tr.TRAIN_PRECISIONS, default="fp32_split",
                     help="NBP.train_precision: the split path (default) or scaled fp16 mixed precision")
+    ap.add_argument("--augment", type=float, default=0.0,
+                    help="augment_probability: with P > 0 every step draws its op codes, remaps the targets on the host, copies the "
+                         "codes to the device and moves the batch with hipops.augment_batch (the trainer's per-batch work)")
     a = ap.parse_args()
     dev = torch.device("cuda")
     torch.manual_seed(9)
@@ -35,9 +41,27 @@ def main():
     db = make_synthetic_experiences(a.batch, a.size, seed=3)
     xs, gt, coords, gains, bidx = _collate(db, dev)
 
+    aug_rng = random.Random(5)
+    ops_dev = torch.zeros(a.batch, dtype=torch.int32, device=dev)
+
+    def targets(records):
+        """The sparse targets of remapped records on the device (pinned, asynchronous copies as the trainer's stager makes)."""
+        cd = np.concatenate([d["target_value_map_pixel"] for d in records])
+        gn = np.concatenate([d["actual_coverage_gain"] for d in records])
+        bi = np.repeat(np.arange(len(records)), [len(d["target_value_map_pixel"]) for d in records])
+        return [torch.from_numpy(v).pin_memory().to(dev, non_blocking=True) for v in (cd, gn, bi)]
+
     def step():
-        o1, o2 = net(xs)
-        loss = net.loss(tr.gather_values(o1, bidx, coords), gains, o2, gt)
+        if a.augment > 0:
+            ops = augment.draw_ops(aug_rng, a.batch, a.augment)
+            ops_dev.copy_(torch.from_numpy(ops).pin_memory(), non_blocking=True)
+            cd, gn, bi = targets(augment.augment_records(db, ops, a.size // 4))
+            xa, ga = hipops.augment_batch(xs, gt, ops_dev)
+            o1, o2 = net(xa)
+            loss = net.loss(tr.gather_values(o1, bi, cd), gn, o2, ga)
+        else:
+            o1, o2 = net(xs)
+            loss = net.loss(tr.gather_values(o1, bidx, coords), gains, o2, gt)
         loss.backward()
         opt.step()
         opt.zero_grad(set_to_none=True)
@@ -74,7 +98,7 @@ def main():
     print(json.dumps({
         "metric": f"NBP training maps/s (fwd+bwd+AdamW, {a.precision})", "value": round(a.batch / dt, 3), "unit": "maps/s",
         "n_gpus": 1, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(dt * 1e3, 2), "dtype": "f32",
-        "train_precision": a.precision,
+        "train_precision": a.precision, "augment_probability": a.augment,
         "data": "synthetic", "config": {"workload": f"configs[2]: train step, batch {a.batch} x {a.size}x{a.size}"},
         "tflops_reference_formulation": round(a.batch * flop_map / dt / 1e12, 2), "frac_of_split_ceiling_reference_formulation": round(a.batch * flop_map / dt / (2500e12 / 3), 4),
         "loss": float(loss.item()), "producer_notes": dict(tr.HANDOFF_STATS),
