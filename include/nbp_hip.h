@@ -879,6 +879,42 @@ int nbp_loss_f32(int mode, const float* p, const float* t, long long n, float gr
 int nbp_augment_batch_f32(const float* x, const float* gt, const int* ops_dev, int B, int S, float* x_out, float* gt_out,
                           void* stream);
 
+/* ---- The optimizer step (csrc/nbp_optim.hip): the reference's torch.optim.AdamW(lr 1e-3, betas (0.9, 0.999), eps 1e-8, weight decay
+ * 0.01) of next_best_path/utility/nbp_utils.py:228 and its scaler.step(optimizer) / scaler.update() of nbp_utils.py:386-388 (a
+ * GradScaler drops a step whose gradients hold an inf or a NaN), plus the global-norm clipping of torch.nn.utils.clip_grad_norm_,
+ * as multi-tensor kernels over separately allocated fp32 tensors.  Host binding: nextbestpath_amd/optim.py::HipAdamW.
+ * Tables on the device, built by the caller:
+ *   descs   one record per tensor  { float* p; const float* g; float* m; float* v; int64 numel; }     (nbp_optim_desc_bytes() = 40)
+ *   chunks  one record per workgroup { int64 first; int32 tensor; int32 pad; } (16 bytes): elements [first, first + chunk) of that
+ *           tensor, clipped to numel; first is a multiple of nbp_optim_chunk_elems() (16384).  Any numel >= 1; 16-byte accesses
+ *           where the tensor's four base addresses are 16-byte aligned, 4-byte accesses otherwise (same results).
+ *   state   nbp_optim_state_bytes(n_groups) = 32 + 8 n_groups bytes, zeroed before the first step:
+ *           { f32 total_norm; f32 clip_coef; i32 finite; i32 applied; f32 step; i32 skipped_steps; i32 pad[2];
+ *             { f32 bc1 = 1 - beta1^step; f32 sqrt_bc2 = sqrt(1 - beta2^step); } per param group }
+ * nbp_optim_workspace_bytes(n_chunks): one double per chunk.  n_groups <= 16. */
+int nbp_optim_desc_bytes(void);
+int nbp_optim_chunk_elems(void);
+size_t nbp_optim_workspace_bytes(long long n_chunks);
+size_t nbp_optim_state_bytes(int n_groups);
+/* clip_grad_norm_'s reduction (the norm behind nbp_utils.py:386-388's inf / NaN test): ws[c] = sum of g^2 over chunk c, products and
+ * additions in double in an order fixed by element position (no atomics: two runs give the same bits). */
+int nbp_grad_sqnorm_f32(const void* descs_dev, const void* chunks_dev, int n_chunks, void* ws, size_t ws_bytes, void* stream);
+/* One workgroup: total_norm = sqrt(sum of ws[0 .. n_chunks) in a fixed order, double); clip_coef = min(1, max_norm / (total_norm + 1e-6))
+ * (clip_grad_norm_'s rule; exactly 1.0f when max_norm <= 0 = clipping off); finite = the sum is finite; the step is applied unless
+ * skip_nonfinite and not finite (scaler.step, nbp_utils.py:386): then step += 1, the bias corrections of every group are recomputed
+ * in double from betas_host [n_groups][2] (read during the call) and steps_or_null [n_steps] (the per-parameter `step` scalars of the
+ * optimizer state, nbp_utils.py:228) all receive the new step; otherwise skipped_steps += 1 and nothing else moves.
+ * ws_or_null = NULL: no norm pass ran (then max_norm <= 0 and skip_nonfinite = 0, else NBP_E_ARG): total_norm = 0, coef = 1. */
+int nbp_optim_finalize_f32(const void* ws_or_null, int n_chunks, double max_norm, int skip_nonfinite, const double* betas_host,
+                           int n_groups, void* state, void* steps_or_null, int n_steps, void* stream);
+/* torch.optim.AdamW's update (nbp_utils.py:228) of the tensors the chunks name, for param group `group` of the state block:
+ *   g^ = clip_coef g;  p <- p (1 - lr wd);  m <- beta1 m + (1 - beta1) g^;  v <- beta2 v + (1 - beta2) g^^2;
+ *   p <- p - (lr / bc1) m / (sqrt(v) / sqrt_bc2 + eps)
+ * m and v are evaluated in double and rounded once, p in fp32.  g is only read (clip_grad_norm_ scales the gradients in place; here
+ * the coefficient is applied on load).  Writes nothing when the state block says the step is skipped (state.applied = 0). */
+int nbp_adamw_f32(const void* descs_dev, const void* chunks_dev, int n_chunks, const void* state, int group, double lr, double beta1,
+                  double beta2, double eps, double weight_decay, void* stream);
+
 /* ---- The replay store's container in LMDB's on-disk format (csrc/nbp_mdb.cpp; host only).  The reference keeps its experience
  * records in an LMDB environment (next_best_path/trainers/train_nbp_model.py:61-63 lmdb.open(path, map_size);
  * next_best_path/utility/nbp_utils.py:32-141: txn.put per record, ordered cursors, txn.delete of the validation records).  liblmdb is

@@ -212,6 +212,13 @@ SIGNATURES["nbp_slice_obstacle_fig_f32"] = (_i, [_vp, _vp, _i, _f, _f, _f, _i, _
 SIGNATURES["nbp_slice_obstacle_fig_batch_f32"] = (_i, [_i, _vp, _vp, _vp, _vp, _i, _f, _f, _f, _f, _f, _f, _vp, _vp])
 SIGNATURES["nbp_goal_values_batch_f32"] = (_i, [_i, _vp, _vp, _vp, _vp, _i, _f, _f, _vp, _vp, _vp])
 SIGNATURES["nbp_hindsight_cells_batch_i32"] = (_i, [_i, _vp, _vp, _i, _f, _f, _vp, _vp])
+SIGNATURES["nbp_optim_desc_bytes"] = (_i, [])
+SIGNATURES["nbp_optim_chunk_elems"] = (_i, [])
+SIGNATURES["nbp_optim_workspace_bytes"] = (_sz, [_ll])
+SIGNATURES["nbp_optim_state_bytes"] = (_sz, [_i])
+SIGNATURES["nbp_grad_sqnorm_f32"] = (_i, [_vp, _vp, _i, _vp, _sz, _vp])
+SIGNATURES["nbp_optim_finalize_f32"] = (_i, [_vp, _i, _d, _i, C.POINTER(_d), _i, _vp, _vp, _i, _vp])
+SIGNATURES["nbp_adamw_f32"] = (_i, [_vp, _vp, _i, _vp, _i, _d, _d, _d, _d, _d, _vp])
 
 _lock = threading.Lock()
 _lib = None

@@ -5,7 +5,9 @@ Reference: next_best_path/utility/nbp_utils.py:340-395 (train_experience_data) d
 ``nbp.train(); out1, out2 = nbp(x); loss = nbp.loss(...); loss.backward()``; the layers are
 next_best_path/networks/nbp_model.py:8-62.  Here every layer is a ``torch.autograd.Function`` whose
 forward and backward are C-ABI kernel launches; torch's autograd engine only threads them together
-(plumbing) and torch.optim.AdamW applies the update, as the survey's build plan allows.
+(plumbing).  The update is applied by the optimizer trainers/train_nbp_model.py::make_optimizer returns:
+torch's fused AdamW by default, or this package's own kernels (nextbestpath_amd/optim.py::HipAdamW,
+csrc/nbp_optim.hip) with the trainer option "optimizer": "hip".
 
 Activations are NHWC ``[B,H,W,C]`` fp32; channel counts are padded to multiples of 64 where the
 matrix-core kernels need it (network input 5->64, F_int 32->64, final 8/1->64) and sliced back, so

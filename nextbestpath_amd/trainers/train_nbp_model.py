@@ -23,12 +23,31 @@ from ..networks.nbp_model import NBP
 from ..utility import augment, hipops
 
 
-def make_optimizer(nbp, lr=0.001):
-    """The reference's optimizer (nbp_utils.py:228): AdamW(lr 1e-3, betas (0.9, 0.999), eps 1e-8, weight decay 0.01).  On the device the
-    update of the 200 MB of parameters runs as torch's FUSED multi-tensor kernel (one pass over p, g, m, v instead of the ~10
-    element-wise passes of the default `foreach` form: 3 % of a B = 32 training step); same update rule."""
+OPTIMIZERS = ("torch", "hip")
+
+
+def make_optimizer(nbp, lr=0.001, impl="torch", grad_clip_norm=None, skip_nonfinite_steps=False):
+    """The reference's optimizer (nbp_utils.py:228): AdamW(lr 1e-3, betas (0.9, 0.999), eps 1e-8, weight decay 0.01).
+
+    impl "torch" (the default): on the device the update of the 200 MB of parameters runs as torch's FUSED multi-tensor kernel (one
+    pass over p, g, m, v instead of the ~10 element-wise passes of the default `foreach` form: 3 % of a B = 32 training step); same
+    update rule.  impl "hip": nextbestpath_amd.optim.HipAdamW, the same rule on this project's kernels (csrc/nbp_optim.hip), which
+    can also clip the global gradient norm to `grad_clip_norm` (clip_grad_norm_'s coefficient, applied as the gradients are read:
+    p.grad itself is left alone) and drop a step whose gradients hold an inf or a NaN (`skip_nonfinite_steps`; what the
+    reference's GradScaler does at nbp_utils.py:386-388), both decided on the device without a host synchronisation.  The two
+    options exist only there: with impl "torch" they raise instead of being emulated with torch operations."""
+    if impl not in OPTIMIZERS:
+        raise ValueError(f"optimizer {impl!r}: expected one of {OPTIMIZERS}")
+    if grad_clip_norm is not None and not (isinstance(grad_clip_norm, (int, float)) and not isinstance(grad_clip_norm, bool)
+                                           and grad_clip_norm > 0 and np.isfinite(grad_clip_norm)):
+        raise ValueError(f"grad_clip_norm must be a positive number or None, not {grad_clip_norm!r}")
     kw = dict(lr=lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01)
     params = list(nbp.parameters())
+    if impl == "hip":
+        from ..optim import HipAdamW
+        return HipAdamW(params, max_grad_norm=grad_clip_norm, skip_nonfinite=bool(skip_nonfinite_steps), **kw)
+    if grad_clip_norm is not None or skip_nonfinite_steps:
+        raise ValueError('grad_clip_norm / skip_nonfinite_steps need the HIP optimizer: set "optimizer": "hip" (impl="hip")')
     if params and all(p.is_cuda for p in params):
         try:
             return torch.optim.AdamW(params, fused=True, **kw)
@@ -38,8 +57,11 @@ def make_optimizer(nbp, lr=0.001):
 
 
 def initialize_nbp(params, nbp, torch_seed=9, initialize=False, pretrained=False, ddp_rank=None):
-    """ref nbp_utils.py:213-231: AdamW(lr 1e-3, betas (0.9, 0.999), eps 1e-8, weight decay 0.01)."""
-    return nbp, make_optimizer(nbp), 10000.0, 0
+    """ref nbp_utils.py:213-231: AdamW(lr 1e-3, betas (0.9, 0.999), eps 1e-8, weight decay 0.01).  The config's `optimizer`
+    ("torch" | "hip"), `grad_clip_norm` (null | > 0) and `skip_nonfinite_steps` choose make_optimizer's form."""
+    opt = make_optimizer(nbp, impl=getattr(params, "optimizer", "torch"), grad_clip_norm=getattr(params, "grad_clip_norm", None),
+                         skip_nonfinite_steps=bool(getattr(params, "skip_nonfinite_steps", False)))
+    return nbp, opt, 10000.0, 0
 
 
 def make_synthetic_experiences(n, S=256, seed=0):
@@ -244,7 +266,7 @@ def _augment_rng(params):
     return rng
 
 
-def train_experience_data(training_set_db, params, optimizer, nbp, device, current_epoch):
+def train_experience_data(training_set_db, params, optimizer, nbp, device, current_epoch, grad_norms=None):
     """ref nbp_utils.py:340-395 (GradScaler without autocast is the identity scale for fp32; omitted -- the "fp16"
     train_precision scales every fp16 operand per tensor instead, NBP.train_precision).  As in the
     reference the early poses (pose_i <= 10) are dropped INSIDE each batch during epoch 1 (:348-362), a batch left empty
@@ -328,7 +350,13 @@ def train_experience_data(training_set_db, params, optimizer, nbp, device, curre
             optimizer.step()
             optimizer.zero_grad()
             accumulated = 0.0
-            for v in torch.stack(pending).tolist():       # (one device -> host copy per optimizer step)
+            with_norm = bool(getattr(optimizer, "norm_pass", False))
+            values = torch.stack(pending + [optimizer.last_grad_norm] if with_norm else pending).tolist()   # (one device -> host copy per optimizer step)
+            if with_norm:
+                norm = values.pop()
+                if grad_norms is not None:
+                    grad_norms.append(norm)
+            for v in values:
                 accumulated += v
             training_loss.append(accumulated / accumulation_steps)
             pending, updates = [], 0
@@ -374,13 +402,13 @@ def validation_model(training_set_db, params, nbp, device):
 
 
 def train_nbp(training_set_db, params, optimizer, nbp, device, current_epoch, validation_data, lr_patience=2,
-              lr_factor=0.1, num_epochs=5):
-    """ref nbp_utils.py:430-468: 5 inner epochs, validation after each, ReduceLROnPlateau."""
+              lr_factor=0.1, num_epochs=5, grad_norms=None):
+    """ref nbp_utils.py:430-468: 5 inner epochs, validation after each, ReduceLROnPlateau.  grad_norms: see train_experience_data."""
     sched = torch.optim.lr_scheduler.ReduceLROnPlateau(optimizer, mode="min", factor=lr_factor, patience=lr_patience)
     tl, vl = [], []
     for _ in range(num_epochs):
         nbp.train()
-        losses = train_experience_data(training_set_db, params, optimizer, nbp, device, current_epoch)
+        losses = train_experience_data(training_set_db, params, optimizer, nbp, device, current_epoch, grad_norms)
         tl.append(float(np.mean(losses)) if losses else float("nan"))
         sync_buffers(nbp)
         nbp.eval()
@@ -412,11 +440,15 @@ def run_training_nbp(params):
     collect = bool(getattr(params, "collect", True)) and data_path and os.path.isdir(data_path)
     history = {}
 
-    def save(epoch, vl, tl):
+    with_norm = bool(getattr(optimizer, "norm_pass", False))      # the HIP optimizer with clipping or skipping on
+
+    def save(epoch, vl, tl, grad_norms):
         nonlocal best_loss
         if rank != 0:
             return
         history[epoch] = {"training_loss": tl, "validation_loss": vl}
+        if with_norm:       # one norm per optimizer step of the epoch; the running count of dropped steps (validation has synchronised)
+            history[epoch].update(grad_norm=list(grad_norms), skipped_steps=int(optimizer.skipped_steps.item()))
         ck = {"epoch": epoch, "model_state_dict": nbp.state_dict(), "optimizer_state_dict": optimizer.state_dict()}
         if vl < best_loss:
             best_loss = vl
@@ -430,9 +462,10 @@ def run_training_nbp(params):
         validation = make_synthetic_experiences(getattr(params, "n_validation_synthetic", 16), S, seed=1)
         for epoch in range(1, params.epochs + 1):
             db = make_synthetic_experiences(params.samples_per_epoch, S, seed=100 + epoch + 1000 * rank)
-            tl, vl = train_nbp(db, params, optimizer, nbp, device, epoch, validation, num_epochs=params.inner_epochs)
+            norms = []
+            tl, vl = train_nbp(db, params, optimizer, nbp, device, epoch, validation, num_epochs=params.inner_epochs, grad_norms=norms)
             print(f"epoch {epoch}: training {tl:.4f} validation {vl:.4f}")
-            save(epoch, vl, tl)
+            save(epoch, vl, tl, norms)
         return history
 
     dataset = sim_scene.SceneDataset(data_path, getattr(params, "train_scenes", []))
@@ -455,8 +488,9 @@ def run_training_nbp(params):
         # every rank must take the same branch (the training loop below contains collectives)
         if _common_count(1 if (db and validation) else 0, device) == 0:
             continue
-        tl, vl = train_nbp(db, params, optimizer, nbp, device, epoch, validation, num_epochs=params.inner_epochs)
+        norms = []
+        tl, vl = train_nbp(db, params, optimizer, nbp, device, epoch, validation, num_epochs=params.inner_epochs, grad_norms=norms)
         print(f"epoch {epoch}: training {tl:.4f} validation {vl:.4f}")
-        save(epoch, vl, tl)
+        save(epoch, vl, tl, norms)
     env.close()
     return history

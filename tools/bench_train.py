@@ -1,6 +1,7 @@
 #!/usr/bin/env python
 """Config 3 of BASELINE.json: NBP fwd + bwd + AdamW step, batch of 256x256 maps, fp32, 1 MI355X.
     python tools/bench_train.py [--batch 32] [--steps 5] [--size 256] [--precision fp32_split|fp16] [--augment P]
+                                [--optimizer torch|hip] [--clip X]
 Prints one JSON line: train maps/s, TFLOP/s against 546.9 GFLOP/map, and the torch-CPU baseline
 (stock autograd on the same weights = the reference's arithmetic) on a bounded sample."""
 import argparse
@@ -32,12 +33,16 @@ def main():
     ap.add_argument("--augment", type=float, default=0.0,
                     help="augment_probability: with P > 0 every step draws its op codes, remaps the targets on the host, copies the "
                          "codes to the device and moves the batch with hipops.augment_batch (the trainer's per-batch work)")
+    ap.add_argument("--optimizer", choices=("torch", "hip"), default="torch",
+                    help="make_optimizer's impl: torch's fused AdamW (default) or HipAdamW (csrc/nbp_optim.hip)")
+    ap.add_argument("--clip", type=float, default=None,
+                    help="grad_clip_norm X > 0: global-norm clipping inside HipAdamW.step() (needs --optimizer hip)")
     a = ap.parse_args()
     dev = torch.device("cuda")
     torch.manual_seed(9)
     net = NBP().to(dev).train()
     net.train_precision = a.precision
-    opt = make_optimizer(net)
+    opt = make_optimizer(net, impl=a.optimizer, grad_clip_norm=a.clip)
     db = make_synthetic_experiences(a.batch, a.size, seed=3)
     xs, gt, coords, gains, bidx = _collate(db, dev)
 
@@ -98,7 +103,7 @@ def main():
     print(json.dumps({
         "metric": f"NBP training maps/s (fwd+bwd+AdamW, {a.precision})", "value": round(a.batch / dt, 3), "unit": "maps/s",
         "n_gpus": 1, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(dt * 1e3, 2), "dtype": "f32",
-        "train_precision": a.precision, "augment_probability": a.augment,
+        "train_precision": a.precision, "augment_probability": a.augment, "optimizer": a.optimizer, "grad_clip_norm": a.clip,
         "data": "synthetic", "config": {"workload": f"configs[2]: train step, batch {a.batch} x {a.size}x{a.size}"},
         "tflops_reference_formulation": round(a.batch * flop_map / dt / 1e12, 2), "frac_of_split_ceiling_reference_formulation": round(a.batch * flop_map / dt / (2500e12 / 3), 4),
         "loss": float(loss.item()), "producer_notes": dict(tr.HANDOFF_STATS),
