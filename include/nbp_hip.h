@@ -915,6 +915,25 @@ int nbp_optim_finalize_f32(const void* ws_or_null, int n_chunks, double max_norm
 int nbp_adamw_f32(const void* descs_dev, const void* chunks_dev, int n_chunks, const void* state, int group, double lr, double beta1,
                   double beta2, double eps, double weight_decay, void* stream);
 
+/* ---- Weight averaging (csrc/nbp_ema.hip).  Not in the reference: an exponential moving average of the tensors of the
+ * network under training, kept on the device behind the optimizer step.  Host binding: nextbestpath_amd/optim.py::WeightEMA.
+ * Tables on the device, built by the caller:
+ *   descs   one record per tensor  { const float* p; float* e; int64 numel; }                           (nbp_ema_desc_bytes() = 24)
+ *   chunks  the optimizer's chunk records { int64 first; int32 tensor; int32 pad; }: nbp_optim_chunk_elems() elements of a tensor
+ *           per workgroup.  Any numel >= 1; 16-byte accesses where p and e are 16-byte aligned, 4-byte accesses otherwise (same
+ *           results).  p and e must not overlap.
+ *   state   nbp_ema_state_bytes() = 16 bytes, zeroed before the first update: { i32 num_updates; i32 pad[3]; }
+ * One update:  d = warmup ? min(decay, (1 + num_updates) / (10 + num_updates)) : decay   (double, on the device);
+ *              e <- fl32(d e + (1 - d) p)   evaluated in double and rounded once;   num_updates += 1 (a one-thread launch behind the
+ *              update's, so the workgroups that read the counter never race its increment).
+ * optim_state_or_null: the state block of nbp_optim_finalize_f32, read behind it on the same stream; when its `applied` word is 0
+ * (a step dropped for non-finite gradients) the update writes nothing: e and num_updates keep their bits.  NULL: always applied.
+ * No atomics: two runs give the same bits.  NBP_E_ARG: null table or state, n_chunks < 1, decay outside [0, 1). */
+int nbp_ema_desc_bytes(void);
+size_t nbp_ema_state_bytes(void);
+int nbp_ema_update_f32(const void* descs_dev, const void* chunks_dev, int n_chunks, void* ema_state, const void* optim_state_or_null,
+                       double decay, int warmup, void* stream);
+
 /* ---- The replay store's container in LMDB's on-disk format (csrc/nbp_mdb.cpp; host only).  The reference keeps its experience
  * records in an LMDB environment (next_best_path/trainers/train_nbp_model.py:61-63 lmdb.open(path, map_size);
  * next_best_path/utility/nbp_utils.py:32-141: txn.put per record, ordered cursors, txn.delete of the validation records).  liblmdb is

@@ -219,6 +219,9 @@ SIGNATURES["nbp_optim_state_bytes"] = (_sz, [_i])
 SIGNATURES["nbp_grad_sqnorm_f32"] = (_i, [_vp, _vp, _i, _vp, _sz, _vp])
 SIGNATURES["nbp_optim_finalize_f32"] = (_i, [_vp, _i, _d, _i, C.POINTER(_d), _i, _vp, _vp, _i, _vp])
 SIGNATURES["nbp_adamw_f32"] = (_i, [_vp, _vp, _i, _vp, _i, _d, _d, _d, _d, _d, _vp])
+SIGNATURES["nbp_ema_desc_bytes"] = (_i, [])
+SIGNATURES["nbp_ema_state_bytes"] = (_sz, [])
+SIGNATURES["nbp_ema_update_f32"] = (_i, [_vp, _vp, _i, _vp, _vp, _d, _i, _vp])
 
 _lock = threading.Lock()
 _lib = None

@@ -138,6 +138,13 @@ class NBP(nn.Module):
         self._packed_key = None
         self._tensors = None
 
+    def __getstate__(self):
+        # copy.deepcopy / pickle: the pack handle and the captured graphs belong to THIS object (a copied handle would be freed
+        # twice); the copy packs its own weights at its first eval forward
+        state = dict(self.__dict__)
+        state.update(_packed=None, _graphs={}, _packed_key=None, _tensors=None)
+        return state
+
     def forward_static(self, x: torch.Tensor):
         """Eval forward on a PERSISTENT input tensor (a rollout's net_in): captured once per (tensor, weights) into a hipGraph and
         replayed (packing.ForwardGraph).  Returns the graph's own out1 / out2: ALIASED buffers, overwritten by the next call on

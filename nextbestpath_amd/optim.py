@@ -25,9 +25,13 @@ pinned memory on the stream.  Dtypes and layouts are validated when the tables a
 and the param groups carry torch's keys, so a ``state_dict()`` loads into a ``torch.optim.AdamW`` and back.  One step counter serves
 every parameter: all parameters that are ever updated must have a gradient from the first step on, and a loaded state whose ``step``
 values differ is refused.  There is no CPU path: parameters off the GPU raise ``RuntimeError``.
+
+``WeightEMA`` (below, csrc/nbp_ema.hip) keeps an exponential moving average of a module's weights on the device, gated by the
+optimizer's own decision to apply or drop a step.
 """
 from __future__ import annotations
 
+import copy
 import ctypes
 
 import numpy as np
@@ -39,6 +43,7 @@ _DESC = np.dtype([("p", "<u8"), ("g", "<u8"), ("m", "<u8"), ("v", "<u8"), ("nume
 _CHUNK = np.dtype([("first", "<i8"), ("tensor", "<i4"), ("pad", "<i4")])
 # the state block as 32-bit words (include/nbp_hip.h): floats 0 total_norm, 1 clip_coef, 4 step; ints 2 finite, 3 applied, 5 skipped_steps
 _W_NORM, _W_STEP, _W_SKIPPED, _W_HEADER = 0, 4, 5, 8
+_EMA_DESC = np.dtype([("p", "<u8"), ("e", "<u8"), ("numel", "<i8")])
 
 
 def _upload(arr, dst=None, device=None):
@@ -282,3 +287,190 @@ class HipAdamW(torch.optim.Optimizer):
             st["step"] = steps[i]
         self._state_block()[_W_STEP] = step
         self._started = True
+
+
+# ---------------------------------------------------------------------------------------------------------------- weight averaging
+def check_ema_decay(decay) -> float:
+    """An EMA decay is a number in [0, 1); anything else raises ValueError."""
+    if isinstance(decay, bool) or not isinstance(decay, (int, float, np.integer, np.floating)) or not 0.0 <= float(decay) < 1.0:
+        raise ValueError(f"the EMA decay must be a number in [0, 1), not {decay!r}")
+    return float(decay)
+
+
+class TensorEMA:
+    """The binding of nbp_ema_update_f32: ``shadow[i] <- d shadow[i] + (1 - d) live[i]`` over two lists of fp32 device tensors, one
+    launch for all of them (plus the one-thread launch that counts the update).  The number of applied updates lives in a device
+    block of this object; the kernel forms ``d`` from it (``min(decay, (1 + n) / (10 + n))`` with warm-up), so the host never reads it.
+
+    The shadows keep their addresses for the life of the object; the addresses of the live tensors are compared at every update (one
+    ``data_ptr()`` each) and the record table is refreshed with one small copy when one moved."""
+
+    def __init__(self, live, shadow):
+        live, shadow = list(live), list(shadow)
+        if not live or len(live) != len(shadow):
+            raise ValueError("TensorEMA needs two tensor lists of the same, non-zero length")
+        for t in live + shadow:
+            if not isinstance(t, torch.Tensor):
+                raise TypeError("TensorEMA averages Tensors")
+            if not t.is_cuda:
+                raise RuntimeError("TensorEMA runs on the GPU only (no CPU fallback): a tensor lives on " + str(t.device))
+        self._device = live[0].device
+        for p, e in zip(live, shadow):
+            self._validate(p, "live tensor")
+            self._validate(e, "shadow tensor")
+            if p.shape != e.shape:
+                raise ValueError("TensorEMA: a shadow tensor does not have its live tensor's shape")
+        self._live, self._shadow = live, shadow
+        self._tables = None
+        L = _lib.lib()
+        assert L.nbp_ema_desc_bytes() == _EMA_DESC.itemsize
+        self._block = torch.zeros(int(L.nbp_ema_state_bytes()) // 4, dtype=torch.int32, device=self._device)
+
+    def _validate(self, t, name):
+        if t.layout is not torch.strided or t.dtype != torch.float32:
+            raise ValueError(f"TensorEMA averages dense fp32 tensors only (the kernel is fp32): a {name} is {t.dtype}")
+        if t.device != self._device:
+            raise ValueError(f"TensorEMA needs all tensors on one device ({self._device} and {t.device})")
+        if not t.is_contiguous() or t.data_ptr() % 4:
+            raise ValueError(f"TensorEMA needs a contiguous, 4-byte aligned {name}")
+        if t.numel() < 1:
+            raise ValueError(f"TensorEMA cannot average an empty {name}")
+
+    @property
+    def num_updates(self) -> torch.Tensor:
+        """0-dim int32 device tensor (a view of the state block): the number of updates applied so far."""
+        return self._block[0]
+
+    def set_num_updates(self, n: int) -> None:
+        self._block[0] = int(n)
+
+    def _build(self, sig):
+        chunk = int(_lib.lib().nbp_optim_chunk_elems())
+        desc = np.zeros(len(self._live), dtype=_EMA_DESC)
+        chunks = []
+        for i, (p, e) in enumerate(zip(self._live, self._shadow)):
+            n = p.numel()
+            desc[i] = (p.data_ptr(), e.data_ptr(), n)
+            c = np.zeros((n + chunk - 1) // chunk, dtype=_CHUNK)
+            c["first"] = np.arange(len(c), dtype=np.int64) * chunk
+            c["tensor"] = i
+            chunks.append(c)
+        chunks = np.concatenate(chunks)
+        self._tables = {"sig": sig, "desc_host": desc, "descs": _upload(desc, device=self._device),
+                        "chunks": _upload(chunks, device=self._device), "n_chunks": len(chunks)}
+
+    @torch.no_grad()
+    def update(self, decay, warmup=True, optimizer=None):
+        """Enqueues one update on the current stream.  `optimizer`: a HipAdamW whose step() was enqueued before this call -- the
+        update is dropped on the device when that step was (skip_nonfinite); anything else, or None: the update always applies."""
+        decay = check_ema_decay(decay)
+        dev = self._device
+        if torch.cuda.current_device() != dev.index:
+            with torch.cuda.device(dev):
+                return self.update(decay, warmup, optimizer)
+        gate = 0
+        if isinstance(optimizer, HipAdamW):
+            if optimizer._device != dev:
+                raise ValueError(f"the optimizer lives on {optimizer._device}, the averaged tensors on {dev}")
+            gate = optimizer._state_block().data_ptr()
+        sig = [p.data_ptr() for p in self._live]
+        tab = self._tables
+        if tab is None:
+            self._build(sig)
+            tab = self._tables
+        elif tab["sig"] != sig:                  # a live tensor moved (the shadows never do): refresh the addresses
+            for p, e in zip(self._live, self._shadow):
+                self._validate(p, "live tensor")
+                if p.shape != e.shape:
+                    raise ValueError("TensorEMA: a live tensor changed its shape")
+            tab["desc_host"]["p"] = sig
+            _upload(tab["desc_host"], dst=tab["descs"])
+            tab["sig"] = sig
+        _lib.check(_lib.lib().nbp_ema_update_f32(tab["descs"].data_ptr(), tab["chunks"].data_ptr(), tab["n_chunks"],
+                                                 self._block.data_ptr(), gate, decay, int(bool(warmup)), _lib.current_stream()),
+                   "ema_update")
+
+
+class WeightEMA:
+    """An exponential moving average of a module's weights, kept on the device (csrc/nbp_ema.hip).
+
+    ``WeightEMA(module, decay, warmup=True)``: ``.module`` is the shadow -- a deep copy of `module` made here, in eval mode, with
+    ``requires_grad=False`` and the same attributes (``conv_precision``).  Every parameter and every floating-point buffer (the
+    BatchNorm running statistics) is averaged, as timm's ``ModelEmaV2`` and ``swa_utils.AveragedModel(use_buffers=True)`` do:
+    ``e <- d e + (1 - d) p`` with ``d = min(decay, (1 + n) / (10 + n))`` after n applied updates (``warmup=False``: ``d = decay``).
+    Integer buffers (``num_batches_tracked``) are copied from the live module when the shadow is next handed out.
+
+    ``update(optimizer=None)`` enqueues one update on the current stream and never waits for the device.  Call it right after
+    ``optimizer.step()``.  Given a ``HipAdamW``, a step that optimizer dropped on the device (``skip_nonfinite``) drops the update
+    too: shadow and counter keep their bits.  Any other optimizer, or None: every update applies.
+
+    The kernel writes the shadow's tensors without touching their version counters, on which the packed eval weights and the
+    captured forward graphs of an ``NBP`` are keyed: ``update()`` therefore drops the shadow's pack (``invalidate_packed()``), and
+    the next forward of ``.module`` packs the averaged weights.
+
+    ``num_updates`` is a 0-dim int32 device tensor; ``state_dict()`` / ``load_state_dict()`` exchange ``{"decay", "warmup",
+    "num_updates", "shadow"}`` (a host read of the counter: not the training loop), and a restored average continues bit for bit.
+    There is no CPU path: a module off the GPU raises ``RuntimeError``."""
+
+    def __init__(self, module, decay, warmup=True):
+        self.decay = check_ema_decay(decay)
+        self.warmup = bool(warmup)
+        tensors = list(module.parameters()) + list(module.buffers())
+        if not tensors:
+            raise ValueError("WeightEMA: the module has no parameters or buffers")
+        if any(not t.is_cuda for t in tensors):
+            raise RuntimeError("WeightEMA runs on the GPU only (no CPU fallback): the module is not on the device")
+        shadow = copy.deepcopy(module)
+        shadow.eval()
+        shadow.requires_grad_(False)
+        live_t, shadow_t, self._copied = [], [], []
+        for (_, p), (_, e) in zip(module.named_parameters(), shadow.named_parameters()):
+            live_t.append(p)
+            shadow_t.append(e)
+        for (_, p), (_, e) in zip(module.named_buffers(), shadow.named_buffers()):
+            if p.dtype.is_floating_point:
+                live_t.append(p)
+                shadow_t.append(e)
+            else:
+                self._copied.append((p, e))
+        self._shadow = shadow
+        self._set = TensorEMA(live_t, shadow_t)
+        self._stale = False          # the integer buffers of the shadow are behind the live ones
+
+    @property
+    def module(self):
+        if self._stale:
+            with torch.no_grad():
+                for src, dst in self._copied:
+                    dst.copy_(src)
+            self._stale = False
+        return self._shadow
+
+    @property
+    def num_updates(self) -> torch.Tensor:
+        return self._set.num_updates
+
+    def _drop_pack(self):
+        drop = getattr(self._shadow, "invalidate_packed", None)
+        if drop is not None:
+            drop()
+
+    def update(self, optimizer=None):
+        self._set.update(self.decay, self.warmup, optimizer)
+        self._stale = True
+        self._drop_pack()
+
+    def state_dict(self):
+        return {"decay": self.decay, "warmup": self.warmup, "num_updates": int(self.num_updates.item()),
+                "shadow": self.module.state_dict()}
+
+    def load_state_dict(self, state):
+        decay = check_ema_decay(state["decay"])
+        n = int(state["num_updates"])
+        if n < 0:
+            raise ValueError(f"num_updates of the loaded state is {n}")
+        self._shadow.load_state_dict(state["shadow"], strict=True)
+        self.decay, self.warmup = decay, bool(state["warmup"])
+        self._set.set_num_updates(n)
+        self._stale = False
+        self._drop_pack()

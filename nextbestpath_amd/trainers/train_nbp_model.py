@@ -64,6 +64,25 @@ def initialize_nbp(params, nbp, torch_seed=9, initialize=False, pretrained=False
     return nbp, opt, 10000.0, 0
 
 
+def make_ema(params, nbp):
+    """The config's `ema_decay` (null = off, the default | a number in [0, 1)) and `ema_warmup` -> None or a
+    nextbestpath_amd.optim.WeightEMA of `nbp` (csrc/nbp_ema.hip).  Not in the reference, which keeps no averaged weights: the
+    average is an observer of the training run -- validated and checkpointed beside the live weights, which it never changes."""
+    decay = getattr(params, "ema_decay", None)
+    if decay is None:
+        return None
+    from ..optim import WeightEMA, check_ema_decay
+    return WeightEMA(nbp, check_ema_decay(decay), warmup=bool(getattr(params, "ema_warmup", True)))
+
+
+def collection_model(params, nbp, ema):
+    """The network that acts during trajectory collection: the live one, or with `ema_collect` the averaged one (the role of a
+    target network).  The one place where the average changes what the training run computes."""
+    if ema is not None and bool(getattr(params, "ema_collect", False)):
+        return ema.module
+    return nbp
+
+
 def make_synthetic_experiences(n, S=256, seed=0):
     """Replay records with the reference's schema and the input recipe of SURVEY.md 8d (config 3)."""
     from ..utility.synthetic import make_count_maps
@@ -266,7 +285,7 @@ def _augment_rng(params):
     return rng
 
 
-def train_experience_data(training_set_db, params, optimizer, nbp, device, current_epoch, grad_norms=None):
+def train_experience_data(training_set_db, params, optimizer, nbp, device, current_epoch, grad_norms=None, ema=None):
     """ref nbp_utils.py:340-395 (GradScaler without autocast is the identity scale for fp32; omitted -- the "fp16"
     train_precision scales every fp16 operand per tensor instead, NBP.train_precision).  As in the
     reference the early poses (pose_i <= 10) are dropped INSIDE each batch during epoch 1 (:348-362), a batch left empty
@@ -278,7 +297,8 @@ def train_experience_data(training_set_db, params, optimizer, nbp, device, curre
     every sample is moved, with probability p, by one of the seven non-identity symmetries of the square about the camera
     (utility/augment.py) -- the targets' cells and heading channels on the host before collation, on shallow copies of the records,
     the six planes on the device behind the staged copy (one launch, hipops.augment_batch).  p = 0 (the default) draws nothing and
-    launches nothing."""
+    launches nothing.  `ema` (make_ema; None = off) is updated once per optimizer step, right behind it on the stream; with the HIP
+    optimizer a step dropped on the device drops the update too."""
     random.shuffle(training_set_db)
     aug_p = float(getattr(params, "augment_probability", 0.0) or 0.0)
     if not 0.0 <= aug_p <= 1.0:
@@ -348,6 +368,8 @@ def train_experience_data(training_set_db, params, optimizer, nbp, device, curre
         if updates % accumulation_steps == 0 or bi + 1 == n_batches:
             allreduce_gradients(nbp)
             optimizer.step()
+            if ema is not None:
+                ema.update(optimizer)
             optimizer.zero_grad()
             accumulated = 0.0
             with_norm = bool(getattr(optimizer, "norm_pass", False))
@@ -402,18 +424,27 @@ def validation_model(training_set_db, params, nbp, device):
 
 
 def train_nbp(training_set_db, params, optimizer, nbp, device, current_epoch, validation_data, lr_patience=2,
-              lr_factor=0.1, num_epochs=5, grad_norms=None):
-    """ref nbp_utils.py:430-468: 5 inner epochs, validation after each, ReduceLROnPlateau.  grad_norms: see train_experience_data."""
+              lr_factor=0.1, num_epochs=5, grad_norms=None, ema=None, ema_losses=None):
+    """ref nbp_utils.py:430-468: 5 inner epochs, validation after each, ReduceLROnPlateau.  grad_norms: see train_experience_data.
+    With `ema` the averaged network is validated after each inner epoch as well (same data, same function) and `ema_losses`, a
+    list, receives its loss; the scheduler and the returned pair see the live network only."""
     sched = torch.optim.lr_scheduler.ReduceLROnPlateau(optimizer, mode="min", factor=lr_factor, patience=lr_patience)
     tl, vl = [], []
     for _ in range(num_epochs):
         nbp.train()
-        losses = train_experience_data(training_set_db, params, optimizer, nbp, device, current_epoch, grad_norms)
+        losses = train_experience_data(training_set_db, params, optimizer, nbp, device, current_epoch, grad_norms, ema=ema)
         tl.append(float(np.mean(losses)) if losses else float("nan"))
         sync_buffers(nbp)
         nbp.eval()
         with torch.no_grad():
             vl.append(_mean_over_ranks(validation_model(validation_data, params, nbp, device), device))
+        if ema is not None:
+            shadow = ema.module
+            sync_buffers(shadow)
+            with torch.no_grad():
+                ve = _mean_over_ranks(validation_model(validation_data, params, shadow, device), device)
+            if ema_losses is not None:
+                ema_losses.append(ve)
         sched.step(vl[-1])
     return sum(tl) / len(tl), sum(vl) / len(vl)
 
@@ -434,6 +465,8 @@ def run_training_nbp(params):
     # checkpoints are fp32 state_dicts either way
     nbp.train_precision = getattr(params, "train_precision", "fp32_split")
     nbp, optimizer, best_loss, _ = initialize_nbp(params, nbp, params.torch_seed)
+    ema = make_ema(params, nbp)          # None unless `ema_decay` is set
+    best_ema_loss = best_loss
     S = getattr(params, "grid_size", 256)
     os.makedirs(params.output_dir, exist_ok=True)
     data_path = getattr(params, "data_path", None)
@@ -442,14 +475,23 @@ def run_training_nbp(params):
 
     with_norm = bool(getattr(optimizer, "norm_pass", False))      # the HIP optimizer with clipping or skipping on
 
-    def save(epoch, vl, tl, grad_norms):
-        nonlocal best_loss
+    def save(epoch, vl, tl, grad_norms, ema_losses):
+        nonlocal best_loss, best_ema_loss
         if rank != 0:
             return
         history[epoch] = {"training_loss": tl, "validation_loss": vl}
+        if ema is not None:
+            history[epoch]["validation_loss_ema"] = sum(ema_losses) / len(ema_losses)
         if with_norm:       # one norm per optimizer step of the epoch; the running count of dropped steps (validation has synchronised)
             history[epoch].update(grad_norm=list(grad_norms), skipped_steps=int(optimizer.skipped_steps.item()))
         ck = {"epoch": epoch, "model_state_dict": nbp.state_dict(), "optimizer_state_dict": optimizer.state_dict()}
+        if ema is not None:
+            ck["ema_state_dict"] = ema.state_dict()
+            vle = history[epoch]["validation_loss_ema"]
+            if vle < best_ema_loss:      # the averaged weights as a checkpoint of their own: model_state_dict IS the shadow's
+                best_ema_loss = vle
+                torch.save({"epoch": epoch, "model_state_dict": ck["ema_state_dict"]["shadow"], "validation_loss_ema": vle},
+                           os.path.join(params.output_dir, params.nbp_model_name + "_best_val_ema.pth"))
         if vl < best_loss:
             best_loss = vl
             torch.save(ck, os.path.join(params.output_dir, params.nbp_model_name + "_best_val.pth"))
@@ -462,10 +504,11 @@ def run_training_nbp(params):
         validation = make_synthetic_experiences(getattr(params, "n_validation_synthetic", 16), S, seed=1)
         for epoch in range(1, params.epochs + 1):
             db = make_synthetic_experiences(params.samples_per_epoch, S, seed=100 + epoch + 1000 * rank)
-            norms = []
-            tl, vl = train_nbp(db, params, optimizer, nbp, device, epoch, validation, num_epochs=params.inner_epochs, grad_norms=norms)
+            norms, ema_losses = [], []
+            tl, vl = train_nbp(db, params, optimizer, nbp, device, epoch, validation, num_epochs=params.inner_epochs, grad_norms=norms,
+                               ema=ema, ema_losses=ema_losses)
             print(f"epoch {epoch}: training {tl:.4f} validation {vl:.4f}")
-            save(epoch, vl, tl, norms)
+            save(epoch, vl, tl, norms, ema_losses)
         return history
 
     dataset = sim_scene.SceneDataset(data_path, getattr(params, "train_scenes", []))
@@ -476,7 +519,7 @@ def run_training_nbp(params):
         cov = []
         with torch.no_grad():
             n = nu.trajectory_collection(params, epoch, dataset, env, (S, S), (S // 4, S // 4), (-40 * S // 256, 40 * S // 256),
-                                         nbp, cov, None, device, rank=rank, world=world,
+                                         collection_model(params, nbp, ema), cov, None, device, rank=rank, world=world,
                                          n_poses=getattr(params, "n_collect_poses", 100),
                                          n_gt_points=getattr(params, "n_gt_surface_points", 50000),
                                          rollouts_per_gpu=getattr(params, "collect_rollouts_per_gpu", 1))
@@ -488,9 +531,10 @@ def run_training_nbp(params):
         # every rank must take the same branch (the training loop below contains collectives)
         if _common_count(1 if (db and validation) else 0, device) == 0:
             continue
-        norms = []
-        tl, vl = train_nbp(db, params, optimizer, nbp, device, epoch, validation, num_epochs=params.inner_epochs, grad_norms=norms)
+        norms, ema_losses = [], []
+        tl, vl = train_nbp(db, params, optimizer, nbp, device, epoch, validation, num_epochs=params.inner_epochs, grad_norms=norms,
+                           ema=ema, ema_losses=ema_losses)
         print(f"epoch {epoch}: training {tl:.4f} validation {vl:.4f}")
-        save(epoch, vl, tl, norms)
+        save(epoch, vl, tl, norms, ema_losses)
     env.close()
     return history

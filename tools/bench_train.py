@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Config 3 of BASELINE.json: NBP fwd + bwd + AdamW step, batch of 256x256 maps, fp32, 1 MI355X.
     python tools/bench_train.py [--batch 32] [--steps 5] [--size 256] [--precision fp32_split|fp16] [--augment P]
-                                [--optimizer torch|hip] [--clip X]
+                                [--optimizer torch|hip] [--clip X] [--ema D]
 Prints one JSON line: train maps/s, TFLOP/s against 546.9 GFLOP/map, and the torch-CPU baseline
 (stock autograd on the same weights = the reference's arithmetic) on a bounded sample."""
 import argparse
@@ -37,12 +37,18 @@ def main():
                     help="make_optimizer's impl: torch's fused AdamW (default) or HipAdamW (csrc/nbp_optim.hip)")
     ap.add_argument("--clip", type=float, default=None,
                     help="grad_clip_norm X > 0: global-norm clipping inside HipAdamW.step() (needs --optimizer hip)")
+    ap.add_argument("--ema", type=float, default=None,
+                    help="ema_decay D in [0, 1): a WeightEMA of the network (csrc/nbp_ema.hip), updated behind every optimizer step")
     a = ap.parse_args()
     dev = torch.device("cuda")
     torch.manual_seed(9)
     net = NBP().to(dev).train()
     net.train_precision = a.precision
     opt = make_optimizer(net, impl=a.optimizer, grad_clip_norm=a.clip)
+    ema = None
+    if a.ema is not None:
+        from nextbestpath_amd.optim import WeightEMA
+        ema = WeightEMA(net, a.ema)
     db = make_synthetic_experiences(a.batch, a.size, seed=3)
     xs, gt, coords, gains, bidx = _collate(db, dev)
 
@@ -69,6 +75,8 @@ def main():
             loss = net.loss(tr.gather_values(o1, bidx, coords), gains, o2, gt)
         loss.backward()
         opt.step()
+        if ema is not None:
+            ema.update(opt)
         opt.zero_grad(set_to_none=True)
         return loss
 
@@ -104,6 +112,7 @@ def main():
         "metric": f"NBP training maps/s (fwd+bwd+AdamW, {a.precision})", "value": round(a.batch / dt, 3), "unit": "maps/s",
         "n_gpus": 1, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(dt * 1e3, 2), "dtype": "f32",
         "train_precision": a.precision, "augment_probability": a.augment, "optimizer": a.optimizer, "grad_clip_norm": a.clip,
+        "ema_decay": a.ema, "ema_updates": None if ema is None else int(ema.num_updates),
         "data": "synthetic", "config": {"workload": f"configs[2]: train step, batch {a.batch} x {a.size}x{a.size}"},
         "tflops_reference_formulation": round(a.batch * flop_map / dt / 1e12, 2), "frac_of_split_ceiling_reference_formulation": round(a.batch * flop_map / dt / (2500e12 / 3), 4),
         "loss": float(loss.item()), "producer_notes": dict(tr.HANDOFF_STATS),
