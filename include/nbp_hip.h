@@ -878,6 +878,20 @@ int nbp_loss_f32(int mode, const float* p, const float* t, long long n, float gr
  * aliasing buffers; NBP_E_SHAPE: S % 16 != 0, 6 B > 65535, a pointer off the 16-byte grid; nothing is written on an error. */
 int nbp_augment_batch_f32(const float* x, const float* gt, const int* ops_dev, int B, int S, float* x_out, float* gt_out,
                           void* stream);
+/* The D4 symmetry ensemble of the eval forward (csrc/nbp_ensemble.hip; not in the reference): the network is run on n
+ * moved copies of every input and the outputs, moved back, are averaged.  ops_dev: n op codes (as above) on the device, 1 <= n <= 8.
+ *   expand   x [B,5,S,S] -> x_out [n,B,5,S,S], x_out[k][b] = ops[k] applied to x[b]; bit-exact moves, one launch.
+ *   reduce   raw1 [n,B,8,S/4,S/4], raw2 [n,B,1,S,S] (the outputs on the expanded batch) -> out1 [B,8,S/4,S/4], out2 [B,1,S,S]:
+ *            member k is moved back by the inverse element of ops[k] (itself, except that codes 3 and 5 swap); a value map's heading
+ *            channels are permuted with it (utility/augment.py::transform_value_map).  The moved members are summed in fp32 in the
+ *            order k = 0 .. n-1 and each cell is divided by the number of members that reach it: a member whose inverse reflects
+ *            rows does not reach row 0, likewise columns (utility/augment.py::ensemble_reference is the float64 definition).  One
+ *            launch, no atomics: two runs give the same bits.
+ * Out of place, nothing may alias.  NBP_E_ARG: null pointer, B < 1, n outside 1..8, aliasing buffers; NBP_E_SHAPE: S % 16 != 0, more
+ * than 65535 planes (5 n B / 9 B), a pointer off the 16-byte grid; nothing is written on an error. */
+int nbp_ensemble_expand_f32(const float* x, int B, int S, const int* ops_dev, int n, float* x_out, void* stream);
+int nbp_ensemble_reduce_f32(const float* raw1, const float* raw2, int B, int S, const int* ops_dev, int n, float* out1, float* out2,
+                            void* stream);
 
 /* ---- The optimizer step (csrc/nbp_optim.hip): the reference's torch.optim.AdamW(lr 1e-3, betas (0.9, 0.999), eps 1e-8, weight decay
  * 0.01) of next_best_path/utility/nbp_utils.py:228 and its scaler.step(optimizer) / scaler.update() of nbp_utils.py:386-388 (a

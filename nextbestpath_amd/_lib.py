@@ -222,6 +222,8 @@ SIGNATURES["nbp_adamw_f32"] = (_i, [_vp, _vp, _i, _vp, _i, _d, _d, _d, _d, _d, _
 SIGNATURES["nbp_ema_desc_bytes"] = (_i, [])
 SIGNATURES["nbp_ema_state_bytes"] = (_sz, [])
 SIGNATURES["nbp_ema_update_f32"] = (_i, [_vp, _vp, _i, _vp, _vp, _d, _i, _vp])
+SIGNATURES["nbp_ensemble_expand_f32"] = (_i, [_vp, _i, _i, _vp, _i, _vp, _vp])
+SIGNATURES["nbp_ensemble_reduce_f32"] = (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp])
 
 _lock = threading.Lock()
 _lib = None

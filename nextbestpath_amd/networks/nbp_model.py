@@ -121,6 +121,21 @@ class NBP(nn.Module):
         #                and rounded once to fp16, ONE MFMA per product, fp32 accumulation, fp32 epilogues / master weights / AdamW.
         # Eval mode (conv_precision) is not affected.
         self.train_precision = "fp32_split"
+        # eval-mode symmetry ensemble (test-time augmentation, the inference half of the D4 training augmentation): None (default)
+        # = the plain forward, same launches, same bits; a name of utility/augment.py::ENSEMBLES ("c2", "flips", "d4") or a sequence
+        # of distinct op codes starting with 0 = every eval forward (forward, forward_static, the planner's packed calls) runs the
+        # network on the moved copies of its input and returns the average of the outputs moved back (augment.ensemble_reference):
+        # about n times the forward plus two small launches.  Training mode ignores it.
+        self._symmetry_ensemble = None
+
+    @property
+    def symmetry_ensemble(self):
+        return self.__dict__.get("_symmetry_ensemble")
+
+    @symmetry_ensemble.setter
+    def symmetry_ensemble(self, spec):
+        from ..utility import augment
+        self.__dict__["_symmetry_ensemble"] = augment.check_ensemble(spec)
 
     # ------------------------------------------------------------------ packing
     def _state_key(self):
@@ -172,7 +187,7 @@ class NBP(nn.Module):
         return super()._apply(fn, *a, **k)
 
     def _ensure_packed(self, device):
-        key = (self._state_key(), str(device), self.conv_precision)
+        key = (self._state_key(), str(device), self.conv_precision, self.symmetry_ensemble)
         if self._packed is None or key != self._packed_key:
             from . import packing
             self._graphs = {}            # captured forwards point into the pack that is being replaced

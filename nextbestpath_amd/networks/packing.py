@@ -51,6 +51,9 @@ class PackedWeights:
     def __init__(self, handle, buf, keep, bf16=False, precision=None):
         self.handle, self.buf, self.keep = handle, buf, keep
         self.precision = precision or ("bf16" if bf16 else "fp32")
+        # None, or the op codes of the symmetry ensemble every forward through this pack returns (pack_eval_weights sets it from
+        # NBP.symmetry_ensemble): carried here so that forward_packed's direct callers (the lock-step planner) follow the module
+        self.ensemble = None
 
     @property
     def bf16(self):
@@ -107,19 +110,107 @@ def pack_state_dict(sd, device, bf16: bool = False, precision: str = None) -> Pa
 
 
 def pack_eval_weights(module, device) -> PackedWeights:
-    return pack_state_dict(module.state_dict(), device, precision=getattr(module, "conv_precision", "fp32"))
+    from ..utility import augment
+    packed = pack_state_dict(module.state_dict(), device, precision=getattr(module, "conv_precision", "fp32"))
+    packed.ensemble = augment.check_ensemble(getattr(module, "symmetry_ensemble", None))
+    return packed
+
+
+# ---- the symmetry ensemble (NBP.symmetry_ensemble; utility/augment.py::ensemble_reference is the definition).  The n moved copies
+# of a batch of B maps are a batch of n B maps for the plain forward; where that is more than ENSEMBLE_MAX_INNER_BATCH maps (memory:
+# 48 rollouts x 8 members), or more than the C forward takes, the plain forward runs over slices of it -- the expanded layout is
+# member-major, so any run of consecutive maps is a valid batch.
+ENSEMBLE_MAX_INNER_BATCH = 64
+
+
+def _align256(n):
+    return (int(n) + 255) // 256 * 256
+
+
+_layouts = {}
+
+
+def _ensemble_layout(ops, B, S, precision):
+    """(slice length, inner workspace bytes, byte offsets of (inner workspace, expanded input, raw out1, raw out2) from the 256-byte
+    aligned base, total bytes) of the one byte buffer an ensemble forward of B maps works in; None: unsupported size."""
+    key = (ops, B, S, precision, int(ENSEMBLE_MAX_INNER_BATCH))
+    if key not in _layouts:
+        size = getattr(_lib.lib(), _FWD[precision][1])
+        NB = len(ops) * B
+        chunk = max(1, min(int(ENSEMBLE_MAX_INNER_BATCH), NB))
+        while chunk > 1 and size(chunk, S) == 0:
+            chunk = (chunk + 1) // 2
+        sizes = [int(size(b, S)) for b in {chunk, NB % chunk or chunk}]       # the full slices and the last one
+        if min(sizes) == 0:
+            _layouts[key] = None
+        else:
+            offs, off = [], 0
+            for nbytes in (max(sizes), NB * 5 * S * S * 4, NB * 8 * (S // 4) ** 2 * 4, NB * S * S * 4):
+                offs.append(off)
+                off += _align256(nbytes)
+            _layouts[key] = (chunk, max(sizes), offs, off + 256)
+    return _layouts[key]
+
+
+def forward_workspace_bytes(packed: PackedWeights, B, S, precision=None):
+    """Bytes of the workspace forward_packed(packed, x [B,5,S,S], ws=...) needs; 0: a size the kernels do not take.  With an
+    ensemble: the inner forward's workspace at its slice size, the expanded input and the raw outputs, at 256-byte offsets."""
+    precision = precision or packed.precision
+    if packed.ensemble is None:
+        return int(getattr(_lib.lib(), _FWD[precision][1])(B, S))
+    if B < 1 or S < 16 or S % 16:
+        return 0
+    lay = _ensemble_layout(packed.ensemble, B, S, precision)
+    return lay[3] if lay else 0
+
+
+def _forward_ensemble(packed, x, precision, out, ws):
+    from ..utility import hipops
+    ops = packed.ensemble
+    B, _, S, _ = x.shape
+    n, V = len(ops), S // 4
+    NB = n * B
+    if out is None:
+        out = (torch.empty(B, 8, V, V, dtype=torch.float32, device=x.device),
+               torch.empty(B, 1, S, S, dtype=torch.float32, device=x.device))
+    with torch.cuda.device(x.device):
+        lay = _ensemble_layout(ops, B, S, precision)
+        if lay is None:
+            raise _lib.NbpHipError(f"unsupported NBP input size B={B} S={S}")
+        chunk, inner, offs, total = lay
+        if ws is None:
+            ws = _workspace(B, S, x.device, precision, packed)
+        base = (-ws.data_ptr()) % 256
+        if ws.numel() < base + total - 256:
+            raise _lib.NbpHipError("forward_packed: workspace too small for the symmetry ensemble (forward_workspace_bytes)")
+        part = lambda i, shape: ws[base + offs[i]:base + offs[i] + 4 * int(torch.Size(shape).numel())].view(torch.float32).view(shape)
+        xe, raw1, raw2 = part(1, (NB, 5, S, S)), part(2, (NB, 8, V, V)), part(3, (NB, 1, S, S))
+        ops_dev = hipops.symmetry_ops(ops, x.device)
+        hipops.symmetry_expand(x, ops_dev, out=xe.view(n, B, 5, S, S))
+        fn = getattr(_lib.lib(), _FWD[precision][0])
+        inner_ws = ws.data_ptr() + base + offs[0]
+        for s in range(0, NB, chunk):
+            b = min(chunk, NB - s)
+            rc = fn(packed.handle, xe[s].data_ptr(), b, S, raw1[s].data_ptr(), raw2[s].data_ptr(), inner_ws, inner,
+                    _lib.current_stream())
+            _lib.check(rc, _FWD[precision][0])
+        return hipops.symmetry_reduce(raw1.view(n, B, 8, V, V), raw2.view(n, B, 1, S, S), ops_dev, out=out)
 
 
 _ws_cache = {}
 
 
-def _workspace(B, S, device, precision="fp32"):
+def _workspace(B, S, device, precision="fp32", packed=None):
     # one workspace per (shape, stream): forwards enqueued on different streams may run concurrently
     key = (B, S, device.index if isinstance(device, torch.device) else str(device), precision, _lib.current_stream())
+    if packed is not None and packed.ensemble is not None:
+        key += (packed.ensemble, int(ENSEMBLE_MAX_INNER_BATCH))
     ws = _ws_cache.get(key)
     if ws is None:
-        L = _lib.lib()
-        n = getattr(L, _FWD[precision][1])(B, S)
+        if packed is not None and packed.ensemble is not None:
+            n = forward_workspace_bytes(packed, B, S, precision)
+        else:
+            n = getattr(_lib.lib(), _FWD[precision][1])(B, S)
         if n == 0:
             raise _lib.NbpHipError(f"unsupported NBP input size B={B} S={S}")
         ws = torch.empty(n, dtype=torch.uint8, device=device)
@@ -133,12 +224,15 @@ def _workspace(B, S, device, precision="fp32"):
 def forward_packed(packed: PackedWeights, x: torch.Tensor, precision: str = None, out=None, ws=None):
     """precision overrides the handle's own only where the handle allows it ("fp32" on a "fp32_split" handle).
     out = (out1, out2) / ws: caller-owned result tensors and workspace (ForwardGraph: everything a captured launch touches
-    must outlive the graph)."""
+    must outlive the graph), ws of at least forward_workspace_bytes(packed, B, S).  A pack that carries a symmetry ensemble
+    returns the ensemble: expand, the plain forward over the n B moved maps (in slices where needed) and reduce, all inside ws."""
     precision = precision or packed.precision
     if precision != packed.precision and not (precision == "fp32" and packed.precision == "fp32_split"):
         raise ValueError(f"weights packed for {packed.precision!r} cannot run the {precision!r} forward")
     B, _, S, _ = x.shape
     x = x.contiguous().float()
+    if packed.ensemble is not None:
+        return _forward_ensemble(packed, x, precision, out, ws)
     if out is None:
         out1 = torch.empty(B, 8, S // 4, S // 4, dtype=torch.float32, device=x.device)
         out2 = torch.empty(B, 1, S, S, dtype=torch.float32, device=x.device)
@@ -175,10 +269,9 @@ class ForwardGraph:
         assert x.is_cuda and x.is_contiguous() and x.dtype == torch.float32
         precision = precision or packed.precision
         B, _, S, _ = x.shape
-        L = _lib.lib()
         self.packed, self.x, self.precision = packed, x, precision
         with torch.cuda.device(x.device):
-            n = getattr(L, _FWD[precision][1])(B, S)
+            n = forward_workspace_bytes(packed, B, S, precision)
             if n == 0:
                 raise _lib.NbpHipError(f"unsupported NBP input size B={B} S={S}")
             self.ws = torch.empty(n, dtype=torch.uint8, device=x.device)
@@ -203,3 +296,34 @@ class ForwardGraph:
 def forward_eval(module, x: torch.Tensor):
     packed = module._ensure_packed(x.device)
     return forward_packed(packed, x)
+
+
+def equivariance_error(nbp, x, ops="d4"):
+    """How equivariant is this network on x [B,5,S,S]?  -> (e1, e2): the largest |g^-1 f(g x) - f(x)| over the members g of `ops`
+    and over the interior cells (row and column >= 1: the cells every member reaches) of out1 and of out2, f the PLAIN eval forward
+    (the module's symmetry_ensemble is set aside for the measurement and restored).  0 for an exactly equivariant network; the
+    symmetry ensemble averages exactly these differences away."""
+    from ..utility import augment, hipops
+    ops = augment.check_ensemble(ops)
+    if ops is None:
+        raise ValueError("equivariance_error: an ensemble expected")
+    keep, was_training = nbp.symmetry_ensemble, nbp.training
+    nbp.symmetry_ensemble = None
+    nbp.eval()
+    try:
+        with torch.no_grad():
+            x = x.contiguous().float()
+            B, _, S, _ = x.shape
+            f1, f2 = (t.clone() for t in nbp(x))
+            e1 = e2 = 0.0
+            for op in ops[1:]:
+                one = hipops.symmetry_ops((0, op), x.device)[1:]
+                r1, r2 = nbp(hipops.symmetry_expand(x, one)[0])
+                # one member, moved back: the reduce of a one-member ensemble (its cells off row 0 / column 0 are divided by one)
+                b1, b2 = hipops.symmetry_reduce(r1[None], r2[None], one)
+                e1 = max(e1, float((b1 - f1)[..., 1:, 1:].abs().max()))
+                e2 = max(e2, float((b2 - f2)[..., 1:, 1:].abs().max()))
+    finally:
+        nbp.symmetry_ensemble = keep
+        nbp.train(was_training)
+    return e1, e2

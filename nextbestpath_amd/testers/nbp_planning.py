@@ -116,12 +116,25 @@ def setup_test_camera(params, mesh, start_cam_idx, settings, device, seed=0):
     return cam
 
 
+_UNSET = object()
+
+
+def _set_symmetry_ensemble(nbp, params, spec=_UNSET):
+    """The planning option `symmetry_ensemble` (None, a name of utility/augment.py::ENSEMBLES or a list of op codes) goes onto the
+    network the rollouts evaluate: the keyword where given, else the params' key where present, else the network keeps its own."""
+    if spec is _UNSET:
+        spec = getattr(params, "symmetry_ensemble", _UNSET)
+    if spec is not _UNSET:
+        nbp.symmetry_ensemble = spec
+
+
 class Rollout:
     """One exploration rollout, steppable (bench.py times K consecutive ``step()`` calls)."""
 
     def __init__(self, params, nbp, camera, gt_scene_pc, mesh, mesh_for_check, y_bins, device, state=None, seed=0,
-                 grid=256):
+                 grid=256, symmetry_ensemble=_UNSET):
         self.params, self.nbp, self.camera, self.mesh, self.mesh_for_check = params, nbp, camera, mesh, mesh_for_check
+        _set_symmetry_ensemble(nbp, params, symmetry_ensemble)
         self.y_bins, self.device = y_bins, device
         # the reference hard-codes 256 / 64 / +-40 (nbp_planning.py:43-45); other grids keep 0.3125 units per pixel
         self.S, self.V, self.grid_range = grid, grid // 4, (-40 * grid // 256, 40 * grid // 256)
@@ -415,8 +428,10 @@ class MultiRollout:
     un-projection, map accumulation, raster, planner) run underneath the other group's convolutions instead of
     in front of them.  Each rollout's results are identical to running it alone (tests/test_gpu_rollout.py)."""
 
-    def __init__(self, rollouts, nbp, device, grid=None, streams=True, n_groups=None, elide_dead_forward=False):
+    def __init__(self, rollouts, nbp, device, grid=None, streams=True, n_groups=None, elide_dead_forward=False,
+                 symmetry_ensemble=_UNSET):
         self.rollouts, self.nbp = list(rollouts), nbp
+        _set_symmetry_ensemble(nbp, getattr(self.rollouts[0], "params", None), symmetry_ensemble)
         # The reference runs the network at every step and uses its output only when it replans (nbp_planning.py:166 / :252).
         # Default (False): every rollout's map goes through the forward at every step, as there.  True (reported beside the
         # headline, never as it): only the replanning rollouts' maps are forwarded -- same trajectories, same coverage
@@ -570,11 +585,12 @@ class MultiRollout:
                 out1, out2 = self._forward(net_in)
             return out1, out2, None
         st = self._sub.get(gi)
+        if st is not None and st["packed"] is not self._packed:     # a new pack (weights, precision, ensemble): other sizes
+            st = None
         if st is None:
             n, S = net_in.shape[0], net_in.shape[-1]
-            prec = self._packed.precision
-            nbytes = max(int(getattr(_lib.lib(), packing._FWD[prec][1])(b, S)) for b in range(1, n + 1))
-            st = self._sub[gi] = {"pin": [torch.zeros(n, dtype=torch.int64).pin_memory() for _ in range(4)], "k": 0,
+            nbytes = max(packing.forward_workspace_bytes(self._packed, b, S) for b in range(1, n + 1))
+            st = self._sub[gi] = {"packed": self._packed,"pin": [torch.zeros(n, dtype=torch.int64).pin_memory() for _ in range(4)], "k": 0,
                                   "idx": torch.zeros(n, dtype=torch.int64, device=self.device), "x": torch.empty_like(net_in),
                                   "ws": torch.empty(nbytes, dtype=torch.uint8, device=self.device)}
         k = len(need)
@@ -735,6 +751,11 @@ def compute_nbp_trajectory(params, nbp, camera, gt_scene_pc, mesh, mesh_for_chec
     return coverage_evolution, camera.X_cam_history, camera.V_cam_history, ro.st.cloud[:n_cloud], colors
 
 
+# the `symmetry_ensemble` key of the configs/test/ file load_params read last (a file with the NBP options: `nbp_weights`); the entry
+# script passes test_nbp_planning the options it knows by keyword, and this one reaches it here
+_test_config_ensemble = [_UNSET]
+
+
 def load_params(path):
     """macarons/utility/utils.py:44-83: JSON -> attribute object, `_section` keys flattened away."""
     with open(path) as fh:
@@ -754,6 +775,8 @@ def load_params(path):
     p = Params()
     for k, v in flat(raw, {}).items():
         setattr(p, k, v)
+    if hasattr(p, "nbp_weights"):
+        _test_config_ensemble[0] = getattr(p, "symmetry_ensemble", _UNSET)
     return p
 
 
@@ -830,9 +853,11 @@ def run_many(params, nbp, dataset, runs, device, seeds, test_resolution=0.05, n_
 def test_nbp_planning(params_file, model_file, results_json_file, numGPU, test_scenes, test_resolution=0.05,
                       use_perfect_depth_map=False, compute_collision=False, load_json=False, dataset_path=None,
                       nbp_weights=None, configs_dir=None, results_dir=None, n_poses=N_POSES, seed=8, torch_seed=9,
-                      rollouts_per_gpu=48, grid_size=256, nbp_precision=None):
+                      rollouts_per_gpu=48, grid_size=256, nbp_precision=None, symmetry_ensemble=_UNSET):
     """Same arguments as the reference (nbp_planning.py:364-374); `grid_size` / `nbp_precision` select
-    BASELINE.json configs[4] (512 grid at the same 0.3125 units per pixel, bf16 convolutions).  Under torchrun the flattened
+    BASELINE.json configs[4] (512 grid at the same 0.3125 units per pixel, bf16 convolutions).  `symmetry_ensemble` (None = off, a
+    name of utility/augment.py::ENSEMBLES or a list of op codes) is NBP.symmetry_ensemble of the loaded network; not given, it is
+    the key of that name in the configs/test/ file load_params read last (absent there: off).  Under torchrun the flattened
     (scene, start pose) runs are sharded round-robin over the ranks and the coverage curves are
     gathered with ONE all_gather over RCCL (backend "nccl" on ROCm; "gloo" on CPU-only hosts)."""
     import time
@@ -859,6 +884,9 @@ def test_nbp_planning(params_file, model_file, results_json_file, numGPU, test_s
     assert nbp_precision in (None, "fp32", "fp32_split", "bf16"), nbp_precision
     if nbp_precision is not None:           # None: the model's default ("fp32_split")
         nbp.conv_precision = nbp_precision
+    if symmetry_ensemble is _UNSET:
+        symmetry_ensemble = None if _test_config_ensemble[0] is _UNSET else _test_config_ensemble[0]
+    nbp.symmetry_ensemble = params.symmetry_ensemble = symmetry_ensemble      # (ValueError on anything but None, a name, op codes)
     dataset = sim_scene.SceneDataset(dataset_path, test_scenes)
     runs = list_runs(dataset, params)
     mine = shard(runs, rank, world)

@@ -21,6 +21,11 @@ permute the channels: transpose ``h -> (2 - h) mod 8``, reflect rows ``h -> (4 -
 
 The images of a batch are moved on the device by ``hipops.augment_batch`` (nbp_augment_batch_f32); ``transform_maps`` is the same
 action in numpy for tests and small arrays.
+
+The same action serves inference: the SYMMETRY ENSEMBLE of the eval forward (``NBP.symmetry_ensemble``) runs the network on the
+moved copies ``g_k x`` of its input, moves every output back with ``g_k^-1`` and averages.  ``ENSEMBLES`` names the subsets,
+``ensemble_reference`` is the definition in float64; the device side is ``hipops.symmetry_expand`` / ``symmetry_reduce``
+(csrc/nbp_ensemble.hip).
 """
 from __future__ import annotations
 
@@ -66,6 +71,79 @@ def transform_maps(a, op):
         r[..., :, 1:] = out[..., :, :0:-1]
         out = r
     return np.array(out, copy=True, order="C")
+
+
+def inverse_op(op):
+    """Op code of the inverse element.  With the code order transpose, reflect rows, reflect cols the two quarter turns 3 and 5 are
+    each other's inverse and every other element is its own (tests/test_ensemble_host.py finds them again by brute force)."""
+    op = _check(op)
+    return {3: 5, 5: 3}.get(op, op)
+
+
+def transform_value_map(y, op):
+    """`op` on a value map [..., 8, V, V]: the planes move as in transform_maps and channel heading_map(op)[h] of the result is the
+    moved plane h -- dense content moves exactly as transform_targets moves the sparse targets."""
+    op = _check(op)
+    y = np.asarray(y)
+    if y.ndim < 3 or y.shape[-3] != 8:
+        raise ValueError("transform_value_map: [..., 8, V, V] expected")
+    out = np.empty_like(transform_maps(y, op))
+    out[..., heading_map(op), :, :] = transform_maps(y, op)
+    return out
+
+
+# the named symmetry ensembles: subsets of D4 that hold the identity (first) and the inverse of each of their elements
+ENSEMBLES = {"c2": (0, 6), "flips": (0, 2, 4, 6), "d4": tuple(range(N_OPS))}
+
+
+def check_ensemble(spec):
+    """None, a name of ENSEMBLES, or a sequence of distinct op codes that starts with 0 -> None or the tuple of op codes."""
+    if spec is None:
+        return None
+    if isinstance(spec, str):
+        if spec not in ENSEMBLES:
+            raise ValueError(f"unknown symmetry ensemble {spec!r} (known: {sorted(ENSEMBLES)})")
+        return ENSEMBLES[spec]
+    try:
+        ops = tuple(spec)
+    except TypeError:
+        raise ValueError(f"symmetry ensemble: None, a name or a sequence of op codes expected, got {spec!r}") from None
+    for op in ops:
+        if isinstance(op, (bool, str, float)) or not isinstance(op, (int, np.integer)) or not 0 <= int(op) < N_OPS:
+            raise ValueError(f"symmetry ensemble: op code {op!r} outside 0..7")
+    ops = tuple(int(op) for op in ops)
+    if not ops or ops[0] != 0:
+        raise ValueError("symmetry ensemble: the first member must be the identity (op code 0)")
+    if len(set(ops)) != len(ops):
+        raise ValueError(f"symmetry ensemble: duplicate op codes in {ops}")
+    return ops
+
+
+def ensemble_reference(raw1, raw2, ops):
+    """The symmetry ensemble, in float64.  raw1 [n,B,8,V,V] and raw2 [n,B,1,S,S] are the network's outputs on the moved inputs,
+    raw[k] = f(g_k x) with g_k = ops[k].  Plane k is moved back by inverse_op(ops[k]) (transform_value_map / transform_maps), the
+    planes are summed and every cell is divided by the number of members that reach it: a member whose inverse reflects rows says
+    nothing about row 0, whose mirror image lies outside the window (likewise columns), so that the ensemble of a constant,
+    heading-independent map is that constant everywhere, edge included.  The identity reaches every cell.  -> (out1, out2)."""
+    ops = check_ensemble(ops)
+    raw1, raw2 = np.asarray(raw1, np.float64), np.asarray(raw2, np.float64)
+    if ops is None or raw1.ndim != 5 or raw2.ndim != 5 or raw1.shape[0] != len(ops) or raw2.shape[0] != len(ops):
+        raise ValueError("ensemble_reference: raw1 [n,B,8,V,V], raw2 [n,B,1,S,S] and n op codes expected")
+    outs = []
+    for raw, move in ((raw1, transform_value_map), (raw2, transform_maps)):
+        side = raw.shape[-1]
+        total, count = np.zeros(raw.shape[1:]), np.zeros((side, side))
+        for k, op in enumerate(ops):
+            g = inverse_op(op)
+            total += move(raw[k], g)
+            reach = np.ones((side, side))
+            if g & REFLECT_ROWS:
+                reach[0, :] = 0
+            if g & REFLECT_COLS:
+                reach[:, 0] = 0
+            count += reach
+        outs.append(total / count)
+    return outs[0], outs[1]
 
 
 def transform_targets(pixels, gains, op, V):

@@ -666,3 +666,75 @@ def augment_batch(x, gt, ops):
         rc = _lib.lib().nbp_augment_batch_f32(_lib.ptr(x), _lib.ptr(gt), _lib.ptr(ops), B, S, _lib.ptr(x_out), _lib.ptr(gt_out), _st())
     _lib.check(rc, "nbp_augment_batch_f32")
     return x_out, gt_out
+
+
+_ensemble_ops = {}
+
+
+def symmetry_ops(ops, device):
+    """The op codes of a symmetry ensemble (utility/augment.py::check_ensemble) as a device int32 tensor, one per (device, tuple):
+    uploaded at first use, so a step loop -- or a graph capture behind a warm-up -- uploads nothing."""
+    from . import augment
+    ops = augment.check_ensemble(ops)
+    if ops is None:
+        raise ValueError("symmetry_ops: an ensemble expected, got None")
+    device = torch.device(device)
+    key = (device.index if device.index is not None else torch.cuda.current_device(), ops)
+    t = _ensemble_ops.get(key)
+    if t is None:
+        t = _ensemble_ops[key] = torch.tensor(ops, dtype=torch.int32, device=device)
+    return t
+
+
+def _ensemble_args(what, ops, *tensors):
+    for name, t in tensors + (("ops", ops),):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError(f"{what}: the HIP path needs a cuda tensor for {name} (no CPU fallback)")
+    if ops.dtype != torch.int32 or ops.dim() != 1 or not 1 <= ops.shape[0] <= 8:
+        raise ValueError(f"{what}: ops is an int32 tensor of 1..8 op codes")
+    for name, t in tensors:
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"{what}: {name} must be a contiguous fp32 tensor")
+    return int(ops.shape[0])
+
+
+def symmetry_expand(x, ops, out=None):
+    """x [B,5,S,S] fp32 and ops int32 [n] (symmetry_ops), on the device -> x_out [n,B,5,S,S], x_out[k][b] = ops[k] applied to x[b]
+    about the camera: one launch (nbp_ensemble_expand_f32), out of place.  out: a caller-owned result tensor (graph capture)."""
+    n = _ensemble_args("symmetry_expand", ops, ("x", x), *((("out", out),) if out is not None else ()))
+    B, S = (x.shape[0], x.shape[-1]) if x.dim() == 4 else (0, 0)
+    if tuple(x.shape) != (B, 5, S, S) or B < 1 or S % 16:
+        raise ValueError("symmetry_expand: x [B,5,S,S] fp32 with S % 16 == 0 expected")
+    if out is None:
+        out = torch.empty(n, B, 5, S, S, dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != (n, B, 5, S, S):
+        raise ValueError("symmetry_expand: out [n,B,5,S,S] expected")
+    with torch.cuda.device(x.device):
+        rc = _lib.lib().nbp_ensemble_expand_f32(_lib.ptr(x), B, S, _lib.ptr(ops), n, _lib.ptr(out), _st())
+    _lib.check(rc, "nbp_ensemble_expand_f32")
+    return out
+
+
+def symmetry_reduce(raw1, raw2, ops, out=None):
+    """raw1 [n,B,8,S/4,S/4] and raw2 [n,B,1,S,S] fp32, the network's outputs on symmetry_expand's batch, and ops int32 [n] ->
+    (out1 [B,8,S/4,S/4], out2 [B,1,S,S]): every member moved back by its inverse element and averaged over the members that reach
+    the cell (utility/augment.py::ensemble_reference); one launch (nbp_ensemble_reduce_f32).  out = (out1, out2): caller-owned."""
+    tensors = (("raw1", raw1), ("raw2", raw2)) + ((("out1", out[0]), ("out2", out[1])) if out is not None else ())
+    n = _ensemble_args("symmetry_reduce", ops, *tensors)
+    if raw1.dim() != 5 or raw2.dim() != 5:
+        raise ValueError("symmetry_reduce: raw1 [n,B,8,S/4,S/4] and raw2 [n,B,1,S,S] expected")
+    B, S = raw2.shape[1], raw2.shape[-1]
+    if tuple(raw2.shape) != (n, B, 1, S, S) or B < 1 or S % 16 or tuple(raw1.shape) != (n, B, 8, S // 4, S // 4):
+        raise ValueError("symmetry_reduce: raw1 [n,B,8,S/4,S/4] and raw2 [n,B,1,S,S] with S % 16 == 0 and n = len(ops) expected")
+    if out is None:
+        out1 = torch.empty(B, 8, S // 4, S // 4, dtype=torch.float32, device=raw1.device)
+        out2 = torch.empty(B, 1, S, S, dtype=torch.float32, device=raw1.device)
+    else:
+        out1, out2 = out
+        if tuple(out1.shape) != (B, 8, S // 4, S // 4) or tuple(out2.shape) != (B, 1, S, S):
+            raise ValueError("symmetry_reduce: out = (out1 [B,8,S/4,S/4], out2 [B,1,S,S]) expected")
+    with torch.cuda.device(raw1.device):
+        rc = _lib.lib().nbp_ensemble_reduce_f32(_lib.ptr(raw1), _lib.ptr(raw2), B, S, _lib.ptr(ops), n, _lib.ptr(out1), _lib.ptr(out2),
+                                                _st())
+    _lib.check(rc, "nbp_ensemble_reduce_f32")
+    return out1, out2
