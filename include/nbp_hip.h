@@ -893,6 +893,26 @@ int nbp_ensemble_expand_f32(const float* x, int B, int S, const int* ops_dev, in
 int nbp_ensemble_reduce_f32(const float* raw1, const float* raw2, int B, int S, const int* ops_dev, int n, float* out1, float* out2,
                             void* stream);
 
+/* The compact replay record (csrc/nbp_replay.hip; not in the reference): a lossless, bit-exact encoding of the 6
+ * planes of a replay record ('current_model_input' [1,5,S,S] + 'current_gt_2d_layout' [1,1,S,S], fp32) whose definition is
+ * nextbestpath_amd/utility/replay_codec.py ("NBPC" version 1): a 64-byte header, then per channel a bitmap of the pixels whose
+ * fp32 bit pattern is not zero and those pixels at 0 (all 1.0f), 1 (u8), 2 (u16) or 4 (raw fp32 bits) bytes each.
+ *   nbp_replay_stream_bound  the largest stream of a record of side S, 64 + 6 (S^2/8 + 4 S^2); 0 for an unsupported S.
+ *   encode   rec [n,6,S,S] -> the stream of record r at arena + r * stride_bytes, byte for byte replay_codec.encode's, padding
+ *            included; no byte of a slot beyond the stream's total_bytes is written.  stride_bytes >= nbp_replay_stream_bound(S)
+ *            and a multiple of 16 (else NBP_E_WS).  Two launches, no atomics: two runs give the same bytes.
+ *   decode   `streams`: one device byte buffer that holds n streams at the 16-byte-aligned byte offsets offsets_host[r] (a HOST
+ *            array, read during the call: the offsets ride in the kernel arguments, 64 records per launch) -> x_out [n,5,S,S] and
+ *            gt_out [n,1,S,S], every pixel written, zeros included.  The host validates the headers first
+ *            (replay_codec.parse_header); the kernel clamps nnz, the widths and every value index again, so whatever the bytes it
+ *            reads no further than nbp_replay_stream_bound(S) bytes behind an offset and writes nothing outside the outputs.
+ * 16 <= S <= 512, S % 16 == 0, 16-byte aligned pointers (else NBP_E_SHAPE); NBP_E_ARG: null pointer, n < 1, an offset that is
+ * negative or off the 16-byte grid; nothing is launched or written on an error. */
+size_t nbp_replay_stream_bound(int S);
+int nbp_replay_encode_f32(const float* rec, int n, int S, void* arena, size_t stride_bytes, void* stream);
+int nbp_replay_decode_f32(const void* streams, const long long* offsets_host, int n, int S, float* x_out, float* gt_out,
+                          void* stream);
+
 /* ---- The optimizer step (csrc/nbp_optim.hip): the reference's torch.optim.AdamW(lr 1e-3, betas (0.9, 0.999), eps 1e-8, weight decay
  * 0.01) of next_best_path/utility/nbp_utils.py:228 and its scaler.step(optimizer) / scaler.update() of nbp_utils.py:386-388 (a
  * GradScaler drops a step whose gradients hold an inf or a NaN), plus the global-norm clipping of torch.nn.utils.clip_grad_norm_,

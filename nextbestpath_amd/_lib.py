@@ -224,6 +224,9 @@ SIGNATURES["nbp_ema_state_bytes"] = (_sz, [])
 SIGNATURES["nbp_ema_update_f32"] = (_i, [_vp, _vp, _i, _vp, _vp, _d, _i, _vp])
 SIGNATURES["nbp_ensemble_expand_f32"] = (_i, [_vp, _i, _i, _vp, _i, _vp, _vp])
 SIGNATURES["nbp_ensemble_reduce_f32"] = (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp])
+SIGNATURES["nbp_replay_stream_bound"] = (_sz, [_i])
+SIGNATURES["nbp_replay_encode_f32"] = (_i, [_vp, _i, _i, _vp, _sz, _vp])
+SIGNATURES["nbp_replay_decode_f32"] = (_i, [_vp, C.POINTER(_ll), _i, _i, _vp, _vp, _vp])
 
 _lock = threading.Lock()
 _lib = None

@@ -104,7 +104,21 @@ def make_synthetic_experiences(n, S=256, seed=0):
 _STAGE_BATCHES = True      # False: every batch through _collate's synchronous copies (the bit-identity tests' reference)
 
 
+def _expanded(batch_data):
+    """Records read with keep_compact=True -> the five-key form (compact ones decoded on the host by the numpy codec)."""
+    if any("nbpc" in d for d in batch_data):
+        from ..utility.nbp_utils import expand_record
+        return [expand_record(d) for d in batch_data]
+    return batch_data
+
+
+def _record_side(d):
+    """Side S of a record's maps, in either form."""
+    return int(d["S"]) if "nbpc" in d else d["current_model_input"].shape[-1]
+
+
 def _collate(batch_data, device):
+    batch_data = _expanded(batch_data)
     # (np.concatenate, not torch.cat of 32 x 1.3 MB: on a 256-core host torch's intra-op thread pool made that concatenation cost
     # 50-600 ms per batch, tools/diag/train_loop_ab.py)
     xs = torch.from_numpy(np.concatenate([d["current_model_input"] for d in batch_data])).to(device)
@@ -204,8 +218,80 @@ def _collate_staged(batch_data, device, stager, ops=None):
     return (out if ops is None else out + (dev["ops"],)), ev
 
 
+class _PendingDecode:
+    """The images of a batch of compact records on their way to the device: the streams back to back in one staged uint8 buffer.
+    `finish` expands them with one launch (hipops.replay_decode) on the CURRENT stream, which must have waited for the stager's
+    event: the same xs / gt tensors, bit for bit, as the reference-format records' staged copy."""
+
+    def __init__(self, streams, offsets, S):
+        self.streams, self.offsets, self.S = streams, offsets, S
+
+    def finish(self, device):
+        self.streams.record_stream(torch.cuda.current_stream(device))
+        return hipops.replay_decode(self.streams, self.offsets, self.S)
+
+
+def _collate_compact(batch_data, device, stager, ops=None):
+    """_collate_staged for a batch whose records are all compact (unpack_record(..., keep_compact=True): headers validated): the
+    streams go back to back, each padded to 16 bytes, into one pinned uint8 staging buffer -- a few per cent of the 1.3 MB per record
+    of the expanded maps through pinned memory and over the host-to-device link; targets, gains, indices and op codes as ever.
+    -> ((_PendingDecode, None, coords, gains, bidx[, ops]), event); _await_batch turns the first two into xs and gt."""
+    n = len(batch_data)
+    S = _record_side(batch_data[0])
+    if any(_record_side(d) != S for d in batch_data):
+        raise ValueError("replay records of different map sizes in one batch")
+    coords = [np.asarray(d["target_value_map_pixel"]) for d in batch_data]
+    V = S // 4
+    for d, c in zip(batch_data, coords):
+        if c.size and (c.min() < 0 or c[:, 0].max() >= 8 or c[:, 1:].max() >= V):
+            raise IndexError(f"target_value_map_pixel out of range for an [8,{V},{V}] value map (pose_i={d.get('pose_i')})")
+    K = int(sum(len(c) for c in coords))
+    offsets, total = [], 0
+    for d in batch_data:
+        offsets.append(total)
+        total += (len(d["nbpc"]) + 15) & ~15
+    stager.begin()
+    buf = stager.buffer("streams", (total,), torch.uint8).numpy()
+    cd = stager.buffer("coords", (K, 3), torch.int64).numpy()
+    gn = stager.buffer("gains", (K,), torch.float32).numpy()
+    bi = stager.buffer("bidx", (K,), torch.int64).numpy()
+    if ops is not None:
+        stager.buffer("ops", (n,), torch.int32).numpy()[:] = ops
+    k = 0
+    for i, (d, c) in enumerate(zip(batch_data, coords)):
+        m = len(d["nbpc"])
+        buf[offsets[i]:offsets[i] + m] = np.frombuffer(d["nbpc"], dtype=np.uint8)
+        buf[offsets[i] + m:offsets[i + 1] if i + 1 < n else total] = 0
+        m = len(c)
+        cd[k:k + m] = c
+        gn[k:k + m] = d["actual_coverage_gain"]
+        bi[k:k + m] = i
+        k += m
+    dev, ev = stager.commit()
+    out = (_PendingDecode(dev["streams"], offsets, S), None, dev["coords"], dev["gains"], dev["bidx"])
+    return (out if ops is None else out + (dev["ops"],)), ev
+
+
+def _await_batch(tensors, ev, device):
+    """The consumer's side of a staged batch: the current stream waits for the copies, keeps their buffers, and expands a compact
+    batch's streams.  -> the tensors, xs and gt first."""
+    cur = torch.cuda.current_stream(device)
+    cur.wait_event(ev)
+    pending = tensors[0] if isinstance(tensors[0], _PendingDecode) else None
+    for t in tensors[2 if pending else 0:]:
+        t.record_stream(cur)
+    if pending:
+        tensors = pending.finish(device) + tuple(tensors[2:])
+    return tensors
+
+
 def _collate_any(batch_data, device, stager, ops=None):
-    """Staged collation for records of the replay store's shape (one map per record); anything else through _collate."""
+    """Staged collation for records of the replay store's shape (one map per record); anything else through _collate.  A batch of
+    compact records only goes to the device as streams (_collate_compact); a batch that mixes the formats has its compact records
+    decoded on the host first."""
+    if all("nbpc" in d for d in batch_data):
+        return _collate_compact(batch_data, device, stager, ops)
+    batch_data = _expanded(batch_data)
     if all(d["current_model_input"].shape[0] == 1 and d["current_gt_2d_layout"].shape[0] == 1 for d in batch_data):
         return _collate_staged(batch_data, device, stager, ops)
     ev = torch.cuda.Event()
@@ -325,7 +411,7 @@ def train_experience_data(training_set_db, params, optimizer, nbp, device, curre
         if aug_rng is None:
             return batch, None
         ops = augment.draw_ops(aug_rng, len(batch), aug_p)
-        return augment.augment_records(batch, ops, batch[0]["current_model_input"].shape[-1] // 4), ops
+        return augment.augment_records(batch, ops, _record_side(batch[0]) // 4), ops
 
     staged = None            # (batch index, tensors, event) of the batch whose copies were started under the previous one's compute
     for bi in range(n_batches):
@@ -344,10 +430,7 @@ def train_experience_data(training_set_db, params, optimizer, nbp, device, curre
             if staged is None or staged[0] != bi:
                 batch, ops = augmented(batch)
                 staged = (bi,) + _collate_any(batch, device, stager, ops)
-            tensors, ev = staged[1], staged[2]
-            torch.cuda.current_stream(device).wait_event(ev)
-            for t in tensors:
-                t.record_stream(torch.cuda.current_stream(device))
+            tensors = _await_batch(staged[1], staged[2], device)
             xs, gt, coords, gains, bidx = tensors[:5]
             ops = tensors[5] if len(tensors) > 5 else None
         if ops is not None:
@@ -409,10 +492,8 @@ def validation_model(training_set_db, params, nbp, device):
         if stager is None:
             xs, gt, coords, gains, bidx = _collate(training_set_db[i:i + bs], device)
         else:
-            (xs, gt, coords, gains, bidx), ev = _collate_any(training_set_db[i:i + bs], device, stager)
-            torch.cuda.current_stream(device).wait_event(ev)
-            for t in (xs, gt, coords, gains, bidx):
-                t.record_stream(torch.cuda.current_stream(device))
+            tensors, ev = _collate_any(training_set_db[i:i + bs], device, stager)
+            xs, gt, coords, gains, bidx = _await_batch(tensors, ev, device)
         out1, out2 = nbp(xs)
         pred = tr.gather_values(out1, bidx, coords)
         parts.append((tr.MeanLossFn.apply(pred, gains, 0) + tr.MeanLossFn.apply(out2, gt, 1)).detach())    # (no sync per batch)
@@ -525,9 +606,11 @@ def run_training_nbp(params):
                                          rollouts_per_gpu=getattr(params, "collect_rollouts_per_gpu", 1))
         print(f"[rank {rank}] epoch {epoch}: collected {n} records ({env.entries()} in the store)")
         if epoch == 0:
-            validation = nu.store_validation_data(env, getattr(params, "n_validation", 1200))
+            validation = nu.store_validation_data(env, getattr(params, "n_validation", 1200), keep_compact=True)
             continue
-        db = nu.read_combined_data(env, sample_m=None) if epoch == 1 else nu.read_combined_data(env)   # ref :436-440
+        # (compact records stay streams in host memory and are expanded on the device, batch by batch: _collate_compact)
+        db = (nu.read_combined_data(env, sample_m=None, keep_compact=True) if epoch == 1
+              else nu.read_combined_data(env, keep_compact=True))   # ref :436-440
         # every rank must take the same branch (the training loop below contains collectives)
         if _common_count(1 if (db and validation) else 0, device) == 0:
             continue

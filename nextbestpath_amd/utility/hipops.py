@@ -738,3 +738,59 @@ def symmetry_reduce(raw1, raw2, ops, out=None):
                                                 _st())
     _lib.check(rc, "nbp_ensemble_reduce_f32")
     return out1, out2
+
+
+def replay_stream_bound(S):
+    """Largest compact stream of a record of side S (nbp_replay_stream_bound; utility/replay_codec.py::stream_bound)."""
+    n = int(_lib.lib().nbp_replay_stream_bound(int(S)))
+    if n == 0:
+        raise ValueError(f"replay_stream_bound: S = {S} is not a multiple of 16 in 16..512")
+    return n
+
+
+def replay_encode(rec, arena=None):
+    """rec [n,6,S,S] fp32 on the device (five input maps + the obstacle label per record) -> arena [n, stride] uint8 on the device:
+    row r starts with record r's compact stream (utility/replay_codec.py's bytes; its header holds total_bytes), the rest of the
+    row is left as it was.  Two launches (nbp_replay_encode_f32), no host synchronisation.  arena: a caller-owned [n, stride]
+    uint8 tensor with stride >= replay_stream_bound(S), a multiple of 16."""
+    if not isinstance(rec, torch.Tensor) or not rec.is_cuda:
+        raise RuntimeError("replay_encode: the HIP path needs a cuda tensor for rec (no CPU fallback)")
+    if rec.dtype != torch.float32 or rec.dim() != 4 or rec.shape[1] != 6 or rec.shape[2] != rec.shape[3] or rec.shape[0] < 1:
+        raise ValueError("replay_encode: rec [n,6,S,S] fp32 expected")
+    n, S = rec.shape[0], rec.shape[-1]
+    if arena is None:
+        arena = torch.empty(n, replay_stream_bound(S), dtype=torch.uint8, device=rec.device)
+    elif (not isinstance(arena, torch.Tensor) or not arena.is_cuda or arena.dtype != torch.uint8 or arena.dim() != 2
+          or arena.shape[0] != n):
+        raise ValueError("replay_encode: arena [n, stride] uint8 on the device expected")
+    with torch.cuda.device(rec.device):
+        rc = _lib.lib().nbp_replay_encode_f32(_lib.ptr(rec), n, S, _lib.ptr(arena), int(arena.shape[1]), _st())
+    _lib.check(rc, "nbp_replay_encode_f32")
+    return arena
+
+
+def replay_decode(streams, offsets, S, out=None):
+    """streams: a uint8 device buffer that holds n compact streams at the byte offsets `offsets` (a host sequence of ints, each a
+    multiple of 16), headers already validated by the host (replay_codec.parse_header) -> (x [n,5,S,S], gt [n,1,S,S]) fp32, every
+    pixel written: one launch (nbp_replay_decode_f32; per 64 records).  out = (x, gt): caller-owned results."""
+    if not isinstance(streams, torch.Tensor) or not streams.is_cuda:
+        raise RuntimeError("replay_decode: the HIP path needs a cuda tensor for streams (no CPU fallback)")
+    if streams.dtype != torch.uint8 or streams.dim() != 1:
+        raise ValueError("replay_decode: streams is a flat uint8 tensor")
+    offs = [int(o) for o in offsets]
+    n = len(offs)
+    if n < 1 or min(offs) < 0 or max(offs) + 64 > streams.numel():
+        raise ValueError("replay_decode: 1 or more offsets inside the buffer expected")
+    if out is None:
+        x = torch.empty(n, 5, S, S, dtype=torch.float32, device=streams.device)
+        gt = torch.empty(n, 1, S, S, dtype=torch.float32, device=streams.device)
+    else:
+        x, gt = out
+        if (x.dtype != torch.float32 or gt.dtype != torch.float32 or tuple(x.shape) != (n, 5, S, S)
+                or tuple(gt.shape) != (n, 1, S, S) or x.device != streams.device or gt.device != streams.device):
+            raise ValueError("replay_decode: out = (x [n,5,S,S], gt [n,1,S,S]) fp32 on the streams' device expected")
+    arr = (C.c_longlong * n)(*offs)
+    with torch.cuda.device(streams.device):
+        rc = _lib.lib().nbp_replay_decode_f32(_lib.ptr(streams), arr, n, int(S), _lib.ptr(x), _lib.ptr(gt), _st())
+    _lib.check(rc, "nbp_replay_decode_f32")
+    return x, gt

@@ -28,6 +28,7 @@ import torch
 
 from . import hipops
 from . import planner_host
+from . import replay_codec
 from . import utils as hu
 
 
@@ -53,22 +54,71 @@ def _decode(obj):
     return np.frombuffer(g("data"), dtype=dt)[0]
 
 
-def pack_record(data) -> bytes:
-    """ref :35-41 (tensors -> numpy -> msgpack with use_bin_type)."""
+REPLAY_FORMATS = ("reference", "compact")
+
+
+def check_replay_format(replay_format):
+    if replay_format not in REPLAY_FORMATS:
+        raise ValueError(f"replay_format {replay_format!r}: expected one of {REPLAY_FORMATS}")
+    return replay_format
+
+
+def _stream_of(data) -> bytes:
+    """The compact stream a record dict carries under 'nbpc' (bytes, or a uint8 array / host tensor that starts with it)."""
+    st = data["nbpc"]
+    if isinstance(st, (bytes, bytearray)):
+        return bytes(st)
+    a = st.detach().cpu().numpy() if isinstance(st, torch.Tensor) else np.asarray(st)
+    a = np.ascontiguousarray(a, dtype=np.uint8).reshape(-1)
+    return a[:replay_codec.used_bytes(a)].tobytes()
+
+
+def pack_record(data, replay_format="reference") -> bytes:
+    """ref :35-41 (tensors -> numpy -> msgpack with use_bin_type).  replay_format "reference" (the default): the reference's
+    bytes.  "compact": the same map with the two image arrays replaced by key 'nbpc', the record's compact stream
+    (utility/replay_codec.py; lossless) -- the one `data` carries under 'nbpc', else the numpy codec's from its arrays."""
+    check_replay_format(replay_format)
     np_ = lambda v: v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
-    return msgpack.packb({
-        "current_model_input": np_(data["current_model_input"]),
-        "current_gt_2d_layout": np_(data["current_gt_2d_layout"]),
+    small = {
         "target_value_map_pixel": np_(data["target_value_map_pixel"]),
         "actual_coverage_gain": np_(data["actual_coverage_gain"]),
         "pose_i": np.array(data["pose_i"]),
-    }, use_bin_type=True, default=_encode)
+    }
+    if replay_format == "compact":
+        stream = _stream_of(data) if "nbpc" in data else replay_codec.encode(np_(data["current_model_input"]),
+                                                                             np_(data["current_gt_2d_layout"]))
+        return msgpack.packb({"nbpc": stream, **small}, use_bin_type=True, default=_encode)
+    if "nbpc" in data and "current_model_input" not in data:
+        x, gt = replay_codec.decode(_stream_of(data))
+    else:
+        x, gt = np_(data["current_model_input"]), np_(data["current_gt_2d_layout"])
+    return msgpack.packb({"current_model_input": x, "current_gt_2d_layout": gt, **small}, use_bin_type=True, default=_encode)
 
 
-def unpack_record(value: bytes):
+def unpack_record(value: bytes, keep_compact=False):
+    """A stored value -> the record dict.  The record itself says how it is read: a reference-format one comes back as ever,
+    whatever the flag; a compact one comes back with the same five keys, its images decoded by the numpy codec -- or, with
+    keep_compact, as {'nbpc': stream, 'S': side, + the three small keys} after the stream's header has been validated (the
+    trainer expands such records on the device, hipops.replay_decode)."""
     rec = msgpack.unpackb(value, object_hook=_decode, raw=False, strict_map_key=False)
     rec["pose_i"] = int(np.asarray(rec["pose_i"]))
+    if "nbpc" in rec:
+        if keep_compact:
+            rec["S"] = replay_codec.parse_header(rec["nbpc"])[0]
+            return rec
+        stream = rec.pop("nbpc")
+        x, gt = replay_codec.decode(stream)
+        rec = {"current_model_input": x, "current_gt_2d_layout": gt, **rec}
     return rec
+
+
+def expand_record(rec):
+    """A record as unpack_record(..., keep_compact=True) returns it -> the five-key form (host decode); others pass through."""
+    if "nbpc" not in rec:
+        return rec
+    rest = {k: v for k, v in rec.items() if k not in ("nbpc", "S")}
+    x, gt = replay_codec.decode(rec["nbpc"])
+    return {"current_model_input": x, "current_gt_2d_layout": gt, **rest}
 
 
 # ------------------------------------------------------------------ containers
@@ -252,10 +302,10 @@ def open_experience_db(path, map_size=200 * 1024 ** 3):
 _last_key = [0]
 
 
-def store_experience(env, data):
+def store_experience(env, data, replay_format="reference"):
     """ref :32-44.  The key is the millisecond clock; two records in the same millisecond would overwrite each
     other in the reference -- here the key is bumped so that none is lost."""
-    store_packed(env, pack_record(data))
+    store_packed(env, pack_record(data, replay_format))
 
 
 def store_packed(env, value: bytes):
@@ -265,7 +315,7 @@ def store_packed(env, value: bytes):
     env.put(f"{ms:012d}".encode(), value)
 
 
-def store_validation_data(env, num=600 * 2):
+def store_validation_data(env, num=600 * 2, keep_compact=False):
     """ref :78-100: every ceil(total/num)-th record, up to `num`, is MOVED out of the store."""
     total = env.entries()
     print("Number of total data in the database:", total)
@@ -273,7 +323,7 @@ def store_validation_data(env, num=600 * 2):
     selected, delete_keys = [], []
     for count, (key, value) in enumerate(env.items()):
         if count % n == 0 and len(selected) < num:
-            selected.append(unpack_record(value))
+            selected.append(unpack_record(value, keep_compact))
             delete_keys.append(key)
             if len(selected) == num:
                 break
@@ -282,29 +332,29 @@ def store_validation_data(env, num=600 * 2):
     return selected
 
 
-def store_validation_data_readonly(env, num=600 * 2):
+def store_validation_data_readonly(env, num=600 * 2, keep_compact=False):
     """ref :46-61."""
     total = env.entries()
     n = max(math.ceil(total / num), 1)
     selected = []
     for count, (key, value) in enumerate(env.items()):
         if count % n == 0 and len(selected) < num:
-            selected.append(unpack_record(value))
+            selected.append(unpack_record(value, keep_compact))
     return selected
 
 
-def read_random_data_readonly(env, num_samples=64):
+def read_random_data_readonly(env, num_samples=64, keep_compact=False):
     """ref :63-76."""
     indices = set(random.sample(range(env.entries()), num_samples))
-    return [unpack_record(v) for i, (k, v) in enumerate(env.items()) if i in indices]
+    return [unpack_record(v, keep_compact) for i, (k, v) in enumerate(env.items()) if i in indices]
 
 
-def read_combined_data(env, sample_m=2304 * 2, sample_size=2176 * 2):
+def read_combined_data(env, sample_m=2304 * 2, sample_size=2176 * 2, keep_compact=False):
     """ref :103-141: a random sample of the older records + the newest `sample_m` in order."""
     total = env.entries()
     print("number of total data in the database:", total)
     if sample_m is None:
-        return [unpack_record(v) for _, v in env.items()]
+        return [unpack_record(v, keep_compact) for _, v in env.items()]
     n = total - sample_m
     if n < 0:
         n = 1
@@ -313,9 +363,9 @@ def read_combined_data(env, sample_m=2304 * 2, sample_size=2176 * 2):
     first_tail = max(total - sample_m, 0)
     for i, (key, value) in enumerate(env.items()):
         if i < n and i in sample_indices:
-            selected.append(unpack_record(value))
+            selected.append(unpack_record(value, keep_compact))
         if i >= first_tail:
-            tail.append(unpack_record(value))
+            tail.append(unpack_record(value, keep_compact))
     return selected + tail
 
 
@@ -339,8 +389,9 @@ class CollectionRollout:
     P_RANDOM_HEADING = 0.6         # ref :768
 
     def __init__(self, params, nbp, camera, gt_scene_pc, mesh, y_bins, device, db_env, seed=0, grid=256,
-                 value_size=64, grid_range=(-40, 40)):
+                 value_size=64, grid_range=(-40, 40), replay_format="reference"):
         from ..testers.nbp_planning import RolloutState
+        self.replay_format = check_replay_format(replay_format)
         from .long_term_utils import LatticePlanner
         self.params, self.nbp, self.camera, self.mesh, self.device, self.db = params, nbp, camera, mesh, device, db_env
         self.y_bins, self.S, self.V, self.grid_range = y_bins, grid, value_size, grid_range
@@ -483,15 +534,18 @@ class CollectionRollout:
                     pixels.append([int(e[4]), r, c])
                     gains.append(d * 100 if d > 0 else 0)
             if pixels:
+                # (compact collection: the experience holds its encoded slot, no label -- pack_record keeps the stream's bytes)
+                images = ({"nbpc": ex_list[a][1]} if ex_list[a][2] is None else
+                          {"current_model_input": ex_list[a][1], "current_gt_2d_layout": ex_list[a][2]})
                 self.put({
-                    "current_model_input": ex_list[a][1], "current_gt_2d_layout": ex_list[a][2],
+                    **images,
                     "target_value_map_pixel": np.asarray(pixels, np.int64),
                     "actual_coverage_gain": np.asarray(gains, np.float32), "pose_i": pose_i})
                 self.n_stored += 1
         self.experiences = []
 
     def put(self, data):
-        store_experience(self.db, data)
+        store_experience(self.db, data, self.replay_format)
 
     def _replan(self, pose, model_input):
         """Boltzmann goal sampling + search (ref :695-745).  Returns the path or None."""
@@ -546,6 +600,8 @@ class CollectionRollout:
             if self._needs_replan():
                 self._decide_begin(pose_i)
                 self.path = self._replan(pose, model_input)
+            if self.replay_format == "compact":     # the record's planes through the encoder, one record: the experience keeps the slot
+                model_input, gt_obs = hipops.replay_encode(torch.cat((model_input, gt_obs), 1))[0], None
             if self._decide_end(self.coverage_evolution[-1], pose, model_input, gt_obs):
                 break
             self._move(pose_i)
@@ -562,8 +618,9 @@ class CollectionGroup:
     and its slot takes the rank's next scene.  Records are packed per scene and reach the store in serial order: scene order, then
     flush order within a scene (the earliest unfinished scene streams its records; later scenes hold theirs until it is done)."""
 
-    def __init__(self, make_rollout, scenes, K, n_poses, device, timing=None):
+    def __init__(self, make_rollout, scenes, K, n_poses, device, timing=None, replay_format="reference"):
         self.make, self.queue, self.K, self.n_poses, self.device = make_rollout, list(scenes), int(K), n_poses, device
+        self.replay_format = check_replay_format(replay_format)
         self.order = list(scenes)                  # commit order
         self.held = {si: [] for si in self.order}  # packed records not yet in the store
         self.done = {}                             # si -> finished rollout's (coverage_at_trajectory, n_stored)
@@ -613,7 +670,7 @@ class CollectionGroup:
     def _pack(self):
         t0 = time.perf_counter()
         for held in self.held.values():             # in place: the rollouts' put() appends to these lists
-            held[:] = [v if isinstance(v, bytes) else pack_record(v) for v in held]
+            held[:] = [v if isinstance(v, bytes) else pack_record(v, self.replay_format) for v in held]
         self._tick("pack_s", t0)
 
     def _buffers(self, n, S):
@@ -692,8 +749,12 @@ class CollectionGroup:
         rec[:, 5].copy_(label)
         # the records' tensors: one copy per group step (complete before any flush reads them: a flush happens in a later group step,
         # after that step's blocking read-back of the coverage counts on this stream)
-        rec_h = torch.empty(rec.shape, dtype=torch.float32, pin_memory=True)
-        rec_h.copy_(rec, non_blocking=True)
+        # (compact records: the step's planes through the encoder first -- two more launches on this stream, no synchronisation --
+        # and the copy moves the arena of streams instead; an experience keeps its slot, the flush keeps the stream's total_bytes)
+        compact = self.replay_format == "compact"
+        src = hipops.replay_encode(rec) if compact else rec
+        rec_h = torch.empty(src.shape, dtype=src.dtype, pin_memory=True)
+        rec_h.copy_(src, non_blocking=True)
         # -- decide: flush the finished segments (hindsight cells in one launch), ONE forward of the replanning rollouts' inputs
         replan = [i for i, ro in enumerate(grp) if ro._needs_replan()]
         flush = [i for i in replan if len(grp[i].experiences) > 1]
@@ -739,7 +800,7 @@ class CollectionGroup:
         t0 = self._tick("gpu_step_s", t0)
         alive = []
         for i, ro in enumerate(grp):
-            model_input, gt_obs = rec_h[i:i + 1, :5], rec_h[i:i + 1, 5:6]
+            model_input, gt_obs = (rec_h[i], None) if compact else (rec_h[i:i + 1, :5], rec_h[i:i + 1, 5:6])
             if i in goal:
                 ro._decide_begin(ro.pose_i, cells_h.get(i))
                 ro.path = ro._search(poses[i], *goal[i])
@@ -788,14 +849,17 @@ class CollectionGroup:
 
 def trajectory_collection(params, current_epoch, dataset, db_env, pc2img_size, value_map_size, prediction_range, nbp,
                           coverage_after_trajectory, memory, device, folder_img_path=None, rank=0, world=1, n_poses=100,
-                          n_gt_points=None, rollouts_per_gpu=1, timing=None):
+                          n_gt_points=None, rollouts_per_gpu=1, timing=None, replay_format=None):
     """ref :470-852.  `dataset` is a simulator.scene.SceneDataset; with world > 1 each rank collects the scenes
     rank, rank + world, ... into its own store (collection is embarrassingly parallel).
     rollouts_per_gpu = K > 1: up to K of the rank's scenes in lock-step (CollectionGroup); the store receives the same records in
-    the same order as with K = 1.  `timing` (a dict, K > 1) receives the seconds of the group's stages."""
+    the same order as with K = 1.  `timing` (a dict, K > 1) receives the seconds of the group's stages.
+    replay_format: "reference" (the reference's record bytes) or "compact" (utility/replay_codec.py: the same record, its images
+    encoded on the device before they leave it); None = params.replay_format, "reference" when the config does not name one."""
     from ..simulator import scene as sim_scene
     from ..testers.nbp_planning import setup_test_camera
     nbp.eval()
+    replay_format = check_replay_format(getattr(params, "replay_format", "reference") if replay_format is None else replay_format)
 
     def make(si):
         sd = dataset[si]
@@ -807,11 +871,12 @@ def trajectory_collection(params, current_epoch, dataset, db_env, pc2img_size, v
         _, gt_dev = sim_scene.setup_gt_scene(params, settings, mesh, device, 0.05, seed=seed, n_points=n_gt_points)
         camera = setup_test_camera(params, mesh, settings.camera.start_positions[0], settings, device, seed=seed)
         return CollectionRollout(params, nbp, camera, gt_dev, mesh, y_bins, device, db_env, seed,
-                                 pc2img_size[0], value_map_size[0], prediction_range)
+                                 pc2img_size[0], value_map_size[0], prediction_range, replay_format=replay_format)
 
     scenes = list(range(rank, len(dataset), world))
     if int(rollouts_per_gpu) > 1:
-        return CollectionGroup(make, scenes, rollouts_per_gpu, n_poses, device, timing).run(db_env, coverage_after_trajectory)
+        return CollectionGroup(make, scenes, rollouts_per_gpu, n_poses, device, timing, replay_format).run(db_env,
+                                                                                                           coverage_after_trajectory)
     stored = 0
     for si in scenes:
         ro = make(si)

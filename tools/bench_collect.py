@@ -24,7 +24,7 @@ from nextbestpath_amd.utility import nbp_utils as nu  # noqa: E402
 from nextbestpath_amd.utility.synthetic import make_explorer_state_dict  # noqa: E402
 
 
-def run(params, ds, net, K, n_poses, tmp, tag):
+def run(params, ds, net, K, n_poses, tmp, tag, replay_format="reference"):
     env = nu.open_experience_db(os.path.join(tmp, tag))
     timing = {}
     counted = []
@@ -39,14 +39,16 @@ def run(params, ds, net, K, n_poses, tmp, tag):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         n = nu.trajectory_collection(params, 1, ds, env, (256, 256), (64, 64), (-40, 40), net, [], None, torch.device("cuda"),
-                                     n_poses=n_poses, n_gt_points=50000, rollouts_per_gpu=K, timing=timing)
+                                     n_poses=n_poses, n_gt_points=50000, rollouts_per_gpu=K, timing=timing,
+                                     replay_format=replay_format)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
     finally:
         nu.CollectionRollout._observed = orig
     entries = env.entries()
+    value_bytes = sum(len(v) for _, v in env.items())
     env.close()
-    out = {"K": K, "seconds": round(dt, 3), "poses": len(counted), "records": n, "entries": entries,
+    out = {"replay_format": replay_format, "value_bytes": value_bytes, "K": K, "seconds": round(dt, 3), "poses": len(counted), "records": n, "entries": entries,
            "poses_per_s": round(len(counted) / dt, 1), "records_per_s": round(n / dt, 1)}
     if timing:
         out["stages_s"] = {k: round(v, 3) for k, v in timing.items()}
@@ -60,6 +62,8 @@ def main():
     ap.add_argument("--poses", type=int, default=100)
     ap.add_argument("--reps", type=int, default=2)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles/r07/collect_lockstep.json"))
+    ap.add_argument("--replay-format", choices=nu.REPLAY_FORMATS, default="reference",
+                    help="the records' format (nbp_utils.pack_record): the reference's, or the compact one encoded on the device")
     a = ap.parse_args()
     params = tp.load_params(os.path.join(ROOT, "configs/macarons/macarons_default_training_config.json"))
     net = NBP()
@@ -73,14 +77,14 @@ def main():
         runs = []
         with torch.no_grad():
             for K in (1, a.k):                                     # warm-up of each setting
-                run(params, ds, net, K, a.poses, tmp, f"warm_k{K}")
+                run(params, ds, net, K, a.poses, tmp, f"warm_k{K}", a.replay_format)
             for r in range(a.reps):
                 for K in (1, a.k):
-                    res = run(params, ds, net, K, a.poses, tmp, f"r{r}_k{K}")
+                    res = run(params, ds, net, K, a.poses, tmp, f"r{r}_k{K}", a.replay_format)
                     print(json.dumps(res), flush=True)
                     runs.append(res)
     best = {K: max((x for x in runs if x["K"] == K), key=lambda x: x["poses_per_s"]) for K in (1, a.k)}
-    summary = {"scenes": a.scenes, "n_poses": a.poses, "K": a.k, "runs": runs,
+    summary = {"replay_format": a.replay_format, "scenes": a.scenes, "n_poses": a.poses, "K": a.k, "runs": runs,
                "poses_per_s": {str(K): v["poses_per_s"] for K, v in best.items()},
                "records_per_s": {str(K): v["records_per_s"] for K, v in best.items()},
                "speedup_poses": round(best[a.k]["poses_per_s"] / best[1]["poses_per_s"], 2),

@@ -39,7 +39,13 @@ def main():
                     help="grad_clip_norm X > 0: global-norm clipping inside HipAdamW.step() (needs --optimizer hip)")
     ap.add_argument("--ema", type=float, default=None,
                     help="ema_decay D in [0, 1): a WeightEMA of the network (csrc/nbp_ema.hip), updated behind every optimizer step")
+    ap.add_argument("--replay-format", choices=("reference", "compact"), default=None,
+                    help="with a format every step also runs the trainer's per-batch data path on records of that format: staged "
+                         "collation (reference: the expanded maps; compact: the streams + one hipops.replay_decode launch).  "
+                         "Default: the batch is collated once, outside the timed steps")
     a = ap.parse_args()
+    if a.replay_format and a.augment > 0:
+        ap.error("--replay-format and --augment time different per-batch work: one at a time")
     dev = torch.device("cuda")
     torch.manual_seed(9)
     net = NBP().to(dev).train()
@@ -51,6 +57,13 @@ def main():
         ema = WeightEMA(net, a.ema)
     db = make_synthetic_experiences(a.batch, a.size, seed=3)
     xs, gt, coords, gains, bidx = _collate(db, dev)
+
+    stager = None
+    if a.replay_format:
+        from nextbestpath_amd.trainers.train_nbp_model import _BatchStager, _await_batch, _collate_any
+        from nextbestpath_amd.utility import nbp_utils as nu
+        records = [nu.unpack_record(nu.pack_record(d, a.replay_format), keep_compact=True) for d in db]
+        stager = _BatchStager(dev)
 
     aug_rng = random.Random(5)
     ops_dev = torch.zeros(a.batch, dtype=torch.int32, device=dev)
@@ -70,6 +83,11 @@ def main():
             xa, ga = hipops.augment_batch(xs, gt, ops_dev)
             o1, o2 = net(xa)
             loss = net.loss(tr.gather_values(o1, bi, cd), gn, o2, ga)
+        elif stager is not None:
+            tensors, ev = _collate_any(records, dev, stager)
+            xb, gb, cd, gn, bi = _await_batch(tensors, ev, dev)
+            o1, o2 = net(xb)
+            loss = net.loss(tr.gather_values(o1, bi, cd), gn, o2, gb)
         else:
             o1, o2 = net(xs)
             loss = net.loss(tr.gather_values(o1, bidx, coords), gains, o2, gt)
@@ -112,7 +130,7 @@ def main():
         "metric": f"NBP training maps/s (fwd+bwd+AdamW, {a.precision})", "value": round(a.batch / dt, 3), "unit": "maps/s",
         "n_gpus": 1, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(dt * 1e3, 2), "dtype": "f32",
         "train_precision": a.precision, "augment_probability": a.augment, "optimizer": a.optimizer, "grad_clip_norm": a.clip,
-        "ema_decay": a.ema, "ema_updates": None if ema is None else int(ema.num_updates),
+        "replay_format": a.replay_format, "ema_decay": a.ema, "ema_updates": None if ema is None else int(ema.num_updates),
         "data": "synthetic", "config": {"workload": f"configs[2]: train step, batch {a.batch} x {a.size}x{a.size}"},
         "tflops_reference_formulation": round(a.batch * flop_map / dt / 1e12, 2), "frac_of_split_ceiling_reference_formulation": round(a.batch * flop_map / dt / (2500e12 / 3), 4),
         "loss": float(loss.item()), "producer_notes": dict(tr.HANDOFF_STATS),
