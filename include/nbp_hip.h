@@ -913,6 +913,23 @@ int nbp_replay_encode_f32(const float* rec, int n, int S, void* arena, size_t st
 int nbp_replay_decode_f32(const void* streams, const long long* offsets_host, int n, int S, float* x_out, float* gt_out,
                           void* stream);
 
+/* Planner-facing validation metrics of one batch, per sample (csrc/nbp_metrics.hip; not in the reference; the
+ * definition of record is nextbestpath_amd/utility/metrics.py).  out1 [B,8,S/4,S/4], out2 and gt [B,1,S,S] fp32; coords [K,3] int64
+ * (heading, row, col), gains [K] fp32, bidx [K] int64 in any order (an index outside [0,B) belongs to no sample); thresholds_host: T
+ * floats on the HOST, 1 <= T <= 8, read during the call (they ride in the kernel arguments).  Into caller memory:
+ *   obst  int64 [B,T,4]  (tp, fp, fn, tn) of `out2 >= threshold` (fp32; a NaN is negative) against `gt > 0.5`
+ *   rank  int64 [B,6]    (n, n_bad, comparable, concordant, discordant, hit) over the sample's targets in record order; a target
+ *                        whose heading is outside [0,8) or whose row / column is outside [0,S/4) is counted in n_bad and never
+ *                        dereferenced
+ *   val   double [B,4]   (sum |p - g|, sum (p - g)^2, max g, g[pred_best]) over the good targets, in float64; zeros when n = 0
+ * One memset of obst and two launches on `stream`, no host synchronisation, no allocation.  Integer atomics only, the float64 sums by
+ * a fixed tree: two runs give the same bits.  K = 0 is legal (coords, gains and bidx may then be NULL).  NBP_E_ARG: null pointer,
+ * B < 1, K < 0, T outside 1..8; NBP_E_SHAPE: S % 4 != 0, S outside 4..16384, B > 65535, out2 or gt off the 16-byte grid, an output off
+ * the 8-byte grid; nothing is launched or written on an error. */
+int nbp_val_metrics_f32(const float* out1, const float* out2, const float* gt, const long long* coords, const float* gains,
+                        const long long* bidx, int B, int S, int K, int T, const float* thresholds_host, long long* obst,
+                        long long* rank, double* val, void* stream);
+
 /* ---- The optimizer step (csrc/nbp_optim.hip): the reference's torch.optim.AdamW(lr 1e-3, betas (0.9, 0.999), eps 1e-8, weight decay
  * 0.01) of next_best_path/utility/nbp_utils.py:228 and its scaler.step(optimizer) / scaler.update() of nbp_utils.py:386-388 (a
  * GradScaler drops a step whose gradients hold an inf or a NaN), plus the global-norm clipping of torch.nn.utils.clip_grad_norm_,

@@ -227,6 +227,7 @@ SIGNATURES["nbp_ensemble_reduce_f32"] = (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _v
 SIGNATURES["nbp_replay_stream_bound"] = (_sz, [_i])
 SIGNATURES["nbp_replay_encode_f32"] = (_i, [_vp, _i, _i, _vp, _sz, _vp])
 SIGNATURES["nbp_replay_decode_f32"] = (_i, [_vp, C.POINTER(_ll), _i, _i, _vp, _vp, _vp])
+SIGNATURES["nbp_val_metrics_f32"] = (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, C.POINTER(_f), _vp, _vp, _vp, _vp])
 
 _lock = threading.Lock()
 _lib = None

@@ -483,8 +483,62 @@ def sync_buffers(nbp):
         # num_batches_tracked: identical on every rank (same number of forward passes)
 
 
-def validation_model(training_set_db, params, nbp, device):
-    """ref nbp_utils.py:293-338: plain MSE + BCE in eval mode."""
+def metric_thresholds(params):
+    """The config's `validation_metrics` (false = off, the default) and `metric_thresholds` ([0.13]) -> None, or the checked tuple of
+    thresholds of the obstacle mask."""
+    if not bool(getattr(params, "validation_metrics", False)):
+        return None
+    from ..utility import metrics
+    return metrics.check_thresholds(getattr(params, "metric_thresholds", metrics.DEFAULT_THRESHOLDS))
+
+
+class ValidationMetrics:
+    """Accumulator of the planner-facing validation metrics (utility/metrics.py) for validation_model: `add` computes a batch's three
+    per-sample arrays on the device (hipops.validation_metrics: no synchronisation) and keeps them there; `read` brings all of
+    them to the host in ONE copy and adds their raw sums to `totals`; `summary` sums the totals over the ranks of a
+    torch.distributed job (one all_reduce of a float64 vector: counts far below 2^53, exact) and forms the ratios."""
+
+    def __init__(self, thresholds=(0.13,)):
+        from ..utility import metrics
+        self.thresholds = metrics.check_thresholds(thresholds)
+        self.totals = np.zeros(metrics.totals_size(len(self.thresholds)), np.float64)
+        self._pending = []
+
+    def add(self, out1, out2, gt, coords, gains, bidx):
+        self._pending.append(hipops.validation_metrics(out1.detach(), out2.detach(), gt, coords, gains, bidx, self.thresholds))
+
+    def read(self):
+        from ..utility import metrics
+        if not self._pending:
+            return
+        T, sizes = len(self.thresholds), [o.shape[0] for o, _, _ in self._pending]
+        # (the float64 sums travel as their bit patterns beside the integers: one device -> host copy for the whole loop)
+        flat = torch.cat([t.reshape(-1) if t.dtype == torch.int64 else t.reshape(-1).view(torch.int64)
+                          for group in zip(*self._pending) for t in group]).cpu().numpy()
+        self._pending = []
+        n = sum(sizes)
+        obst = flat[:n * T * 4].reshape(n, T, 4)
+        rank = flat[n * T * 4:n * (T * 4 + 6)].reshape(n, 6)
+        val = flat[n * (T * 4 + 6):].view(np.float64).reshape(n, 4)
+        self.totals += metrics.totals(obst, rank, val)
+
+    def summary(self, device=None):
+        from ..utility import metrics
+        self.read()
+        tot = self.totals
+        dist = _dist()
+        if dist is not None:
+            t = torch.from_numpy(tot.copy())
+            if dist.get_backend() == "nccl":
+                t = t.to(device)
+            dist.all_reduce(t)
+            tot = t.cpu().numpy()
+        return metrics.summarize_totals(tot, self.thresholds)
+
+
+def validation_model(training_set_db, params, nbp, device, metrics=None):
+    """ref nbp_utils.py:293-338: plain MSE + BCE in eval mode.  metrics: None, or a ValidationMetrics that receives every batch
+    (two more launches per batch, kept on the device; read back once behind the loop); the returned loss is the same float."""
     parts, count = [], 0
     bs = params.nbp_batch_size
     stager = _BatchStager(device) if (torch.device(device).type == "cuda" and _STAGE_BATCHES) else None
@@ -497,35 +551,53 @@ def validation_model(training_set_db, params, nbp, device):
         out1, out2 = nbp(xs)
         pred = tr.gather_values(out1, bidx, coords)
         parts.append((tr.MeanLossFn.apply(pred, gains, 0) + tr.MeanLossFn.apply(out2, gt, 1)).detach())    # (no sync per batch)
+        if metrics is not None:
+            metrics.add(out1, out2, gt, coords, gains, bidx)
         count += 1
+    if metrics is not None:
+        metrics.read()
     total = 0.0
     for v in (torch.stack(parts).tolist() if parts else []):
         total += v
     return total / max(count, 1)
 
 
+def _with(acc):
+    """validation_model's extra keyword: none at all with the metrics off (the call as it always was)."""
+    return {} if acc is None else {"metrics": acc}
+
+
 def train_nbp(training_set_db, params, optimizer, nbp, device, current_epoch, validation_data, lr_patience=2,
-              lr_factor=0.1, num_epochs=5, grad_norms=None, ema=None, ema_losses=None):
+              lr_factor=0.1, num_epochs=5, grad_norms=None, ema=None, ema_losses=None, metrics_out=None):
     """ref nbp_utils.py:430-468: 5 inner epochs, validation after each, ReduceLROnPlateau.  grad_norms: see train_experience_data.
     With `ema` the averaged network is validated after each inner epoch as well (same data, same function) and `ema_losses`, a
-    list, receives its loss; the scheduler and the returned pair see the live network only."""
+    list, receives its loss; the scheduler and the returned pair see the live network only.  With the config's `validation_metrics`
+    on and `metrics_out`, a dict, the validation of the LAST inner epoch -- the network that gets checkpointed -- also computes the
+    planner-facing metrics (ValidationMetrics): metrics_out["validation_metrics"], and with `ema` ["validation_metrics_ema"]."""
     sched = torch.optim.lr_scheduler.ReduceLROnPlateau(optimizer, mode="min", factor=lr_factor, patience=lr_patience)
     tl, vl = [], []
-    for _ in range(num_epochs):
+    thresholds = metric_thresholds(params) if metrics_out is not None else None
+    for inner in range(num_epochs):
+        acc = ValidationMetrics(thresholds) if (thresholds is not None and inner + 1 == num_epochs) else None
         nbp.train()
         losses = train_experience_data(training_set_db, params, optimizer, nbp, device, current_epoch, grad_norms, ema=ema)
         tl.append(float(np.mean(losses)) if losses else float("nan"))
         sync_buffers(nbp)
         nbp.eval()
         with torch.no_grad():
-            vl.append(_mean_over_ranks(validation_model(validation_data, params, nbp, device), device))
+            vl.append(_mean_over_ranks(validation_model(validation_data, params, nbp, device, **_with(acc)), device))
+        if acc is not None:
+            metrics_out["validation_metrics"] = acc.summary(device)
         if ema is not None:
             shadow = ema.module
             sync_buffers(shadow)
+            acc = ValidationMetrics(thresholds) if acc is not None else None
             with torch.no_grad():
-                ve = _mean_over_ranks(validation_model(validation_data, params, shadow, device), device)
+                ve = _mean_over_ranks(validation_model(validation_data, params, shadow, device, **_with(acc)), device)
             if ema_losses is not None:
                 ema_losses.append(ve)
+            if acc is not None:
+                metrics_out["validation_metrics_ema"] = acc.summary(device)
         sched.step(vl[-1])
     return sum(tl) / len(tl), sum(vl) / len(vl)
 
@@ -556,23 +628,36 @@ def run_training_nbp(params):
 
     with_norm = bool(getattr(optimizer, "norm_pass", False))      # the HIP optimizer with clipping or skipping on
 
-    def save(epoch, vl, tl, grad_norms, ema_losses):
+    with_metrics = metric_thresholds(params) is not None          # `validation_metrics`: off = nothing new launched or written
+
+    def train_kw(norms, ema_losses, found):
+        kw = dict(num_epochs=params.inner_epochs, grad_norms=norms, ema=ema, ema_losses=ema_losses)
+        if with_metrics:
+            kw["metrics_out"] = found
+        return kw
+
+    def save(epoch, vl, tl, grad_norms, ema_losses, found):
         nonlocal best_loss, best_ema_loss
         if rank != 0:
             return
         history[epoch] = {"training_loss": tl, "validation_loss": vl}
         if ema is not None:
             history[epoch]["validation_loss_ema"] = sum(ema_losses) / len(ema_losses)
+        history[epoch].update(found)         # validation_metrics (and validation_metrics_ema) of the epoch's last inner epoch
         if with_norm:       # one norm per optimizer step of the epoch; the running count of dropped steps (validation has synchronised)
             history[epoch].update(grad_norm=list(grad_norms), skipped_steps=int(optimizer.skipped_steps.item()))
         ck = {"epoch": epoch, "model_state_dict": nbp.state_dict(), "optimizer_state_dict": optimizer.state_dict()}
+        if "validation_metrics" in found:
+            ck["validation_metrics"] = found["validation_metrics"]
         if ema is not None:
             ck["ema_state_dict"] = ema.state_dict()
             vle = history[epoch]["validation_loss_ema"]
             if vle < best_ema_loss:      # the averaged weights as a checkpoint of their own: model_state_dict IS the shadow's
                 best_ema_loss = vle
-                torch.save({"epoch": epoch, "model_state_dict": ck["ema_state_dict"]["shadow"], "validation_loss_ema": vle},
-                           os.path.join(params.output_dir, params.nbp_model_name + "_best_val_ema.pth"))
+                best = {"epoch": epoch, "model_state_dict": ck["ema_state_dict"]["shadow"], "validation_loss_ema": vle}
+                if "validation_metrics_ema" in found:
+                    best["validation_metrics"] = found["validation_metrics_ema"]
+                torch.save(best, os.path.join(params.output_dir, params.nbp_model_name + "_best_val_ema.pth"))
         if vl < best_loss:
             best_loss = vl
             torch.save(ck, os.path.join(params.output_dir, params.nbp_model_name + "_best_val.pth"))
@@ -585,11 +670,10 @@ def run_training_nbp(params):
         validation = make_synthetic_experiences(getattr(params, "n_validation_synthetic", 16), S, seed=1)
         for epoch in range(1, params.epochs + 1):
             db = make_synthetic_experiences(params.samples_per_epoch, S, seed=100 + epoch + 1000 * rank)
-            norms, ema_losses = [], []
-            tl, vl = train_nbp(db, params, optimizer, nbp, device, epoch, validation, num_epochs=params.inner_epochs, grad_norms=norms,
-                               ema=ema, ema_losses=ema_losses)
+            norms, ema_losses, found = [], [], {}
+            tl, vl = train_nbp(db, params, optimizer, nbp, device, epoch, validation, **train_kw(norms, ema_losses, found))
             print(f"epoch {epoch}: training {tl:.4f} validation {vl:.4f}")
-            save(epoch, vl, tl, norms, ema_losses)
+            save(epoch, vl, tl, norms, ema_losses, found)
         return history
 
     dataset = sim_scene.SceneDataset(data_path, getattr(params, "train_scenes", []))
@@ -614,10 +698,9 @@ def run_training_nbp(params):
         # every rank must take the same branch (the training loop below contains collectives)
         if _common_count(1 if (db and validation) else 0, device) == 0:
             continue
-        norms, ema_losses = [], []
-        tl, vl = train_nbp(db, params, optimizer, nbp, device, epoch, validation, num_epochs=params.inner_epochs, grad_norms=norms,
-                           ema=ema, ema_losses=ema_losses)
+        norms, ema_losses, found = [], [], {}
+        tl, vl = train_nbp(db, params, optimizer, nbp, device, epoch, validation, **train_kw(norms, ema_losses, found))
         print(f"epoch {epoch}: training {tl:.4f} validation {vl:.4f}")
-        save(epoch, vl, tl, norms, ema_losses)
+        save(epoch, vl, tl, norms, ema_losses, found)
     env.close()
     return history

@@ -794,3 +794,42 @@ def replay_decode(streams, offsets, S, out=None):
         rc = _lib.lib().nbp_replay_decode_f32(_lib.ptr(streams), arr, n, int(S), _lib.ptr(x), _lib.ptr(gt), _st())
     _lib.check(rc, "nbp_replay_decode_f32")
     return x, gt
+
+
+def validation_metrics(out1, out2, gt, coords, gains, bidx, thresholds=(0.13,)):
+    """One validation batch on the device -> (obst int64 [B,T,4], rank int64 [B,6], val float64 [B,4]) on the device: the per-sample
+    quantities of utility/metrics.py::validation_metrics_reference (the obstacle mask `out2 >= threshold` against `gt > 0.5`; the
+    ranking of the supervised cells of out1 against their gains).  out1 [B,8,S/4,S/4], out2 / gt [B,1,S,S] fp32, coords [K,3] int64,
+    gains [K] fp32, bidx [K] int64 (any order), thresholds: 1 to 8 numbers.  One memset and two launches on the current stream
+    (nbp_val_metrics_f32), no host synchronisation.  K = 0 is legal."""
+    from . import metrics
+    ts = metrics.check_thresholds(thresholds)
+    named = (("out1", out1), ("out2", out2), ("gt", gt), ("coords", coords), ("gains", gains), ("bidx", bidx))
+    for name, t in named:
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError(f"validation_metrics: the HIP path needs a cuda tensor for {name} (no CPU fallback)")
+    if out2.dim() != 4 or out1.dim() != 4:
+        raise ValueError("validation_metrics: out1 [B,8,S/4,S/4] and out2 [B,1,S,S] expected")
+    B, S = out2.shape[0], out2.shape[-1]
+    K = coords.shape[0] if coords.dim() == 2 else -1
+    if (B < 1 or S < 4 or S % 4 or tuple(out2.shape) != (B, 1, S, S) or tuple(gt.shape) != (B, 1, S, S)
+            or tuple(out1.shape) != (B, 8, S // 4, S // 4) or tuple(coords.shape) != (K, 3) or tuple(gains.shape) != (K,)
+            or tuple(bidx.shape) != (K,)):
+        raise ValueError("validation_metrics: out1 [B,8,S/4,S/4], out2 / gt [B,1,S,S], coords [K,3], gains [K] and bidx [K] expected")
+    if (out1.dtype != torch.float32 or out2.dtype != torch.float32 or gt.dtype != torch.float32 or gains.dtype != torch.float32
+            or coords.dtype != torch.int64 or bidx.dtype != torch.int64):
+        raise ValueError("validation_metrics: fp32 out1 / out2 / gt / gains and int64 coords / bidx expected")
+    if any(t.device != out2.device for _, t in named):
+        raise ValueError("validation_metrics: all tensors on one device expected")
+    if not all(t.is_contiguous() for _, t in named):
+        raise ValueError("validation_metrics: contiguous tensors expected")
+    dev = out2.device
+    obst = torch.empty(B, len(ts), 4, dtype=torch.int64, device=dev)
+    rank = torch.empty(B, 6, dtype=torch.int64, device=dev)
+    val = torch.empty(B, 4, dtype=torch.float64, device=dev)
+    th = (C.c_float * len(ts))(*ts)
+    with torch.cuda.device(dev):
+        rc = _lib.lib().nbp_val_metrics_f32(_lib.ptr(out1), _lib.ptr(out2), _lib.ptr(gt), _lib.ptr(coords), _lib.ptr(gains),
+                                            _lib.ptr(bidx), B, S, K, len(ts), th, _lib.ptr(obst), _lib.ptr(rank), _lib.ptr(val), _st())
+    _lib.check(rc, "nbp_val_metrics_f32")
+    return obst, rank, val
