@@ -703,6 +703,13 @@ __global__ __launch_bounds__(256) void gate_mid_bwd_apply4_kernel(const float* _
 // ------------------------------------------------------------------ small elementwise pieces
 // op 0: out = relu(a + b)          op 1: out = dy * (y > 0)         op 2: out = sigmoid(a)
 // op 3: out = dy * y * (1 - y)     op 4: out = a + b                op 5: out = a + b[0]
+// sigmoid: 1 / (1 + e^-a) wherever e^-a is finite.  Below a = -88.7 expf(-a) overflows and the quotient was 0 although the value
+// (down to e^-103) is an fp32 denormal: there e^a / (1 + e^a), whose numerator is that denormal.
+__device__ __forceinline__ float ew_sigmoid(float a) {
+    if (a < -88.f) { const float e = expf(a); return e / (1.f + e); }
+    return 1.f / (1.f + expf(-a));
+}
+
 __global__ __launch_bounds__(256) void ew_kernel(int op, const float* __restrict__ a, const float* __restrict__ b,
                                                  long long n, float* __restrict__ out) {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
@@ -710,7 +717,7 @@ __global__ __launch_bounds__(256) void ew_kernel(int op, const float* __restrict
         switch (op) {
             case 0: v = fmaxf(a[i] + b[i], 0.f); break;
             case 1: v = b[i] > 0.f ? a[i] : 0.f; break;
-            case 2: v = 1.f / (1.f + expf(-a[i])); break;
+            case 2: v = ew_sigmoid(a[i]); break;
             case 3: v = a[i] * b[i] * (1.f - b[i]); break;
             case 5: v = a[i] + b[0]; break;
             default: v = a[i] + b[i]; break;
@@ -742,7 +749,7 @@ __global__ __launch_bounds__(256) void ew4_kernel(int op, const float* __restric
             switch (op) {
                 case 0: v[e] = fmaxf(x[e] + y[e], 0.f); break;
                 case 1: v[e] = y[e] > 0.f ? x[e] : 0.f; break;
-                case 2: v[e] = 1.f / (1.f + expf(-x[e])); break;
+                case 2: v[e] = ew_sigmoid(x[e]); break;
                 case 3: v[e] = x[e] * y[e] * (1.f - y[e]); break;
                 case 5: v[e] = x[e] + b0; break;
                 default: v[e] = x[e] + y[e]; break;
@@ -862,7 +869,7 @@ __global__ __launch_bounds__(256) void maxpool2_bwd4_kernel(const float* __restr
             int arg = 0;
 #pragma unroll
             for (int k = 1; k < 4; ++k)
-                if (v[k][e] > best || (v[k][e] != v[k][e] && best == best)) { best = v[k][e]; arg = k; }
+                if (v[k][e] > best || v[k][e] != v[k][e]) { best = v[k][e]; arg = k; }
 #pragma unroll
             for (int k = 0; k < 4; ++k) o[k][e] = k == arg ? g[e] : 0.f;
         }
@@ -923,6 +930,7 @@ __global__ __launch_bounds__(256) void outer_kernel(const float* __restrict__ s,
 }
 
 // MaxPool2d(2,2) backward: the gradient goes to the FIRST maximum of the window in (dy,dx) scan order (ATen rule).
+// A NaN takes over from whatever came before it, another NaN included (ATen: val > max || isnan(val)): the LAST NaN of a window wins.
 __global__ __launch_bounds__(256) void maxpool2_bwd_kernel(const float* __restrict__ x, const float* __restrict__ dy, int B,
                                                            int H, int W, int C, float* __restrict__ dx) {
     const int Ho = H >> 1, Wo = W >> 1;
@@ -941,7 +949,7 @@ __global__ __launch_bounds__(256) void maxpool2_bwd_kernel(const float* __restri
 #pragma unroll
         for (int k = 1; k < 4; ++k) {
             const float v = x[base + off[k]];
-            if (v > best || (v != v && best == best)) { best = v; arg = k; }
+            if (v > best || v != v) { best = v; arg = k; }
         }
 #pragma unroll
         for (int k = 0; k < 4; ++k) dx[base + off[k]] = k == arg ? dy[i] : 0.f;

@@ -813,7 +813,7 @@ class RowScaleFn(torch.autograd.Function):
         if not (dy.dim() == 4 and dy.stride(3) == 1 and ld >= C and ld % 4 == 0 and dy.stride(1) == W * ld
                 and dy.stride(0) == H * W * ld and dy.data_ptr() % 16 == 0):
             dy, ld = dy.contiguous(), C
-        if C % 4 == 0:
+        if C % 4 == 0 and x.data_ptr() % 16 == 0:          # (the one-pass kernel reads x and writes dx sixteen bytes at a time)
             _chk(L.nbp_rowscale_backward_f32(dy.data_ptr(), ld, _lib.ptr(x), _lib.ptr(s), M, C, _lib.ptr(dx), _lib.ptr(ds), _st()), "rowscale_bwd")
         else:
             dy = dy.contiguous()
