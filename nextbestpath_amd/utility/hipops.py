@@ -454,8 +454,13 @@ def unproject_append_batch(items, H, W, n_frames, gathering_factor=0.05, fov_ran
     """unproject_append for several rollouts in three launches.  items = [(key, depth frames [F tensors [H,W]], cams host
     [F,12], cloud, cloud_count, seed, cloud_rgb | None, shade | None)] with shade = (zface frames [F tensors [H,W] int64], verts,
     faces, vcolors, ambient); the frames need not be adjacent in memory; `key` is the rollout OBJECT: it owns its scratch.
-    More than 12 items go in chunks of 12."""
+    More than 12 items go in chunks of 12.  The coloured items of a call share ONE ambient: different values raise ValueError
+    before anything is launched, in whichever chunks they fall."""
     import numpy as np
+    # ONE ambient reaches the kernel: the coloured items must agree on it (checked on the whole list, before the chunking)
+    ambients = {float(it[7][4]) for it in items if it[7] is not None and it[6] is not None}
+    if len(ambients) > 1:
+        raise ValueError(f"unproject_append_batch: the coloured items of one call carry different ambient values {sorted(ambients)}")
     if len(items) > 12:
         for i in range(0, len(items), 12):
             unproject_append_batch(items[i:i + 12], H, W, n_frames, gathering_factor, fov_range, tan_half_fov)
@@ -468,7 +473,7 @@ def unproject_append_batch(items, H, W, n_frames, gathering_factor=0.05, fov_ran
     ve, fa, vc, cnts, cl, crgb, ccount, cap, wsp, seeds = (VP * n)(), (VP * n)(), (VP * n)(), (VP * n)(), (VP * n)(), (VP * n)(), (VP * n)(), \
         (LL * n)(), (VP * n)(), (U * n)()
     cams = np.zeros((n, n_frames, 12), np.float32)
-    ambient = 0.85
+    ambient = ambients.pop() if ambients else 0.85
     for i, (key, depth, cam, cloud, cloud_count, seed, cloud_rgb, shade) in enumerate(items):
         ws = _item_ws("unproject", key, (n_frames, H, W), wsb, cloud.device)
         cl[i], ccount[i], cap[i], wsp[i], seeds[i] = cloud.data_ptr(), cloud_count.data_ptr(), cloud.shape[0], ws.data_ptr(), \
@@ -478,7 +483,7 @@ def unproject_append_batch(items, H, W, n_frames, gathering_factor=0.05, fov_ran
         for f in range(n_frames):
             dep[i * n_frames + f] = depth[f] if isinstance(depth[f], int) else depth[f].data_ptr()
         if shade is not None and cloud_rgb is not None:
-            zface, verts, faces, vcolors, ambient = shade
+            zface, verts, faces, vcolors, _ = shade
             for f in range(n_frames):
                 zf[i * n_frames + f] = zface[f] if isinstance(zface[f], int) else zface[f].data_ptr()
             ve[i], fa[i], vc[i], crgb[i] = verts.data_ptr(), faces.data_ptr(), vcolors.data_ptr(), cloud_rgb.data_ptr()
