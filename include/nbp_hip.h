@@ -938,7 +938,7 @@ int nbp_val_metrics_f32(const float* out1, const float* out2, const float* gt, c
  *   descs   one record per tensor  { float* p; const float* g; float* m; float* v; int64 numel; }     (nbp_optim_desc_bytes() = 40)
  *   chunks  one record per workgroup { int64 first; int32 tensor; int32 pad; } (16 bytes): elements [first, first + chunk) of that
  *           tensor, clipped to numel; first is a multiple of nbp_optim_chunk_elems() (16384).  Any numel >= 1; 16-byte accesses
- *           where the tensor's four base addresses are 16-byte aligned, 4-byte accesses otherwise (same results).
+ *           where the tensor's four base addresses are 16-byte aligned, 4-byte accesses otherwise (the backward: same bits; the forward: the same terms, added in another order).
  *   state   nbp_optim_state_bytes(n_groups) = 32 + 8 n_groups bytes, zeroed before the first step:
  *           { f32 total_norm; f32 clip_coef; i32 finite; i32 applied; f32 step; i32 skipped_steps; i32 pad[2];
  *             { f32 bc1 = 1 - beta1^step; f32 sqrt_bc2 = sqrt(1 - beta2^step); } per param group }
@@ -984,6 +984,32 @@ int nbp_ema_desc_bytes(void);
 size_t nbp_ema_state_bytes(void);
 int nbp_ema_update_f32(const void* descs_dev, const void* chunks_dev, int n_chunks, void* ema_state, const void* optim_state_or_null,
                        double decay, int warmup, void* stream);
+
+/* ---- The training objective with per-sample terms (csrc/nbp_objective.hip).  Not in the reference: what
+ * loss-prioritised replay needs, and the fused form of gather + MSE + BCE (nbp_model.py:162-173, nbp_utils.py:373-381).  The
+ * definition of record is nextbestpath_amd/utility/priority.py::objective_reference.  Host binding: hipops.objective_forward /
+ * objective_backward, networks/training.py::ObjectiveFn.
+ *   out1_nchw [B,C,H,W] fp32; coords_bcxy [K,4] int64 (b, c, x, y), rows in any order; gains [K] fp32; out2, gt [B,S,S] fp32;
+ *   weights_or_null [B] fp32 (NULL: every weight 1).  A row with a coordinate out of range (b among them) contributes nothing.
+ *   v_b = sum_{k: b_k = b} (out1[b,c,x,y] - gain_k)^2,  n_b = the number of those rows,
+ *   o_b = sum_pixels -(t max(log p, -100) + (1 - t) max(log(1 - p), -100))      (terms in fp32 as nbp_loss_f32 forms them, sums in double)
+ * forward:  per_sample [B,3] double = (v_b, n_b, o_b);  totals [2] double = (sum_b w_b v_b, sum_b w_b o_b).  Two launches; every sum
+ *           in a fixed order that depends on the sample's own data and S only (not on B, the slot b, or the position of its rows among
+ *           the others'); no floating-point atomics: two runs give the same bits.  K = 0 is legal (v = n = 0).
+ * backward: coef_dev [2] fp32 ON THE DEVICE = (dL/dmse, dL/dbce) for mse = totals[0] / K, bce = totals[1] / (B S^2);
+ *           d_out2 [B,S,S] = coef1 w_b (p - t) / max(p (1 - p), 1e-12) / (B S^2);  d_out1 [B,C,H,W] zero-filled, then
+ *           += coef0 w_b 2 (pred - gain) / K per row (atomicAdd: a cell named twice receives both).  One asynchronous fill and one
+ *           launch, no host synchronisation.
+ * ws: nbp_objective_workspace_bytes(B, S) bytes (0 for B < 1 or S < 1).  16-byte accesses where S^2 % 4 == 0 and out2 / gt / d_out2
+ * are 16-byte aligned, 4-byte accesses otherwise (the backward: same bits; the forward: the same terms, added in another order).  NBP_E_ARG: a null pointer (coords / gains only when K > 0), B < 1,
+ * S < 1, K < 0, C / H / W < 1; NBP_E_SHAPE: B > 65535 or S > 32768; NBP_E_WS: ws_bytes too small.  Nothing is written on an error. */
+size_t nbp_objective_workspace_bytes(int B, int S);
+int nbp_objective_forward_f32(const float* out1_nchw, const long long* coords_bcxy, const float* gains, int K, int C, int H, int W,
+                              const float* out2, const float* gt, int B, int S, const float* weights_or_null, double* per_sample,
+                              double* totals, void* ws, size_t ws_bytes, void* stream);
+int nbp_objective_backward_f32(const float* out1_nchw, const long long* coords_bcxy, const float* gains, int K, int C, int H, int W,
+                               const float* out2, const float* gt, int B, int S, const float* weights_or_null, const float* coef_dev,
+                               float* d_out1_nchw, float* d_out2, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- The replay store's container in LMDB's on-disk format (csrc/nbp_mdb.cpp; host only).  The reference keeps its experience
  * records in an LMDB environment (next_best_path/trainers/train_nbp_model.py:61-63 lmdb.open(path, map_size);

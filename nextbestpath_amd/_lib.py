@@ -228,6 +228,9 @@ SIGNATURES["nbp_replay_stream_bound"] = (_sz, [_i])
 SIGNATURES["nbp_replay_encode_f32"] = (_i, [_vp, _i, _i, _vp, _sz, _vp])
 SIGNATURES["nbp_replay_decode_f32"] = (_i, [_vp, C.POINTER(_ll), _i, _i, _vp, _vp, _vp])
 SIGNATURES["nbp_val_metrics_f32"] = (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, C.POINTER(_f), _vp, _vp, _vp, _vp])
+SIGNATURES["nbp_objective_workspace_bytes"] = (_sz, [_i, _i])
+SIGNATURES["nbp_objective_forward_f32"] = (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp])
+SIGNATURES["nbp_objective_backward_f32"] = (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp])
 
 _lock = threading.Lock()
 _lib = None

@@ -955,6 +955,41 @@ class MeanLossFn(torch.autograd.Function):
         return dp, None, None
 
 
+class ObjectiveFn(torch.autograd.Function):
+    """(mse, bce, per_sample) of one batch in ONE forward and ONE backward call (csrc/nbp_objective.hip; the definition of record is
+    utility/priority.py::objective_reference): mse = sum_b w_b v_b / K and bce = sum_b w_b o_b / (B S^2), 0-dim fp32 with autograd --
+    with weights None, F.mse_loss of the gathered values and F.binary_cross_entropy as GatherValuesFn + MeanLossFn give them -- and
+    per_sample float64 [B,3] = (v_b, n_b, o_b), detached.  coords_bcxy int64 [K,4], rows in any order; weights None or fp32 [B]
+    (no gradient).  The backward stacks its two incoming gradients on the device, where the kernel reads them: nothing in here waits
+    for the host."""
+
+    @staticmethod
+    def forward(ctx, out1, out2, coords_bcxy, gains, gt, weights):
+        from ..utility import hipops
+        out1, out2, gt = out1.contiguous(), out2.contiguous(), gt.contiguous()
+        coords_bcxy, gains = coords_bcxy.contiguous(), gains.contiguous()
+        weights = None if weights is None else weights.contiguous()
+        per_sample, totals = hipops.objective_forward(out1, coords_bcxy, gains, out2, gt, weights)
+        ctx.save_for_backward(out1, out2, coords_bcxy, gains, gt)
+        ctx.weights = weights
+        ctx.mark_non_differentiable(per_sample)
+        K = coords_bcxy.shape[0]
+        mse = (totals[0] / max(K, 1)).to(torch.float32)
+        bce = (totals[1] / out2.numel()).to(torch.float32)
+        return mse, bce, per_sample
+
+    @staticmethod
+    def backward(ctx, g_mse, g_bce, _g_per_sample):
+        from ..utility import hipops
+        out1, out2, coords_bcxy, gains, gt = ctx.saved_tensors
+        zero = None
+        if g_mse is None or g_bce is None:
+            zero = torch.zeros((), dtype=torch.float32, device=out1.device)
+        coef = torch.stack([zero if g_mse is None else g_mse.to(torch.float32), zero if g_bce is None else g_bce.to(torch.float32)])
+        d_out1, d_out2 = hipops.objective_backward(out1, coords_bcxy, gains, out2, gt, ctx.weights, coef)
+        return d_out1, d_out2, None, None, None, None
+
+
 # ---------------------------------------------------------------------------------------------- network
 # Forward observer: a callable (name, tensor) invoked on every named intermediate (NHWC fp32) right after it is computed -- the
 # train-mode counterpart of a module forward hook (the layers here are autograd Functions, not modules).  None by default; what
@@ -1116,3 +1151,13 @@ def loss(net, pred1, target1, pred2, target2):
     mse = MeanLossFn.apply(pred1, target1, 0)
     bce = MeanLossFn.apply(pred2, target2, 1)
     return mse / (2.0 * torch.exp(2 * s[0])) + s[0] + bce / torch.exp(2 * s[1]) + s[1]
+
+
+def loss_weighted(net, out1, batch_indices, coords, gains, out2, gt, weights=None):
+    """NBP.loss with a weight per sample, on the fused objective (ObjectiveFn) -> (loss, per_sample float64 [B,3] on the device,
+    detached).  The terms of sample b enter the two means multiplied by weights[b] (None: 1, the value of `loss` on the same
+    tensors); the log_vars expression is that of `loss`."""
+    s = net.log_vars
+    full = torch.cat([batch_indices.view(-1, 1).long(), coords.long()], 1)
+    mse, bce, per_sample = ObjectiveFn.apply(out1, out2, full, gains, gt, weights)
+    return mse / (2.0 * torch.exp(2 * s[0])) + s[0] + bce / torch.exp(2 * s[1]) + s[1], per_sample

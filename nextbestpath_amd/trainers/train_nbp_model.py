@@ -184,9 +184,19 @@ class _BatchStager:
         return out, ev
 
 
-def _collate_staged(batch_data, device, stager, ops=None):
+def _with_extras(out, dev, ops, weights):
+    """The staged tensors, then the op codes, then the weights -- each only when the batch has them."""
+    if ops is not None:
+        out = out + (dev["ops"],)
+    if weights is not None:
+        out = out + (dev["weights"],)
+    return out
+
+
+def _collate_staged(batch_data, device, stager, ops=None, weights=None):
     """_collate with the copies on the stager's stream: returns the same five tensors; the CURRENT stream waits for them.
-    `ops` (augmentation op codes, int32 [n]; None without augmentation) ride along as a sixth tensor."""
+    `ops` (augmentation op codes, int32 [n]; None without augmentation) ride along as a sixth tensor, `weights` (the replay draw's
+    importance weights, fp32 [n]; None without prioritised replay) behind them."""
     n = len(batch_data)
     x0 = batch_data[0]["current_model_input"]
     S = x0.shape[-1]
@@ -204,6 +214,8 @@ def _collate_staged(batch_data, device, stager, ops=None):
     bi = stager.buffer("bidx", (K,), torch.int64).numpy()
     if ops is not None:
         stager.buffer("ops", (n,), torch.int32).numpy()[:] = ops
+    if weights is not None:
+        stager.buffer("weights", (n,), torch.float32).numpy()[:] = weights
     k = 0
     for i, (d, c) in enumerate(zip(batch_data, coords)):
         xs[i] = d["current_model_input"][0]
@@ -215,7 +227,7 @@ def _collate_staged(batch_data, device, stager, ops=None):
         k += m
     dev, ev = stager.commit()
     out = (dev["xs"], dev["gt"], dev["coords"], dev["gains"], dev["bidx"])
-    return (out if ops is None else out + (dev["ops"],)), ev
+    return _with_extras(out, dev, ops, weights), ev
 
 
 class _PendingDecode:
@@ -231,7 +243,7 @@ class _PendingDecode:
         return hipops.replay_decode(self.streams, self.offsets, self.S)
 
 
-def _collate_compact(batch_data, device, stager, ops=None):
+def _collate_compact(batch_data, device, stager, ops=None, weights=None):
     """_collate_staged for a batch whose records are all compact (unpack_record(..., keep_compact=True): headers validated): the
     streams go back to back, each padded to 16 bytes, into one pinned uint8 staging buffer -- a few per cent of the 1.3 MB per record
     of the expanded maps through pinned memory and over the host-to-device link; targets, gains, indices and op codes as ever.
@@ -257,6 +269,8 @@ def _collate_compact(batch_data, device, stager, ops=None):
     bi = stager.buffer("bidx", (K,), torch.int64).numpy()
     if ops is not None:
         stager.buffer("ops", (n,), torch.int32).numpy()[:] = ops
+    if weights is not None:
+        stager.buffer("weights", (n,), torch.float32).numpy()[:] = weights
     k = 0
     for i, (d, c) in enumerate(zip(batch_data, coords)):
         m = len(d["nbpc"])
@@ -269,7 +283,7 @@ def _collate_compact(batch_data, device, stager, ops=None):
         k += m
     dev, ev = stager.commit()
     out = (_PendingDecode(dev["streams"], offsets, S), None, dev["coords"], dev["gains"], dev["bidx"])
-    return (out if ops is None else out + (dev["ops"],)), ev
+    return _with_extras(out, dev, ops, weights), ev
 
 
 def _await_batch(tensors, ev, device):
@@ -285,19 +299,22 @@ def _await_batch(tensors, ev, device):
     return tensors
 
 
-def _collate_any(batch_data, device, stager, ops=None):
+def _collate_any(batch_data, device, stager, ops=None, weights=None):
     """Staged collation for records of the replay store's shape (one map per record); anything else through _collate.  A batch of
     compact records only goes to the device as streams (_collate_compact); a batch that mixes the formats has its compact records
     decoded on the host first."""
+    extra = {} if weights is None else {"weights": weights}
     if all("nbpc" in d for d in batch_data):
-        return _collate_compact(batch_data, device, stager, ops)
+        return _collate_compact(batch_data, device, stager, ops, **extra)
     batch_data = _expanded(batch_data)
     if all(d["current_model_input"].shape[0] == 1 and d["current_gt_2d_layout"].shape[0] == 1 for d in batch_data):
-        return _collate_staged(batch_data, device, stager, ops)
+        return _collate_staged(batch_data, device, stager, ops, **extra)
     ev = torch.cuda.Event()
     out = _collate(batch_data, device)
     if ops is not None:
         out = out + (torch.from_numpy(np.asarray(ops, dtype=np.int32)).to(device),)
+    if weights is not None:
+        out = out + (torch.from_numpy(np.asarray(weights, dtype=np.float32)).to(device),)
     ev.record(torch.cuda.current_stream(device))
     return out, ev
 
@@ -371,7 +388,38 @@ def _augment_rng(params):
     return rng
 
 
-def train_experience_data(training_set_db, params, optimizer, nbp, device, current_epoch, grad_norms=None, ema=None):
+def replay_priority_options(params):
+    """The config's `replay_priority_alpha` (null = off, the default | a number >= 0; 0.6 is the paper's), `replay_priority_beta`
+    (0.4, in [0, 1]), `replay_priority_eps` (1e-3, > 0) and `replay_priority_seed` (null = random_seed + rank) -> None, or the
+    checked values (utility/priority.py::check_options; ValueError on a bad one)."""
+    from ..utility import priority
+    return priority.check_options(getattr(params, "replay_priority_alpha", None), getattr(params, "replay_priority_beta", 0.4),
+                                  getattr(params, "replay_priority_eps", 1e-3), getattr(params, "replay_priority_seed", None))
+
+
+def make_replay_priorities(params):
+    """None with the option off, else a fresh utility/priority.py::ReplayPriorities (run_training_nbp keeps one per rank for the run)."""
+    opts = replay_priority_options(params)
+    if opts is None:
+        return None
+    from ..utility.priority import ReplayPriorities
+    return ReplayPriorities(opts["alpha"], opts["beta"], opts["eps"])
+
+
+def _priority_rng(params, opts):
+    """The generator of the replay draws: one per params object, as the augmentation's; seed `replay_priority_seed`, else
+    random_seed + rank."""
+    rng = getattr(params, "_priority_rng", None)
+    if rng is None:
+        seed = opts["seed"]
+        if seed is None:
+            dist = _dist()
+            seed = int(getattr(params, "random_seed", 0)) + (dist.get_rank() if dist is not None else 0)
+        rng = params._priority_rng = np.random.default_rng(int(seed))
+    return rng
+
+
+def train_experience_data(training_set_db, params, optimizer, nbp, device, current_epoch, grad_norms=None, ema=None, priorities=None):
     """ref nbp_utils.py:340-395 (GradScaler without autocast is the identity scale for fp32; omitted -- the "fp16"
     train_precision scales every fp16 operand per tensor instead, NBP.train_precision).  As in the
     reference the early poses (pose_i <= 10) are dropped INSIDE each batch during epoch 1 (:348-362), a batch left empty
@@ -384,7 +432,23 @@ def train_experience_data(training_set_db, params, optimizer, nbp, device, curre
     (utility/augment.py) -- the targets' cells and heading channels on the host before collation, on shallow copies of the records,
     the six planes on the device behind the staged copy (one launch, hipops.augment_batch).  p = 0 (the default) draws nothing and
     launches nothing.  `ema` (make_ema; None = off) is updated once per optimizer step, right behind it on the stream; with the HIP
-    optimizer a step dropped on the device drops the update too."""
+    optimizer a step dropped on the device drops the update too.
+
+    Not in the reference either: loss-prioritised replay (utility/priority.py; Schaul et al. 2016), with params.replay_priority_alpha
+    set (null, the default: everything above, bit for bit -- nothing new launched, drawn or written).  The population is the list
+    itself (in epoch 1 without the records of pose_i <= 10, the ones the in-batch filter drops); instead of a shuffle,
+    ceil(N / batch size) batches are DRAWN with replacement from `priorities` (a ReplayPriorities: the caller's, kept over the run,
+    else one kept on `params`), the last one with the remainder, so that an inner epoch still trains on N samples.  A record's key
+    is its store key d["_key"] (read_combined_data(with_keys=True)) or, without one, its position in the list.  The draw's weights
+    travel with the staged batch, the objective is tr.loss_weighted, and every batch's per-sample terms stay on the device until
+    the optimizer step's read-back, which grows by ONE device-to-host copy per optimizer step (the window's per-sample terms and
+    log_vars as they were before the step); the table is then updated with priority.sample_loss.  The batch prefetched under the
+    current one is drawn from the table as it stands: the priorities LAG by up to one accumulation window (8 batches) plus the
+    prefetched batch.  Augmentation composes unchanged (the draw picks records, the augmentation then moves them).  Under torchrun
+    each rank draws from its own records; the batch count goes through _common_count as ever."""
+    prio = replay_priority_options(params)
+    if prio is not None:
+        return _train_prioritised(training_set_db, params, optimizer, nbp, device, current_epoch, grad_norms, ema, priorities, prio)
     random.shuffle(training_set_db)
     aug_p = float(getattr(params, "augment_probability", 0.0) or 0.0)
     if not 0.0 <= aug_p <= 1.0:
@@ -465,6 +529,95 @@ def train_experience_data(training_set_db, params, optimizer, nbp, device, curre
                 accumulated += v
             training_loss.append(accumulated / accumulation_steps)
             pending, updates = [], 0
+    return training_loss
+
+
+def _train_prioritised(training_set_db, params, optimizer, nbp, device, current_epoch, grad_norms, ema, priorities, prio):
+    """train_experience_data with replay_priority_alpha set (its docstring): same accumulation, optimizer step and loss list."""
+    from ..utility import priority
+    aug_p = float(getattr(params, "augment_probability", 0.0) or 0.0)
+    if not 0.0 <= aug_p <= 1.0:
+        raise ValueError(f"augment_probability {aug_p} outside [0, 1]")
+    aug_rng = _augment_rng(params) if aug_p > 0 else None
+    if priorities is None:
+        priorities = getattr(params, "_replay_priorities", None)
+        if priorities is None:
+            priorities = params._replay_priorities = make_replay_priorities(params)
+    rng = _priority_rng(params, prio)
+    keep = [i for i, d in enumerate(training_set_db) if current_epoch != 1 or d["pose_i"] > 10]
+    population = [training_set_db[i] for i in keep]
+    priorities.begin([training_set_db[i].get("_key", i) for i in keep])
+    N = len(population)
+    training_loss, pending, window, updates = [], [], [], 0
+    accumulation_steps = 8
+    bs = params.nbp_batch_size
+    n_batches = _common_count((N + bs - 1) // bs, device)
+    stager = _BatchStager(device) if (torch.device(device).type == "cuda" and _STAGE_BATCHES) else None
+
+    def drawn(bi):
+        """-> (records, their keys, weights fp32, op codes or None) of batch bi, drawn from the table as it stands"""
+        idx, w = priorities.draw(rng, min(bs, N - bi * bs))
+        batch = [population[i] for i in idx]
+        keys = [priorities.keys[i] for i in idx]
+        ops = None
+        if aug_rng is not None:
+            ops = augment.draw_ops(aug_rng, len(batch), aug_p)
+            batch = augment.augment_records(batch, ops, _record_side(batch[0]) // 4)
+        return batch, keys, w.astype(np.float32), ops
+
+    staged = None            # (batch index, keys, tensors, event) of the batch whose copies were started under the previous one's compute
+    for bi in range(n_batches):
+        if stager is None:
+            batch, keys, w, ops = drawn(bi)
+            xs, gt, coords, gains, bidx = _collate(batch, device)
+            ops = None if ops is None else torch.from_numpy(ops).to(device)
+            w = torch.from_numpy(w).to(device)
+        else:
+            if staged is None or staged[0] != bi:
+                batch, keys, w, ops = drawn(bi)
+                staged = (bi, keys) + _collate_any(batch, device, stager, ops, weights=w)
+            keys = staged[1]
+            tensors = _await_batch(staged[2], staged[3], device)
+            xs, gt, coords, gains, bidx = tensors[:5]
+            extras = list(tensors[5:])
+            ops = extras.pop(0) if aug_rng is not None else None
+            w = extras.pop(0)
+        if ops is not None:
+            xs, gt = hipops.augment_batch(xs, gt, ops)
+        out1, out2 = nbp(xs)
+        loss, per_sample = tr.loss_weighted(nbp, out1, bidx, coords, gains, out2, gt, w)
+        loss.backward()
+        pending.append(loss.detach())
+        window.append((keys, per_sample, xs.shape[-1]))
+        updates += 1
+        if stager is not None and bi + 1 < n_batches:       # the next batch's draw, collation and copies, under this batch's kernels
+            nb, nkeys, nw, nops = drawn(bi + 1)
+            staged = (bi + 1, nkeys) + _collate_any(nb, device, stager, nops, weights=nw)
+        if updates % accumulation_steps == 0 or bi + 1 == n_batches:
+            # the window's per-sample terms and the log_vars they were formed with, gathered on the device BEFORE the step changes them
+            terms = torch.cat([ps.reshape(-1) for _, ps, _ in window] + [nbp.log_vars.detach().to(torch.float64)])
+            allreduce_gradients(nbp)
+            optimizer.step()
+            if ema is not None:
+                ema.update(optimizer)
+            optimizer.zero_grad()
+            accumulated = 0.0
+            with_norm = bool(getattr(optimizer, "norm_pass", False))
+            values = torch.stack(pending + [optimizer.last_grad_norm] if with_norm else pending).tolist()   # (the read-back as ever)
+            terms = terms.cpu().numpy()                                                                    # (and the ONE more copy)
+            if with_norm:
+                norm = values.pop()
+                if grad_norms is not None:
+                    grad_norms.append(norm)
+            for v in values:
+                accumulated += v
+            training_loss.append(accumulated / accumulation_steps)
+            log_vars, at = terms[-2:], 0
+            for keys, ps, S in window:
+                n = ps.shape[0]
+                priorities.update(keys, priority.sample_loss(terms[at:at + 3 * n].reshape(n, 3), S, log_vars))
+                at += 3 * n
+            pending, window, updates = [], [], 0
     return training_loss
 
 
@@ -568,19 +721,21 @@ def _with(acc):
 
 
 def train_nbp(training_set_db, params, optimizer, nbp, device, current_epoch, validation_data, lr_patience=2,
-              lr_factor=0.1, num_epochs=5, grad_norms=None, ema=None, ema_losses=None, metrics_out=None):
+              lr_factor=0.1, num_epochs=5, grad_norms=None, ema=None, ema_losses=None, metrics_out=None, priorities=None):
     """ref nbp_utils.py:430-468: 5 inner epochs, validation after each, ReduceLROnPlateau.  grad_norms: see train_experience_data.
     With `ema` the averaged network is validated after each inner epoch as well (same data, same function) and `ema_losses`, a
     list, receives its loss; the scheduler and the returned pair see the live network only.  With the config's `validation_metrics`
     on and `metrics_out`, a dict, the validation of the LAST inner epoch -- the network that gets checkpointed -- also computes the
-    planner-facing metrics (ValidationMetrics): metrics_out["validation_metrics"], and with `ema` ["validation_metrics_ema"]."""
+    planner-facing metrics (ValidationMetrics): metrics_out["validation_metrics"], and with `ema` ["validation_metrics_ema"].
+    `priorities`: the run's ReplayPriorities with `replay_priority_alpha` set (train_experience_data), None otherwise."""
     sched = torch.optim.lr_scheduler.ReduceLROnPlateau(optimizer, mode="min", factor=lr_factor, patience=lr_patience)
     tl, vl = [], []
     thresholds = metric_thresholds(params) if metrics_out is not None else None
     for inner in range(num_epochs):
         acc = ValidationMetrics(thresholds) if (thresholds is not None and inner + 1 == num_epochs) else None
         nbp.train()
-        losses = train_experience_data(training_set_db, params, optimizer, nbp, device, current_epoch, grad_norms, ema=ema)
+        losses = train_experience_data(training_set_db, params, optimizer, nbp, device, current_epoch, grad_norms, ema=ema,
+                                       **({} if priorities is None else {"priorities": priorities}))
         tl.append(float(np.mean(losses)) if losses else float("nan"))
         sync_buffers(nbp)
         nbp.eval()
@@ -609,6 +764,7 @@ def run_training_nbp(params):
     from ..parallel_rollout import init_distributed
     from ..simulator import scene as sim_scene
     from ..utility import nbp_utils as nu
+    prio_opts = replay_priority_options(params)                   # (a bad value raises before any work)
     rank, world, local_rank = init_distributed()
     device = torch.device("cuda", local_rank if world > 1 else getattr(params, "numGPU", 0))
     torch.cuda.set_device(device)
@@ -629,12 +785,21 @@ def run_training_nbp(params):
     with_norm = bool(getattr(optimizer, "norm_pass", False))      # the HIP optimizer with clipping or skipping on
 
     with_metrics = metric_thresholds(params) is not None          # `validation_metrics`: off = nothing new launched or written
+    # `replay_priority_alpha`: one table per rank for the whole run, so that a record drawn again in a later outer epoch keeps its
+    # priority (kept in memory only: not checkpointed); off = None, and nothing new drawn, launched or written
+    priorities = make_replay_priorities(params)
 
     def train_kw(norms, ema_losses, found):
         kw = dict(num_epochs=params.inner_epochs, grad_norms=norms, ema=ema, ema_losses=ema_losses)
         if with_metrics:
             kw["metrics_out"] = found
+        if priorities is not None:
+            kw["priorities"] = priorities
         return kw
+
+    def note_priorities(found):
+        if priorities is not None:      # the table as the epoch's last inner epoch left it
+            found["replay_priority"] = {"alpha": prio_opts["alpha"], "beta": prio_opts["beta"], **priorities.stats()}
 
     def save(epoch, vl, tl, grad_norms, ema_losses, found):
         nonlocal best_loss, best_ema_loss
@@ -672,6 +837,7 @@ def run_training_nbp(params):
             db = make_synthetic_experiences(params.samples_per_epoch, S, seed=100 + epoch + 1000 * rank)
             norms, ema_losses, found = [], [], {}
             tl, vl = train_nbp(db, params, optimizer, nbp, device, epoch, validation, **train_kw(norms, ema_losses, found))
+            note_priorities(found)
             print(f"epoch {epoch}: training {tl:.4f} validation {vl:.4f}")
             save(epoch, vl, tl, norms, ema_losses, found)
         return history
@@ -693,13 +859,15 @@ def run_training_nbp(params):
             validation = nu.store_validation_data(env, getattr(params, "n_validation", 1200), keep_compact=True)
             continue
         # (compact records stay streams in host memory and are expanded on the device, batch by batch: _collate_compact)
-        db = (nu.read_combined_data(env, sample_m=None, keep_compact=True) if epoch == 1
-              else nu.read_combined_data(env, keep_compact=True))   # ref :436-440
+        keyed = {} if priorities is None else {"with_keys": True}
+        db = (nu.read_combined_data(env, sample_m=None, keep_compact=True, **keyed) if epoch == 1
+              else nu.read_combined_data(env, keep_compact=True, **keyed))   # ref :436-440
         # every rank must take the same branch (the training loop below contains collectives)
         if _common_count(1 if (db and validation) else 0, device) == 0:
             continue
         norms, ema_losses, found = [], [], {}
         tl, vl = train_nbp(db, params, optimizer, nbp, device, epoch, validation, **train_kw(norms, ema_losses, found))
+        note_priorities(found)
         print(f"epoch {epoch}: training {tl:.4f} validation {vl:.4f}")
         save(epoch, vl, tl, norms, ema_losses, found)
     env.close()

@@ -838,3 +838,67 @@ def validation_metrics(out1, out2, gt, coords, gains, bidx, thresholds=(0.13,)):
                                             _lib.ptr(bidx), B, S, K, len(ts), th, _lib.ptr(obst), _lib.ptr(rank), _lib.ptr(val), _st())
     _lib.check(rc, "nbp_val_metrics_f32")
     return obst, rank, val
+
+
+def _objective_args(name, out1, coords_bcxy, gains, out2, gt, weights):
+    """Checks the tensors the objective's forward and backward share -> (B, S, C, H, W, K)."""
+    named = [("out1", out1), ("coords_bcxy", coords_bcxy), ("gains", gains), ("out2", out2), ("gt", gt)]
+    if weights is not None:
+        named.append(("weights", weights))
+    for n, t in named:
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError(f"{name}: the HIP path needs a cuda tensor for {n} (no CPU fallback)")
+    if out1.dim() != 4 or out2.dim() not in (3, 4) or out2.shape[-1] != out2.shape[-2] or (out2.dim() == 4 and out2.shape[1] != 1):
+        raise ValueError(f"{name}: out1 [B,C,H,W] and out2 [B,S,S] (or [B,1,S,S]) expected")
+    B, C, H, W = out1.shape
+    S = out2.shape[-1]
+    K = coords_bcxy.shape[0] if coords_bcxy.dim() == 2 else -1
+    if (B < 1 or S < 1 or out2.shape[0] != B or gt.shape != out2.shape or tuple(coords_bcxy.shape) != (K, 4)
+            or tuple(gains.shape) != (K,) or (weights is not None and tuple(weights.shape) != (B,))):
+        raise ValueError(f"{name}: out1 [B,C,H,W], out2 / gt [B,S,S], coords_bcxy [K,4], gains [K] and weights [B] expected")
+    if (coords_bcxy.dtype != torch.int64 or any(t.dtype != torch.float32 for n, t in named if n != "coords_bcxy")):
+        raise ValueError(f"{name}: fp32 out1 / out2 / gt / gains / weights and int64 coords_bcxy expected")
+    if any(t.device != out2.device for _, t in named):
+        raise ValueError(f"{name}: all tensors on one device expected")
+    if not all(t.is_contiguous() for _, t in named):
+        raise ValueError(f"{name}: contiguous tensors expected")
+    return B, S, C, H, W, K
+
+
+def objective_forward(out1, coords_bcxy, gains, out2, gt, weights=None):
+    """The training objective's per-sample terms on the device (csrc/nbp_objective.hip; the definition of record is
+    utility/priority.py::objective_reference) -> (per_sample float64 [B,3] = (v_b, n_b, o_b), totals float64 [2] =
+    (sum w_b v_b, sum w_b o_b)).  out1 [B,C,H,W], out2 / gt [B,S,S] or [B,1,S,S] fp32, coords_bcxy [K,4] int64 (rows in any order),
+    gains [K] fp32, weights None or [B] fp32.  Two launches on the current stream, no host synchronisation; K = 0 is legal."""
+    B, S, C, H, W, K = _objective_args("objective_forward", out1, coords_bcxy, gains, out2, gt, weights)
+    dev = out2.device
+    L = _lib.lib()
+    per_sample = torch.empty(B, 3, dtype=torch.float64, device=dev)
+    totals = torch.empty(2, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        ws = _workspace("objective", L.nbp_objective_workspace_bytes(B, S), dev)
+        rc = L.nbp_objective_forward_f32(_lib.ptr(out1), _lib.ptr(coords_bcxy), _lib.ptr(gains), K, C, H, W, _lib.ptr(out2), _lib.ptr(gt),
+                                         B, S, _lib.ptr(weights), _lib.ptr(per_sample), _lib.ptr(totals), _lib.ptr(ws), ws.numel(),
+                                         _st())
+    _lib.check(rc, "nbp_objective_forward_f32")
+    return per_sample, totals
+
+
+def objective_backward(out1, coords_bcxy, gains, out2, gt, weights, coef):
+    """The gradients of coef[0] * mse + coef[1] * bce (mse = totals[0] / K, bce = totals[1] / (B S^2)) -> (d_out1, d_out2), shaped as
+    out1 and out2.  coef: fp32 [2] ON THE DEVICE, read there: one asynchronous fill and one launch, no host synchronisation."""
+    B, S, C, H, W, K = _objective_args("objective_backward", out1, coords_bcxy, gains, out2, gt, weights)
+    dev = out2.device
+    if (not isinstance(coef, torch.Tensor) or coef.device != dev or coef.dtype != torch.float32 or tuple(coef.shape) != (2,)
+            or not coef.is_contiguous()):
+        raise ValueError("objective_backward: coef fp32 [2] on the tensors' device expected")
+    L = _lib.lib()
+    d_out1 = torch.empty_like(out1)
+    d_out2 = torch.empty_like(out2)
+    with torch.cuda.device(dev):
+        ws = _workspace("objective", L.nbp_objective_workspace_bytes(B, S), dev)
+        rc = L.nbp_objective_backward_f32(_lib.ptr(out1), _lib.ptr(coords_bcxy), _lib.ptr(gains), K, C, H, W, _lib.ptr(out2),
+                                          _lib.ptr(gt), B, S, _lib.ptr(weights), _lib.ptr(coef), _lib.ptr(d_out1), _lib.ptr(d_out2),
+                                          _lib.ptr(ws), ws.numel(), _st())
+    _lib.check(rc, "nbp_objective_backward_f32")
+    return d_out1, d_out2

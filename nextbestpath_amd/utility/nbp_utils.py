@@ -349,12 +349,23 @@ def read_random_data_readonly(env, num_samples=64, keep_compact=False):
     return [unpack_record(v, keep_compact) for i, (k, v) in enumerate(env.items()) if i in indices]
 
 
-def read_combined_data(env, sample_m=2304 * 2, sample_size=2176 * 2, keep_compact=False):
-    """ref :103-141: a random sample of the older records + the newest `sample_m` in order."""
+def read_combined_data(env, sample_m=2304 * 2, sample_size=2176 * 2, keep_compact=False, with_keys=False):
+    """ref :103-141: a random sample of the older records + the newest `sample_m` in order.  with_keys: every record also carries
+    its store key as d["_key"] (what prioritised replay files a record's priority under); the default leaves the records as they are."""
+    if with_keys:
+        def unpack(key, value):
+            d = unpack_record(value, keep_compact)
+            d["_key"] = bytes(key)
+            return d
+        return _read_combined(env, sample_m, sample_size, unpack)
+    return _read_combined(env, sample_m, sample_size, lambda key, value: unpack_record(value, keep_compact))
+
+
+def _read_combined(env, sample_m, sample_size, unpack):
     total = env.entries()
     print("number of total data in the database:", total)
     if sample_m is None:
-        return [unpack_record(v, keep_compact) for _, v in env.items()]
+        return [unpack(k, v) for k, v in env.items()]
     n = total - sample_m
     if n < 0:
         n = 1
@@ -363,9 +374,9 @@ def read_combined_data(env, sample_m=2304 * 2, sample_size=2176 * 2, keep_compac
     first_tail = max(total - sample_m, 0)
     for i, (key, value) in enumerate(env.items()):
         if i < n and i in sample_indices:
-            selected.append(unpack_record(value, keep_compact))
+            selected.append(unpack(key, value))
         if i >= first_tail:
-            tail.append(unpack_record(value, keep_compact))
+            tail.append(unpack(key, value))
     return selected + tail
 
 

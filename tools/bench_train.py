@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Config 3 of BASELINE.json: NBP fwd + bwd + AdamW step, batch of 256x256 maps, fp32, 1 MI355X.
     python tools/bench_train.py [--batch 32] [--steps 5] [--size 256] [--precision fp32_split|fp16] [--augment P]
-                                [--optimizer torch|hip] [--clip X] [--ema D]
+                                [--optimizer torch|hip] [--clip X] [--ema D] [--priority ALPHA]
 Prints one JSON line: train maps/s, TFLOP/s against 546.9 GFLOP/map, and the torch-CPU baseline
 (stock autograd on the same weights = the reference's arithmetic) on a bounded sample."""
 import argparse
@@ -43,9 +43,16 @@ def main():
                     help="with a format every step also runs the trainer's per-batch data path on records of that format: staged "
                          "collation (reference: the expanded maps; compact: the streams + one hipops.replay_decode launch).  "
                          "Default: the batch is collated once, outside the timed steps")
+    ap.add_argument("--priority", type=float, default=None, metavar="ALPHA",
+                    help="replay_priority_alpha: every step draws its batch from a ReplayPriorities over the records (with replacement), "
+                         "copies the draw's weights to the device, runs the fused objective (tr.loss_weighted) instead of gather + "
+                         "nbp.loss, and behind the optimizer step reads the per-sample terms back and updates the table (the trainer "
+                         "does that once per 8 batches).  0 = uniform draws, unit weights")
     a = ap.parse_args()
     if a.replay_format and a.augment > 0:
         ap.error("--replay-format and --augment time different per-batch work: one at a time")
+    if a.priority is not None and (a.replay_format or a.augment > 0):
+        ap.error("--priority times its own per-batch work: not with --replay-format or --augment")
     dev = torch.device("cuda")
     torch.manual_seed(9)
     net = NBP().to(dev).train()
@@ -65,6 +72,29 @@ def main():
         records = [nu.unpack_record(nu.pack_record(d, a.replay_format), keep_compact=True) for d in db]
         stager = _BatchStager(dev)
 
+    prio = None
+    if a.priority is not None:
+        from nextbestpath_amd.utility import priority
+        prio = priority.ReplayPriorities(a.priority)
+        prio.begin(list(range(a.batch)))
+        prio_rng = np.random.default_rng(5)
+        first = torch.zeros(a.batch + 1, dtype=torch.int64)
+        first[1:] = torch.bincount(bidx.cpu(), minlength=a.batch).cumsum(0)
+
+    def prioritised_step():
+        """A batch of drawn records: the planes by one device gather, the targets by index arithmetic on the host (the trainer collates
+        the drawn records and stages them; the bytes that move to the device are the same weights, targets and op-free planes)."""
+        idx, w = prio.draw(prio_rng, a.batch)
+        idx_dev = torch.from_numpy(idx).pin_memory().to(dev, non_blocking=True)
+        w_dev = torch.from_numpy(w.astype(np.float32)).pin_memory().to(dev, non_blocking=True)
+        rows = np.concatenate([np.arange(int(first[i]), int(first[i + 1])) for i in idx])
+        sizes = np.array([int(first[i + 1] - first[i]) for i in idx])
+        rows_dev = torch.from_numpy(rows).pin_memory().to(dev, non_blocking=True)
+        bi = torch.from_numpy(np.repeat(np.arange(a.batch), sizes)).pin_memory().to(dev, non_blocking=True)
+        o1, o2 = net(xs[idx_dev])
+        loss, per_sample = tr.loss_weighted(net, o1, bi, coords[rows_dev], gains[rows_dev], o2, gt[idx_dev], w_dev)
+        return loss, idx, per_sample
+
     aug_rng = random.Random(5)
     ops_dev = torch.zeros(a.batch, dtype=torch.int32, device=dev)
 
@@ -76,7 +106,10 @@ def main():
         return [torch.from_numpy(v).pin_memory().to(dev, non_blocking=True) for v in (cd, gn, bi)]
 
     def step():
-        if a.augment > 0:
+        drawn = None
+        if prio is not None:
+            loss, *drawn = prioritised_step()
+        elif a.augment > 0:
             ops = augment.draw_ops(aug_rng, a.batch, a.augment)
             ops_dev.copy_(torch.from_numpy(ops).pin_memory(), non_blocking=True)
             cd, gn, bi = targets(augment.augment_records(db, ops, a.size // 4))
@@ -96,6 +129,9 @@ def main():
         if ema is not None:
             ema.update(opt)
         opt.zero_grad(set_to_none=True)
+        if drawn is not None:
+            terms = torch.cat([drawn[1].reshape(-1), net.log_vars.detach().double()]).cpu().numpy()
+            prio.update(drawn[0].tolist(), priority.sample_loss(terms[:-2].reshape(-1, 3), a.size, terms[-2:]))
         return loss
 
     for _ in range(a.warmup):
@@ -131,6 +167,7 @@ def main():
         "n_gpus": 1, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(dt * 1e3, 2), "dtype": "f32",
         "train_precision": a.precision, "augment_probability": a.augment, "optimizer": a.optimizer, "grad_clip_norm": a.clip,
         "replay_format": a.replay_format, "ema_decay": a.ema, "ema_updates": None if ema is None else int(ema.num_updates),
+        "replay_priority_alpha": a.priority, "replay_priority": None if prio is None else prio.stats(),
         "data": "synthetic", "config": {"workload": f"configs[2]: train step, batch {a.batch} x {a.size}x{a.size}"},
         "tflops_reference_formulation": round(a.batch * flop_map / dt / 1e12, 2), "frac_of_split_ceiling_reference_formulation": round(a.batch * flop_map / dt / (2500e12 / 3), 4),
         "loss": float(loss.item()), "producer_notes": dict(tr.HANDOFF_STATS),
