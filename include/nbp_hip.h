@@ -1011,6 +1011,46 @@ int nbp_objective_backward_f32(const float* out1_nchw, const long long* coords_b
                                const float* out2, const float* gt, int B, int S, const float* weights_or_null, const float* coef_dev,
                                float* d_out1_nchw, float* d_out2, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- Reconstruction-quality metrics (csrc/nbp_recon.hip).  Not in the reference: accuracy, completeness, Chamfer
+ * distance and precision / recall / F-score of a rollout's cloud against the GT surface.  The definition of record is
+ * nextbestpath_amd/utility/recon_metrics.py.  Host binding: hipops.nn_dist2 / recon_stats / ReconMetrics.
+ *
+ * Truncated exact nearest-neighbour squared distance, fp32:
+ *   d2[i] = min(cap2, min over the targets j INSIDE THE BOX of ((ex ex + ey ey) + ez ez)),  e = t_j - q_i,  cap2 = fl(cap cap),
+ * every operation rounded to fp32 (no contraction).  Inside the box: lo <= t <= hi on the three axes, compared in fp32 (a NaN is
+ * outside); the caller chooses the box so that ignoring the others is harmless (the GT bounds grown by cap).  q3 [Q][3], t3 [T][3],
+ * d2 [Q]; Q and T are host bounds and, where the *_dev_or_null pointer is given, the device counter (clipped to the bound) is the
+ * length: rows at or beyond it are never read, entries of d2 at or beyond it are never written.  lo_host / hi_host [3]; hi == lo on
+ * an axis is one cell.  cell = the width w > 0 of the uniform grid the in-box targets are counting-sorted into (cells of 1.001 w);
+ * the query walks the shells of cells at Chebyshev distance r = 0 .. ceil(cap / w) around its cell and stops after shell r once
+ * best <= fl(r w)^2: the result is the brute-force minimum bit for bit, and two runs give the same bits (no atomics on the output).
+ * A query more than ceil(cap / w) cells outside the grid gets cap2 without a memory access.  Q = 0 and T = 0 are legal.
+ *   nbp_nn_dist2_f32             sorts the targets and queries them (ws: nbp_nn_dist2_workspace_bytes)
+ *   nbp_nn_plan_build_f32        sorts a static target set once into `plan` (nbp_nn_plan_bytes; ws: nbp_nn_plan_workspace_bytes)
+ *   nbp_nn_dist2_planned_f32     queries a plan built with the same lo / hi / cell
+ * No allocation, no host synchronisation.  NBP_E_ARG: a null pointer, a negative or > 2^31 - 1 count, cell or cap not positive and
+ * finite, cap / cell > 2^24, hi < lo; NBP_E_SHAPE: more than 2048 cells on an axis (beyond that the fp32 cell coordinates no longer
+ * carry the early exit's proof) or more than 2^28 cells; NBP_E_WS.  The size queries return 0 where the call would fail. */
+size_t nbp_nn_plan_bytes(const float* lo_host, const float* hi_host, float cell, long long T);
+size_t nbp_nn_plan_workspace_bytes(const float* lo_host, const float* hi_host, float cell, long long T);
+int nbp_nn_plan_build_f32(const float* t3, long long T, const long long* T_dev_or_null, const float* lo_host, const float* hi_host,
+                          float cell, void* plan, size_t plan_bytes, void* ws, size_t ws_bytes, void* stream);
+int nbp_nn_dist2_planned_f32(const void* plan, const float* lo_host, const float* hi_host, float cell, float cap, const float* q3,
+                             long long Q, const long long* Q_dev_or_null, float* d2, void* stream);
+size_t nbp_nn_dist2_workspace_bytes(const float* lo_host, const float* hi_host, float cell, long long T);
+int nbp_nn_dist2_f32(const float* q3, long long Q, const long long* Q_dev_or_null, const float* t3, long long T,
+                     const long long* T_dev_or_null, const float* lo_host, const float* hi_host, float cap, float cell, float* d2,
+                     void* ws, size_t ws_bytes, void* stream);
+/* Summary of d2 [n] (n: host bound, and the device counter where given): sums2 [2] float64 = (sum sqrt(d2), sum d2), the square root
+ * taken in float64; counts [T] int64 = #{ sqrtf(d2) < thresholds_host[t] }, decided as d2 <= the largest float whose sqrtf is below
+ * the threshold (the same decision: sqrtf is monotone and correctly rounded).  1 <= T <= 8 thresholds on the HOST, positive and
+ * finite.  Two launches of a fixed geometry: per-thread strided float64 partials, a fixed tree inside the block, one stored row
+ * per block, the rows added in index order -- no floating-point atomics, two runs give the same bits.  n = 0 gives zeros.
+ * ws: nbp_recon_stats_workspace_bytes().  NBP_E_SHAPE: sums2 or counts off the 8-byte grid. */
+size_t nbp_recon_stats_workspace_bytes(void);
+int nbp_recon_stats_f64(const float* d2, long long n, const long long* n_dev_or_null, int T, const float* thresholds_host,
+                        double* sums2, long long* counts, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- The replay store's container in LMDB's on-disk format (csrc/nbp_mdb.cpp; host only).  The reference keeps its experience
  * records in an LMDB environment (next_best_path/trainers/train_nbp_model.py:61-63 lmdb.open(path, map_size);
  * next_best_path/utility/nbp_utils.py:32-141: txn.put per record, ordered cursors, txn.delete of the validation records).  liblmdb is

@@ -228,6 +228,14 @@ SIGNATURES["nbp_replay_stream_bound"] = (_sz, [_i])
 SIGNATURES["nbp_replay_encode_f32"] = (_i, [_vp, _i, _i, _vp, _sz, _vp])
 SIGNATURES["nbp_replay_decode_f32"] = (_i, [_vp, C.POINTER(_ll), _i, _i, _vp, _vp, _vp])
 SIGNATURES["nbp_val_metrics_f32"] = (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, C.POINTER(_f), _vp, _vp, _vp, _vp])
+SIGNATURES["nbp_nn_plan_bytes"] = (_sz, [_fpp, _fpp, _f, _ll])
+SIGNATURES["nbp_nn_plan_workspace_bytes"] = (_sz, [_fpp, _fpp, _f, _ll])
+SIGNATURES["nbp_nn_plan_build_f32"] = (_i, [_vp, _ll, _vp, _fpp, _fpp, _f, _vp, _sz, _vp, _sz, _vp])
+SIGNATURES["nbp_nn_dist2_planned_f32"] = (_i, [_vp, _fpp, _fpp, _f, _f, _vp, _ll, _vp, _vp, _vp])
+SIGNATURES["nbp_nn_dist2_workspace_bytes"] = (_sz, [_fpp, _fpp, _f, _ll])
+SIGNATURES["nbp_nn_dist2_f32"] = (_i, [_vp, _ll, _vp, _vp, _ll, _vp, _fpp, _fpp, _f, _f, _vp, _vp, _sz, _vp])
+SIGNATURES["nbp_recon_stats_workspace_bytes"] = (_sz, [])
+SIGNATURES["nbp_recon_stats_f64"] = (_i, [_vp, _ll, _vp, _i, _fpp, _vp, _vp, _vp, _sz, _vp])
 SIGNATURES["nbp_objective_workspace_bytes"] = (_sz, [_i, _i])
 SIGNATURES["nbp_objective_forward_f32"] = (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp])
 SIGNATURES["nbp_objective_backward_f32"] = (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp])

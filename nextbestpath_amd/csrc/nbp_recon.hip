@@ -1,0 +1,393 @@
+// nbp_recon.hip -- reconstruction-quality metrics: exact truncated nearest-neighbour distances between two point sets that are
+// already on the device, and their reproducible summary (include/nbp_hip.h: nbp_nn_*, nbp_recon_stats_f64; the definition of
+// record is nextbestpath_amd/utility/recon_metrics.py).  Not in the reference.
+//
+// Nearest neighbour.  The targets inside the caller's box are counting-sorted into a uniform grid (bin, grid_exclusive_scan,
+// scatter to float4 -- the coverage plan's three steps).  One launch over the queries follows: NN_LANES lanes per query walk the
+// shells of cells at Chebyshev cell distance r = 0, 1, ..., R = ceil(cap / w) around the query's UNCLAMPED cell.  k is the fastest
+// cell index, so the z cells of an (x, y) column are one contiguous run of the sorted array: a column on the rim of the shell's
+// square is one run over its 2 r + 1 cells (two loads of `start`), a column inside the square contributes its two end cells.
+//
+// Why the walk may stop after shell r once best <= fl(r w)^2, and after shell R whatever it found.  Cells are 1.001 w wide.  A
+// target in a cell that shells 0..r do not hold differs from the query's cell by at least r + 1 on some axis, so their cell
+// coordinates u = fl(fl(x - lo) inv) differ by more than r there.  u carries a relative error below 2^-23, i.e. below n 2^-23
+// cells on an axis of n cells; with n <= NN_MAX_AXIS = 2048 (more is NBP_E_SHAPE) the two errors together stay below 0.0005 cells
+// (plus r 2^-23 for a query r cells outside the grid), so for r >= 1 the real separation on that axis exceeds (r - 0.0005) 1.001 w
+// > r w by a margin of 4e-4 relative, which dwarfs the 2^-24 roundings of e = fl(t - q), fl(e e) and fl(r w).  Rounding is
+// monotone, so the pair's fp32 squared distance
+// ((ex ex + ey ey) + ez ez) >= fl(e e) > fl(r w)^2 >= best: it cannot lower the minimum.  (r = 0: best <= 0 is a minimum already.)
+// After shell R every unvisited target is farther than R w >= cap: its squared distance exceeds cap2.  So the result is the
+// brute-force minimum over all in-box targets, bit for bit, and -- a minimum being blind to the order of its operands -- the
+// atomicAdd slot order inside a cell does not show: two runs give the same bits.  No atomics touch the output.
+//
+// Summary (nbp_recon_stats_f64): a fixed launch geometry; every thread adds its strided elements in index order in float64, a
+// fixed tree adds the threads of a block (shuffles inside a wave, the four waves in order), each block STORES one row, and a
+// second one-block launch adds the rows in index order.  No floating-point atomics: two runs give the same bits.
+#include "nbp_grid.h"
+
+#include <math.h>
+#include <stddef.h>
+
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int NN_LANES = 8;                      // lanes per query: the 8 rim columns of shell 1 at once
+constexpr int NN_UNROLL = 4;                     // points of a run in flight together (coverage_mark_body: one per iteration
+                                                 // is a chain of dependent round trips)
+constexpr int NN_MAX_AXIS = 2048;                // cells per axis for which the early exit is proven (see above)
+constexpr int STATS_BLOCKS = 256, STATS_THREADS = 256, STATS_WAVES = STATS_THREADS / 64;
+constexpr int STATS_MAX_T = 8;
+constexpr int STATS_ROW = 2 + STATS_MAX_T;       // 8-byte words of a block's row: two float64 sums, then the counts
+
+struct Box { float hi[3]; };
+
+static size_t al256(size_t b) { return (b + 255) / 256 * 256; }
+
+// ---- sort
+__global__ __launch_bounds__(256) void nn_bin_kernel(const float* __restrict__ t, const long long* __restrict__ n_dev, long long n_host,
+                                                     Grid g, Box bx, int* __restrict__ cell_of, int* __restrict__ slot_of,
+                                                     int* __restrict__ count) {
+    long long n = n_dev ? *n_dev : n_host;
+    n = n < 0 ? 0 : (n > n_host ? n_host : n);                       // rows at or beyond the device count are never read
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        const float x = t[3 * i], y = t[3 * i + 1], z = t[3 * i + 2];
+        const bool in = x >= g.lo[0] && x <= bx.hi[0] && y >= g.lo[1] && y <= bx.hi[1] && z >= g.lo[2] && z <= bx.hi[2];   // a NaN is outside
+        int c = -1;
+        if (in) {
+            c = grid_cell(g, x, y, z, nullptr);
+            slot_of[i] = atomicAdd(&count[c], 1);
+        }
+        cell_of[i] = c;
+    }
+}
+
+__global__ __launch_bounds__(256) void nn_scatter_kernel(const float* __restrict__ t, const long long* __restrict__ n_dev,
+                                                         long long n_host, const int* __restrict__ cell_of,
+                                                         const int* __restrict__ slot_of, const int* __restrict__ start,
+                                                         float4* __restrict__ sorted) {
+    long long n = n_dev ? *n_dev : n_host;
+    n = n < 0 ? 0 : (n > n_host ? n_host : n);
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        const int c = cell_of[i];
+        if (c >= 0) sorted[start[c] + slot_of[i]] = make_float4(t[3 * i], t[3 * i + 1], t[3 * i + 2], 0.f);
+    }
+}
+
+// ---- query
+__device__ __forceinline__ float nn_run(const float4* __restrict__ sorted, int p, int hi, float x, float y, float z, float best) {
+    for (; p + NN_UNROLL <= hi; p += NN_UNROLL) {
+        float4 t[NN_UNROLL];
+#pragma unroll
+        for (int u = 0; u < NN_UNROLL; ++u) t[u] = sorted[p + u];
+#pragma unroll
+        for (int u = 0; u < NN_UNROLL; ++u) {
+            const float ex = t[u].x - x, ey = t[u].y - y, ez = t[u].z - z;
+            const float d = (ex * ex + ey * ey) + ez * ez;
+            best = d < best ? d : best;
+        }
+    }
+    for (; p < hi; ++p) {
+        const float4 t = sorted[p];
+        const float ex = t.x - x, ey = t.y - y, ez = t.z - z;
+        const float d = (ex * ex + ey * ey) + ez * ez;
+        best = d < best ? d : best;
+    }
+    return best;
+}
+
+__global__ __launch_bounds__(256) void nn_query_kernel(const float* __restrict__ q, const long long* __restrict__ n_dev, long long n_host,
+                                                       Grid g, int R, float w, float cap2, const float4* __restrict__ sorted,
+                                                       const int* __restrict__ start, float* __restrict__ d2) {
+    long long Q = n_dev ? *n_dev : n_host;
+    Q = Q < 0 ? 0 : (Q > n_host ? n_host : Q);
+    const int sub = threadIdx.x % NN_LANES;
+    const int n0 = g.n[0], n1 = g.n[1], n2 = g.n[2];
+    for (long long j = ((long long)blockIdx.x * blockDim.x + threadIdx.x) / NN_LANES; j < Q;
+         j += ((long long)gridDim.x * blockDim.x) / NN_LANES) {
+        const float x = q[3 * j], y = q[3 * j + 1], z = q[3 * j + 2];
+        // the unclamped cell, clamped as a FLOAT to one cell beyond the reach of R before the conversion (a query 1e6 away, or a
+        // NaN, must not reach the int conversion's undefined range)
+        float fi = floorf((x - g.lo[0]) * g.inv), fj = floorf((y - g.lo[1]) * g.inv), fk = floorf((z - g.lo[2]) * g.inv);
+        const bool reach = fi >= (float)-R && fi <= (float)(n0 - 1 + R) && fj >= (float)-R && fj <= (float)(n1 - 1 + R) &&
+                           fk >= (float)-R && fk <= (float)(n2 - 1 + R);
+        float best = cap2;
+        if (reach) {                                               // (uniform over the query's lanes)
+            const int ci = (int)fi, cj = (int)fj, ck = (int)fk;
+            // shells closer than the grid hold no cell: a query outside starts at its Chebyshev cell distance to the grid (<= R)
+            const int r0 = max(max(max(-ci, ci - (n0 - 1)), max(-cj, cj - (n1 - 1))), max(max(-ck, ck - (n2 - 1)), 0));
+            for (int r = r0; r <= R; ++r) {
+                // the shell's square of columns, cut to the grid
+                const int a0 = max(ci - r, 0), a1 = min(ci + r, n0 - 1), b0 = max(cj - r, 0), b1 = min(cj + r, n1 - 1);
+                const int na = a1 - a0 + 1, nb = b1 - b0 + 1;
+                if (na > 0 && nb > 0) {
+                    const int zl = ck - r, zh = ck + r;
+                    for (int it = sub; it < na * nb; it += NN_LANES) {
+                        const int a = a0 + it / nb, b = b0 + it % nb;
+                        const int base = (a * n1 + b) * n2;
+                        if (a == ci - r || a == ci + r || b == cj - r || b == cj + r) {      // rim: the column's whole run
+                            const int z0 = max(zl, 0), z1 = min(zh, n2 - 1);
+                            if (z0 <= z1) best = nn_run(sorted, start[base + z0], start[base + z1 + 1], x, y, z, best);
+                        } else {                                                             // inside: the two end cells
+                            if (zl >= 0 && zl < n2) best = nn_run(sorted, start[base + zl], start[base + zl + 1], x, y, z, best);
+                            if (zh >= 0 && zh < n2) best = nn_run(sorted, start[base + zh], start[base + zh + 1], x, y, z, best);
+                        }
+                    }
+                }
+#pragma unroll
+                for (int o = NN_LANES / 2; o; o >>= 1) {
+                    const float other = __shfl_xor(best, o);
+                    best = other < best ? other : best;
+                }
+                const float rw = (float)r * w;
+                if (best <= rw * rw) break;
+                // every cell of the grid has been visited
+                if (ci - r <= 0 && ci + r >= n0 - 1 && cj - r <= 0 && cj + r >= n1 - 1 && ck - r <= 0 && ck + r >= n2 - 1) break;
+            }
+        }
+        if (sub == 0) d2[j] = best;
+    }
+}
+
+// ---- summary
+struct StatsThresholds { float v[STATS_MAX_T]; };
+
+template <int T>
+__global__ __launch_bounds__(STATS_THREADS) void stats_partial_kernel(const float* __restrict__ d2, const long long* __restrict__ n_dev,
+                                                                     long long n_host, StatsThresholds th,
+                                                                     unsigned long long* __restrict__ rows) {
+    __shared__ double ws1[STATS_WAVES], ws2[STATS_WAVES];
+    __shared__ long long wc[STATS_WAVES][STATS_MAX_T];
+    long long n = n_dev ? *n_dev : n_host;
+    n = n < 0 ? 0 : (n > n_host ? n_host : n);
+    double s1 = 0.0, s2 = 0.0;
+    long long c[T];
+#pragma unroll
+    for (int t = 0; t < T; ++t) c[t] = 0;
+    for (long long i = (long long)blockIdx.x * STATS_THREADS + threadIdx.x; i < n; i += (long long)STATS_BLOCKS * STATS_THREADS) {
+        const float v = d2[i];
+        s1 += sqrt((double)v);
+        s2 += (double)v;
+#pragma unroll
+        for (int t = 0; t < T; ++t) c[t] += v <= th.v[t] ? 1 : 0;
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        s1 += __shfl_down(s1, off, 64);
+        s2 += __shfl_down(s2, off, 64);
+#pragma unroll
+        for (int t = 0; t < T; ++t) c[t] += __shfl_down(c[t], off, 64);
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) {
+        ws1[wave] = s1;
+        ws2[wave] = s2;
+#pragma unroll
+        for (int t = 0; t < T; ++t) wc[wave][t] = c[t];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double r1 = ws1[0], r2 = ws2[0];
+        for (int k = 1; k < STATS_WAVES; ++k) { r1 += ws1[k]; r2 += ws2[k]; }
+        unsigned long long* row = rows + (size_t)blockIdx.x * STATS_ROW;
+        row[0] = (unsigned long long)__double_as_longlong(r1);
+        row[1] = (unsigned long long)__double_as_longlong(r2);
+        for (int t = 0; t < STATS_MAX_T; ++t) {
+            long long s = 0;
+            if (t < T)
+                for (int k = 0; k < STATS_WAVES; ++k) s += wc[k][t];
+            row[2 + t] = (unsigned long long)s;
+        }
+    }
+}
+
+__global__ __launch_bounds__(64) void stats_final_kernel(const unsigned long long* __restrict__ rows, int T, double* __restrict__ sums,
+                                                         long long* __restrict__ counts) {
+    const int col = threadIdx.x;
+    if (col < 2) {
+        double s = 0.0;
+        for (int b = 0; b < STATS_BLOCKS; ++b) s += __longlong_as_double((long long)rows[(size_t)b * STATS_ROW + col]);
+        sums[col] = s;
+    } else if (col < 2 + T) {
+        long long s = 0;
+        for (int b = 0; b < STATS_BLOCKS; ++b) s += (long long)rows[(size_t)b * STATS_ROW + col];
+        counts[col - 2] = s;
+    }
+}
+
+template <int T>
+void launch_stats(hipStream_t st, const float* d2, const long long* n_dev, long long n, const StatsThresholds& th,
+                  unsigned long long* rows) {
+    stats_partial_kernel<T><<<STATS_BLOCKS, STATS_THREADS, 0, st>>>(d2, n_dev, n, th, rows);
+}
+
+// ---- host
+// The grid over the caller's box [lo, hi]: cells 1.001 w wide (inv), one cell on an axis with hi == lo.
+int nn_grid(const float* lo, const float* hi, float w, Grid* g, Box* bx, size_t* ncell) {
+    size_t n = 1;
+    for (int a = 0; a < 3; ++a) {
+        g->lo[a] = lo[a];
+        bx->hi[a] = hi[a];
+        const double ext = (double)hi[a] - (double)lo[a];
+        if (!(ext >= 0) || !(ext / (double)w < (double)NN_MAX_AXIS * 65536.0)) return ext >= 0 ? NBP_E_SHAPE : NBP_E_ARG;
+        const long long na = (long long)(ext / (double)w) + 1;
+        if (na > NN_MAX_AXIS) return NBP_E_SHAPE;
+        g->n[a] = (int)na;
+        n *= (size_t)na;
+    }
+    g->inv = (float)(1.0 / ((double)w * 1.001));
+    if (n > (size_t)1 << 28) return NBP_E_SHAPE;
+    *ncell = n;
+    return 0;
+}
+
+void nn_plan_carve(void* plan, size_t ncell, int** start, float4** sorted) {
+    char* p = (char*)(((uintptr_t)plan + 255) / 256 * 256);
+    *start = (int*)p; p += al256((ncell + 1) * 4);
+    *sorted = (float4*)p;
+}
+
+size_t nn_plan_bytes(size_t ncell, long long T) { return 256 + al256((ncell + 1) * 4) + al256((size_t)(T > 0 ? T : 1) * 16); }
+size_t nn_plan_ws_bytes(size_t ncell, long long T) {
+    return 256 + al256(ncell * 4) + al256((ncell / SCAN_TILE + 1) * 4) + 2 * al256((size_t)(T > 0 ? T : 1) * 4);
+}
+
+int nn_build(const float* t3, long long T, const long long* T_dev, const Grid& g, const Box& bx, size_t ncell, void* plan, void* ws,
+             hipStream_t st) {
+    int* start; float4* sorted;
+    nn_plan_carve(plan, ncell, &start, &sorted);
+    char* p = (char*)(((uintptr_t)ws + 255) / 256 * 256);
+    int* count = (int*)p; p += al256(ncell * 4);
+    int* tsum = (int*)p; p += al256((ncell / SCAN_TILE + 1) * 4);
+    int* cell_of = (int*)p; p += al256((size_t)(T > 0 ? T : 1) * 4);
+    int* slot_of = (int*)p;
+    hipError_t e = hipMemsetAsync(count, 0, ncell * 4, st);
+    if (e != hipSuccess) return (int)e;
+    int rc;
+    const int grid = nbp_ew_grid(T > 0 ? T : 1, 256);
+    if (T > 0) {
+        nn_bin_kernel<<<grid, 256, 0, st>>>(t3, T_dev, T, g, bx, cell_of, slot_of, count);
+        if ((rc = nbp_launch_status())) return rc;
+    }
+    if ((rc = grid_exclusive_scan(count, (long long)ncell, tsum, start, st))) return rc;
+    if (T > 0) {
+        nn_scatter_kernel<<<grid, 256, 0, st>>>(t3, T_dev, T, cell_of, slot_of, start, sorted);
+        if ((rc = nbp_launch_status())) return rc;
+    }
+    return 0;
+}
+
+int nn_query(const void* plan, const Grid& g, size_t ncell, float cap, float w, const float* q3, long long Q, const long long* Q_dev,
+             float* d2, hipStream_t st) {
+    if (Q == 0) return 0;
+    int* start; float4* sorted;
+    nn_plan_carve(const_cast<void*>(plan), ncell, &start, &sorted);
+    const int R = (int)ceil((double)cap / (double)w);               // <= 2^24 (nn_args_ok)
+    const float cap2 = cap * cap;
+    nn_query_kernel<<<nbp_ew_grid(Q * NN_LANES, 256), 256, 0, st>>>(q3, Q_dev, Q, g, R, w, cap2, sorted, start, d2);
+    return nbp_launch_status();
+}
+
+bool nn_args_ok(const float* lo, const float* hi, float w) { return lo && hi && w > 0 && isfinite(w); }
+// cap > 0 and at most 2^24 cells: the shell index and the cell coordinates stay inside int and exact in float
+bool nn_cap_ok(float cap, float w) { return cap > 0 && isfinite(cap) && (double)cap / (double)w <= 16777216.0; }
+
+}  // namespace
+
+// Largest float x with sqrtf(x) < thr (thr > 0 finite): the squared-distance form of `distance < thr` (the coverage plan's helper,
+// nbp_planner.hip, which keeps its own copy: that file is not part of the C ABI's shared headers).
+static float recon_sq_below(float thr) {
+    float x = thr * thr;
+    while (sqrtf(x) >= thr) x = nextafterf(x, 0.f);
+    while (sqrtf(nextafterf(x, INFINITY)) < thr) x = nextafterf(x, INFINITY);
+    return x;
+}
+
+extern "C" size_t nbp_nn_plan_bytes(const float* lo_host, const float* hi_host, float cell, long long T) {
+    Grid g; Box bx; size_t ncell;
+    if (!nn_args_ok(lo_host, hi_host, cell) || T < 0 || T > 0x7fffffffll) return 0;
+    if (nn_grid(lo_host, hi_host, cell, &g, &bx, &ncell)) return 0;
+    return nn_plan_bytes(ncell, T);
+}
+
+extern "C" size_t nbp_nn_plan_workspace_bytes(const float* lo_host, const float* hi_host, float cell, long long T) {
+    Grid g; Box bx; size_t ncell;
+    if (!nn_args_ok(lo_host, hi_host, cell) || T < 0 || T > 0x7fffffffll) return 0;
+    if (nn_grid(lo_host, hi_host, cell, &g, &bx, &ncell)) return 0;
+    return nn_plan_ws_bytes(ncell, T);
+}
+
+extern "C" int nbp_nn_plan_build_f32(const float* t3, long long T, const long long* T_dev_or_null, const float* lo_host,
+                                     const float* hi_host, float cell, void* plan, size_t plan_bytes, void* ws, size_t ws_bytes,
+                                     void* stream) {
+    NBP_ENTER();
+    NBP_RETURN_IF(!plan || !ws || !nn_args_ok(lo_host, hi_host, cell) || T < 0 || T > 0x7fffffffll || (T > 0 && !t3), NBP_E_ARG);
+    Grid g; Box bx; size_t ncell;
+    const int rc = nn_grid(lo_host, hi_host, cell, &g, &bx, &ncell);
+    if (rc) return rc;
+    NBP_RETURN_IF(plan_bytes < nn_plan_bytes(ncell, T) || ws_bytes < nn_plan_ws_bytes(ncell, T), NBP_E_WS);
+    return nn_build(t3, T, T_dev_or_null, g, bx, ncell, plan, ws, (hipStream_t)stream);
+}
+
+extern "C" int nbp_nn_dist2_planned_f32(const void* plan, const float* lo_host, const float* hi_host, float cell, float cap,
+                                        const float* q3, long long Q, const long long* Q_dev_or_null, float* d2, void* stream) {
+    NBP_ENTER();
+    NBP_RETURN_IF(!plan || !nn_args_ok(lo_host, hi_host, cell) || !nn_cap_ok(cap, cell) || Q < 0 || Q > 0x7fffffffll, NBP_E_ARG);
+    NBP_RETURN_IF(Q > 0 && (!q3 || !d2), NBP_E_ARG);
+    Grid g; Box bx; size_t ncell;
+    const int rc = nn_grid(lo_host, hi_host, cell, &g, &bx, &ncell);
+    if (rc) return rc;
+    return nn_query(plan, g, ncell, cap, cell, q3, Q, Q_dev_or_null, d2, (hipStream_t)stream);
+}
+
+extern "C" size_t nbp_nn_dist2_workspace_bytes(const float* lo_host, const float* hi_host, float cell, long long T) {
+    Grid g; Box bx; size_t ncell;
+    if (!nn_args_ok(lo_host, hi_host, cell) || T < 0 || T > 0x7fffffffll) return 0;
+    if (nn_grid(lo_host, hi_host, cell, &g, &bx, &ncell)) return 0;
+    return nn_plan_bytes(ncell, T) + nn_plan_ws_bytes(ncell, T);
+}
+
+extern "C" int nbp_nn_dist2_f32(const float* q3, long long Q, const long long* Q_dev_or_null, const float* t3, long long T,
+                                const long long* T_dev_or_null, const float* lo_host, const float* hi_host, float cap, float cell,
+                                float* d2, void* ws, size_t ws_bytes, void* stream) {
+    NBP_ENTER();
+    NBP_RETURN_IF(!ws || !nn_args_ok(lo_host, hi_host, cell) || !nn_cap_ok(cap, cell), NBP_E_ARG);
+    NBP_RETURN_IF(Q < 0 || Q > 0x7fffffffll || T < 0 || T > 0x7fffffffll || (T > 0 && !t3) || (Q > 0 && (!q3 || !d2)), NBP_E_ARG);
+    Grid g; Box bx; size_t ncell;
+    int rc = nn_grid(lo_host, hi_host, cell, &g, &bx, &ncell);
+    if (rc) return rc;
+    NBP_RETURN_IF(ws_bytes < nn_plan_bytes(ncell, T) + nn_plan_ws_bytes(ncell, T), NBP_E_WS);
+    void* plan = ws;
+    void* scratch = (char*)ws + nn_plan_bytes(ncell, T);
+    if ((rc = nn_build(t3, T, T_dev_or_null, g, bx, ncell, plan, scratch, (hipStream_t)stream))) return rc;
+    return nn_query(plan, g, ncell, cap, cell, q3, Q, Q_dev_or_null, d2, (hipStream_t)stream);
+}
+
+extern "C" size_t nbp_recon_stats_workspace_bytes(void) { return 256 + (size_t)STATS_BLOCKS * STATS_ROW * 8; }
+
+extern "C" int nbp_recon_stats_f64(const float* d2, long long n, const long long* n_dev_or_null, int T, const float* thresholds_host,
+                                   double* sums2, long long* counts, void* ws, size_t ws_bytes, void* stream) {
+    NBP_ENTER();
+    NBP_RETURN_IF(!thresholds_host || !sums2 || !counts || !ws || n < 0 || (n > 0 && !d2) || T < 1 || T > STATS_MAX_T, NBP_E_ARG);
+    for (int t = 0; t < T; ++t) NBP_RETURN_IF(!(thresholds_host[t] > 0) || !isfinite(thresholds_host[t]), NBP_E_ARG);
+    NBP_RETURN_IF((((uintptr_t)sums2 | (uintptr_t)counts) & 7), NBP_E_SHAPE);
+    NBP_RETURN_IF(ws_bytes < nbp_recon_stats_workspace_bytes(), NBP_E_WS);
+    hipStream_t st = (hipStream_t)stream;
+    StatsThresholds th;
+    for (int t = 0; t < STATS_MAX_T; ++t) th.v[t] = recon_sq_below(thresholds_host[t < T ? t : 0]);
+    unsigned long long* rows = (unsigned long long*)(((uintptr_t)ws + 255) / 256 * 256);
+    switch (T) {
+        case 1: launch_stats<1>(st, d2, n_dev_or_null, n, th, rows); break;
+        case 2: launch_stats<2>(st, d2, n_dev_or_null, n, th, rows); break;
+        case 3: launch_stats<3>(st, d2, n_dev_or_null, n, th, rows); break;
+        case 4: launch_stats<4>(st, d2, n_dev_or_null, n, th, rows); break;
+        case 5: launch_stats<5>(st, d2, n_dev_or_null, n, th, rows); break;
+        case 6: launch_stats<6>(st, d2, n_dev_or_null, n, th, rows); break;
+        case 7: launch_stats<7>(st, d2, n_dev_or_null, n, th, rows); break;
+        default: launch_stats<8>(st, d2, n_dev_or_null, n, th, rows); break;
+    }
+    const int rc = nbp_launch_status();
+    if (rc) return rc;
+    stats_final_kernel<<<1, 64, 0, st>>>(rows, T, sums2, counts);
+    return nbp_launch_status();
+}

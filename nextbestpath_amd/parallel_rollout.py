@@ -3,7 +3,8 @@
 Each (scene, start pose) rollout is independent (next_best_path/testers/nbp_planning.py:414-467
 runs them in nested loops on one GPU), so rank r takes runs r, r+W, r+2W, ... and the only
 collective is ONE all_gather of a padded fp32 tensor [runs_per_rank, n_poses + 3] holding
-(run id, final coverage, AUC, coverage curve) -- a few KB over RCCL/xGMI, latency bound.  One
+(run id, final coverage, AUC, coverage curve) -- a few KB over RCCL/xGMI, latency bound (with the
+planning option `recon_metrics` on, a second one of float64 sums and counts: gather_reconstruction).  One
 process per GPU; backend "nccl" (= RCCL on ROCm) with CUDA tensors, "gloo" on CPU-only hosts
 (that path is what the world_size-2 CPU tests exercise)."""
 from __future__ import annotations
@@ -101,3 +102,28 @@ def gather_results(results, runs, rank, world, device, n_poses):
         out.append(rec)
     out.sort(key=lambda r: r["run_id"])
     return out
+
+
+def gather_reconstruction(results, runs, rank, world, device, thresholds, cap):
+    """The planning option `recon_metrics`: all ranks call this behind gather_results.  The raw float64 sums and counts of every
+    run's reconstruction metrics (results[i]["reconstruction_raw"], utility/recon_metrics.py::pack_raw) travel in ONE all_gather
+    of a padded float64 tensor [runs_per_rank, 1 + 6 + 2 T] (run id first; pad rows = -1) -- a gather of its own, so that the
+    coverage gather keeps its shape with the option off.  Rank 0 forms the ratios from them -> {run id: metrics dict}; the other
+    ranks get {}."""
+    from .utility import recon_metrics
+    rows = runs_per_rank(len(runs), world)
+    width = 1 + recon_metrics.RAW_HEAD + 2 * len(thresholds)
+    t = np.full((rows, width), -1.0, np.float64)
+    for j, r in enumerate(results):
+        t[j, 0] = r["run_id"]
+        t[j, 1:] = np.asarray(r["reconstruction_raw"], np.float64)
+    collective = world > 1 or group_is_up()
+    if collective:
+        import torch.distributed as dist
+        local = torch.from_numpy(t).to(collective_device(device))
+        buf = [torch.empty_like(local) for _ in range(world)]
+        dist.all_gather(buf, local)
+        t = torch.stack(buf).cpu().numpy().reshape(-1, width)
+    if rank != 0:
+        return {}
+    return {int(row[0]): recon_metrics.summarise_raw(row[1:], thresholds, cap) for row in t if row[0] >= 0}

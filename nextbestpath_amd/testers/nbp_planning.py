@@ -28,6 +28,7 @@ from ..networks.nbp_model import NBP
 from ..simulator import scene as sim_scene
 from ..simulator.camera import Camera
 from ..utility import hipops
+from ..utility import recon_metrics as recon_options
 from ..utility import utils as hu
 from ..utility.long_term_utils import LatticePlanner, compute_auc
 
@@ -132,7 +133,7 @@ class Rollout:
     """One exploration rollout, steppable (bench.py times K consecutive ``step()`` calls)."""
 
     def __init__(self, params, nbp, camera, gt_scene_pc, mesh, mesh_for_check, y_bins, device, state=None, seed=0,
-                 grid=256, symmetry_ensemble=_UNSET):
+                 grid=256, symmetry_ensemble=_UNSET, recon_metrics=None):
         self.params, self.nbp, self.camera, self.mesh, self.mesh_for_check = params, nbp, camera, mesh, mesh_for_check
         _set_symmetry_ensemble(nbp, params, symmetry_ensemble)
         self.y_bins, self.device = y_bins, device
@@ -161,6 +162,10 @@ class Rollout:
         self.gt = gt_scene_pc.contiguous()
         self.bbox = (self.gt.min(0).values.tolist(), self.gt.max(0).values.tolist())
         self.cov_plan = hipops.CoveragePlan(self.gt, 1.0, 2, self.bbox)          # GT sorted once per rollout
+        # the planning option `recon_metrics` (None = off: nothing is built or launched; True; a dict thresholds / cap / cell)
+        self.recon_spec = recon_options.option_spec(recon_metrics)
+        self.recon = hipops.ReconMetrics(self.gt, self.bbox, **self.recon_spec) if self.recon_spec is not None else None
+        self._recon_default = None
         self.path, self.path_record = [], 0
         self.collision_list, self.passable_list, self.idx_history = [], [], []
         self.step_seed = seed * 1_000_003
@@ -373,6 +378,19 @@ class Rollout:
         Idempotent; coverage_evolution() -- what every driver ends a rollout with -- calls it, and a Rollout that takes over a used
         state waits in its constructor, so a loop over step() that never calls finish() is safe as well."""
         self._wait_forwards()
+
+    def reconstruction_metrics(self, raw=False):
+        """Reconstruction quality of the WHOLE cloud so far (no sub-sampling) against the GT surface: the dict of
+        utility/recon_metrics.py::summarise (accuracy, completeness, Chamfer distance, precision / recall / F-score per threshold),
+        or with raw=True its raw float64 sums and counts (recon_metrics.pack_raw: what travels between ranks).  Evaluated on the
+        device (hipops.ReconMetrics: both nearest-neighbour directions and their summaries, no host synchronisation), read back
+        with one copy.  With the rollout's own `recon_metrics` option, or the defaults where it was built without one."""
+        self.finish()
+        rec = self.recon or self._recon_default
+        if rec is None:             # (kept apart from self.recon: a rollout built with the option off keeps reporting as such)
+            rec = self._recon_default = hipops.ReconMetrics(self.gt, self.bbox, **recon_options.option_spec(True))
+        rec.evaluate(self.st.cloud, self.st.cloud_count)
+        return rec.raw() if raw else rec.summary()
 
     def coverage_evolution(self, n):
         self.finish()
@@ -754,6 +772,7 @@ def compute_nbp_trajectory(params, nbp, camera, gt_scene_pc, mesh, mesh_for_chec
 # the `symmetry_ensemble` key of the configs/test/ file load_params read last (a file with the NBP options: `nbp_weights`); the entry
 # script passes test_nbp_planning the options it knows by keyword, and this one reaches it here
 _test_config_ensemble = [_UNSET]
+_test_config_recon = [_UNSET]            # ... and its `recon_metrics` key, the same way
 
 
 def load_params(path):
@@ -777,6 +796,7 @@ def load_params(path):
         setattr(p, k, v)
     if hasattr(p, "nbp_weights"):
         _test_config_ensemble[0] = getattr(p, "symmetry_ensemble", _UNSET)
+        _test_config_recon[0] = getattr(p, "recon_metrics", _UNSET)
     return p
 
 
@@ -791,7 +811,7 @@ def list_runs(dataset, params):
     return runs
 
 
-def build_rollout(params, nbp, dataset, run, device, test_resolution=0.05, state=None, seed=0, grid=256):
+def build_rollout(params, nbp, dataset, run, device, test_resolution=0.05, state=None, seed=0, grid=256, recon_metrics=None):
     """Scene + GT surface + camera + Rollout for one (scene, start pose) run (nbp_planning.py:414-492)."""
     si, k = run
     sd = dataset[si]
@@ -801,19 +821,24 @@ def build_rollout(params, nbp, dataset, run, device, test_resolution=0.05, state
     y_bins = sim_scene.y_bins_for(mesh.verts_host, 4)
     _, gt_dev = sim_scene.setup_gt_scene(params, settings, mesh, device, test_resolution, seed=seed)
     camera = setup_test_camera(params, mesh, settings.camera.start_positions[k], settings, device, seed=seed)
-    ro = Rollout(params, nbp, camera, gt_dev, mesh, mesh, y_bins, device, state, seed, grid)
+    ro = Rollout(params, nbp, camera, gt_dev, mesh, mesh, y_bins, device, state, seed, grid, recon_metrics=recon_metrics)
     ro.scene_name, ro.start = sd["scene_name"], k
     return ro
 
 
 def _result(ro, n_poses):
-    return {"scene": ro.scene_name, "start": ro.start, "coverage": ro.coverage_evolution(n_poses),
-            "X_cam_history": ro.camera.X_cam_history.tolist(), "V_cam_history": ro.camera.V_cam_history.tolist(),
-            "n_points": int(ro.st.cloud_count.item())}
+    res = {"scene": ro.scene_name, "start": ro.start, "coverage": ro.coverage_evolution(n_poses),
+           "X_cam_history": ro.camera.X_cam_history.tolist(), "V_cam_history": ro.camera.V_cam_history.tolist(),
+           "n_points": int(ro.st.cloud_count.item())}
+    if ro.recon is not None:        # the option `recon_metrics`: the whole cloud once, at the rollout's end
+        raw = ro.reconstruction_metrics(raw=True)
+        res["reconstruction"] = recon_options.summarise_raw(raw, ro.recon.thresholds, ro.recon.cap)
+        res["reconstruction_raw"] = raw.tolist()       # the sums and counts behind the ratios (parallel_rollout.gather_reconstruction)
+    return res
 
 
-def run_one(params, nbp, dataset, run, device, test_resolution=0.05, state=None, n_poses=N_POSES, seed=0):
-    ro = build_rollout(params, nbp, dataset, run, device, test_resolution, state, seed)
+def run_one(params, nbp, dataset, run, device, test_resolution=0.05, state=None, n_poses=N_POSES, seed=0, *, recon_metrics=None):
+    ro = build_rollout(params, nbp, dataset, run, device, test_resolution, state, seed, recon_metrics=recon_metrics)
     nbp.eval()
     for _ in range(n_poses):
         ro.step()
@@ -822,7 +847,7 @@ def run_one(params, nbp, dataset, run, device, test_resolution=0.05, state=None,
 
 
 def run_many(params, nbp, dataset, runs, device, seeds, test_resolution=0.05, n_poses=N_POSES, rollouts_per_gpu=48,
-             grid=256, timing=None):
+             grid=256, timing=None, *, recon_metrics=None):
     """Runs `runs` in lock-step groups of `rollouts_per_gpu` (MultiRollout); same results as run_one each.  `timing` (a dict)
     receives the wall-clock seconds of scene / GT-surface / camera setup and of the stepping (device-synchronised)."""
     import time
@@ -831,7 +856,7 @@ def run_many(params, nbp, dataset, runs, device, seeds, test_resolution=0.05, n_
     for g0 in range(0, len(runs), rollouts_per_gpu):
         t0 = time.perf_counter()
         chunk = list(zip(runs[g0:g0 + rollouts_per_gpu], seeds[g0:g0 + rollouts_per_gpu]))
-        ros = [build_rollout(params, nbp, dataset, run, device, test_resolution, None, seed, grid)
+        ros = [build_rollout(params, nbp, dataset, run, device, test_resolution, None, seed, grid, recon_metrics=recon_metrics)
                for run, seed in chunk]
         multi = MultiRollout(ros, nbp, device)
         if timing is not None:
@@ -853,15 +878,17 @@ def run_many(params, nbp, dataset, runs, device, seeds, test_resolution=0.05, n_
 def test_nbp_planning(params_file, model_file, results_json_file, numGPU, test_scenes, test_resolution=0.05,
                       use_perfect_depth_map=False, compute_collision=False, load_json=False, dataset_path=None,
                       nbp_weights=None, configs_dir=None, results_dir=None, n_poses=N_POSES, seed=8, torch_seed=9,
-                      rollouts_per_gpu=48, grid_size=256, nbp_precision=None, symmetry_ensemble=_UNSET):
+                      rollouts_per_gpu=48, grid_size=256, nbp_precision=None, symmetry_ensemble=_UNSET, recon_metrics=_UNSET):
     """Same arguments as the reference (nbp_planning.py:364-374); `grid_size` / `nbp_precision` select
     BASELINE.json configs[4] (512 grid at the same 0.3125 units per pixel, bf16 convolutions).  `symmetry_ensemble` (None = off, a
     name of utility/augment.py::ENSEMBLES or a list of op codes) is NBP.symmetry_ensemble of the loaded network; not given, it is
-    the key of that name in the configs/test/ file load_params read last (absent there: off).  Under torchrun the flattened
+    the key of that name in the configs/test/ file load_params read last (absent there: off).  `recon_metrics` (None = off, True =
+    the defaults, or a dict with thresholds / cap / cell; not given, the key of that name in the same file) adds the reconstruction
+    quality of every rollout's final cloud (utility/recon_metrics.py) to its record, next to coverage and auc.  Under torchrun the flattened
     (scene, start pose) runs are sharded round-robin over the ranks and the coverage curves are
     gathered with ONE all_gather over RCCL (backend "nccl" on ROCm; "gloo" on CPU-only hosts)."""
     import time
-    from ..parallel_rollout import gather_results, init_distributed, shard
+    from ..parallel_rollout import gather_reconstruction, gather_results, init_distributed, shard
     t_start = time.perf_counter()
     here = os.path.dirname(os.path.abspath(__file__))
     configs_dir = configs_dir or os.path.join(here, "../../configs/macarons")
@@ -887,22 +914,33 @@ def test_nbp_planning(params_file, model_file, results_json_file, numGPU, test_s
     if symmetry_ensemble is _UNSET:
         symmetry_ensemble = None if _test_config_ensemble[0] is _UNSET else _test_config_ensemble[0]
     nbp.symmetry_ensemble = params.symmetry_ensemble = symmetry_ensemble      # (ValueError on anything but None, a name, op codes)
+    if recon_metrics is _UNSET:
+        recon_metrics = None if _test_config_recon[0] is _UNSET else _test_config_recon[0]
+    recon_spec = recon_options.option_spec(recon_metrics)                     # (ValueError on anything but None, True, a dict)
     dataset = sim_scene.SceneDataset(dataset_path, test_scenes)
     runs = list_runs(dataset, params)
     mine = shard(runs, rank, world)
     timing = {"load_s": time.perf_counter() - t_start}          # parameters, weights (packed on first use), dataset listing
     with torch.no_grad():
         results = run_many(params, nbp, dataset, mine, device, [seed + 1000 * r[0] + r[1] for r in mine],
-                           test_resolution, n_poses, rollouts_per_gpu, grid_size, timing=timing)
+                           test_resolution, n_poses, rollouts_per_gpu, grid_size, timing=timing, recon_metrics=recon_spec)
     for run, res in zip(mine, results):
         res["run_id"] = runs.index(run)
     t_gather = time.perf_counter()
     gathered = gather_results(results, runs, rank, world, device, n_poses)
+    if recon_spec is not None:      # a second, float64 gather of the raw sums and counts; the ratios are formed on rank 0
+        recon = gather_reconstruction(results, runs, rank, world, device, recon_spec["thresholds"], recon_spec["cap"])
+        for r in gathered:
+            r.pop("reconstruction_raw", None)
+            if rank == 0:
+                r["reconstruction"] = recon[r["run_id"]]
     if rank == 0:
         out = {}
         for r in gathered:
             si, k = runs[r["run_id"]]
             rec = {"coverage": r["coverage"], "auc": r["auc"]}
+            if recon_spec is not None:
+                rec["reconstruction"] = r["reconstruction"]
             for key in ("X_cam_history", "V_cam_history"):      # histories of other ranks stay in their part files
                 if key in r:
                     rec[key] = r[key]

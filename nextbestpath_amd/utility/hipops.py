@@ -902,3 +902,168 @@ def objective_backward(out1, coords_bcxy, gains, out2, gt, weights, coef):
                                           _lib.ptr(ws), ws.numel(), _st())
     _lib.check(rc, "nbp_objective_backward_f32")
     return d_out1, d_out2
+
+
+# ---- reconstruction-quality metrics (csrc/nbp_recon.hip; the definition of record is utility/recon_metrics.py)
+def _nn_points(name, t, what):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError(f"{name}: the HIP path needs a cuda tensor for {what} (no CPU fallback)")
+    if t.dim() != 2 or t.shape[1] != 3 or t.dtype != torch.float32 or not t.is_contiguous():
+        raise ValueError(f"{name}: {what} must be a contiguous fp32 [n,3] tensor")
+
+
+def _nn_count(name, n_dev, device):
+    if n_dev is not None and (not isinstance(n_dev, torch.Tensor) or n_dev.device != device or n_dev.dtype != torch.int64
+                              or n_dev.numel() != 1):
+        raise ValueError(f"{name}: a device counter is one int64 element on the points' device")
+
+
+def _nn_box(box):
+    lo, hi = box
+    return (C.c_float * 3)(*[float(v) for v in lo]), (C.c_float * 3)(*[float(v) for v in hi])
+
+
+def _nn_out(name, out, n, device):
+    if out is None:
+        return torch.empty(n, dtype=torch.float32, device=device)
+    if out.dtype != torch.float32 or out.device != device or out.dim() != 1 or out.shape[0] < n or not out.is_contiguous():
+        raise ValueError(f"{name}: out must be a contiguous fp32 tensor of at least {n} elements on the points' device")
+    return out
+
+
+def nn_dist2(query, target, box, cap, cell=1.0, n_query_dev=None, n_target_dev=None, out=None):
+    """Truncated exact nearest-neighbour squared distances -> fp32 [Q] on the device: out[i] = min(cap^2, min over the targets inside
+    box = (lo, hi) of |t - q_i|^2), bit for bit recon_metrics.nn_dist2_reference.  query [Q,3], target [T,3] fp32; n_query_dev /
+    n_target_dev: int64 device counters (rows beyond them are never read, entries of out beyond n_query_dev never written).  The
+    targets are sorted into a grid of `cell`-wide cells per call (NNPlan sorts a static set once).  No host synchronisation."""
+    _nn_points("nn_dist2", query, "query")
+    _nn_points("nn_dist2", target, "target")
+    if target.device != query.device:
+        raise ValueError("nn_dist2: query and target on one device expected")
+    _nn_count("nn_dist2", n_query_dev, query.device)
+    _nn_count("nn_dist2", n_target_dev, query.device)
+    L = _lib.lib()
+    lo, hi = _nn_box(box)
+    Q, T = query.shape[0], target.shape[0]
+    out = _nn_out("nn_dist2", out, Q, query.device)
+    with torch.cuda.device(query.device):
+        nbytes = L.nbp_nn_dist2_workspace_bytes(lo, hi, float(cell), T)
+        ws = _workspace("nn_dist2", nbytes, query.device)
+        # (a zero size: the call names the reason -- its argument and shape checks come before the workspace's)
+        rc = L.nbp_nn_dist2_f32(_lib.ptr(query), Q, _lib.ptr(n_query_dev), _lib.ptr(target), T, _lib.ptr(n_target_dev), lo, hi,
+                                float(cap), float(cell), _lib.ptr(out), _lib.ptr(ws), ws.numel() if nbytes else 0, _st())
+    _lib.check(rc, "nbp_nn_dist2_f32")
+    return out
+
+
+class NNPlan:
+    """A static target set sorted once into the nearest-neighbour grid (nbp_nn_plan_build_f32); `dist2` then costs one launch."""
+
+    def __init__(self, target, box, cell=1.0, n_target_dev=None):
+        _nn_points("NNPlan", target, "target")
+        _nn_count("NNPlan", n_target_dev, target.device)
+        L = _lib.lib()
+        self.target, self.cell, self.T = target, float(cell), target.shape[0]
+        self.lo, self.hi = _nn_box(box)
+        with torch.cuda.device(target.device):
+            nplan = L.nbp_nn_plan_bytes(self.lo, self.hi, self.cell, self.T)
+            nws = L.nbp_nn_plan_workspace_bytes(self.lo, self.hi, self.cell, self.T)
+            # (a zero size: the build call names the reason)
+            self.plan = torch.empty(max(nplan, 256), dtype=torch.uint8, device=target.device)
+            ws = torch.empty(max(nws, 256), dtype=torch.uint8, device=target.device)
+            rc = L.nbp_nn_plan_build_f32(_lib.ptr(target), self.T, _lib.ptr(n_target_dev), self.lo, self.hi, self.cell,
+                                         _lib.ptr(self.plan), nplan, _lib.ptr(ws), nws, _st())
+        _lib.check(rc, "nbp_nn_plan_build_f32")
+
+    def dist2(self, query, cap, n_query_dev=None, out=None):
+        """nn_dist2(query, the plan's targets, ...) without the sort."""
+        _nn_points("NNPlan.dist2", query, "query")
+        if query.device != self.plan.device:
+            raise ValueError("NNPlan.dist2: query on the plan's device expected")
+        _nn_count("NNPlan.dist2", n_query_dev, query.device)
+        Q = query.shape[0]
+        out = _nn_out("NNPlan.dist2", out, Q, query.device)
+        with torch.cuda.device(query.device):
+            rc = _lib.lib().nbp_nn_dist2_planned_f32(_lib.ptr(self.plan), self.lo, self.hi, self.cell, float(cap), _lib.ptr(query), Q,
+                                                     _lib.ptr(n_query_dev), _lib.ptr(out), _st())
+        _lib.check(rc, "nbp_nn_dist2_planned_f32")
+        return out
+
+
+def recon_stats(d2, thresholds, n_dev=None):
+    """Summary of squared distances d2 fp32 [n] (n_dev: int64 device counter; the tail beyond it is ignored) -> (sums float64 [2] =
+    (sum sqrt(d2), sum d2), counts int64 [T] = #{sqrt(d2) < threshold}) on the device; 1 to 8 thresholds.  Two launches, no
+    floating-point atomics (two calls give the same bits), no host synchronisation."""
+    from . import recon_metrics
+    if not isinstance(d2, torch.Tensor) or not d2.is_cuda:
+        raise RuntimeError("recon_stats: the HIP path needs a cuda tensor for d2 (no CPU fallback)")
+    if d2.dim() != 1 or d2.dtype != torch.float32 or not d2.is_contiguous():
+        raise ValueError("recon_stats: d2 must be a contiguous fp32 [n] tensor")
+    ts = [float(t) for t in thresholds]
+    if not 1 <= len(ts) <= recon_metrics.MAX_THRESHOLDS:
+        raise ValueError(f"recon_stats: 1 to {recon_metrics.MAX_THRESHOLDS} thresholds expected, got {len(ts)}")
+    _nn_count("recon_stats", n_dev, d2.device)
+    L = _lib.lib()
+    sums = torch.empty(2, dtype=torch.float64, device=d2.device)
+    counts = torch.empty(len(ts), dtype=torch.int64, device=d2.device)
+    th = (C.c_float * len(ts))(*ts)
+    with torch.cuda.device(d2.device):
+        ws = _workspace_for("recon_stats", 0, L.nbp_recon_stats_workspace_bytes, d2.device)
+        rc = L.nbp_recon_stats_f64(_lib.ptr(d2), d2.shape[0], _lib.ptr(n_dev), len(ts), th, _lib.ptr(sums), _lib.ptr(counts),
+                                   _lib.ptr(ws), ws.numel(), _st())
+    _lib.check(rc, "nbp_recon_stats_f64")
+    return sums, counts
+
+
+class ReconMetrics:
+    """Accuracy, completeness, Chamfer distance and precision / recall / F-score of a cloud against a GT surface, on the device.
+    The GT [G,3] is sorted once (its plan serves cloud -> GT); GT -> cloud sorts the cloud per evaluation.  bbox = (lo, hi) of the
+    GT on the host; both directions work inside it grown by `cap` (recon_metrics.grown_box)."""
+
+    def __init__(self, gt, bbox, thresholds=(1.0,), cap=5.0, cell=1.0):
+        from . import recon_metrics
+        self.thresholds, self.cap, self.cell = recon_metrics.check_options(thresholds, cap, cell)
+        _nn_points("ReconMetrics", gt, "gt")
+        if gt.shape[0] < 1:
+            raise ValueError("ReconMetrics: an empty GT surface")
+        self.gt, self.G = gt, gt.shape[0]
+        lo, hi = recon_metrics.grown_box(bbox[0], bbox[1], self.cap)
+        self.box = (lo.tolist(), hi.tolist())
+        self.plan = NNPlan(gt, self.box, self.cell)
+        self.result = None
+
+    def evaluate(self, cloud, n_dev=None):
+        """Enqueues both directions and their summaries on the current stream -> dict of device tensors (acc_sums / comp_sums float64
+        [2], acc_counts / comp_counts int64 [T], n_points int64 [1]); no host synchronisation.  Kept for summary() / raw()."""
+        _nn_points("ReconMetrics.evaluate", cloud, "cloud")
+        dev, N = cloud.device, cloud.shape[0]
+        # the distances are scratch of the stream (consumed by the summaries enqueued right behind them)
+        d2c = _workspace("recon_d2_cloud", 4 * max(N, 1), dev)[:4 * N].view(torch.float32)
+        d2g = _workspace("recon_d2_gt", 4 * self.G, dev)[:4 * self.G].view(torch.float32)
+        self.plan.dist2(cloud, self.cap, n_query_dev=n_dev, out=d2c)
+        acc_sums, acc_counts = recon_stats(d2c, self.thresholds, n_dev)
+        nn_dist2(self.gt, cloud, self.box, self.cap, self.cell, n_target_dev=n_dev, out=d2g)
+        comp_sums, comp_counts = recon_stats(d2g, self.thresholds)
+        if n_dev is None:
+            n_points = torch.full((1,), N, dtype=torch.int64, device=dev)
+        else:
+            n_points = n_dev.reshape(1).clamp(0, N)          # (a copy: the counter may move on)
+        self.result = {"acc_sums": acc_sums, "acc_counts": acc_counts, "comp_sums": comp_sums, "comp_counts": comp_counts,
+                       "n_points": n_points}
+        return self.result
+
+    def raw(self):
+        """The last evaluation's raw numbers on the host (ONE device -> host copy): recon_metrics.pack_raw's float64 vector."""
+        from . import recon_metrics
+        if self.result is None:
+            raise RuntimeError("ReconMetrics: evaluate() first")
+        r = self.result
+        T = len(self.thresholds)
+        flat = torch.cat([r["acc_sums"], r["comp_sums"], r["n_points"].double(), r["acc_counts"].double(),
+                          r["comp_counts"].double()]).cpu().numpy()
+        return recon_metrics.pack_raw(flat[0:2], flat[5:5 + T], flat[4], flat[2:4], flat[5 + T:5 + 2 * T], self.G)
+
+    def summary(self):
+        """The last evaluation as the dict of recon_metrics.summarise (ratios formed on the host from the raw sums and counts)."""
+        from . import recon_metrics
+        return recon_metrics.summarise_raw(self.raw(), self.thresholds, self.cap)
