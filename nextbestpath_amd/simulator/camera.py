@@ -18,7 +18,6 @@ import os
 import numpy as np
 import torch
 
-from .. import _lib
 from ..utility import hipops
 
 f32 = np.float32
@@ -81,7 +80,7 @@ class Camera:
         self.gathering_factor, self.sensor_range = gathering_factor, sensor_range
         self.seed = int(seed)
         self.ambient, self.contrast_factor = float(ambient_light_intensity), float(contrast_factor)
-        self.render_rgb = render_rgb and _lib.tune("NBP_RENDER_RGB", "1") != "0"      # A/B switch
+        self.render_rgb = render_rgb
         self._rgb_ring = None
         self._zface_ring = None
         self._mesh = None
@@ -265,9 +264,12 @@ class Camera:
         assert self.deferred_colours(mesh)
         out, slot = self._reserve(len(cams_host))
         self._mesh = mesh
+        return out, self._zface_slots(slot, len(cams_host)), slot
+
+    def _zface_slots(self, slot, n):
         if self._zface_ring is None:
             self._zface_ring = torch.empty(16, self.image_height, self.image_width, dtype=torch.int64, device=self.device)
-        return out, self._zface_ring[slot:slot + len(cams_host)], slot
+        return self._zface_ring[slot:slot + n]
 
     def capture_commit(self, out, cams_host, slot):
         self._commit(out, cams_host, slot)
@@ -281,10 +283,8 @@ class Camera:
             # depth AND the nearest face per pixel: the colours of the reference's renderer (mu:2743-2763) are a pure
             # function of (face, pixel, camera, mesh), so they are evaluated where they are consumed -- for the ~5 % of
             # pixels the un-projection keeps (colour_source), or as whole images on request (frames_rgb)
-            if self._zface_ring is None:
-                self._zface_ring = torch.empty(16, self.image_height, self.image_width, dtype=torch.int64, device=self.device)
             hipops.raster_zface(mesh.verts, mesh.faces, cams_host, self.image_height, self.image_width, out_z=out,
-                                out_zface=self._zface_ring[slot:slot + n])
+                                out_zface=self._zface_slots(slot, n))
         elif self.render_rgb and getattr(mesh, "colors", None) is not None:
             # a contrast change needs every pixel's luminance: eager colour render, colours in a ring beside the depths
             if self._rgb_ring is None:
@@ -349,6 +349,25 @@ class Camera:
         if self._rgb_ring is not None:
             return {"rgb": self._ring_view(self._rgb_ring, which)}
         return {}
+
+    def ring_frames(self, which, colours):
+        """Frames `which` as ring-slot pointers, for the batched un-projection of several cameras (hipops.unproject_append_batch):
+        (depth frame pointers, cams host [F,12], shade), shade = (nearest-face frame pointers, verts, faces, vertex colours, ambient)
+        when `colours` are wanted and this camera defers them, else None.  None when the frames are not ring slots or the camera
+        renders colours eagerly (those travel as whole images: the single call)."""
+        if self._zbuf_ring is None or self._rgb_ring is not None:
+            return None
+        slots = [self.frames[w][2] for w in which]
+        hw4 = self.image_height * self.image_width * 4
+        z0 = self._zbuf_ring.data_ptr()
+        depth = [z0 + k * hw4 for k in slots]                  # (the ring's frames are [H,W] fp32, 16-byte aligned)
+        cams = np.stack([self.frames[w][1] for w in which]).astype(f32)
+        shade = None
+        if colours and self._zface_ring is not None:
+            m = self._mesh
+            f0 = self._zface_ring.data_ptr()
+            shade = ([f0 + 2 * k * hw4 for k in slots], m.verts, m.faces, m.colors, self.ambient)
+        return depth, cams, shade
 
     @property
     def renders_colours(self):

@@ -25,96 +25,18 @@ import torch
 
 from .. import _lib
 from ..networks.nbp_model import NBP
+from ..simulator import lockstep
 from ..simulator import scene as sim_scene
-from ..simulator.camera import Camera
+from ..simulator.lockstep import N_POSES, RolloutState, _concurrent_streams, _settle_gc, setup_test_camera  # noqa: F401
 from ..utility import hipops
 from ..utility import recon_metrics as recon_options
 from ..utility import utils as hu
 from ..utility.long_term_utils import LatticePlanner, compute_auc
 
-N_POSES = 101            # range(101) at nbp_planning.py:60
-_STEP_MAPS = _lib.tune("NBP_STEP_MAPS", "1") == "1"      # A/B: 0 = the step's map stage as separate reference-API calls
-# the eval forward as a replayed hipGraph (packing.ForwardGraph): 0 = never, 1 = a single rollout's B = 1 forward, 2 = also the
-# lock-step groups' batched forwards
-_FWD_GRAPH = int(_lib.tune("NBP_FWD_GRAPH", "1"))
 # Rollout.step: the step's forward on a stream of its own, behind the map stage by an event.  The reference runs the network at
 # every step and reads its output only when it replans (nbp_planning.py:166 / :252): a step that does not replan goes on to the move
 # and the next observation while its forward (every kernel of it, on the same input) is still running.  0 = everything in stream order.
 _STEP_OVERLAP = _lib.tune("NBP_STEP_OVERLAP", "1") == "1"
-# the step's maps from the tile-binned shadow copy of the cloud (utils.CloudBins; bit-identical maps): 0 = the append-order kernel
-_MAP_BINS = _lib.tune("NBP_MAP_BINS", "1") == "1"
-# single rollout: the un-projection launches file the points they append into the bins and clear the maps, so that the step's map
-# build is ONE launch (nbp_step_maps_prefiled_f32; bit-identical maps): 0 = bin_append_kernel + map_binned_kernel per build
-_MAP_PREFILED = _lib.tune("NBP_MAP_PREFILED", "1") == "1"
-_GC_FREEZE = _lib.tune("NBP_GC_FREEZE", "1") == "1"
-
-
-def _settle_gc():
-    """A rollout's setup leaves ~10^5 long-lived Python objects behind (the lattice planner's node / edge tables); CPython's
-    generational collector walks all of them in every full collection -- 70-80 ms, once or twice per 100-step rollout, i.e. as long
-    as 80 exploration steps (tools/diag/single_step_spikes.py: 1140 steps/s with the collector off, 450-500 with it on over steps
-    40-100).  After setup they are collected once and then FROZEN (gc.freeze: moved to the permanent generation, no longer walked;
-    reference counting still frees them).  NBP_GC_FREEZE=0: off."""
-    if _GC_FREEZE:
-        import gc
-        gc.collect()
-        gc.freeze()
-
-
-class RolloutState:
-    """Device-resident rollout buffers (cloud, counters, per-step coverage counts)."""
-
-    def __init__(self, device, capacity=3_400_000, grid=256):
-        self.device = device
-        self.cloud = torch.zeros(capacity, 3, dtype=torch.float32, device=device)
-        self.cloud_rgb = torch.zeros(capacity, 3, dtype=torch.float32, device=device)        # full_pc_colors (ref :39)
-        self.cloud_count = torch.zeros(1, dtype=torch.int64, device=device)
-        self.coverage_counts = torch.zeros(N_POSES, 2, dtype=torch.int32, device=device)
-        self.maps6 = torch.zeros(6, grid, grid, dtype=torch.float32, device=device)
-        self.net_in = torch.zeros(1, 5, grid, grid, dtype=torch.float32, device=device)
-        self.bins = None             # utils.CloudBins of `cloud` (made by the rollout: the tile grid needs the scene's extent)
-        self.frames_appended = 0     # frames un-projected into the cloud so far (host bound of its size: <= that many x per-frame keep)
-        self.frames_filed = 0        # ... of which the bins have seen (filed by the appending launch, or caught up by a two-launch build)
-        self._overlap = None         # forward_overlap(): two network inputs / streams / event pairs, used alternately
-
-    def forward_overlap(self):
-        """Two network-input buffers with a forward stream and an event pair each (Rollout.step alternates between them, so that
-        the forward of step t may still be reading its input while step t + 1 builds the next one)."""
-        if self._overlap is None:
-            main = torch.cuda.current_stream(self.device)
-            ins = [self.net_in, torch.zeros_like(self.net_in)]
-            # streams that really run beside `main` and beside each other (HIP maps streams onto four hardware queues; a forward
-            # stream that shares main's queue serialises the step: 1100 -> 890 steps/s, seen in about one bench run in eight)
-            streams, self.overlap_info = _concurrent_streams(self.device, len(ins), against=(main,))
-            # (a high-priority third stream for the forward of a replanning step -- the one the step waits for, ahead of the dead
-            # forwards still running beside it -- was measured: 1142 / 1157 against 1135 / 1138 steps/s, within noise; not kept)
-            for f in streams:
-                f.wait_stream(main)
-            self._overlap = {"net_in": ins, "streams": streams, "maps": [torch.cuda.Event() for _ in ins],
-                             "done": [torch.cuda.Event() for _ in ins], "used": [False for _ in ins]}
-        return self._overlap
-
-
-def setup_test_camera(params, mesh, start_cam_idx, settings, device, seed=0):
-    """macarons/testers/scene.py:410-488: build the camera, step to the first collision-free
-    neighbour of the start pose, capture, then walk to the start pose capturing 4 frames."""
-    cam = Camera(settings.camera.x_min, settings.camera.x_max, settings.camera.pose_l, settings.camera.pose_w,
-                 settings.camera.pose_h, settings.camera.pose_n_elev, settings.camera.pose_n_azim,
-                 params.n_interpolation_steps, params.zfar, params.image_height, params.image_width, device,
-                 params.gathering_factor, params.sensor_range, seed=seed,
-                 ambient_light_intensity=getattr(params, "ambient_light_intensity", 0.85),
-                 contrast_factor=getattr(settings.camera, "contrast_factor", 1.0))
-    start = tuple(int(v) for v in start_cam_idx)
-    neigh = cam.get_neighboring_poses(start)
-    segs = torch.from_numpy(np.stack([np.concatenate([cam.pose_from_idx(n)[:3], cam.pose_from_idx(start)[:3]])
-                                      for n in neigh]).astype(np.float32)).to(device)
-    hit = hipops.segments_hit_mesh(mesh.verts, mesh.faces, segs).cpu().numpy()
-    free = [n for n, h in zip(neigh, hit) if not h]
-    first = free[0] if free else neigh[0]          # the reference raises NameError when none is free
-    cam.initialize_camera(first)
-    cam.capture_image(mesh)
-    cam.move_and_capture(mesh, start)
-    return cam
 
 
 _UNSET = object()
@@ -129,7 +51,7 @@ def _set_symmetry_ensemble(nbp, params, spec=_UNSET):
         nbp.symmetry_ensemble = spec
 
 
-class Rollout:
+class Rollout(lockstep.LockstepRollout):
     """One exploration rollout, steppable (bench.py times K consecutive ``step()`` calls)."""
 
     def __init__(self, params, nbp, camera, gt_scene_pc, mesh, mesh_for_check, y_bins, device, state=None, seed=0,
@@ -147,16 +69,14 @@ class Rollout:
         self.st.coverage_counts.zero_()
         self.st.frames_appended = 0
         self.st.frames_filed = 0
-        if _MAP_BINS:
-            vh = np.asarray(mesh.verts_host, np.float32)
-            lo, hi = (float(vh[:, 0].min()), float(vh[:, 2].min())), (float(vh[:, 0].max()), float(vh[:, 2].max()))
-            b = self.st.bins
-            if b is None or (tuple(b.lo), tuple(b.hi), b.capacity) != (lo, hi, self.st.cloud.shape[0]):
-                self.st.bins = hu.CloudBins(lo, hi, self.st.cloud.shape[0], device)
-            else:
-                b.reset()                     # the cloud starts from zero points again
+        # the step's maps come from the tile-binned shadow copy of the cloud (utils.CloudBins; bit-identical maps)
+        vh = np.asarray(mesh.verts_host, np.float32)
+        lo, hi = (float(vh[:, 0].min()), float(vh[:, 2].min())), (float(vh[:, 0].max()), float(vh[:, 2].max()))
+        b = self.st.bins
+        if b is None or (tuple(b.lo), tuple(b.hi), b.capacity) != (lo, hi, self.st.cloud.shape[0]):
+            self.st.bins = hu.CloudBins(lo, hi, self.st.cloud.shape[0], device)
         else:
-            self.st.bins = None
+            b.reset()                     # the cloud starts from zero points again
         self.rng = random.Random(seed)
         self.planner = LatticePlanner(camera, mesh_for_check, device, self.V, self.S, self.grid_range, rng=self.rng)
         self.gt = gt_scene_pc.contiguous()
@@ -177,74 +97,21 @@ class Rollout:
     # rollouts and share one stream synchronisation per step; step() is the single-rollout composition.
     def pre(self, net_in=None):
         """S2-S8: coverage, un-projection of the current frame, maps, replan decision.  No host sync."""
-        st, S = self.st, self.S
+        st = self.st
         net_in = st.net_in if net_in is None else net_in
         # the bins are in step with the cloud (every frame so far was filed): this step's un-projection files its points too and
-        # clears the maps, and the build below is the page launch alone
-        prefiled = _MAP_PREFILED and _STEP_MAPS and st.bins is not None and st.frames_filed == st.frames_appended
-        self.pre_coverage()
-        self.pre_unproject(clear=(st.maps6, net_in[0, 4]) if prefiled else None)
+        # clears the maps, and the build below is the page launch alone (nbp_step_maps_prefiled_f32; bit-identical maps)
+        prefiled = st.frames_filed == st.frames_appended
+        self.count_coverage()
+        self.unproject(lockstep.CURRENT, True, clear=(st.maps6, net_in[0, 4]) if prefiled else None)
         prefiled = prefiled and st.frames_filed == st.frames_appended
-        # S5-S7 in one call: six maps, trajectory channel, network input (was seven launches: accumulate_step_maps,
-        # transform_points_to_n_pieces, map_points_to_n_imgs and two copies)
-        if _STEP_MAPS:
-            full_pc, n_upper, n_dev, pose, y_bins, traj_dev, n_old, fresh, bins = self.maps_item()
-            hu.step_maps(full_pc, pose, y_bins, S, self.grid_range, traj_dev, n_old, fresh, st.maps6, net_in[0], n_dev=n_dev,
-                         bins=bins, n_upper=n_upper, prefiled=prefiled)
-            if bins is not None:
-                st.frames_filed = st.frames_appended   # (a two-launch build files whatever the store had not seen)
-            self.traj_img = net_in[0, 4]               # stays valid until this rollout's next pre()
-        else:
-            hu.accumulate_step_maps(st.cloud, self.pose, self.y_bins, S, self.grid_range, n_dev=st.cloud_count, out=st.maps6)
-            traj2d = hu.transform_points_to_n_pieces(self.camera.trajectory_points(), self.pose)
-            self.traj_img = hu.map_points_to_n_imgs(traj2d, (S, S), self.grid_range)
-            net_in[0, :4] = st.maps6[:4]
-            net_in[0, 4] = self.traj_img[0]
+        # S5-S7 in one call: six maps, trajectory channel, network input
+        full_pc, n_upper, n_dev, pose, y_bins, traj_dev, n_old, fresh, bins = self.maps_item()
+        hu.step_maps(full_pc, pose, y_bins, self.S, self.grid_range, traj_dev, n_old, fresh, st.maps6, net_in[0], n_dev=n_dev,
+                     bins=bins, n_upper=n_upper, prefiled=prefiled)
+        st.frames_filed = st.frames_appended       # (a two-launch build files whatever the store had not seen)
+        self.traj_img = net_in[0, 4]               # stays valid until this rollout's next pre()
         self.pre_decide()
-
-    def coverage_item(self):
-        st, pose_i = self.st, self.pose_i
-        return (self.cov_plan, st.cloud, st.coverage_counts[pose_i % N_POSES], st.cloud_count, st.cloud.shape[0],
-                self.step_seed + 7 * pose_i, pose_i < N_POSES)
-
-    def pre_observe(self):
-        """S2-S4: coverage of the cloud so far, un-projection of the current frame into it."""
-        self.pre_coverage()
-        self.pre_unproject()
-
-    def pre_coverage(self):
-        st, pose_i = self.st, self.pose_i
-        self.cov_plan.count(st.cloud, st.coverage_counts[pose_i % N_POSES], n_dev=st.cloud_count, n=st.cloud.shape[0],
-                            seed=self.step_seed + 7 * pose_i, out_is_zero=pose_i < N_POSES)
-
-    def _filing(self, depth):
-        """The bins, when this un-projection call may file into them (in step with the cloud, three-launch form), else None."""
-        st = self.st
-        ok = _MAP_PREFILED and st.bins is not None and st.frames_filed == st.frames_appended and hipops.unproject_files(depth, None)
-        return st.bins if ok else None
-
-    def pre_unproject(self, clear=None):
-        st, camera, params, pose_i = self.st, self.camera, self.params, self.pose_i
-        depth, cams = camera.frames_batch([-1])
-        colour = camera.colour_source([-1])
-        bins = self._filing(depth)
-        hipops.unproject_append(depth, None, cams, st.cloud, st.cloud_count, params.gathering_factor,
-                                params.sensor_range, seed=self.step_seed + 11 * pose_i,
-                                cloud_rgb=st.cloud_rgb if colour else None, bins=bins, clear=clear if bins is not None else None, **colour)
-        st.frames_appended += 1
-        if bins is not None:
-            st.frames_filed += 1
-        self.pose, _ = camera.get_pose_from_idx(camera.cam_idx)
-
-    def maps_item(self):
-        """The map stage's arguments (utils.step_maps / step_maps_batch): (cloud, host upper bound of its size, device size,
-        pose, y_bins, trajectory history, n_old, fresh positions, bins).  The bound counts the frames actually un-projected into
-        the cloud (a frame keeps at most int(H W gathering_factor) pixels); it only sizes grids -- the kernels read the device
-        count, and the binned build walks every page whatever the bound (a guessed bound must not drop points)."""
-        traj_dev, n_old, fresh = self.camera.trajectory_pending()
-        per_frame = int(self.params.image_height * self.params.image_width * self.params.gathering_factor) + 1
-        n_upper = self.st.cloud.shape[0] if self.st.bins is None else min(self.st.cloud.shape[0], self.st.frames_appended * per_frame)
-        return self.st.cloud, n_upper, self.st.cloud_count, self.pose, self.y_bins, traj_dev, n_old, fresh, self.st.bins
 
     def pre_decide(self):
         """S8: does this step replan?  Host only."""
@@ -274,18 +141,8 @@ class Rollout:
 
     def post(self):
         """S10-S14: next pose, move (4 poses, one raster launch), un-project the supervision frames."""
-        st, camera, params = self.st, self.camera, self.params
-        next_idx = self.post_choose()
-        camera.move_and_capture(self.mesh, next_idx)
-        depth, cams = camera.frames_batch([-5, -4, -3, -2])
-        colour = camera.colour_source([-5, -4, -3, -2])
-        bins = self._filing(depth)
-        hipops.unproject_append(depth, None, cams, st.cloud, st.cloud_count, params.gathering_factor,
-                                params.sensor_range, seed=self.step_seed + 11 * self.pose_i + 5,
-                                cloud_rgb=st.cloud_rgb if colour else None, bins=bins, **colour)
-        st.frames_appended += 4
-        if bins is not None:
-            st.frames_filed += 4
+        self.camera.move_and_capture(self.mesh, self.post_choose())
+        self.unproject(lockstep.SUPERVISION, True)
         self.post_finish()
 
     def post_choose(self):
@@ -307,27 +164,9 @@ class Rollout:
         self.path_record += 1
         self.pose_i += 1
 
-    def unproject_item(self, which, seed):
-        """Arguments of hipops.unproject_append_batch for frames `which` of this rollout (None: the camera renders eager colours --
-        the caller falls back to the single call)."""
-        camera, st = self.camera, self.st
-        if camera._rgb_ring is not None:
-            return None
-        slots = [camera.frames[w][2] for w in which]
-        hw4 = camera.image_height * camera.image_width * 4
-        z0 = camera._zbuf_ring.data_ptr()
-        depth = [z0 + k * hw4 for k in slots]                  # frame pointers (the ring's frames are [H,W] fp32, 16-byte aligned)
-        cams = np.stack([camera.frames[w][1] for w in which]).astype(np.float32)
-        shade = None
-        if camera._zface_ring is not None:
-            m = camera._mesh
-            f0 = camera._zface_ring.data_ptr()
-            shade = ([f0 + 2 * k * hw4 for k in slots], m.verts, m.faces, m.colors, camera.ambient)
-        return (self, depth, cams, st.cloud, st.cloud_count, seed, st.cloud_rgb if shade else None, shade)
-
     def step(self):
-        static = getattr(self.nbp, "forward_static", None) if _FWD_GRAPH >= 1 else None
-        if static is not None and _STEP_OVERLAP and _STEP_MAPS and not self.nbp.training:
+        static = getattr(self.nbp, "forward_static", None)
+        if static is not None and _STEP_OVERLAP and not self.nbp.training:
             return self._step_forward_on_its_own_stream(static)
         self.pre()
         with torch.no_grad():          # S9: one NBP forward per step (the reference also runs it without replanning, :252)
@@ -399,44 +238,6 @@ class Rollout:
         return [float(np.float32(c) / G) for c in counts[:, 0]]
 
 
-def _concurrent_streams(device, n, tries=24, cycles=300_000, against=(), priority=0):
-    """n torch streams whose kernels the runtime really runs side by side, and how that was established.
-
-    HIP maps streams onto a few hardware queues (GPU_MAX_HW_QUEUES, default 4) when they are first used, and two streams on one
-    queue run their kernels strictly one after the other -- the lock-step's two groups then stop overlapping.  Measured: after
-    ANY hipGraph capture in the process (the single-rollout path's ForwardGraph) the next two pool streams land on one queue and
-    the 48-rollout lock-step loses 6 % (profiles/r04/stream_queue_collision.txt).  So the streams are not taken on trust: a
-    candidate is kept only if a short spin kernel on it overlaps with one on every stream already chosen (and on every stream of
-    `against`: the single rollout's forward streams must run beside the stream the step itself is enqueued on)."""
-    def overlap(a, b):
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
-        torch.cuda.synchronize(device)
-        with torch.cuda.stream(a):
-            ev[0].record()
-            torch.cuda._sleep(cycles)
-            ev[1].record()
-        with torch.cuda.stream(b):
-            torch.cuda._sleep(cycles)
-            ev[2].record()
-        torch.cuda.synchronize(device)
-        return ev[0].elapsed_time(ev[2]) < 1.5 * ev[0].elapsed_time(ev[1])
-
-    if not hasattr(torch.cuda, "_sleep"):          # (a torch without the spin kernel: the streams are taken as they come)
-        return [torch.cuda.Stream(device, priority=priority) for _ in range(n)], {"streams_tested": 0, "concurrent": None}
-    chosen, tested = [], 0
-    while len(chosen) < n and tested < tries:
-        st = torch.cuda.Stream(device, priority=priority)
-        tested += 1
-        with torch.cuda.stream(st):
-            torch.cuda._sleep(1)                   # first use: the stream gets its hardware queue here
-        if all(overlap(c, st) for c in list(against) + chosen):
-            chosen.append(st)
-    ok = len(chosen) == n
-    while len(chosen) < n:                         # (never seen: fewer than n distinct queues among `tries` streams)
-        chosen.append(torch.cuda.Stream(device, priority=priority))
-    return chosen, {"streams_tested": tested, "concurrent": ok}
-
-
 class MultiRollout:
     """R independent rollouts (different scenes / start poses) on one GPU ("B_rollout
     concurrent rollouts per rank").  They are split in two groups that are software-pipelined: while the GPU
@@ -466,11 +267,10 @@ class MultiRollout:
         per = (R + n_groups - 1) // n_groups
         self.groups = [self.rollouts[i:i + per] for i in range(0, R, per)]
         self.net_in = [torch.zeros(len(g), 5, grid, grid, dtype=torch.float32, device=device) for g in self.groups]
-        # the rollouts' map stacks as slices of one tensor per group: the group's map stage is ONE batched launch
-        # (NBP_STEP_BATCH=0: one launch per rollout, the A/B switch)
-        self.batched = _lib.tune("NBP_STEP_BATCH", "1") == "1" and _STEP_MAPS
-        # which stages of the group's step go as one launch each (A/B: NBP_STEP_BATCH_STAGES=maps,coverage,...)
-        self.batch_stages = set(_lib.tune("NBP_STEP_BATCH_STAGES", "maps,coverage,unproject,raster,replan").split(","))
+        # the rollouts' map stacks as slices of one tensor per group: each latency-bound stage of the group's step is ONE batched
+        # launch.  False: the per-rollout composition (Rollout.pre / plan_enqueue / post, one event per rollout), the reference of
+        # tests/test_gpu_rollout.py::test_group_larger_than_the_batched_kernels_hold
+        self.batched = True
         self.maps6 = [torch.zeros(len(g), 6, grid, grid, dtype=torch.float32, device=device) for g in self.groups]
         self._out1_pin = [torch.empty(len(g), 8, grid // 4, grid // 4, dtype=torch.float32).pin_memory() for g in self.groups]
         self._plan_event = [None] * len(self.groups)
@@ -492,100 +292,49 @@ class MultiRollout:
             else:
                 self._res.append(None)
         self.inflight = [False] * len(self.groups)
-        # Streams.  One HIP stream per group carries the group's small kernels and its batched forward.
-        # NBP_ROLLOUT_STREAMS = k > 0 (A/B switch) adds k side streams per group for the rollouts' ~20 small kernels per step
-        # (rollout i on side stream i % k), chained to the forward by one event per side stream.  Measured on MI355X (16
-        # rollouts, split path): 1843-1883 steps/s without side streams, 1380-1394 with k = 1, 1772-1800 with k = 2,
-        # 1667-1683 with k = 4 -- every cross-stream event dependency costs more than the overlap returns (k = 1 adds
-        # nothing but the two dependencies per group and lock-step and loses 2.9 ms of 8.6), and the convolutions hold
-        # every CU's registers and LDS, so a small kernel that "overlaps" takes CUs away from them anyway.
+        # Streams.  One HIP stream per group carries the group's small kernels and its batched forward.  (Side streams for the
+        # rollouts' small kernels were measured and rejected, HISTORY.md: every cross-stream event dependency costs more than the
+        # overlap returns, and the convolutions hold every CU's registers and LDS anyway.)
         main = torch.cuda.current_stream(device)
-        multi = streams and len(self.groups) >= 2
-        k = int(_lib.tune("NBP_ROLLOUT_STREAMS", "0")) if multi else 0
         self.stream_check = None
-        if multi:
-            self.fwd_streams, self.stream_check = _concurrent_streams(device, len(self.groups))
-            self.side = [[torch.cuda.Stream(device) for _ in range(min(k, len(g)))] for g in self.groups]
-            for st in self.fwd_streams + [x for g in self.side for x in g]:
+        if streams and len(self.groups) >= 2:
+            self.streams, self.stream_check = _concurrent_streams(device, len(self.groups))
+            for st in self.streams:
                 st.wait_stream(main)          # the rollouts were built on the caller's stream
         else:
-            self.fwd_streams = [main for _ in self.groups]
-            self.side = [[] for _ in self.groups]
-        self.streams = self.fwd_streams
-        self.ev_pre = [[torch.cuda.Event() for _ in sd] for sd in self.side]
-        self.ev_plan = [[torch.cuda.Event() for _ in (sd or g)] for sd, g in zip(self.side, self.groups)]
-        self.ev_fwd = [torch.cuda.Event() for _ in self.groups]
+            self.streams = [main for _ in self.groups]
+        self.ev_plan = [[torch.cuda.Event() for _ in g] for g in self.groups]
 
     def _launch(self, gi):
-        grp, net_in, fwd, side = self.groups[gi], self.net_in[gi], self.fwd_streams[gi], self.side[gi]
-        if not side:
-            # one stream per group: a single stream guard around the whole group (a guard per rollout is ~10 us of host time)
-            with torch.cuda.stream(fwd):
-                if self.batched:
-                    self._pre_group(gi)
-                else:
-                    for i, r in enumerate(grp):
-                        r.pre(net_in[i:i + 1])
-                rows = None
-                if self.elide_dead_forward and self.batched and "replan" in self.batch_stages and self._packed is not None:
-                    out1, out2, rows = self._forward_replanning_only(gi)
-                else:
-                    with torch.no_grad():
-                        out1, out2 = self._forward(net_in)
-                if self.batched and "replan" in self.batch_stages:
-                    self._plan_group(gi, out1, out2, rows)
-                else:
-                    for i, r in enumerate(grp):
-                        r.plan_enqueue(out1[i], out2[i])
-                        self.ev_plan[gi][i].record()
-            self.inflight[gi] = True
-            return
-        k = len(side)
-        for si, st in enumerate(side):
-            with torch.cuda.stream(st):
-                for i in range(si, len(grp), k):
-                    grp[i].pre(net_in[i:i + 1])
-                self.ev_pre[gi][si].record()
-        with torch.cuda.stream(fwd):
-            for ev in self.ev_pre[gi]:
-                fwd.wait_event(ev)
-            with torch.no_grad():
-                out1, out2 = self._forward(net_in)
-            self.ev_fwd[gi].record()
-        for si, st in enumerate(side):
-            with torch.cuda.stream(st):
-                st.wait_event(self.ev_fwd[gi])     # also orders the next pre() after this forward's read of net_in
-                out1.record_stream(st); out2.record_stream(st)
-                for i in range(si, len(grp), k):
-                    grp[i].plan_enqueue(out1[i], out2[i])
-                self.ev_plan[gi][si].record()
+        grp, net_in = self.groups[gi], self.net_in[gi]
+        # a single stream guard around the whole group (a guard per rollout is ~10 us of host time)
+        with torch.cuda.stream(self.streams[gi]):
+            if self.batched:
+                self._pre_group(gi)
+            else:
+                for i, r in enumerate(grp):
+                    r.pre(net_in[i:i + 1])
+            rows = None
+            if self.elide_dead_forward and self.batched and self._packed is not None:
+                out1, out2, rows = self._forward_replanning_only(gi)
+            else:
+                with torch.no_grad():
+                    out1, out2 = self._forward(net_in)
+            if self.batched:
+                self._plan_group(gi, out1, out2, rows)
+            else:
+                for i, r in enumerate(grp):
+                    r.plan_enqueue(out1[i], out2[i])
+                    self.ev_plan[gi][i].record()
         self.inflight[gi] = True
 
     def _pre_group(self, gi):
         """Rollout.pre for every rollout of the group, each latency-bound stage as ONE batched launch (identical results)."""
         grp, net_in = self.groups[gi], self.net_in[gi]
-        p0, stages = grp[0].params, self.batch_stages
-        if "coverage" in stages:
-            hipops.coverage_count_batch([r.coverage_item() for r in grp])
-        else:
-            for r in grp:
-                r.pre_coverage()
-        items = [r.unproject_item([-1], r.step_seed + 11 * r.pose_i) for r in grp] if "unproject" in stages else [None]
-        if all(it is not None for it in items):
-            hipops.unproject_append_batch(items, p0.image_height, p0.image_width, 1, p0.gathering_factor, p0.sensor_range)
-            for r in grp:
-                r.st.frames_appended += 1
-                r.pose, _ = r.camera.get_pose_from_idx(r.camera.cam_idx)
-        else:
-            for r in grp:
-                r.pre_unproject()
-        if "maps" in stages:
-            hu.step_maps_batch([r.maps_item() for r in grp], grp[0].S, grp[0].grid_range, self.maps6[gi], net_in)
+        hipops.coverage_count_batch([r.coverage_item() for r in grp])
+        lockstep.unproject_group(grp, lockstep.CURRENT, True)
+        hu.step_maps_batch([r.maps_item() for r in grp], grp[0].S, grp[0].grid_range, self.maps6[gi], net_in)
         for i, r in enumerate(grp):
-            if "maps" not in stages:
-                full_pc, n_upper, n_dev, pose, y_bins, traj_dev, n_old, fresh, bins = r.maps_item()
-                hu.step_maps(full_pc, pose, y_bins, r.S, r.grid_range, traj_dev, n_old, fresh, r.st.maps6, net_in[i], n_dev=n_dev,
-                             bins=bins, n_upper=n_upper)
             r.traj_img = net_in[i, 4]
             r.pre_decide()
 
@@ -651,37 +400,8 @@ class MultiRollout:
     def _post_group(self, grp):
         """Rollout.post for the rollouts of a group: their moves are rendered in ONE batched rasteriser call and their
         supervision frames un-projected in one (identical results)."""
-        p0 = grp[0].params
-        H, W = p0.image_height, p0.image_width
-        stages = self.batch_stages
-        can_raster = "raster" in stages and all(r.camera.deferred_colours(r.mesh) for r in grp)
-        pend = []
-        for r in grp:
-            cams = r.camera.move_poses(r.post_choose())
-            if can_raster:
-                out, zf, slot = r.camera.capture_begin(r.mesh, cams)
-                pend.append((r, cams, out, zf, slot))
-            else:
-                r.camera.capture_images(r.mesh, cams)
-        if can_raster:
-            hipops.raster_zface_batch([(r, r.mesh.verts, r.mesh.faces, cams, out, zf) for r, cams, out, zf, _ in pend], H, W,
-                                      len(pend[0][1]))
-            for r, cams, out, _, slot in pend:
-                r.camera.capture_commit(out, cams, slot)
-        which = [-5, -4, -3, -2]
-        items = [r.unproject_item(which, r.step_seed + 11 * r.pose_i + 5) for r in grp] if "unproject" in stages else [None]
-        if all(it is not None for it in items):
-            hipops.unproject_append_batch(items, H, W, 4, p0.gathering_factor, p0.sensor_range)
-            for r in grp:
-                r.st.frames_appended += 4
-        else:
-            for r in grp:
-                st, camera = r.st, r.camera
-                depth, cams = camera.frames_batch(which)
-                colour = camera.colour_source(which)
-                hipops.unproject_append(depth, None, cams, st.cloud, st.cloud_count, p0.gathering_factor, p0.sensor_range,
-                                        seed=r.step_seed + 11 * r.pose_i + 5, cloud_rgb=st.cloud_rgb if colour else None, **colour)
-                st.frames_appended += 4
+        lockstep.render_moves(grp, [r.post_choose() for r in grp])
+        lockstep.unproject_group(grp, lockstep.SUPERVISION, True)
         for r in grp:
             r.post_finish()
 
@@ -690,40 +410,26 @@ class MultiRollout:
         versions) once per lock-step, not once per forward."""
         if self._packed is None:
             return self.nbp(net_in)
-        if _FWD_GRAPH >= 2:
-            return self.nbp.forward_static(net_in)
         from ..networks import packing
         return packing.forward_packed(self._packed, net_in)
 
     def _complete(self, gi):
-        grp, side = self.groups[gi], self.side[gi]
-        if not side:
-            if self._plan_event[gi] is not None:
-                if any(r.need_replan for r in grp):
-                    self._plan_event[gi].synchronize()     # one event for the group's batched replan results
-                self._plan_event[gi] = None
+        grp = self.groups[gi]
+        if self._plan_event[gi] is not None:
+            if any(r.need_replan for r in grp):
+                self._plan_event[gi].synchronize()     # one event for the group's batched replan results
+            self._plan_event[gi] = None
+        else:
+            for i, r in enumerate(grp):
+                if r.need_replan:
+                    self.ev_plan[gi][i].synchronize()      # the GPU keeps running whatever was queued after the event
+        with torch.cuda.stream(self.streams[gi]):
+            for r in grp:
+                r.plan_finish()
+            if self.batched:
+                self._post_group(grp)
             else:
-                for i, r in enumerate(grp):
-                    if r.need_replan:
-                        self.ev_plan[gi][i].synchronize()      # the GPU keeps running whatever was queued after the event
-            with torch.cuda.stream(self.fwd_streams[gi]):
                 for r in grp:
-                    r.plan_finish()
-                if self.batched:
-                    self._post_group(grp)
-                else:
-                    for r in grp:
-                        r.post()
-            self.inflight[gi] = False
-            return
-        k = len(side)
-        for si, st in enumerate(side):
-            mine = grp[si::k]
-            if any(r.need_replan for r in mine):
-                self.ev_plan[gi][si].synchronize()         # the GPU keeps running whatever was queued after the event
-            with torch.cuda.stream(st):
-                for r in mine:
-                    r.plan_finish()
                     r.post()
         self.inflight[gi] = False
 
@@ -748,7 +454,7 @@ class MultiRollout:
             if self.inflight[gi]:
                 self._complete(gi)
         main = torch.cuda.current_stream()
-        for st in set(self.fwd_streams) | {x for g in self.side for x in g}:
+        for st in set(self.streams):
             if st is not main:
                 main.wait_stream(st)           # later work on the caller's stream sees every rollout's results
 

@@ -26,10 +26,13 @@ import msgpack
 import numpy as np
 import torch
 
+from ..simulator import lockstep
+from ..simulator import scene as sim_scene
 from . import hipops
 from . import planner_host
 from . import replay_codec
 from . import utils as hu
+from .long_term_utils import LatticePlanner
 
 
 # ------------------------------------------------------------------ record encoding (msgpack-numpy layout)
@@ -393,7 +396,7 @@ def get_binary_obstacle_array(mesh, camera_pose, view_size=80, grid_size=256, re
 
 
 # ------------------------------------------------------------------ trajectory collection
-class CollectionRollout:
+class CollectionRollout(lockstep.LockstepRollout):
     """One training rollout of trajectory_collection (ref :470-852) on one scene."""
 
     BETA = 0.5                     # Boltzmann temperature, ref :719
@@ -401,20 +404,18 @@ class CollectionRollout:
 
     def __init__(self, params, nbp, camera, gt_scene_pc, mesh, y_bins, device, db_env, seed=0, grid=256,
                  value_size=64, grid_range=(-40, 40), replay_format="reference"):
-        from ..testers.nbp_planning import RolloutState
         self.replay_format = check_replay_format(replay_format)
-        from .long_term_utils import LatticePlanner
         self.params, self.nbp, self.camera, self.mesh, self.device, self.db = params, nbp, camera, mesh, device, db_env
         self.y_bins, self.S, self.V, self.grid_range = y_bins, grid, value_size, grid_range
-        self.st = RolloutState(device, grid=grid)
-        self.st.cloud_count.zero_(); self.st.coverage_counts.zero_()
+        self.st = lockstep.RolloutState(device, grid=grid)         # (depth only, maps without bins: st.bins stays None)
         self.rng = random.Random(seed)
         self.planner = LatticePlanner(camera, mesh, device, value_size, grid, grid_range, rng=self.rng)
         self.gt = gt_scene_pc.contiguous()
         self.bbox = (self.gt.min(0).values.tolist(), self.gt.max(0).values.tolist())
         self.cov_plan = hipops.CoveragePlan(self.gt, 1.0, 2, self.bbox)
         self.gen = torch.Generator().manual_seed(seed)
-        self.seed = seed * 1_000_003
+        self.step_seed = seed * 1_000_003
+        self.pose_i = 0
         # check_camera_in_mesh for every lattice position, once per scene (static mesh)
         cnt = hipops.axis_ray_counts(mesh.verts, mesh.faces, self.planner.pos_dev).cpu().numpy()
         self.inside = np.all(cnt % 2 == 1, axis=1)
@@ -425,23 +426,13 @@ class CollectionRollout:
         self.coverage_evolution = []
         self.coverage_at_trajectory = None
         self.n_stored = 0
-        from ..testers.nbp_planning import _settle_gc
-        _settle_gc()                   # the planner's long-lived tables leave the cyclic collector's walks (see there)
+        lockstep._settle_gc()                   # the planner's long-lived tables leave the cyclic collector's walks (see there)
 
     # -- The step in four phases -- observe, inputs, decide, move -- each a GPU half and a host half.  run() composes them for this
     # rollout alone; CollectionGroup runs the GPU halves of a lock-step group as group launches and calls the same host halves.
-    def _observe(self, pose_i):
+    def _observe(self):
         """S1-S4: coverage of the cloud so far (GPU half + the host half `_observed`)."""
-        st = self.st
-        out = st.coverage_counts[pose_i % st.coverage_counts.shape[0]]
-        self.cov_plan.count(st.cloud, out, n_dev=st.cloud_count, n=st.cloud.shape[0], seed=self.seed + 7 * pose_i)
-        return self._coverage(out[0].item())
-
-    def coverage_item(self, pose_i):
-        """The arguments of hipops.coverage_count_batch for this rollout's `_observe`."""
-        st = self.st
-        return (self.cov_plan, st.cloud, st.coverage_counts[pose_i % st.coverage_counts.shape[0]], st.cloud_count, st.cloud.shape[0],
-                self.seed + 7 * pose_i, False)
+        return self._coverage(self.count_coverage()[0].item())
 
     def _coverage(self, count):
         return float(np.float32(count) / np.float32(len(self.gt)))
@@ -453,31 +444,17 @@ class CollectionRollout:
             self.coverage_at_trajectory = cov
         return cov > 0.95
 
-    def _inputs(self, pose_i):
+    def _inputs(self):
         """S5-S8: current frame, maps, trajectory image, GT label -> (pose, model_input [1,5,S,S], gt_obs [1,1,S,S])."""
-        st, cam, params = self.st, self.camera, self.params
-        depth, cams = cam.frames_batch([-1])
-        hipops.unproject_append(depth, None, cams, st.cloud, st.cloud_count, params.gathering_factor,
-                                params.sensor_range, seed=self.seed + 11 * pose_i)
-        pose, _ = cam.get_pose_from_idx(cam.cam_idx)
+        st, cam = self.st, self.camera
+        self.unproject(lockstep.CURRENT, False)
+        pose = cam.pose_from_idx(cam.cam_idx)
         hu.accumulate_step_maps(st.cloud, pose, self.y_bins, self.S, self.grid_range, n_dev=st.cloud_count, out=st.maps6)
         traj2d = hu.transform_points_to_n_pieces(cam.trajectory_points(), pose)
         traj_img = hu.map_points_to_n_imgs(traj2d, (self.S, self.S), self.grid_range)
         model_input = torch.cat((st.maps6[:4], traj_img), 0).unsqueeze(0).clone()
         gt_obs = get_binary_obstacle_array(self.mesh, pose, self.grid_range[1] * 2, self.S).reshape(1, 1, self.S, self.S)
         return pose, model_input, gt_obs
-
-    def unproject_item(self, which, seed):
-        """Arguments of hipops.unproject_append_batch (depth only) for frames `which`; None when the camera's frames are not
-        ring slots (the caller then un-projects this rollout alone)."""
-        cam, st = self.camera, self.st
-        if cam._zbuf_ring is None or cam._rgb_ring is not None:
-            return None
-        slots = [cam.frames[w][2] for w in which]
-        hw4 = cam.image_height * cam.image_width * 4
-        z0 = cam._zbuf_ring.data_ptr()
-        cams = np.stack([cam.frames[w][1] for w in which]).astype(np.float32)
-        return (self, [z0 + k * hw4 for k in slots], cams, st.cloud, st.cloud_count, seed, None, None)
 
     def label_item(self, pose):
         x, y, z = (float(v) for v in list(pose)[:3])
@@ -507,13 +484,10 @@ class CollectionRollout:
             next_idx[4] = self.rng.randrange(8)
         return next_idx
 
-    def _move(self, pose_i):
+    def _move(self):
         """S10-S14: move (4 poses, one raster launch), un-project the supervision frames."""
-        cam, params, st = self.camera, self.params, self.st
-        cam.move_and_capture(self.mesh, self._next_idx())
-        depth, cams = cam.frames_batch([-5, -4, -3, -2])
-        hipops.unproject_append(depth, None, cams, st.cloud, st.cloud_count, params.gathering_factor,
-                                params.sensor_range, seed=self.seed + 11 * pose_i + 5)
+        self.camera.move_and_capture(self.mesh, self._next_idx())
+        self.unproject(lockstep.SUPERVISION, False)
         self.path_record += 1
 
     def hindsight_xz(self):
@@ -601,13 +575,14 @@ class CollectionRollout:
 
     def run(self, n_poses=100, coverage_after_trajectory=None):
         for pose_i in range(n_poses):
-            done = self._observed(pose_i, self._observe(pose_i))
+            self.pose_i = pose_i
+            done = self._observed(pose_i, self._observe())
             if coverage_after_trajectory is not None and self.coverage_at_trajectory is not None:
                 coverage_after_trajectory.append(self.coverage_at_trajectory)
                 self.coverage_at_trajectory = None
             if done:
                 break
-            pose, model_input, gt_obs = self._inputs(pose_i)
+            pose, model_input, gt_obs = self._inputs()
             if self._needs_replan():
                 self._decide_begin(pose_i)
                 self.path = self._replan(pose, model_input)
@@ -615,7 +590,7 @@ class CollectionRollout:
                 model_input, gt_obs = hipops.replay_encode(torch.cat((model_input, gt_obs), 1))[0], None
             if self._decide_end(self.coverage_evolution[-1], pose, model_input, gt_obs):
                 break
-            self._move(pose_i)
+            self._move()
         return self.coverage_evolution
 
 
@@ -651,7 +626,6 @@ class CollectionGroup:
         while len(self.live) < self.K and self.queue:
             si = self.queue.pop(0)
             ro = self.make(si)
-            ro.pose_i, ro.frames_appended = 0, 0
             held = self.held[si]
             ro.put = lambda data, held=held: held.append(data)       # packed in one place per group step (_pack)
             self.live.append((si, ro))
@@ -714,10 +688,9 @@ class CollectionGroup:
         t0 = time.perf_counter()
         grp = [ro for _, ro in self.live]
         r0 = grp[0]
-        S, V, gr, p0 = r0.S, r0.V, r0.grid_range, r0.params
-        H, W = p0.image_height, p0.image_width
+        S, V, gr = r0.S, r0.V, r0.grid_range
         # -- observe: coverage in one group launch, one read-back of the counts
-        hipops.coverage_count_batch([ro.coverage_item(ro.pose_i) for ro in grp])
+        hipops.coverage_count_batch([ro.coverage_item() for ro in grp])
         counts = torch.stack([ro.st.coverage_counts[ro.pose_i % ro.st.coverage_counts.shape[0], 0] for ro in grp]).cpu().tolist()
         t0 = self._tick("gpu_step_s", t0)
         covs = {}
@@ -734,26 +707,11 @@ class CollectionGroup:
             return
         t0 = self._tick("host_search_s", t0)
         # -- inputs: the current frame, the maps + trajectory channel, the label
-        items = [ro.unproject_item([-1], ro.seed + 11 * ro.pose_i) for ro in grp]
-        if all(it is not None for it in items):
-            hipops.unproject_append_batch(items, H, W, 1, p0.gathering_factor, p0.sensor_range)
-        else:
-            for ro in grp:
-                depth, cams = ro.camera.frames_batch([-1])
-                hipops.unproject_append(depth, None, cams, ro.st.cloud, ro.st.cloud_count, p0.gathering_factor, p0.sensor_range,
-                                        seed=ro.seed + 11 * ro.pose_i)
-        per_frame = int(H * W * p0.gathering_factor) + 1
-        poses, maps = [], []
-        for ro in grp:
-            ro.frames_appended += 1
-            pose, _ = ro.camera.get_pose_from_idx(ro.camera.cam_idx)
-            poses.append(pose)
-            traj_dev, n_old, fresh = ro.camera.trajectory_pending()
-            maps.append((ro.st.cloud, min(ro.st.cloud.shape[0], ro.frames_appended * per_frame), ro.st.cloud_count, pose, ro.y_bins,
-                         traj_dev, n_old, fresh))
+        lockstep.unproject_group(grp, lockstep.CURRENT, False)
         n = len(grp)
         maps6, net_in = self._buffers(n, S)
-        hu.step_maps_batch(maps, S, gr, maps6, net_in)
+        hu.step_maps_batch([ro.maps_item() for ro in grp], S, gr, maps6, net_in)
+        poses = [ro.pose for ro in grp]
         label = hipops.slice_obstacle_fig_batch([ro.label_item(pose) for ro, pose in zip(grp, poses)], S, float(gr[1] * 2))
         rec = torch.empty(n, 6, S, S, dtype=torch.float32, device=self.device)
         rec[:, :5].copy_(net_in)
@@ -823,33 +781,12 @@ class CollectionGroup:
         grp = alive
         if not grp:
             return
-        can_raster = all(ro.camera.deferred_colours(ro.mesh) for ro in grp)
-        pend = []
-        for ro in grp:
-            cams = ro.camera.move_poses(ro._next_idx())
-            if can_raster:
-                out, zf, slot = ro.camera.capture_begin(ro.mesh, cams)
-                pend.append((ro, cams, out, zf, slot))
-            else:
-                ro.camera.capture_images(ro.mesh, cams)
+        next_idx = [ro._next_idx() for ro in grp]
         t0 = self._tick("host_search_s", t0)
-        if can_raster:
-            hipops.raster_zface_batch([(ro, ro.mesh.verts, ro.mesh.faces, cams, out, zf) for ro, cams, out, zf, _ in pend], H, W,
-                                      len(pend[0][1]))
-            for ro, cams, out, _, slot in pend:
-                ro.camera.capture_commit(out, cams, slot)
-        which = [-5, -4, -3, -2]
-        items = [ro.unproject_item(which, ro.seed + 11 * ro.pose_i + 5) for ro in grp]
-        if all(it is not None for it in items):
-            hipops.unproject_append_batch(items, H, W, 4, p0.gathering_factor, p0.sensor_range)
-        else:
-            for ro in grp:
-                depth, cams = ro.camera.frames_batch(which)
-                hipops.unproject_append(depth, None, cams, ro.st.cloud, ro.st.cloud_count, p0.gathering_factor, p0.sensor_range,
-                                        seed=ro.seed + 11 * ro.pose_i + 5)
+        lockstep.render_moves(grp, next_idx)
+        lockstep.unproject_group(grp, lockstep.SUPERVISION, False)
         alive = []
         for ro in grp:
-            ro.frames_appended += 4
             ro.path_record += 1
             ro.pose_i += 1
             if ro.pose_i < self.n_poses:
@@ -867,8 +804,6 @@ def trajectory_collection(params, current_epoch, dataset, db_env, pc2img_size, v
     the same order as with K = 1.  `timing` (a dict, K > 1) receives the seconds of the group's stages.
     replay_format: "reference" (the reference's record bytes) or "compact" (utility/replay_codec.py: the same record, its images
     encoded on the device before they leave it); None = params.replay_format, "reference" when the config does not name one."""
-    from ..simulator import scene as sim_scene
-    from ..testers.nbp_planning import setup_test_camera
     nbp.eval()
     replay_format = check_replay_format(getattr(params, "replay_format", "reference") if replay_format is None else replay_format)
 
@@ -880,7 +815,7 @@ def trajectory_collection(params, current_epoch, dataset, db_env, pc2img_size, v
         y_bins = sim_scene.y_bins_for(mesh.verts_host, 4)
         seed = 7919 * current_epoch + si
         _, gt_dev = sim_scene.setup_gt_scene(params, settings, mesh, device, 0.05, seed=seed, n_points=n_gt_points)
-        camera = setup_test_camera(params, mesh, settings.camera.start_positions[0], settings, device, seed=seed)
+        camera = lockstep.setup_test_camera(params, mesh, settings.camera.start_positions[0], settings, device, seed=seed)
         return CollectionRollout(params, nbp, camera, gt_dev, mesh, y_bins, device, db_env, seed,
                                  pc2img_size[0], value_map_size[0], prediction_range, replay_format=replay_format)
 

@@ -302,6 +302,50 @@ def test_group_larger_than_the_batched_kernels_hold(hip, dataset, nbp_weights):
         assert torch.equal(a.st.maps6, b.st.maps6)
 
 
+def test_group_with_an_eager_colour_camera_matches_single_rollouts(hip, nbp_weights, tmp_path):
+    """The per-rollout fallback inside the group stages (simulator/lockstep.py): a camera with contrast_factor != 1 renders its
+    colours eagerly, so a group that holds one cannot take the batched rasteriser / un-projection calls and goes one call per
+    rollout.  Two rollouts in ONE group, the first deferring its colours and the second eager, over step 0's replan, a move and the
+    supervision frames: each walks the trajectory, sees the coverage and builds the cloud AND its colours of the same rollout
+    stepped alone, bit for bit."""
+    from nextbestpath_amd.simulator import scene as sc
+    from nextbestpath_amd.simulator.mesh import make_maze_scene
+    from nextbestpath_amd.testers import nbp_planning as tp
+    for i in range(2):
+        make_maze_scene(str(tmp_path / f"maze_{i}"), seed=30 + i, cells=8, size=4.8, height=1.2, tess=0.3)
+    path = tmp_path / "maze_1" / "settings.json"
+    st = json.loads(path.read_text())
+    st["camera"]["contrast_factor"] = 1.4
+    path.write_text(json.dumps(st))
+    params = tp.load_params(os.path.join(ROOT, "configs/macarons/macarons_default_training_config.json"))
+    ds = sc.SceneDataset(str(tmp_path))
+    net = _net(nbp_weights)
+    dev = torch.device("cuda")
+    n = 3
+    singles = [tp.build_rollout(params, net, ds, (i, 0), dev, seed=50 + i) for i in range(2)]
+    for r in singles:
+        for _ in range(n):
+            r.step()
+    multi_r = [tp.build_rollout(params, net, ds, (i, 0), dev, seed=50 + i) for i in range(2)]
+    m = tp.MultiRollout(multi_r, net, dev, n_groups=1)
+    assert len(m.groups) == 1 and len(m.groups[0]) == 2
+    for _ in range(n):
+        m.step()
+    m.flush()
+    torch.cuda.synchronize()
+    for a, b in zip(singles, multi_r):
+        assert a.camera.cam_idx_history == b.camera.cam_idx_history
+        assert a.coverage_evolution(n) == b.coverage_evolution(n)
+        k = int(a.st.cloud_count.item())
+        assert k > 0 and k == int(b.st.cloud_count.item())
+        assert torch.equal(a.st.cloud[:k], b.st.cloud[:k])
+        assert torch.equal(a.st.cloud_rgb[:k], b.st.cloud_rgb[:k])
+        assert float(b.st.cloud_rgb[:k].abs().sum()) > 0
+    # the group really was mixed: the first camera defers its colours, the second renders them eagerly
+    assert multi_r[0].camera._zface_ring is not None and multi_r[0].camera._rgb_ring is None
+    assert multi_r[1].camera._rgb_ring is not None and multi_r[1].camera._zface_ring is None
+
+
 def test_rollout_on_512_grid(hip, dataset, nbp_weights):
     """BASELINE configs[4] geometry: 512x512 grid, +-80 window (same 0.3125 units / pixel), value map 128x128."""
     from nextbestpath_amd.simulator import scene as sc

@@ -1,5 +1,5 @@
 # steps/s of the default lock-step with one switch flipped, same box, same process settings
-# usage: bash tools/diag/step_ab.sh "NBP_MAP_BINS=0" "NBP_FWD_GRAPH=2" ...   (each argument = one variant; the default runs first and last)
+# usage: bash tools/diag/step_ab.sh "NBP_STEP_OVERLAP=0" "NBP_ROLLOUT_GROUPS=3" ...   (each argument = one variant; the default runs first and last)
 set -u
 OUT=gpurun_out/step_ab; mkdir -p $OUT
 B="python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-live-traffic --no-extra-stages --no-strong"
