@@ -1072,6 +1072,24 @@ int nbp_mdb_get(void* env, const void* key, size_t klen, void* buf, size_t cap, 
 int nbp_mdb_keys(void* env, void* buf, size_t cap, size_t* needed_out);
 int nbp_mdb_stat(void* env, unsigned long long* out8);
 
+/* ---- The seeded depth-sensor noise model (csrc/nbp_depth_noise.hip; the definition, which the kernel equals bit for bit, is
+ * nextbestpath_amd/utility/depth_noise.py).  Not in the reference.  Clean [H][W] fp32 frames (z = -1: no return) ->
+ * noisy frames: axial noise zn = max(z + (sigma_base + sigma_quad z z) g, z_min) with g a 16-byte Irwin-Hall stand-in for a
+ * Gaussian, dropout (pixel dropped iff its fifth word < drop_thr; 0 = off) and, for edge_threshold > 0, flying-pixel dropout
+ * against the clean 4-neighbours; dropped and background pixels come out at -1.  A frame's noise depends on (seed, frame id, pixel)
+ * only.  Out of place: a clean frame that overlaps an output frame is NBP_E_ARG.  One launch, no workspace, no atomics.
+ *   nbp_depth_noise_f32        n (<= 65535) consecutive frames of one camera; frame i has id first_frame + i (mod 2^32)
+ *   nbp_depth_noise_batch_f32  n (<= 48: 12 items of <= 4 frames) frames, each with its own clean / out pointer, seed and frame id
+ *                              (HOST arrays of n entries; they travel as kernel arguments)
+ * 16-byte accesses when W % 4 == 0 and every frame lies on the 16-byte grid, 4-byte accesses otherwise: any H, W >= 1.
+ * NBP_E_ARG: null pointer, n / H / W < 1, a negative or NaN parameter, z_min <= 0, overlapping frames; NBP_E_SHAPE: H W > 2^29 or
+ * more frames than the form takes.  Nothing is written on an error. */
+int nbp_depth_noise_f32(const float* clean, float* out, int n, int H, int W, unsigned seed, unsigned first_frame, float sigma_base,
+                        float sigma_quad, float z_min, unsigned drop_thr, float edge_threshold, void* stream);
+int nbp_depth_noise_batch_f32(int n, const float* const* clean, float* const* out, const unsigned* seeds, const unsigned* frames,
+                              int H, int W, float sigma_base, float sigma_quad, float z_min, unsigned drop_thr, float edge_threshold,
+                              void* stream);
+
 #ifdef __cplusplus
 }
 #endif

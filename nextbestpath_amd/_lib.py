@@ -239,6 +239,8 @@ SIGNATURES["nbp_recon_stats_f64"] = (_i, [_vp, _ll, _vp, _i, _fpp, _vp, _vp, _vp
 SIGNATURES["nbp_objective_workspace_bytes"] = (_sz, [_i, _i])
 SIGNATURES["nbp_objective_forward_f32"] = (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp])
 SIGNATURES["nbp_objective_backward_f32"] = (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp])
+SIGNATURES["nbp_depth_noise_f32"] = (_i, [_vp, _vp, _i, _i, _i, C.c_uint, C.c_uint, _f, _f, _f, C.c_uint, _f, _vp])
+SIGNATURES["nbp_depth_noise_batch_f32"] = (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _f, _f, _f, C.c_uint, _f, _vp])
 
 _lock = threading.Lock()
 _lib = None

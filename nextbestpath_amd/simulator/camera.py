@@ -18,6 +18,7 @@ import os
 import numpy as np
 import torch
 
+from ..utility import depth_noise as noise_options
 from ..utility import hipops
 
 f32 = np.float32
@@ -67,7 +68,7 @@ def camera_RT(X_cam, V_cam):
 class Camera:
     def __init__(self, x_min, x_max, pose_l, pose_w, pose_h, pose_n_elev, pose_n_azim, n_interpolation_steps,
                  zfar, image_height, image_width, device, gathering_factor=0.05, sensor_range=70.0, seed=0,
-                 ambient_light_intensity=0.85, contrast_factor=1.0, render_rgb=True):
+                 ambient_light_intensity=0.85, contrast_factor=1.0, render_rgb=True, depth_noise=None):
         self.x_min_arg = np.asarray(x_min, f32)
         self.x_min = self.x_min_arg + f32(3)             # mu:2230-2231 (kept for parity of attributes)
         self.x_max = np.asarray(x_max, f32) - f32(3)
@@ -102,6 +103,12 @@ class Camera:
         self.frames = []                                # last frames: (zbuf [H,W] device view, cam12 host row)
         self._zbuf_ring = None
         self._cursor = 0
+        # the option `depth_noise` (None = off: nothing is allocated or launched; a dict: utility/depth_noise.py::option_spec).  On:
+        # the rasteriser renders into _zclean_ring, the noise launch behind it writes the same slot of _zbuf_ring, which every
+        # consumer reads; frame ids count this camera's captures, the words' seed mixes the spec's seed with the camera's
+        self.depth_noise = noise_options.option_spec(depth_noise)
+        self._zclean_ring = None
+        self._noise_seed = None if self.depth_noise is None else noise_options.word_seed(self.depth_noise, self.seed)
         self._traj_dev = torch.zeros(512, 3, dtype=torch.float32, device=device)
         self._traj_n = 0
         self._overflow = torch.zeros(1, dtype=torch.int32, device=device)
@@ -246,6 +253,20 @@ class Camera:
         self._cursor += n
         return ring[slot:slot + n], slot
 
+    def _clean_slots(self, slot, n):
+        """Noise on: the slots of the clean ring that the rasteriser renders into (same numbering as the depth ring's)."""
+        if self._zclean_ring is None:
+            self._zclean_ring = torch.empty(16, self.image_height, self.image_width, dtype=torch.float32, device=self.device)
+        return self._zclean_ring[slot:slot + n]
+
+    def noise_item(self, slot, n):
+        """hipops.depth_noise_batch's item for the n frames rendered into clean slots slot.. and not committed yet: (clean frame
+        pointers, depth-ring frame pointers, word seed, frame ids = their numbers in this camera's capture order)."""
+        hw4 = self.image_height * self.image_width * 4
+        c0, z0 = self._zclean_ring.data_ptr(), self._zbuf_ring.data_ptr()
+        return ([c0 + k * hw4 for k in range(slot, slot + n)], [z0 + k * hw4 for k in range(slot, slot + n)], self._noise_seed,
+                [self.n_frames_captured + i for i in range(n)])
+
     def _commit(self, out, cams_host, slot):
         n = len(cams_host)
         for i in range(n):
@@ -264,6 +285,8 @@ class Camera:
         assert self.deferred_colours(mesh)
         out, slot = self._reserve(len(cams_host))
         self._mesh = mesh
+        if self.depth_noise is not None:           # the render goes to the clean slots; the caller's noise launch fills `out`
+            out = self._clean_slots(slot, len(cams_host))
         return out, self._zface_slots(slot, len(cams_host)), slot
 
     def _zface_slots(self, slot, n):
@@ -272,13 +295,16 @@ class Camera:
         return self._zface_ring[slot:slot + n]
 
     def capture_commit(self, out, cams_host, slot):
+        if self.depth_noise is not None:           # (`out` were the clean slots: the frames are the depth ring's)
+            out = self._zbuf_ring[slot:slot + len(cams_host)]
         self._commit(out, cams_host, slot)
 
     def capture_images(self, mesh, cams_host):
         """Rasterises len(cams_host) frames in one launch; cams_host [n,12] fp32 (R row-major, T)."""
         n = len(cams_host)
-        out, slot = self._reserve(n)
+        noisy, slot = self._reserve(n)
         self._mesh = mesh
+        out = noisy if self.depth_noise is None else self._clean_slots(slot, n)
         if self.deferred_colours(mesh):
             # depth AND the nearest face per pixel: the colours of the reference's renderer (mu:2743-2763) are a pure
             # function of (face, pixel, camera, mesh), so they are evaluated where they are consumed -- for the ~5 % of
@@ -294,8 +320,10 @@ class Camera:
         else:
             hipops.raster_zbuf(mesh.verts, mesh.faces, cams_host, self.image_height, self.image_width, bin_cap=mesh.bin_cap,
                                out=out, overflow=self._overflow)
-        self._commit(out, cams_host, slot)
-        return out
+        if self.depth_noise is not None:           # same stream, behind the render: clean slot -> depth-ring slot
+            hipops.depth_noise(out, noisy, self._noise_seed, self.n_frames_captured, self.depth_noise)
+        self._commit(noisy, cams_host, slot)
+        return noisy
 
     def capture_image(self, mesh):
         cam = np.concatenate([self.R_cam.reshape(-1), self.T_cam.reshape(-1)]).astype(f32)
@@ -313,15 +341,17 @@ class Camera:
         """The 4 interpolated updates + captures of nbp_planning.py:269-274 with ONE raster launch."""
         return self.capture_images(mesh, self.move_poses(next_idx))
 
-    def frames_batch(self, which):
+    def frames_batch(self, which, clean=False):
         """Stacks frames by negative offsets (e.g. [-1] = current, [-5,-4,-3,-2] = supervision batch):
-        (depth [n,H,W] device, cams [n,12] HOST -- cameras travel as kernel arguments)."""
+        (depth [n,H,W] device, cams [n,12] HOST -- cameras travel as kernel arguments).  clean=True: the frames as rendered, before
+        the option `depth_noise` (the same frames when it is off)."""
         sel = [self.frames[w] for w in which]
         slots = [s[2] for s in sel]
+        ring = self._zclean_ring if clean and self.depth_noise is not None else self._zbuf_ring
         if all(b == a + 1 for a, b in zip(slots, slots[1:])):
-            z = self._zbuf_ring[slots[0]:slots[0] + len(slots)]          # consecutive ring slots: a view, no copy kernel
+            z = ring[slots[0]:slots[0] + len(slots)]                     # consecutive ring slots: a view, no copy kernel
         else:
-            z = torch.stack([s[0] for s in sel])
+            z = torch.stack([ring[k] for k in slots])
         return z, np.stack([s[1] for s in sel]).astype(f32)
 
     def _ring_view(self, ring, which):

@@ -106,15 +106,16 @@ def _concurrent_streams(device, n, tries=24, cycles=300_000, against=(), priorit
     return chosen, {"streams_tested": tested, "concurrent": ok}
 
 
-def setup_test_camera(params, mesh, start_cam_idx, settings, device, seed=0):
+def setup_test_camera(params, mesh, start_cam_idx, settings, device, seed=0, depth_noise=None):
     """macarons/testers/scene.py:410-488: build the camera, step to the first collision-free
-    neighbour of the start pose, capture, then walk to the start pose capturing 4 frames."""
+    neighbour of the start pose, capture, then walk to the start pose capturing 4 frames.  `depth_noise`: the camera's option of
+    that name (None = off), set before these captures: they are frames 0..4 of its noise sequence."""
     cam = Camera(settings.camera.x_min, settings.camera.x_max, settings.camera.pose_l, settings.camera.pose_w,
                  settings.camera.pose_h, settings.camera.pose_n_elev, settings.camera.pose_n_azim,
                  params.n_interpolation_steps, params.zfar, params.image_height, params.image_width, device,
                  params.gathering_factor, params.sensor_range, seed=seed,
                  ambient_light_intensity=getattr(params, "ambient_light_intensity", 0.85),
-                 contrast_factor=getattr(settings.camera, "contrast_factor", 1.0))
+                 contrast_factor=getattr(settings.camera, "contrast_factor", 1.0), depth_noise=depth_noise)
     start = tuple(int(v) for v in start_cam_idx)
     neigh = cam.get_neighboring_poses(start)
     segs = torch.from_numpy(np.stack([np.concatenate([cam.pose_from_idx(n)[:3], cam.pose_from_idx(start)[:3]])
@@ -203,7 +204,10 @@ def unproject_group(grp, frames, colours):
 
 def render_moves(grp, next_idx):
     """Every rollout of a group moves to its next lattice index (next_idx[i]): the 4 interpolated frames of all the moves are
-    rendered in ONE rasteriser call when every camera defers its colours, else one call per rollout (identical frames)."""
+    rendered in ONE rasteriser call when every camera defers its colours, else one call per rollout (identical frames).  Cameras
+    with the option `depth_noise` render into their clean slots (capture_begin hands those out); ONE noise launch per spec over all
+    their new frames follows the render (a frame's noise depends on its camera's seed, its id and the pixel only: the same frames
+    as alone)."""
     p0 = grp[0].params
     moves = [r.camera.move_poses(idx) for r, idx in zip(grp, next_idx)]
     if not all(r.camera.deferred_colours(r.mesh) for r in grp):
@@ -213,5 +217,11 @@ def render_moves(grp, next_idx):
     pend = [r.camera.capture_begin(r.mesh, cams) for r, cams in zip(grp, moves)]
     hipops.raster_zface_batch([(r, r.mesh.verts, r.mesh.faces, cams, out, zf) for r, cams, (out, zf, _) in zip(grp, moves, pend)],
                               p0.image_height, p0.image_width, len(moves[0]))
+    noisy = {}                                     # spec -> items (a group shares one spec unless a caller mixes rollouts)
+    for r, cams, (_, _, slot) in zip(grp, moves, pend):
+        if r.camera.depth_noise is not None:
+            noisy.setdefault(tuple(sorted(r.camera.depth_noise.items())), []).append(r.camera.noise_item(slot, len(cams)))
+    for spec, items in noisy.items():
+        hipops.depth_noise_batch(items, dict(spec), p0.image_height, p0.image_width)
     for r, cams, (out, _, slot) in zip(grp, moves, pend):
         r.camera.capture_commit(out, cams, slot)

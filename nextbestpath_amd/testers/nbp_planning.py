@@ -29,6 +29,7 @@ from ..simulator import lockstep
 from ..simulator import scene as sim_scene
 from ..simulator.lockstep import N_POSES, RolloutState, _concurrent_streams, _settle_gc, setup_test_camera  # noqa: F401
 from ..utility import hipops
+from ..utility import depth_noise as noise_options
 from ..utility import recon_metrics as recon_options
 from ..utility import utils as hu
 from ..utility.long_term_utils import LatticePlanner, compute_auc
@@ -479,6 +480,7 @@ def compute_nbp_trajectory(params, nbp, camera, gt_scene_pc, mesh, mesh_for_chec
 # script passes test_nbp_planning the options it knows by keyword, and this one reaches it here
 _test_config_ensemble = [_UNSET]
 _test_config_recon = [_UNSET]            # ... and its `recon_metrics` key, the same way
+_test_config_noise = [_UNSET]            # ... and its `depth_noise` key
 
 
 def load_params(path):
@@ -503,6 +505,7 @@ def load_params(path):
     if hasattr(p, "nbp_weights"):
         _test_config_ensemble[0] = getattr(p, "symmetry_ensemble", _UNSET)
         _test_config_recon[0] = getattr(p, "recon_metrics", _UNSET)
+        _test_config_noise[0] = getattr(p, "depth_noise", _UNSET)
     return p
 
 
@@ -517,8 +520,10 @@ def list_runs(dataset, params):
     return runs
 
 
-def build_rollout(params, nbp, dataset, run, device, test_resolution=0.05, state=None, seed=0, grid=256, recon_metrics=None):
-    """Scene + GT surface + camera + Rollout for one (scene, start pose) run (nbp_planning.py:414-492)."""
+def build_rollout(params, nbp, dataset, run, device, test_resolution=0.05, state=None, seed=0, grid=256, recon_metrics=None,
+                  depth_noise=None):
+    """Scene + GT surface + camera + Rollout for one (scene, start pose) run (nbp_planning.py:414-492).  `depth_noise`: the camera's
+    sensor model (utility/depth_noise.py; None = off, perfect depth)."""
     si, k = run
     sd = dataset[si]
     settings = sim_scene.Settings(sd["settings"], params.scene_scale_factor)
@@ -526,7 +531,7 @@ def build_rollout(params, nbp, dataset, run, device, test_resolution=0.05, state
                                 params.scene_scale_factor, device)
     y_bins = sim_scene.y_bins_for(mesh.verts_host, 4)
     _, gt_dev = sim_scene.setup_gt_scene(params, settings, mesh, device, test_resolution, seed=seed)
-    camera = setup_test_camera(params, mesh, settings.camera.start_positions[k], settings, device, seed=seed)
+    camera = setup_test_camera(params, mesh, settings.camera.start_positions[k], settings, device, seed=seed, depth_noise=depth_noise)
     ro = Rollout(params, nbp, camera, gt_dev, mesh, mesh, y_bins, device, state, seed, grid, recon_metrics=recon_metrics)
     ro.scene_name, ro.start = sd["scene_name"], k
     return ro
@@ -536,6 +541,8 @@ def _result(ro, n_poses):
     res = {"scene": ro.scene_name, "start": ro.start, "coverage": ro.coverage_evolution(n_poses),
            "X_cam_history": ro.camera.X_cam_history.tolist(), "V_cam_history": ro.camera.V_cam_history.tolist(),
            "n_points": int(ro.st.cloud_count.item())}
+    if ro.camera.depth_noise is not None:              # the option `depth_noise`: the normalised spec the frames were made with
+        res["depth_noise"] = dict(ro.camera.depth_noise)
     if ro.recon is not None:        # the option `recon_metrics`: the whole cloud once, at the rollout's end
         raw = ro.reconstruction_metrics(raw=True)
         res["reconstruction"] = recon_options.summarise_raw(raw, ro.recon.thresholds, ro.recon.cap)
@@ -543,8 +550,10 @@ def _result(ro, n_poses):
     return res
 
 
-def run_one(params, nbp, dataset, run, device, test_resolution=0.05, state=None, n_poses=N_POSES, seed=0, *, recon_metrics=None):
-    ro = build_rollout(params, nbp, dataset, run, device, test_resolution, state, seed, recon_metrics=recon_metrics)
+def run_one(params, nbp, dataset, run, device, test_resolution=0.05, state=None, n_poses=N_POSES, seed=0, *, recon_metrics=None,
+            depth_noise=None):
+    ro = build_rollout(params, nbp, dataset, run, device, test_resolution, state, seed, recon_metrics=recon_metrics,
+                       depth_noise=depth_noise)
     nbp.eval()
     for _ in range(n_poses):
         ro.step()
@@ -553,7 +562,7 @@ def run_one(params, nbp, dataset, run, device, test_resolution=0.05, state=None,
 
 
 def run_many(params, nbp, dataset, runs, device, seeds, test_resolution=0.05, n_poses=N_POSES, rollouts_per_gpu=48,
-             grid=256, timing=None, *, recon_metrics=None):
+             grid=256, timing=None, *, recon_metrics=None, depth_noise=None):
     """Runs `runs` in lock-step groups of `rollouts_per_gpu` (MultiRollout); same results as run_one each.  `timing` (a dict)
     receives the wall-clock seconds of scene / GT-surface / camera setup and of the stepping (device-synchronised)."""
     import time
@@ -562,7 +571,8 @@ def run_many(params, nbp, dataset, runs, device, seeds, test_resolution=0.05, n_
     for g0 in range(0, len(runs), rollouts_per_gpu):
         t0 = time.perf_counter()
         chunk = list(zip(runs[g0:g0 + rollouts_per_gpu], seeds[g0:g0 + rollouts_per_gpu]))
-        ros = [build_rollout(params, nbp, dataset, run, device, test_resolution, None, seed, grid, recon_metrics=recon_metrics)
+        ros = [build_rollout(params, nbp, dataset, run, device, test_resolution, None, seed, grid, recon_metrics=recon_metrics,
+                             depth_noise=depth_noise)
                for run, seed in chunk]
         multi = MultiRollout(ros, nbp, device)
         if timing is not None:
@@ -584,13 +594,16 @@ def run_many(params, nbp, dataset, runs, device, seeds, test_resolution=0.05, n_
 def test_nbp_planning(params_file, model_file, results_json_file, numGPU, test_scenes, test_resolution=0.05,
                       use_perfect_depth_map=False, compute_collision=False, load_json=False, dataset_path=None,
                       nbp_weights=None, configs_dir=None, results_dir=None, n_poses=N_POSES, seed=8, torch_seed=9,
-                      rollouts_per_gpu=48, grid_size=256, nbp_precision=None, symmetry_ensemble=_UNSET, recon_metrics=_UNSET):
+                      rollouts_per_gpu=48, grid_size=256, nbp_precision=None, symmetry_ensemble=_UNSET, recon_metrics=_UNSET,
+                      depth_noise=_UNSET):
     """Same arguments as the reference (nbp_planning.py:364-374); `grid_size` / `nbp_precision` select
     BASELINE.json configs[4] (512 grid at the same 0.3125 units per pixel, bf16 convolutions).  `symmetry_ensemble` (None = off, a
     name of utility/augment.py::ENSEMBLES or a list of op codes) is NBP.symmetry_ensemble of the loaded network; not given, it is
     the key of that name in the configs/test/ file load_params read last (absent there: off).  `recon_metrics` (None = off, True =
     the defaults, or a dict with thresholds / cap / cell; not given, the key of that name in the same file) adds the reconstruction
-    quality of every rollout's final cloud (utility/recon_metrics.py) to its record, next to coverage and auc.  Under torchrun the flattened
+    quality of every rollout's final cloud (utility/recon_metrics.py) to its record, next to coverage and auc.  `depth_noise` (None =
+    off: perfect depth; a dict of utility/depth_noise.py::option_spec; not given, the key of that name in the same file) puts the seeded
+    sensor model between the rasteriser and every consumer of depth, and the normalised spec into every record.  Under torchrun the flattened
     (scene, start pose) runs are sharded round-robin over the ranks and the coverage curves are
     gathered with ONE all_gather over RCCL (backend "nccl" on ROCm; "gloo" on CPU-only hosts)."""
     import time
@@ -623,13 +636,17 @@ def test_nbp_planning(params_file, model_file, results_json_file, numGPU, test_s
     if recon_metrics is _UNSET:
         recon_metrics = None if _test_config_recon[0] is _UNSET else _test_config_recon[0]
     recon_spec = recon_options.option_spec(recon_metrics)                     # (ValueError on anything but None, True, a dict)
+    if depth_noise is _UNSET:
+        depth_noise = None if _test_config_noise[0] is _UNSET else _test_config_noise[0]
+    noise_spec = noise_options.option_spec(depth_noise)                       # (ValueError on anything but None or a dict of its keys)
     dataset = sim_scene.SceneDataset(dataset_path, test_scenes)
     runs = list_runs(dataset, params)
     mine = shard(runs, rank, world)
     timing = {"load_s": time.perf_counter() - t_start}          # parameters, weights (packed on first use), dataset listing
     with torch.no_grad():
         results = run_many(params, nbp, dataset, mine, device, [seed + 1000 * r[0] + r[1] for r in mine],
-                           test_resolution, n_poses, rollouts_per_gpu, grid_size, timing=timing, recon_metrics=recon_spec)
+                           test_resolution, n_poses, rollouts_per_gpu, grid_size, timing=timing, recon_metrics=recon_spec,
+                           depth_noise=noise_spec)
     for run, res in zip(mine, results):
         res["run_id"] = runs.index(run)
     t_gather = time.perf_counter()
@@ -647,6 +664,8 @@ def test_nbp_planning(params_file, model_file, results_json_file, numGPU, test_s
             rec = {"coverage": r["coverage"], "auc": r["auc"]}
             if recon_spec is not None:
                 rec["reconstruction"] = r["reconstruction"]
+            if noise_spec is not None:
+                rec["depth_noise"] = dict(noise_spec)
             for key in ("X_cam_history", "V_cam_history"):      # histories of other ranks stay in their part files
                 if key in r:
                     rec[key] = r[key]

@@ -46,9 +46,10 @@ class RandomWalkRollout:
         self.coverage_evolution = []
         self.pose_i = 0
 
-    def _partial(self, which, seed):
-        """compute_partial_point_cloud of frames `which` into the scratch cloud -> (points view, device count)."""
-        depth, cams = self.camera.frames_batch(which)
+    def _partial(self, which, seed, clean=False):
+        """compute_partial_point_cloud of frames `which` into the scratch cloud -> (points view, device count).  clean=True: of
+        the frames before the camera's option `depth_noise` (the same frames when it is off)."""
+        depth, cams = self.camera.frames_batch(which, clean=clean)
         self.part_count.zero_()
         hipops.unproject_append(depth, None, cams, self.part, self.part_count, self.params.gathering_factor,
                                 self.params.sensor_range, seed=seed)
@@ -74,12 +75,13 @@ class RandomWalkRollout:
                                          random_sampling_max_size=p.n_gt_surface_points, min_n_points_per_cell_fill=3,
                                          progressive_fill=p.progressive_fill,
                                          max_n_points_per_fill=p.max_points_per_progressive_fill, seed=self.seed + 13 * pose_i)
-        # GT surface points of the current frame -> covered scene -> true coverage (:64-92)
-        self._partial([-1], self.seed + 11 * pose_i)
+        # GT surface points of the current frame -> covered scene -> true coverage (:64-92): what the camera really saw, so the
+        # clean frame whatever the sensor model; everything below reads the sensor's (noisy) depth
+        self._partial([-1], self.seed + 11 * pose_i, clean=True)
         self.covered_scene.fill_cells(self.part, n_dev=self.part_count)
         cov, _ = self.gt_scene.scene_coverage(self.covered_scene, surface_epsilon=self.eps)
         self.coverage_evolution.append(cov)
-        # the same frame through the (perfect) depth path -> surface scene + full cloud (:118-136)
+        # the same frame through the depth path (perfect, or the camera's `depth_noise`) -> surface scene + full cloud (:118-136)
         depth, cams = self._partial([-1], self.seed + 11 * pose_i + 3)
         self.surface_scene.fill_cells(self.part, n_dev=self.part_count)
         self._append_full()
@@ -102,7 +104,8 @@ def compute_random_walk_trajectory(params, macarons, camera, gt_scene, surface_s
                                    test_resolution=0.05, use_perfect_depth_map=True, compute_collision=False, n_poses=200,
                                    coverage_gain_fn=None, seed=0):
     """Same leading arguments and return tuple as the reference (random_walk_planning.py:25-400); `macarons` (the depth /
-    occupancy networks) is unused: only the perfect-depth path is available."""
+    occupancy networks) is unused: the depth is the rasteriser's, perfect or through the camera's option `depth_noise` (a seeded
+    sensor model, not the reference's learned depth: use_perfect_depth_map=False keeps raising)."""
     if not use_perfect_depth_map:
         raise NotImplementedError("the MACARONS depth network is not part of this build (SURVEY.md section 2)")
     t1 = time.time()
@@ -118,13 +121,16 @@ def compute_random_walk_trajectory(params, macarons, camera, gt_scene, surface_s
 
 def test_random_walk_planning(params_file, model_file, results_json_file, numGPU, test_scenes, test_resolution=0.05,
                               use_perfect_depth_map=True, compute_collision=False, load_json=False, dataset_path=None,
-                              configs_dir=None, results_dir=None, n_poses=200, seed=8):
+                              configs_dir=None, results_dir=None, n_poses=200, seed=8, depth_noise=None):
     """Same arguments as the reference (random_walk_planning.py:402-411): every (scene, start pose) of the dataset is
     rolled out and {scene: {start: {coverage, X_cam_history, V_cam_history}}} is written as JSON.  `model_file` (the
-    MACARONS weights) is not loaded: perfect depth only."""
+    MACARONS weights) is not loaded: perfect depth, or the seeded sensor model `depth_noise` (utility/depth_noise.py; None = off), whose
+    normalised spec then joins every record."""
     import json
     import os
+    from ..utility.depth_noise import option_spec
     from .nbp_planning import load_params, setup_test_camera
+    noise_spec = option_spec(depth_noise)
     here = os.path.dirname(os.path.abspath(__file__))
     configs_dir = configs_dir or os.path.join(here, "../../configs/macarons")
     results_dir = results_dir or os.path.join(here, "../../data")
@@ -143,11 +149,13 @@ def test_random_walk_planning(params_file, model_file, results_json_file, numGPU
         for k, start in enumerate(settings.camera.start_positions):
             s = seed + 1000 * si + k
             gt_scene, covered, surface, proxy = sim_scene.setup_test_scenes(params, settings, mesh, device, test_resolution, seed=s)
-            camera = setup_test_camera(params, mesh, start, settings, device, seed=s)
+            camera = setup_test_camera(params, mesh, start, settings, device, seed=s, depth_noise=noise_spec)
             cov, X, V, *_ = compute_random_walk_trajectory(params, None, camera, gt_scene, surface, proxy, covered, mesh, device,
                                                            test_resolution, use_perfect_depth_map, compute_collision, n_poses,
                                                            seed=s)
             results[sd["scene_name"]][str(k)] = {"coverage": cov, "X_cam_history": X.tolist(), "V_cam_history": V.tolist()}
+            if noise_spec is not None:
+                results[sd["scene_name"]][str(k)]["depth_noise"] = dict(noise_spec)
     os.makedirs(results_dir, exist_ok=True)
     with open(path, "w") as fh:
         json.dump(results, fh)

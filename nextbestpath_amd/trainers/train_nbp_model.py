@@ -853,7 +853,8 @@ def run_training_nbp(params):
                                          collection_model(params, nbp, ema), cov, None, device, rank=rank, world=world,
                                          n_poses=getattr(params, "n_collect_poses", 100),
                                          n_gt_points=getattr(params, "n_gt_surface_points", 50000),
-                                         rollouts_per_gpu=getattr(params, "collect_rollouts_per_gpu", 1))
+                                         rollouts_per_gpu=getattr(params, "collect_rollouts_per_gpu", 1),
+                                         depth_noise=getattr(params, "collect_depth_noise", None))
         print(f"[rank {rank}] epoch {epoch}: collected {n} records ({env.entries()} in the store)")
         if epoch == 0:
             validation = nu.store_validation_data(env, getattr(params, "n_validation", 1200), keep_compact=True)

@@ -519,6 +519,61 @@ def raster_zface_batch(items, H, W, n_frames, tan_half_fov=TAN_HALF_FOV, z_clip=
     _lib.check(rc, "nbp_raster_zface_batch_f32")
 
 
+# ---- the depth-sensor noise model (csrc/nbp_depth_noise.hip; the definition is utility/depth_noise.py)
+def _noise_args(spec):
+    from . import depth_noise as dn
+    spec = dn.option_spec(spec)
+    if spec is None:
+        raise ValueError("depth_noise: a spec is needed (None means off: nothing to launch)")
+    return (spec["sigma_base"], spec["sigma_quad"], spec["z_min"], dn.dropout_threshold(spec["dropout"]), spec["edge_threshold"])
+
+
+def depth_noise(clean, out, seed, first_frame, spec):
+    """The noise model on clean [n,H,W] (or [H,W]) fp32 -> out (same shape, another buffer): frame i of one camera with word seed
+    `seed` and frame id first_frame + i (mod 2^32); spec: depth_noise.option_spec's dict.  One launch.  Returns out."""
+    if clean.dtype != torch.float32 or out.dtype != torch.float32 or clean.shape != out.shape or clean.dim() not in (2, 3):
+        raise ValueError("depth_noise: clean and out are fp32 [n,H,W] (or [H,W]) of one shape")
+    n = clean.shape[0] if clean.dim() == 3 else 1
+    H, W = clean.shape[-2:]
+    rc = _lib.lib().nbp_depth_noise_f32(_lib.ptr(clean), _lib.ptr(out), n, H, W, int(seed) & 0xFFFFFFFF, int(first_frame) & 0xFFFFFFFF,
+                                        *_noise_args(spec), _st())
+    _lib.check(rc, "nbp_depth_noise_f32")
+    return out
+
+
+def depth_noise_batch(items, spec, H=None, W=None):
+    """depth_noise for several cameras in one launch.  items = [(clean frames, out frames, word seed, frame ids)]: per item up to 4
+    frames, each an [H,W] fp32 tensor or a device pointer (then H and W are needed), which need not be adjacent in memory, and one
+    id per frame.  More than 12 items go in chunks of 12."""
+    if len(items) > 12:
+        for i in range(0, len(items), 12):
+            depth_noise_batch(items[i:i + 12], spec, H, W)
+        return
+    args = _noise_args(spec)
+    cl, ou, seeds, ids = [], [], [], []
+    for clean, out, seed, frames in items:
+        if not (1 <= len(clean) <= 4 and len(out) == len(clean) and len(frames) == len(clean)):
+            raise ValueError("depth_noise_batch: an item has 1 to 4 clean frames and as many output frames and frame ids")
+        for c, o, f in zip(clean, out, frames):
+            for t in (c, o):
+                if not isinstance(t, int):
+                    if t.dtype != torch.float32 or t.dim() != 2 or not t.is_contiguous() or (H is not None and tuple(t.shape) != (H, W)):
+                        raise ValueError("depth_noise_batch: frames are contiguous fp32 [H,W] tensors of one shape")
+                    H, W = t.shape
+            cl.append(c if isinstance(c, int) else c.data_ptr())
+            ou.append(o if isinstance(o, int) else o.data_ptr())
+            seeds.append(int(seed) & 0xFFFFFFFF)
+            ids.append(int(f) & 0xFFFFFFFF)
+    n = len(cl)
+    if n == 0:
+        return
+    if H is None or W is None:
+        raise ValueError("depth_noise_batch: frames given as pointers need H and W")
+    rc = _lib.lib().nbp_depth_noise_batch_f32(n, (C.c_void_p * n)(*cl), (C.c_void_p * n)(*ou), (C.c_uint * n)(*seeds), (C.c_uint * n)(*ids),
+                                              int(H), int(W), *args, _st())
+    _lib.check(rc, "nbp_depth_noise_batch_f32")
+
+
 def carve_update(proxy_pts, depth, mask, cam12_host, zfar, fov_range, tol, score_threshold, n_inside, n_behind, occ,
                  out_of_field, tan_half_fov=TAN_HALF_FOV):
     """A20 (macarons_utils.py:2849-2949, 3329-3363): in-place update of the per-proxy-point carving state."""
