@@ -478,6 +478,15 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     const bool final_out = (a.split_k == 1);
     float* outp = final_out ? o.out : a.partial + (long long)zslice * a.M * a.N;
     float mx = 0.f;
+    // The output stores go through a buffer resource at the tile's first element: the lane's part of the address is ONE 32-bit offset
+    // (its wave's rows, its k half's 4 pixels, its column) and (row block i, register r, column block j, parity) add a wave-uniform
+    // scalar offset, where 64-bit addresses per (i, r) held 2 x 16 TM registers.  pb = q + 4 khalf with q = (r & 3) + 8 (r >> 2)
+    // never carries into pb / TW (TW = 16, 32), so the two parts separate.
+    constexpr int PS = PHO ? 2 : 1;                            // pixel stride of a parity's outputs
+    const long long e0 = (PHO ? ((long long)b * a.H + 2 * y0 + py) * a.W + 2 * x0 : ((long long)b * a.H + y0) * a.W + x0) * a.N + n0;
+    const long long erem = (a.M * a.N - e0) * 4;
+    const __amdgpu_buffer_rsrc_t rso = __builtin_amdgcn_make_buffer_rsrc(outp + e0, 0, erem < 0x7fffffffll ? (int)erem : 0x7fffffff, 0x00020000);
+    const unsigned vout = (unsigned)(((TM * wave * RPB * PS * a.W + 4 * khalf * PS) * a.N + (lane & 31)) * 4);
     constexpr bool HEADABLE = !PH && TN == 2;              // 64 columns = all channels of the head's input in one wave
     const bool head = HEADABLE && final_out && o.head_out;
     const bool bn_stats = BS && final_out && o.bn_part;
@@ -505,16 +514,14 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
         float vals[TM][16];
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
-            const long long mrow = PHO ? ((long long)b * a.H + 2 * (y0 + (TM * wave + i) * RPB) + py) * a.W + 2 * x0 + pxe
-                                       : ((long long)b * a.H + y0 + (TM * wave + i) * RPB) * a.W + x0;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int pb = (r & 3) + 8 * (r >> 2) + 4 * khalf;
-                const int poff = PHO ? 2 * ((pb / TW) * a.W + (pb % TW)) : (pb / TW) * a.W + (pb % TW);
+                const int q = (r & 3) + 8 * (r >> 2);
+                const unsigned soff = (unsigned)((((i * RPB + q / TW) * PS * a.W + (q % TW) * PS + (PHO ? pxe : 0)) * a.N + j * 32) * 4);
                 float v = ldexpf(accs[pq][i][j][r], einv) * sc + sh;
                 if (final_out && a.relu) v = fmaxf(v, 0.f);
                 mx = fmaxf(mx, fabsf(v));
-                if (!head) outp[(mrow + poff) * a.N + n] = v;
+                if (!head) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rso, vout, soff, 0);
                 vals[i][r] = v;
                 if constexpr (HEADABLE) hp[i][r] = fmaf(v, hw, hp[i][r]);
             }
@@ -1710,6 +1717,7 @@ int launch_h2(const SplitArgs& a, hipStream_t st, int tile) {
     }
     // PH: tiles of the low-resolution image, four parities in blockIdx.z (fastest); DG: a.M counts the low-resolution output itself
     constexpr bool PHO = PH && !DG;
+    NBP_RETURN_IF((long long)(2 * TH + 2) * a.W * a.N * 4 >= (1ll << 31), NBP_E_SHAPE);      // a tile's outputs within 32-bit offsets of its first
     dim3 grid((unsigned)(a.M / (PHO ? 4 : 1) / (TH * TW)), (unsigned)(a.N / (TN * 32)), (unsigned)(a.split_k * a.groups * (PHO ? (P2 ? 2 : 4) : 1)));
     conv3x3_halo_h2_kernel<ONE, TW, TM, TN, PH, BS, P2, DG><<<grid, 256, smem, st>>>(a);
     return nbp_launch_status();
