@@ -206,6 +206,10 @@ __global__ __launch_bounds__(256) void points_scatter4_kernel(const float* __res
 // 30 us stand-alone and -2 % in the lock-step -- the launch is bound by its dependent loads (the random gather of the sampled
 // cloud points, two run bounds per column), not by the pair tests (profiles/r05/rejected_experiments.txt).
 constexpr int PLAN_R = 1;
+// a wave-uniform value copied to a vector register where it is stored, not held in one across the loops around the store
+__device__ __forceinline__ unsigned store_copy(unsigned s) { unsigned v; asm volatile("v_mov_b32 %0, %1" : "=v"(v) : "s"(s)); return v; }
+// a wave-uniform float, held in a scalar register
+__device__ __forceinline__ float uniform_f32(float v) { return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(v))); }
 template <int LANES, int UNROLL>
 __device__ __forceinline__ void coverage_mark_body(unsigned bx, unsigned by, unsigned gx, unsigned gy, const float* __restrict__ pc, const long long* __restrict__ n_dev,
                                                             long long n_host, long long k, unsigned seed, Grid g, float d2max,
@@ -221,22 +225,26 @@ __device__ __forceinline__ void coverage_mark_body(unsigned bx, unsigned by, uns
     if (bx == 0 && threadIdx.x == 0) *m_out = (int)M;
     const unsigned bits = perm_bits((unsigned)N);
     const int sub = threadIdx.x % LANES;
-    for (long long j = ((long long)bx * blockDim.x + threadIdx.x) / LANES; j < M;
-         j += ((long long)gx * blockDim.x) / LANES) {
-        const long long src = N > k ? (long long)perm_index((unsigned)j, (unsigned)N, bits, seed) : j;
+    // (perm_index already takes N as 32 bits: the sample index fits an unsigned, and the grid bounds below are wave-uniform scalars)
+    const unsigned Mu = M <= 0 ? 0u : (M > 0xffffffffll ? 0xffffffffu : (unsigned)M), jstep = gx * blockDim.x / LANES;
+    const float hi0 = uniform_f32((float)(g.n[0] - 1 + R)), hi1 = uniform_f32((float)(g.n[1] - 1 + R)), hi2 = uniform_f32((float)(g.n[2] - 1 + R));
+    for (unsigned j = (bx * blockDim.x + threadIdx.x) / LANES; j < Mu; j += jstep) {
+        const long long src = N > k ? (long long)perm_index(j, (unsigned)N, bits, seed) : (long long)j;
         const float x = pc[3 * src], y = pc[3 * src + 1], z = pc[3 * src + 2];
         // unclamped cell: a cloud point outside the grid (= the GT box grown by thr) is farther than thr from every GT point
         const float ux = (x - g.lo[0]) * g.inv, uy = (y - g.lo[1]) * g.inv, uz = (z - g.lo[2]) * g.inv;
         const float fi = floorf(ux), fj = floorf(uy), fk = floorf(uz);
-        if (!(fi >= (float)-R && fi <= (float)(g.n[0] - 1 + R) && fj >= (float)-R && fj <= (float)(g.n[1] - 1 + R) && fk >= (float)-R &&
-              fk <= (float)(g.n[2] - 1 + R)))
-            continue;
+        if (!(fi >= (float)-R && fi <= hi0 && fj >= (float)-R && fj <= hi1 && fk >= (float)-R && fk <= hi2)) continue;
         const int ci = (int)fi, cj = (int)fj, ck = (int)fk;
-        const float ox = ux - fi, oy = uy - fj, oz = uz - fk;          // position inside the cell, [0, 1]
+        const float pox = ux - fi, poy = uy - fj, poz = uz - fk;       // position inside the cell, [0, 1]
         for (int col = sub; col < D * D; col += LANES) {
             const int da = col / D - R, db = col % D - R;
             const int a = ci + da, b = cj + db;
             if (a < 0 || a >= g.n[0] || b < 0 || b >= g.n[1]) continue;
+            // (taken through an empty asm: otherwise 1 - ox, 1 - oy, oz^2 and (1 - oz)^2 are hoisted out of the column loop and held in
+            // four more registers across the point walk below)
+            float ox = pox, oy = poy, oz = poz;
+            asm volatile("" : "+v"(ox), "+v"(oy), "+v"(oz));
             const float dx = da > 0 ? (float)da - ox : (da < 0 ? ox - (float)(da + 1) : 0.f);
             const float dy = db > 0 ? (float)db - oy : (db < 0 ? oy - (float)(db + 1) : 0.f);
             const float rem = (float)(R * R) - (dx * dx + dy * dy);
@@ -253,30 +261,30 @@ __device__ __forceinline__ void coverage_mark_body(unsigned bx, unsigned by, uns
             const int base = (a * g.n[1] + b) * g.n[2];
             const int hi = gt_start[base + d1 + 1];
             int q = gt_start[base + d0];
-            // the run of a column is walked UNROLL points at a time: their stamps and positions are independent loads in
-            // flight together (one point per iteration was a chain of ~100 dependent round trips per lane)
+            // the run of a column is walked UNROLL points at a time: their stamps are independent loads in flight together (one
+            // point per iteration was a chain of ~100 dependent round trips per lane)
             for (; q + UNROLL <= hi; q += UNROLL) {
                 unsigned sp[UNROLL];
-                float4 t[UNROLL];
-                // stamps first, positions only of the points no one has stamped yet in this launch: a covered GT point is near
-                // many of the 100 k sampled cloud points and all but the first find it stamped -- a 4-byte load instead of 20 and
-                // no distance test (lock-step +1.0 %, profiles/r04/coverage_lazy_positions.txt; a stale "unstamped" read from
-                // another XCD's L2 only repeats a test)
 #pragma unroll
                 for (int u = 0; u < UNROLL; ++u) sp[u] = stamp[q + u];
-#pragma unroll
-                for (int u = 0; u < UNROLL; ++u) t[u] = sp[u] != epoch ? gt_sorted[q + u] : make_float4(3e38f, 3e38f, 3e38f, 0.f);
+                // positions only of the points no one has stamped yet in this launch: a covered GT point is near many of the
+                // 100 k sampled cloud points and all but the first find it stamped -- a 4-byte load instead of 20 and no distance
+                // test (lock-step +1.0 %, profiles/r04/coverage_lazy_positions.txt; a stale "unstamped" read from another XCD's
+                // L2 only repeats a test).  One position at a time: the conditional loads were never in flight together (each
+                // sits in its own divergent branch), and four of them held 16 registers (profiles/r08/kernel_budget.txt)
 #pragma unroll
                 for (int u = 0; u < UNROLL; ++u) {
-                    const float ex = t[u].x - x, ey = t[u].y - y, ez = t[u].z - z;
-                    if (sp[u] != epoch && (ex * ex + ey * ey) + ez * ez <= d2max) stamp[q + u] = epoch;
+                    if (sp[u] == epoch) continue;
+                    const float4 t = gt_sorted[q + u];
+                    const float ex = t.x - x, ey = t.y - y, ez = t.z - z;
+                    if ((ex * ex + ey * ey) + ez * ez <= d2max) stamp[q + u] = store_copy(epoch);
                 }
             }
             for (; q < hi; ++q) {
                 if (stamp[q] == epoch) continue;
                 const float4 t = gt_sorted[q];
                 const float ex = t.x - x, ey = t.y - y, ez = t.z - z;
-                if ((ex * ex + ey * ey) + ez * ez <= d2max) stamp[q] = epoch;          // plain store: every writer writes the
+                if ((ex * ex + ey * ey) + ez * ez <= d2max) stamp[q] = store_copy(epoch);         // plain store: every writer writes the
             }                                                                          // same value (device-scope atomics run
         }                                                                              // at ~5 G/s on this part: 30x slower)
     }

@@ -241,7 +241,9 @@ __device__ __forceinline__ void unproject_compact4_body(unsigned bx, unsigned by
 #include "nbp_bins.h"
 struct BinFile { char* store; float* zero6; float* zero1; int SS; };
 
-// K2: gather the sub-sample and append it to the cloud at *cloud_count + sum of earlier frames.
+// K2: gather the sub-sample and append it to the cloud at *cloud_count + sum of earlier frames.  COLOUR = false is the depth-only
+// form (no cloud_rgb): the instantiation the lock-step runs sheds the shading path's registers.
+template <bool COLOUR>
 __device__ __forceinline__ void unproject_append_body(unsigned bx, unsigned by, unsigned gx, unsigned gy, const float* __restrict__ depth, const Cam* cams,
                                                                int H, int W, float tanh_fov, unsigned seed,
                                                                const unsigned* __restrict__ list,
@@ -292,7 +294,7 @@ __device__ __forceinline__ void unproject_append_body(unsigned bx, unsigned by, 
         }
         if (filing) bin_file_wave(bv, bg, active, pt, base + j);
         if (!active) continue;
-        if (cloud_rgb) {                                   // the colours of the kept pixels (mu:2840-2845)
+        if constexpr (COLOUR) if (cloud_rgb) {             // the colours of the kept pixels (mu:2840-2845)
             float* cd = cloud_rgb + (base + j) * 3;
             if (zface) {                                   // deferred shading: only the ~5 % of pixels that are kept
                 const unsigned long long zf = zface[(size_t)f * HW + pix];
@@ -367,6 +369,7 @@ __global__ __launch_bounds__(256) void unproject_compact4_batch_kernel(UnprojBat
     unproject_compact4_body(blockIdx.x, blockIdx.y, gridDim.x, gridDim.y, a.depth[blockIdx.y] - (size_t)blockIdx.y * HW, nullptr, HW, nblk,
                             fov_range, gather, a.blk_count, b.list(blockIdx.z), a.counts);
 }
+template <bool COLOUR>
 __global__ __launch_bounds__(256) void unproject_append_kernel(const float* __restrict__ depth, CamSet cams, int H, int W, float tanh_fov,
                                                                unsigned seed, const unsigned* __restrict__ list,
                                                                const int* __restrict__ counts, float* __restrict__ cloud,
@@ -375,14 +378,15 @@ __global__ __launch_bounds__(256) void unproject_append_kernel(const float* __re
                                                                float* __restrict__ cloud_rgb, const unsigned long long* __restrict__ zface,
                                                                const float* __restrict__ verts, const int* __restrict__ faces,
                                                                const float* __restrict__ vcolors, float ambient, int fence, BinFile bf) {
-    unproject_append_body(blockIdx.x, blockIdx.y, gridDim.x, gridDim.y, depth, cams.c, H, W, tanh_fov, seed, list, counts, cloud, cloud_count,
+    unproject_append_body<COLOUR>(blockIdx.x, blockIdx.y, gridDim.x, gridDim.y, depth, cams.c, H, W, tanh_fov, seed, list, counts, cloud, cloud_count,
                           capacity, n_frames, done_ticket, rgb, cloud_rgb, zface, verts, faces, vcolors, ambient, fence, bf);
 }
+template <bool COLOUR>
 __global__ __launch_bounds__(256) void unproject_append_batch_kernel(UnprojBatch b, int H, int W, float tanh_fov, int n_frames, float ambient,
                                                                      int fence) {
     const UnprojItem& a = b.it[blockIdx.z];
     const size_t shift = (size_t)blockIdx.y * H * W;
-    unproject_append_body(blockIdx.x, blockIdx.y, gridDim.x, gridDim.y, a.depth[blockIdx.y] - shift, a.cam, H, W, tanh_fov, a.seed,
+    unproject_append_body<COLOUR>(blockIdx.x, blockIdx.y, gridDim.x, gridDim.y, a.depth[blockIdx.y] - shift, a.cam, H, W, tanh_fov, a.seed,
                           b.list(blockIdx.z), a.counts, a.cloud, a.cloud_count, a.capacity, n_frames, b.ticket(blockIdx.z), nullptr, a.cloud_rgb,
                           a.zface[blockIdx.y] ? a.zface[blockIdx.y] - shift : nullptr, a.verts, a.faces, a.vcolors, ambient, fence);
 }
@@ -414,7 +418,8 @@ constexpr int COARSE = 8;              // fine tiles per coarse tile side
 constexpr int SEG_DEFAULT = 16384;     // list entries per wave (NBP_RASTER_SEG): with the hit list taken through LDS in pieces a wave can walk a
                                        // whole coarse list, and the empty extra segments of shorter ones cost 1-3 us (4096: 50.3 / 65.1 us for 4 frames of
                                        // the 8 k / 29 k-face scenes, 32768: 49.0 / 62.9)
-constexpr int HITS = 1024;             // ... taken through LDS in pieces of this many
+constexpr int HITS = 320;              // ... taken through LDS in pieces of this many (2.5 KB: with the 13 KB of staged records the workgroup stays
+                                       // inside 16 KB of LDS; 1024 until round 8)
 constexpr unsigned ZBUF_EMPTY = 0x7F7F7F7Fu;   // memset pattern, 3.39e38 as a float
 
 struct BinEntry { int face; unsigned box; };   // box = tx0 | tx1 << 8 | ty0 << 16 | ty1 << 24 (fine-tile coordinates)
@@ -520,6 +525,10 @@ __device__ __forceinline__ void raster_setup_body(unsigned bx, unsigned by, unsi
 // those covering its own tile, gathers their face records through LDS and ray-casts.  The set of faces a pixel is tested against is
 // the same, and the winner (nearest, lowest face id among equal depths) does not depend on the order: the same image bit for bit.
 constexpr int RB = 2;                  // fine tiles per block side
+// number of set bits of a ballot below this lane
+__device__ __forceinline__ int ballot_rank(unsigned long long bal) {
+    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u));
+}
 __device__ __forceinline__ void raster_block_body(unsigned bx, unsigned by, const FaceRec* __restrict__ recs, int n_faces, int H, int W,
                                                   float tanh_fov, float zclip, int tiles_x, int tiles_y, int ctiles_x,
                                                   const int* __restrict__ ccount, const BinEntry* __restrict__ clist,
@@ -539,8 +548,9 @@ __device__ __forceinline__ void raster_block_body(unsigned bx, unsigned by, cons
     const int s0 = seg * SEG;
     if (s0 >= n) return;
     const int s1 = min(n, s0 + SEG);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const unsigned long long lt = (1ull << lane) - 1ull;
+    // (the wave's index, and with it its tile, in scalar registers; a lane's rank in a ballot from mbcnt instead of a 64-bit lane mask
+    // held in two registers: the kernel is built to 32 VGPRs)
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const BinEntry* lst = clist + ((size_t)fr * nct + ct) * n_faces;
     const int btx0 = bxx * RB, btx1 = btx0 + RB - 1, bty0 = byy * RB, bty1 = bty0 + RB - 1;
     const int tx = btx0 + (wave & 1), ty = bty0 + (wave >> 1);
@@ -571,7 +581,7 @@ __device__ __forceinline__ void raster_block_body(unsigned bx, unsigned by, cons
             int wbase = 0;
             if (lane == 0 && bal) wbase = atomicAdd(&nb_sh, __popcll(bal));
             wbase = __shfl(wbase, 0);
-            if (in) bhits[wbase + __popcll(bal & lt)] = e;
+            if (in) bhits[wbase + ballot_rank(bal)] = e;
         }
         __syncthreads();
         const int nb = nb_sh;
@@ -589,7 +599,7 @@ __device__ __forceinline__ void raster_block_body(unsigned bx, unsigned by, cons
                 const unsigned long long bal = __ballot(in);
                 const int m = __popcll(bal);
                 if (in) {
-                    const int k = __popcll(bal & lt);
+                    const int k = ballot_rank(bal);
                     sh[wave][k] = rb[face];
                     shf[wave][k] = face;
                 }
@@ -1049,9 +1059,9 @@ static int unproject_launch(const float* depth, const unsigned char* mask_or_nul
                                                       counts2);
         if ((rc = nbp_launch_status())) return rc;
         if (bf.store && (bf.zero6 || bf.zero1) && grid.x * grid.y < 64u) grid.x = (64u + grid.y - 1) / grid.y;      // enough workgroups for the clear
-        unproject_append_kernel<<<grid, 256, 0, st>>>(depth, cams, H, W, tan_half_fov, seed, list, counts2, cloud, cloud_count,
-                                                      capacity, n_frames, ticket, rgb_or_null, cloud_rgb_or_null, sh.zface, sh.verts, sh.faces,
-                                                      sh.vcolors, sh.ambient, ticket_fence(), bf);
+        auto append = cloud_rgb_or_null ? unproject_append_kernel<true> : unproject_append_kernel<false>;
+        append<<<grid, 256, 0, st>>>(depth, cams, H, W, tan_half_fov, seed, list, counts2, cloud, cloud_count, capacity, n_frames, ticket,
+                                     rgb_or_null, cloud_rgb_or_null, sh.zface, sh.verts, sh.faces, sh.vcolors, sh.ambient, ticket_fence(), bf);
         return nbp_launch_status();
     }
     dim3 gc((unsigned)nblk, (unsigned)n_frames);
@@ -1060,9 +1070,10 @@ static int unproject_launch(const float* depth, const unsigned char* mask_or_nul
     unproject_compact_kernel<<<gc, 256, 0, st>>>(depth, mask_or_null, HW, nblk, fov_range, gathering_factor, blk_count,
                                                  list, counts2);
     if ((rc = nbp_launch_status())) return rc;
-    unproject_append_kernel<<<grid, 256, 0, st>>>(depth, cams, H, W, tan_half_fov, seed, list, counts2, cloud, cloud_count,
-                                                  capacity, n_frames, nullptr, rgb_or_null, cloud_rgb_or_null, sh.zface, sh.verts, sh.faces,
-                                                  sh.vcolors, sh.ambient, 0, BinFile{nullptr, nullptr, nullptr, 0});
+    auto append = cloud_rgb_or_null ? unproject_append_kernel<true> : unproject_append_kernel<false>;
+    append<<<grid, 256, 0, st>>>(depth, cams, H, W, tan_half_fov, seed, list, counts2, cloud, cloud_count, capacity, n_frames, nullptr,
+                                 rgb_or_null, cloud_rgb_or_null, sh.zface, sh.verts, sh.faces, sh.vcolors, sh.ambient, 0,
+                                 BinFile{nullptr, nullptr, nullptr, 0});
     if ((rc = nbp_launch_status())) return rc;
     cloud_count_update_kernel<<<1, 64, 0, st>>>(counts2, n_frames, cloud_count, capacity);
     return nbp_launch_status();
@@ -1200,6 +1211,7 @@ extern "C" int nbp_unproject_append_shaded_batch_f32(int n, const float* const* 
     const int nblk = (int)nbp_cdiv(HW, COMPACT_CHUNK), nb4 = (int)nbp_cdiv(HW, FAST_CHUNK);
     NBP_RETURN_IF(nblk > 4096, NBP_E_SHAPE);
     UnprojBatch b;
+    bool any_colour = false;
     b.ticket_off = n_frames * nb4;
     b.list_off_bytes = (unsigned)(((size_t)n_frames * nblk * sizeof(int) + 255) / 256 * 256);
     for (int r = 0; r < STEP_BATCH; ++r) {
@@ -1211,6 +1223,7 @@ extern "C" int nbp_unproject_append_shaded_batch_f32(int n, const float* const* 
         a.counts = counts2[q]; a.cloud = cloud[q]; a.cloud_count = cloud_count[q]; a.capacity = capacity[q];
         const bool col = zface && zface[(size_t)q * n_frames] && cloud_rgb && cloud_rgb[q] && verts && faces && vcolors;
         a.cloud_rgb = col ? cloud_rgb[q] : nullptr;
+        any_colour = any_colour || col;
         for (int f = 0; f < 4; ++f) {
             const int g = f < n_frames ? f : 0;
             a.depth[f] = depth[(size_t)q * n_frames + g];
@@ -1233,7 +1246,8 @@ extern "C" int nbp_unproject_append_shaded_batch_f32(int n, const float* const* 
     if ((rc = nbp_launch_status())) return rc;
     const int max_keep = (int)((double)H * W * gathering_factor) + 1;
     dim3 grid((unsigned)nbp_cdiv(max_keep, 256), (unsigned)n_frames, (unsigned)n);
-    unproject_append_batch_kernel<<<grid, 256, 0, st>>>(b, H, W, tan_half_fov, n_frames, ambient, ticket_fence());
+    auto append = any_colour ? unproject_append_batch_kernel<true> : unproject_append_batch_kernel<false>;
+    append<<<grid, 256, 0, st>>>(b, H, W, tan_half_fov, n_frames, ambient, ticket_fence());
     return nbp_launch_status();
 }
 
