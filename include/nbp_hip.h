@@ -1051,6 +1051,28 @@ size_t nbp_recon_stats_workspace_bytes(void);
 int nbp_recon_stats_f64(const float* d2, long long n, const long long* n_dev_or_null, int T, const float* thresholds_host,
                         double* sums2, long long* counts, void* ws, size_t ws_bytes, void* stream);
 
+/* Per-step reconstruction curve: the same metrics after every step, updated incrementally (the cloud is append-only, the GT fixed).
+ * n <= 16 items (HOST arrays of n entries) in THREE launches whatever n: one walk over the items' new points, the partial sums, the
+ * items' rows.  Item i: plans[i] = an nbp_nn_plan_build_f32 plan of its G[i] GT points inside lo / hi [n][3] with cell[i] (the plan's
+ * fourth float4 component carries the GT index); cloud3[i] = [capacity[i]][3]; count_dev[i] = the cloud's int64 device size;
+ * seen_dev[i] = int64 device watermark.  The call reads cloud rows [seen, min(count, capacity)) only -- both ends on the device --
+ * and then sets seen = min(count, capacity); seen >= count: nothing new, the row repeats the totals and nothing else moves.
+ * d2_gt[i] fp32 [G[i]] in the GT's order: the running truncated squared distance GT -> cloud, initialised by the caller to
+ * fl(cap cap), lowered by an integer atomicMin on the bit pattern (exact, and the same bits in every run); d2_new[i] fp32
+ * [capacity[i]]: scratch for the new points' own distances; totals[i]: nbp_recon_curve_totals_bytes() bytes, zeroed by the caller
+ * at a reset (running accuracy sums and counts); T[i] thresholds in thresholds_host [n][8]; row[i] float64 [6 + 2 T[i]] = (acc
+ * sums 2, comp sums 2, n_rec, G, acc counts T, comp counts T); new_bound[i] = host bound of the new points: it only sizes the grid.
+ * The completeness half of a row is bit for bit nbp_recon_stats_f64 of d2_gt (the same geometry); batching changes no bit of any
+ * item.  ws: nbp_recon_curve_workspace_bytes(n).  No allocation, no host synchronisation.  NBP_E_ARG / NBP_E_SHAPE as above; totals,
+ * row, seen or count off the 8-byte grid is NBP_E_SHAPE. */
+size_t nbp_recon_curve_workspace_bytes(int n);
+size_t nbp_recon_curve_totals_bytes(void);
+int nbp_recon_curve_update_batch_f32(int n, const void* const* plans, const int* G, const float* lo_host, const float* hi_host,
+                                     const float* cell, const float* cap, const float* const* cloud3, const long long* capacity,
+                                     const long long* const* count_dev, long long* const* seen_dev, float* const* d2_gt,
+                                     float* const* d2_new, void* const* totals, const int* T, const float* thresholds_host,
+                                     double* const* row, const long long* new_bound, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- The replay store's container in LMDB's on-disk format (csrc/nbp_mdb.cpp; host only).  The reference keeps its experience
  * records in an LMDB environment (next_best_path/trainers/train_nbp_model.py:61-63 lmdb.open(path, map_size);
  * next_best_path/utility/nbp_utils.py:32-141: txn.put per record, ordered cursors, txn.delete of the validation records).  liblmdb is

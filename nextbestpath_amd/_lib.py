@@ -236,6 +236,10 @@ SIGNATURES["nbp_nn_dist2_workspace_bytes"] = (_sz, [_fpp, _fpp, _f, _ll])
 SIGNATURES["nbp_nn_dist2_f32"] = (_i, [_vp, _ll, _vp, _vp, _ll, _vp, _fpp, _fpp, _f, _f, _vp, _vp, _sz, _vp])
 SIGNATURES["nbp_recon_stats_workspace_bytes"] = (_sz, [])
 SIGNATURES["nbp_recon_stats_f64"] = (_i, [_vp, _ll, _vp, _i, _fpp, _vp, _vp, _vp, _sz, _vp])
+SIGNATURES["nbp_recon_curve_workspace_bytes"] = (_sz, [_i])
+SIGNATURES["nbp_recon_curve_totals_bytes"] = (_sz, [])
+SIGNATURES["nbp_recon_curve_update_batch_f32"] = (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                       _vp, _vp, _sz, _vp])
 SIGNATURES["nbp_objective_workspace_bytes"] = (_sz, [_i, _i])
 SIGNATURES["nbp_objective_forward_f32"] = (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp])
 SIGNATURES["nbp_objective_backward_f32"] = (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp])

@@ -23,6 +23,19 @@
 // Summary (nbp_recon_stats_f64): a fixed launch geometry; every thread adds its strided elements in index order in float64, a
 // fixed tree adds the threads of a block (shuffles inside a wave, the four waves in order), each block STORES one row, and a
 // second one-block launch adds the rows in index order.  No floating-point atomics: two runs give the same bits.
+//
+// Per-step curve (nbp_recon_curve_update_batch_f32).  The cloud is append-only and the GT fixed, so both directions
+// are incremental: a point's distance to the GT never changes (it is queried once, in the step that appends it), and the minimum
+// over a union is the minimum of the minima (a running per-GT-point minimum d2_gt is lowered by the new points only).  One walk
+// per new point serves both: its NN_LANES lanes visit EVERY GT cell within Chebyshev distance R of its unclamped cell (the early
+// exit above does not apply: the scatter needs every target within reach), each (x, y) column one contiguous run.  The lanes keep
+// the point's own minimum (its accuracy distance), and a visited GT point with d < d2_gt[g] is lowered by an INTEGER atomicMin on
+// the bit pattern: non-negative finite floats order like their bits and a minimum is blind to arrival order, so d2_gt is exact and
+// two runs give the same bits.  The plain read that filters the atomic may be stale (another XCD's L2): values only decrease, so
+// a stale read costs a redundant atomic, never a missed one.  What the walk leaves out is farther than R w >= cap (the argument
+// above with r = R).  The slot -> GT index map is the fourth component of the plan's float4 (its bits; the query never reads it).
+// The summaries follow in two launches of the stats geometry above: d2_gt in full, the step's own distances into the running
+// float64 totals by one thread.  The watermark `seen` moves in the last launch only (the first two read it).
 #include "nbp_grid.h"
 
 #include <math.h>
@@ -70,7 +83,7 @@ __global__ __launch_bounds__(256) void nn_scatter_kernel(const float* __restrict
     n = n < 0 ? 0 : (n > n_host ? n_host : n);
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
         const int c = cell_of[i];
-        if (c >= 0) sorted[start[c] + slot_of[i]] = make_float4(t[3 * i], t[3 * i + 1], t[3 * i + 2], 0.f);
+        if (c >= 0) sorted[start[c] + slot_of[i]] = make_float4(t[3 * i], t[3 * i + 1], t[3 * i + 2], __int_as_float((int)i));   // .w: the target's index (curve walk)
     }
 }
 
@@ -219,6 +232,207 @@ template <int T>
 void launch_stats(hipStream_t st, const float* d2, const long long* n_dev, long long n, const StatsThresholds& th,
                   unsigned long long* rows) {
     stats_partial_kernel<T><<<STATS_BLOCKS, STATS_THREADS, 0, st>>>(d2, n_dev, n, th, rows);
+}
+
+// ---- per-step curve
+constexpr int CURVE_BATCH = 16;
+constexpr int CURVE_TOTALS = 2 + STATS_MAX_T;    // 8-byte words of an item's running accuracy totals: two float64 sums, the counts
+
+struct CurveItem {
+    Grid g;
+    float hi[3];
+    int R;
+    float cap2;
+    int T, G;
+    unsigned gx_walk;
+    const float4* sorted;
+    const int* start;
+    const float* cloud;
+    long long capacity, n_gt;
+    const long long* count;
+    long long* seen;
+    unsigned* d2_gt;
+    float* d2_new;
+    unsigned long long* totals;
+    double* row;
+    unsigned long long* part;                    // [2][STATS_BLOCKS][STATS_ROW]: d2_gt's rows, then the step's
+    float th[STATS_MAX_T];
+};
+struct CurveBatch { CurveItem it[CURVE_BATCH]; };
+
+// The item's new rows [s, e): both ends from the device, e = min(count, capacity); s >= e: nothing new.
+__device__ __forceinline__ void curve_range(const CurveItem& a, long long* s, long long* e) {
+    long long seen = *a.seen, end = *a.count;
+    end = end < 0 ? 0 : (end > a.capacity ? a.capacity : end);
+    seen = seen < 0 ? 0 : seen;
+    *s = seen;
+    *e = seen >= end ? seen : end;
+}
+
+__device__ __forceinline__ float curve_point(unsigned* __restrict__ d2_gt, const float4 t, float x, float y, float z, bool scatter,
+                                             float best) {
+    const float ex = t.x - x, ey = t.y - y, ez = t.z - z;
+    const float d = (ex * ex + ey * ey) + ez * ez;
+    if (scatter) {
+        const int gi = __float_as_int(t.w);
+        if (d < __uint_as_float(d2_gt[gi])) atomicMin(&d2_gt[gi], __float_as_uint(d));
+    }
+    return d < best ? d : best;
+}
+
+__device__ __forceinline__ float curve_run(const float4* __restrict__ sorted, unsigned* __restrict__ d2_gt, int p, int hi, float x,
+                                           float y, float z, bool scatter, float best) {
+    for (; p + NN_UNROLL <= hi; p += NN_UNROLL) {
+        float4 t[NN_UNROLL];
+#pragma unroll
+        for (int u = 0; u < NN_UNROLL; ++u) t[u] = sorted[p + u];
+#pragma unroll
+        for (int u = 0; u < NN_UNROLL; ++u) best = curve_point(d2_gt, t[u], x, y, z, scatter, best);
+    }
+    for (; p < hi; ++p) best = curve_point(d2_gt, sorted[p], x, y, z, scatter, best);
+    return best;
+}
+
+__global__ __launch_bounds__(256) void curve_walk_kernel(const CurveBatch b) {
+    const CurveItem& a = b.it[blockIdx.y];
+    if (blockIdx.x >= a.gx_walk) return;
+    long long s, e;
+    curve_range(a, &s, &e);
+    const int sub = threadIdx.x % NN_LANES;
+    const int n0 = a.g.n[0], n1 = a.g.n[1], n2 = a.g.n[2], R = a.R;
+    for (long long j = s + ((long long)blockIdx.x * blockDim.x + threadIdx.x) / NN_LANES; j < e;
+         j += ((long long)a.gx_walk * blockDim.x) / NN_LANES) {
+        const float x = a.cloud[3 * j], y = a.cloud[3 * j + 1], z = a.cloud[3 * j + 2];
+        // as a target the point counts inside the box only (nn_bin_kernel's test: a NaN is outside) ...
+        const bool in = x >= a.g.lo[0] && x <= a.hi[0] && y >= a.g.lo[1] && y <= a.hi[1] && z >= a.g.lo[2] && z <= a.hi[2];
+        // ... as a query wherever its cell is within reach of the grid (nn_query_kernel's test; a far or NaN point: cap2, no access)
+        const float fi = floorf((x - a.g.lo[0]) * a.g.inv), fj = floorf((y - a.g.lo[1]) * a.g.inv), fk = floorf((z - a.g.lo[2]) * a.g.inv);
+        const bool reach = fi >= (float)-R && fi <= (float)(n0 - 1 + R) && fj >= (float)-R && fj <= (float)(n1 - 1 + R) &&
+                           fk >= (float)-R && fk <= (float)(n2 - 1 + R);
+        float best = a.cap2;
+        if (reach) {                                               // (uniform over the point's lanes)
+            const int ci = (int)fi, cj = (int)fj, ck = (int)fk;
+            const int a0 = max(ci - R, 0), a1 = min(ci + R, n0 - 1), b0 = max(cj - R, 0), b1 = min(cj + R, n1 - 1);
+            const int z0 = max(ck - R, 0), z1 = min(ck + R, n2 - 1);
+            const int na = a1 - a0 + 1, nb = b1 - b0 + 1;
+            if (na > 0 && nb > 0 && z0 <= z1) {
+                for (int it = sub; it < na * nb; it += NN_LANES) {
+                    const int base = ((a0 + it / nb) * n1 + (b0 + it % nb)) * n2;
+                    best = curve_run(a.sorted, a.d2_gt, a.start[base + z0], a.start[base + z1 + 1], x, y, z, in, best);
+                }
+            }
+#pragma unroll
+            for (int o = NN_LANES / 2; o; o >>= 1) {
+                const float other = __shfl_xor(best, o);
+                best = other < best ? other : best;
+            }
+        }
+        if (sub == 0) a.d2_new[j - s] = best;
+    }
+}
+
+// stats_partial_kernel's arithmetic for one block of the fixed geometry (same strides, same order, same tree: the same bits), with
+// the number of thresholds at run time (entries of th beyond T repeat th[0]; their counts are not read).
+__device__ __forceinline__ void curve_block_stats(const float* __restrict__ d2, long long n, const float* th, int block,
+                                                  unsigned long long* __restrict__ row) {
+    __shared__ double ws1[STATS_WAVES], ws2[STATS_WAVES];
+    __shared__ long long wc[STATS_WAVES][STATS_MAX_T];
+    double s1 = 0.0, s2 = 0.0;
+    long long c[STATS_MAX_T];
+#pragma unroll
+    for (int t = 0; t < STATS_MAX_T; ++t) c[t] = 0;
+    for (long long i = (long long)block * STATS_THREADS + threadIdx.x; i < n; i += (long long)STATS_BLOCKS * STATS_THREADS) {
+        const float v = d2[i];
+        s1 += sqrt((double)v);
+        s2 += (double)v;
+#pragma unroll
+        for (int t = 0; t < STATS_MAX_T; ++t) c[t] += v <= th[t] ? 1 : 0;
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        s1 += __shfl_down(s1, off, 64);
+        s2 += __shfl_down(s2, off, 64);
+#pragma unroll
+        for (int t = 0; t < STATS_MAX_T; ++t) c[t] += __shfl_down(c[t], off, 64);
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) {
+        ws1[wave] = s1;
+        ws2[wave] = s2;
+#pragma unroll
+        for (int t = 0; t < STATS_MAX_T; ++t) wc[wave][t] = c[t];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double r1 = ws1[0], r2 = ws2[0];
+        for (int k = 1; k < STATS_WAVES; ++k) { r1 += ws1[k]; r2 += ws2[k]; }
+        row[0] = (unsigned long long)__double_as_longlong(r1);
+        row[1] = (unsigned long long)__double_as_longlong(r2);
+        for (int t = 0; t < STATS_MAX_T; ++t) {
+            long long s = 0;
+            for (int k = 0; k < STATS_WAVES; ++k) s += wc[k][t];
+            row[2 + t] = (unsigned long long)s;
+        }
+    }
+}
+
+// grid (STATS_BLOCKS, 2, n): y = 0 the whole of d2_gt, y = 1 the step's own distances
+__global__ __launch_bounds__(STATS_THREADS) void curve_partial_kernel(const CurveBatch b) {
+    const CurveItem& a = b.it[blockIdx.z];
+    const int half = blockIdx.y;
+    const float* d2 = (const float*)a.d2_gt;
+    long long n = a.n_gt;
+    if (half) {
+        long long s, e;
+        curve_range(a, &s, &e);
+        d2 = a.d2_new;
+        n = e - s;
+    }
+    curve_block_stats(d2, n, a.th, blockIdx.x, a.part + ((size_t)half * STATS_BLOCKS + blockIdx.x) * STATS_ROW);
+}
+
+// One block per item: the rows of either half added in index order (stats_final_kernel's order), the step's sums added to the
+// running totals by one thread, the item's row written, the watermark moved.
+__global__ __launch_bounds__(64) void curve_final_kernel(const CurveBatch b) {
+    const CurveItem& a = b.it[blockIdx.x];
+    __shared__ unsigned long long tot[2][STATS_ROW];
+    const int half = threadIdx.x / 32, col = threadIdx.x % 32;
+    if (col < STATS_ROW) {
+        const unsigned long long* rows = a.part + (size_t)half * STATS_BLOCKS * STATS_ROW;
+        if (col < 2) {
+            double s = 0.0;
+            for (int k = 0; k < STATS_BLOCKS; ++k) s += __longlong_as_double((long long)rows[(size_t)k * STATS_ROW + col]);
+            tot[half][col] = (unsigned long long)__double_as_longlong(s);
+        } else {
+            long long s = 0;
+            for (int k = 0; k < STATS_BLOCKS; ++k) s += (long long)rows[(size_t)k * STATS_ROW + col];
+            tot[half][col] = (unsigned long long)s;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        long long s, e;
+        curve_range(a, &s, &e);
+        const int T = a.T;
+        if (e > s) {                                               // (nothing new: the totals and the watermark stay)
+            for (int c = 0; c < 2; ++c)
+                a.totals[c] = (unsigned long long)__double_as_longlong(__longlong_as_double((long long)a.totals[c]) +
+                                                                       __longlong_as_double((long long)tot[1][c]));
+            for (int t = 0; t < T; ++t) a.totals[2 + t] += tot[1][2 + t];
+            *a.seen = e;
+        }
+        double* row = a.row;
+        row[0] = __longlong_as_double((long long)a.totals[0]);
+        row[1] = __longlong_as_double((long long)a.totals[1]);
+        row[2] = __longlong_as_double((long long)tot[0][0]);
+        row[3] = __longlong_as_double((long long)tot[0][1]);
+        row[4] = (double)e;
+        row[5] = (double)a.n_gt;
+        for (int t = 0; t < T; ++t) {
+            row[6 + t] = (double)(long long)a.totals[2 + t];
+            row[6 + T + t] = (double)(long long)tot[0][2 + t];
+        }
+    }
 }
 
 // ---- host
@@ -389,5 +603,68 @@ extern "C" int nbp_recon_stats_f64(const float* d2, long long n, const long long
     const int rc = nbp_launch_status();
     if (rc) return rc;
     stats_final_kernel<<<1, 64, 0, st>>>(rows, T, sums2, counts);
+    return nbp_launch_status();
+}
+
+extern "C" size_t nbp_recon_curve_workspace_bytes(int n) {
+    if (n < 1 || n > CURVE_BATCH) return 0;
+    return 256 + (size_t)n * 2 * STATS_BLOCKS * STATS_ROW * 8;
+}
+
+extern "C" size_t nbp_recon_curve_totals_bytes(void) { return (size_t)CURVE_TOTALS * 8; }
+
+extern "C" int nbp_recon_curve_update_batch_f32(int n, const void* const* plans, const int* G, const float* lo_host,
+                                                const float* hi_host, const float* cell, const float* cap, const float* const* cloud3,
+                                                const long long* capacity, const long long* const* count_dev, long long* const* seen_dev,
+                                                float* const* d2_gt, float* const* d2_new, void* const* totals, const int* T,
+                                                const float* thresholds_host, double* const* row, const long long* new_bound, void* ws,
+                                                size_t ws_bytes, void* stream) {
+    NBP_ENTER();
+    NBP_RETURN_IF(n < 1 || n > CURVE_BATCH || !plans || !G || !lo_host || !hi_host || !cell || !cap || !cloud3 || !capacity ||
+                  !count_dev || !seen_dev || !d2_gt || !d2_new || !totals || !T || !thresholds_host || !row || !new_bound || !ws,
+                  NBP_E_ARG);
+    NBP_RETURN_IF(ws_bytes < nbp_recon_curve_workspace_bytes(n), NBP_E_WS);
+    unsigned long long* part = (unsigned long long*)(((uintptr_t)ws + 255) / 256 * 256);
+    CurveBatch b;
+    unsigned gwalk = 1;
+    for (int r = 0; r < CURVE_BATCH; ++r) {
+        const int q = r < n ? r : 0;
+        const float* lo = lo_host + 3 * q;
+        const float* hi = hi_host + 3 * q;
+        NBP_RETURN_IF(!plans[q] || !cloud3[q] || !count_dev[q] || !seen_dev[q] || !d2_gt[q] || !d2_new[q] || !totals[q] || !row[q] ||
+                      G[q] < 1 || capacity[q] < 1 || capacity[q] > 0x7fffffffll || new_bound[q] < 0 || T[q] < 1 || T[q] > STATS_MAX_T ||
+                      !nn_args_ok(lo, hi, cell[q]) || !nn_cap_ok(cap[q], cell[q]),
+                      NBP_E_ARG);
+        NBP_RETURN_IF((((uintptr_t)totals[q] | (uintptr_t)row[q] | (uintptr_t)seen_dev[q] | (uintptr_t)count_dev[q]) & 7), NBP_E_SHAPE);
+        CurveItem& a = b.it[r];
+        Box bx; size_t ncell;
+        const int rc = nn_grid(lo, hi, cell[q], &a.g, &bx, &ncell);
+        if (rc) return rc;
+        for (int k = 0; k < 3; ++k) a.hi[k] = bx.hi[k];
+        int* start; float4* sorted;
+        nn_plan_carve(const_cast<void*>(plans[q]), ncell, &start, &sorted);
+        a.sorted = sorted; a.start = start;
+        a.R = (int)ceil((double)cap[q] / (double)cell[q]);
+        a.cap2 = cap[q] * cap[q];
+        a.T = T[q]; a.G = G[q]; a.n_gt = G[q];
+        for (int t = 0; t < STATS_MAX_T; ++t) {
+            const float thr = thresholds_host[STATS_MAX_T * q + (t < T[q] ? t : 0)];
+            NBP_RETURN_IF(!(thr > 0) || !isfinite(thr), NBP_E_ARG);
+            a.th[t] = recon_sq_below(thr);
+        }
+        a.cloud = cloud3[q]; a.capacity = capacity[q]; a.count = count_dev[q]; a.seen = seen_dev[q];
+        a.d2_gt = (unsigned*)d2_gt[q]; a.d2_new = d2_new[q]; a.totals = (unsigned long long*)totals[q]; a.row = row[q];
+        a.part = part + (size_t)q * 2 * STATS_BLOCKS * STATS_ROW;
+        const long long work = new_bound[q] < capacity[q] ? new_bound[q] : capacity[q];
+        a.gx_walk = r < n ? (unsigned)nbp_ew_grid((work > 0 ? work : 1) * NN_LANES, 256) : 0;
+        if (a.gx_walk > gwalk) gwalk = a.gx_walk;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    curve_walk_kernel<<<dim3(gwalk, (unsigned)n), 256, 0, st>>>(b);
+    int rc = nbp_launch_status();
+    if (rc) return rc;
+    curve_partial_kernel<<<dim3(STATS_BLOCKS, 2, (unsigned)n), STATS_THREADS, 0, st>>>(b);
+    if ((rc = nbp_launch_status())) return rc;
+    curve_final_kernel<<<(unsigned)n, 64, 0, st>>>(b);
     return nbp_launch_status();
 }

@@ -4,7 +4,8 @@ Each (scene, start pose) rollout is independent (next_best_path/testers/nbp_plan
 runs them in nested loops on one GPU), so rank r takes runs r, r+W, r+2W, ... and the only
 collective is ONE all_gather of a padded fp32 tensor [runs_per_rank, n_poses + 3] holding
 (run id, final coverage, AUC, coverage curve) -- a few KB over RCCL/xGMI, latency bound (with the
-planning option `recon_metrics` on, a second one of float64 sums and counts: gather_reconstruction).  One
+planning option `recon_metrics` on, a second one of float64 sums and counts: gather_reconstruction; with its `curve`, a third of the
+per-step rows: gather_reconstruction_curve).  One
 process per GPU; backend "nccl" (= RCCL on ROCm) with CUDA tensors, "gloo" on CPU-only hosts
 (that path is what the world_size-2 CPU tests exercise)."""
 from __future__ import annotations
@@ -127,3 +128,29 @@ def gather_reconstruction(results, runs, rank, world, device, thresholds, cap):
     if rank != 0:
         return {}
     return {int(row[0]): recon_metrics.summarise_raw(row[1:], thresholds, cap) for row in t if row[0] >= 0}
+
+
+def gather_reconstruction_curve(results, runs, rank, world, device, thresholds, cap, n_poses):
+    """The planning option `recon_metrics` with `curve`: all ranks call this behind gather_reconstruction.  The raw rows of every
+    run's per-step curve (results[i]["reconstruction_curve_raw"]: n_poses rows of pack_raw's 6 + 2 T numbers) travel in ONE
+    all_gather of a padded float64 tensor [runs_per_rank, 1 + n_poses (6 + 2 T)] (run id first; pad rows = -1) -- a gather of its
+    own: the other two keep their shapes with the curve off.  Rank 0 forms the ratios -> {run id: summarise_curve's dict}; the
+    other ranks get {}."""
+    from .utility import recon_metrics
+    rows = runs_per_rank(len(runs), world)
+    per = recon_metrics.RAW_HEAD + 2 * len(thresholds)
+    width = 1 + n_poses * per
+    t = np.full((rows, width), -1.0, np.float64)
+    for j, r in enumerate(results):
+        t[j, 0] = r["run_id"]
+        t[j, 1:] = np.asarray(r["reconstruction_curve_raw"], np.float64).reshape(n_poses * per)
+    collective = world > 1 or group_is_up()
+    if collective:
+        import torch.distributed as dist
+        local = torch.from_numpy(t).to(collective_device(device))
+        buf = [torch.empty_like(local) for _ in range(world)]
+        dist.all_gather(buf, local)
+        t = torch.stack(buf).cpu().numpy().reshape(-1, width)
+    if rank != 0:
+        return {}
+    return {int(row[0]): recon_metrics.summarise_curve(row[1:].reshape(n_poses, per), thresholds, cap) for row in t if row[0] >= 0}

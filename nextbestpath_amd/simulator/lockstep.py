@@ -145,6 +145,25 @@ class LockstepRollout:
         plan, *args = self.coverage_item()
         return plan.count(*args)                   # (the item's order is CoveragePlan.count's)
 
+    def recon_curve_item(self):
+        """The per-step reconstruction curve's arguments (hipops.recon_curve_update_batch), or None where the rollout has no
+        `recon_curve` (the planning option `recon_metrics` without `curve`): the cloud so far -- the one the coverage stage of this
+        step saw -- into row pose_i of the curve.  The host bound of the new points counts the frames un-projected since the last
+        item was made (making an item moves that mark: an item is made to be launched); it only sizes the grid."""
+        curve = getattr(self, "recon_curve", None)
+        if curve is None:
+            return None
+        st, params = self.st, self.params
+        per_frame = int(params.image_height * params.image_width * params.gathering_factor) + 1
+        new = st.frames_appended - self._curve_frames
+        self._curve_frames = st.frames_appended
+        return curve.item(st.cloud, st.cloud_count, self.pose_i % N_POSES, min(st.cloud.shape[0], new * per_frame))
+
+    def update_recon_curve(self):
+        item = self.recon_curve_item()
+        if item is not None:
+            hipops.recon_curve_update_batch([item])
+
     def unproject(self, frames, colours, clear=None):
         """Un-projects `frames` (CURRENT or SUPERVISION) of this rollout's camera into its cloud, with their colours when `colours`
         are wanted and the camera renders any.  While the state's bins are in step with the cloud (every frame so far filed, frames

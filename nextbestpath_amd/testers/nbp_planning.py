@@ -83,9 +83,14 @@ class Rollout(lockstep.LockstepRollout):
         self.gt = gt_scene_pc.contiguous()
         self.bbox = (self.gt.min(0).values.tolist(), self.gt.max(0).values.tolist())
         self.cov_plan = hipops.CoveragePlan(self.gt, 1.0, 2, self.bbox)          # GT sorted once per rollout
-        # the planning option `recon_metrics` (None = off: nothing is built or launched; True; a dict thresholds / cap / cell)
+        # the planning option `recon_metrics` (None = off: nothing is built or launched; True; a dict thresholds / cap / cell / curve)
         self.recon_spec = recon_options.option_spec(recon_metrics)
-        self.recon = hipops.ReconMetrics(self.gt, self.bbox, **self.recon_spec) if self.recon_spec is not None else None
+        self.recon, self.recon_curve, self._curve_frames = None, None, 0
+        if self.recon_spec is not None:
+            kw = recon_options.metrics_kwargs(self.recon_spec)
+            self.recon = hipops.ReconMetrics(self.gt, self.bbox, **kw)
+            if self.recon_spec.get("curve"):    # ... with `curve`: the same metrics after every step, updated incrementally (pre)
+                self.recon_curve = hipops.ReconCurve(self.gt, self.bbox, **kw, plan=self.recon.plan)
         self._recon_default = None
         self.path, self.path_record = [], 0
         self.collision_list, self.passable_list, self.idx_history = [], [], []
@@ -104,6 +109,7 @@ class Rollout(lockstep.LockstepRollout):
         # clears the maps, and the build below is the page launch alone (nbp_step_maps_prefiled_f32; bit-identical maps)
         prefiled = st.frames_filed == st.frames_appended
         self.count_coverage()
+        self.update_recon_curve()          # (option `recon_metrics` with `curve`: row pose_i = the cloud the coverage just saw)
         self.unproject(lockstep.CURRENT, True, clear=(st.maps6, net_in[0, 4]) if prefiled else None)
         prefiled = prefiled and st.frames_filed == st.frames_appended
         # S5-S7 in one call: six maps, trajectory channel, network input
@@ -232,6 +238,16 @@ class Rollout(lockstep.LockstepRollout):
         rec.evaluate(self.st.cloud, self.st.cloud_count)
         return rec.raw() if raw else rec.summary()
 
+    def reconstruction_curve(self, n, raw=False):
+        """The per-step reconstruction curve (the option `recon_metrics` with `curve`): entry s is the metric of the WHOLE cloud as
+        step s found it -- the cloud that coverage[s] was counted on -- from the incremental device state (hipops.ReconCurve), read
+        back with one copy: the dict of lists of utility/recon_metrics.py::summarise_curve, or with raw=True the float64 rows
+        [n, 6 + 2 T] behind it (what travels between ranks)."""
+        if self.recon_curve is None:
+            raise RuntimeError("reconstruction_curve: the rollout was built without recon_metrics = {..., 'curve': True}")
+        self.finish()
+        return self.recon_curve.raw(n) if raw else self.recon_curve.curve(n)
+
     def coverage_evolution(self, n):
         self.finish()
         counts = self.st.coverage_counts[:n].cpu().numpy()
@@ -333,6 +349,9 @@ class MultiRollout:
         """Rollout.pre for every rollout of the group, each latency-bound stage as ONE batched launch (identical results)."""
         grp, net_in = self.groups[gi], self.net_in[gi]
         hipops.coverage_count_batch([r.coverage_item() for r in grp])
+        curves = [it for it in (r.recon_curve_item() for r in grp) if it is not None]
+        if curves:                         # the option `recon_metrics` with `curve`: ONE call for the group
+            hipops.recon_curve_update_batch(curves)
         lockstep.unproject_group(grp, lockstep.CURRENT, True)
         hu.step_maps_batch([r.maps_item() for r in grp], grp[0].S, grp[0].grid_range, self.maps6[gi], net_in)
         for i, r in enumerate(grp):
@@ -547,6 +566,10 @@ def _result(ro, n_poses):
         raw = ro.reconstruction_metrics(raw=True)
         res["reconstruction"] = recon_options.summarise_raw(raw, ro.recon.thresholds, ro.recon.cap)
         res["reconstruction_raw"] = raw.tolist()       # the sums and counts behind the ratios (parallel_rollout.gather_reconstruction)
+        if ro.recon_curve is not None:                 # ... with `curve`: the same metrics per step (gather_reconstruction_curve)
+            rows = ro.reconstruction_curve(n_poses, raw=True)
+            res["reconstruction_curve"] = recon_options.summarise_curve(rows, ro.recon.thresholds, ro.recon.cap)
+            res["reconstruction_curve_raw"] = rows.tolist()
     return res
 
 
@@ -600,14 +623,15 @@ def test_nbp_planning(params_file, model_file, results_json_file, numGPU, test_s
     BASELINE.json configs[4] (512 grid at the same 0.3125 units per pixel, bf16 convolutions).  `symmetry_ensemble` (None = off, a
     name of utility/augment.py::ENSEMBLES or a list of op codes) is NBP.symmetry_ensemble of the loaded network; not given, it is
     the key of that name in the configs/test/ file load_params read last (absent there: off).  `recon_metrics` (None = off, True =
-    the defaults, or a dict with thresholds / cap / cell; not given, the key of that name in the same file) adds the reconstruction
-    quality of every rollout's final cloud (utility/recon_metrics.py) to its record, next to coverage and auc.  `depth_noise` (None =
+    the defaults, or a dict with thresholds / cap / cell / curve; not given, the key of that name in the same file) adds the reconstruction
+    quality of every rollout's final cloud (utility/recon_metrics.py) to its record, next to coverage and auc, and with `curve` the same
+    metrics after every step ("reconstruction_curve": lists over the steps, with their AUCs).  `depth_noise` (None =
     off: perfect depth; a dict of utility/depth_noise.py::option_spec; not given, the key of that name in the same file) puts the seeded
     sensor model between the rasteriser and every consumer of depth, and the normalised spec into every record.  Under torchrun the flattened
     (scene, start pose) runs are sharded round-robin over the ranks and the coverage curves are
     gathered with ONE all_gather over RCCL (backend "nccl" on ROCm; "gloo" on CPU-only hosts)."""
     import time
-    from ..parallel_rollout import gather_reconstruction, gather_results, init_distributed, shard
+    from ..parallel_rollout import gather_reconstruction, gather_reconstruction_curve, gather_results, init_distributed, shard
     t_start = time.perf_counter()
     here = os.path.dirname(os.path.abspath(__file__))
     configs_dir = configs_dir or os.path.join(here, "../../configs/macarons")
@@ -657,6 +681,12 @@ def test_nbp_planning(params_file, model_file, results_json_file, numGPU, test_s
             r.pop("reconstruction_raw", None)
             if rank == 0:
                 r["reconstruction"] = recon[r["run_id"]]
+        if recon_spec.get("curve"):                    # a third gather: the per-step rows
+            curves = gather_reconstruction_curve(results, runs, rank, world, device, recon_spec["thresholds"], recon_spec["cap"], n_poses)
+            for r in gathered:
+                r.pop("reconstruction_curve_raw", None)
+                if rank == 0:
+                    r["reconstruction_curve"] = curves[r["run_id"]]
     if rank == 0:
         out = {}
         for r in gathered:
@@ -664,6 +694,8 @@ def test_nbp_planning(params_file, model_file, results_json_file, numGPU, test_s
             rec = {"coverage": r["coverage"], "auc": r["auc"]}
             if recon_spec is not None:
                 rec["reconstruction"] = r["reconstruction"]
+                if recon_spec.get("curve"):
+                    rec["reconstruction_curve"] = r["reconstruction_curve"]
             if noise_spec is not None:
                 rec["depth_noise"] = dict(noise_spec)
             for key in ("X_cam_history", "V_cam_history"):      # histories of other ranks stay in their part files

@@ -3,6 +3,7 @@
 the reference-API mirrors and the GPU parity tests."""
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import math
 
@@ -1122,3 +1123,128 @@ class ReconMetrics:
         """The last evaluation as the dict of recon_metrics.summarise (ratios formed on the host from the raw sums and counts)."""
         from . import recon_metrics
         return recon_metrics.summarise_raw(self.raw(), self.thresholds, self.cap)
+
+
+_CurveItem = collections.namedtuple("_CurveItem", "curve cloud n_dev row new_bound")      # what ReconCurve.item hands out
+
+
+class ReconCurve:
+    """The reconstruction metrics after every step of a rollout, updated incrementally on the device (recon_metrics.CurveReference is
+    the definition; csrc/nbp_recon.hip the kernels).  Owns the running per-GT-point minimum `d2_gt` fp32 [G] (the GT's order), the
+    watermark `seen` (int64: the cloud rows already taken in), the running accuracy totals and `rows` float64 [n_rows, 6 + 2 T]
+    (recon_metrics.pack_raw's layout).  n_rows defaults to a row per step of a rollout and a spare (lockstep.N_POSES + 1).
+    bbox = (lo, hi) of the GT on the host: it has to hold every GT point (checked once, here).  plan: the NNPlan of a ReconMetrics
+    over the same GT, box and cell, shared instead of sorting the GT again."""
+
+    def __init__(self, gt, bbox, thresholds=(1.0,), cap=5.0, cell=1.0, n_rows=102, plan=None):
+        from . import recon_metrics
+        self.thresholds, self.cap, self.cell = recon_metrics.check_options(thresholds, cap, cell)
+        _nn_points("ReconCurve", gt, "gt")
+        if gt.shape[0] < 1:
+            raise ValueError("ReconCurve: an empty GT surface")
+        if int(n_rows) < 1:
+            raise ValueError("ReconCurve: n_rows >= 1 expected")
+        self.gt, self.G, self.n_rows = gt, gt.shape[0], int(n_rows)
+        dev = gt.device
+        blo, bhi = torch.tensor(bbox[0], dtype=torch.float32, device=dev), torch.tensor(bbox[1], dtype=torch.float32, device=dev)
+        if tuple(blo.shape) != (3,) or tuple(bhi.shape) != (3,) or not bool(((gt >= blo) & (gt <= bhi)).all()):
+            raise ValueError("ReconCurve: bbox = (lo [3], hi [3]) holding every GT point expected")
+        lo, hi = recon_metrics.grown_box(bbox[0], bbox[1], self.cap)
+        self.box = (lo.tolist(), hi.tolist())
+        if plan is None:
+            plan = NNPlan(gt, self.box, self.cell)
+        elif (not isinstance(plan, NNPlan) or plan.plan.device != dev or plan.T != self.G or plan.cell != self.cell
+              or plan.target.data_ptr() != gt.data_ptr() or [list(plan.lo), list(plan.hi)] != [list(v) for v in _nn_box(self.box)]):
+            raise ValueError("ReconCurve: plan must be the NNPlan of the same GT tensor, grown box and cell")
+        self.plan = plan
+        L = _lib.lib()
+        T = len(self.thresholds)
+        self.width = recon_metrics.RAW_HEAD + 2 * T
+        self.d2_gt = torch.empty(self.G, dtype=torch.float32, device=dev)
+        self.seen = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.totals = torch.zeros(L.nbp_recon_curve_totals_bytes() // 8, dtype=torch.int64, device=dev)
+        self.rows = torch.zeros(self.n_rows, self.width, dtype=torch.float64, device=dev)
+        self._d2_new = None                # the new points' own distances: scratch, one entry per cloud row (made by the first item)
+        self.reset()
+
+    def reset(self):
+        """An empty cloud again: every GT point at the cap, no point seen, zero totals and rows.  Enqueue-only."""
+        import numpy as np
+        self.d2_gt.fill_(float(np.float32(self.cap) * np.float32(self.cap)))
+        self.seen.zero_()
+        self.totals.zero_()
+        self.rows.zero_()
+
+    def item(self, cloud, n_dev, row, new_bound):
+        """The arguments of recon_curve_update_batch for one update: the cloud rows [seen, min(n_dev, capacity)) are taken in and the
+        metrics of the cloud so far go into rows[row].  new_bound: host bound of the number of new rows (it only sizes the grid)."""
+        _nn_points("ReconCurve.item", cloud, "cloud")
+        if cloud.device != self.gt.device:
+            raise ValueError("ReconCurve.item: cloud on the GT's device expected")
+        if n_dev is None:
+            raise ValueError("ReconCurve.item: the cloud's device counter is needed (both ends of the new range are read on the device)")
+        _nn_count("ReconCurve.item", n_dev, cloud.device)
+        if cloud.shape[0] < 1:
+            raise ValueError("ReconCurve.item: a cloud buffer of at least one row expected")
+        if isinstance(row, bool) or not isinstance(row, int) or not 0 <= row < self.n_rows:
+            raise ValueError(f"ReconCurve.item: row {row!r} outside [0, {self.n_rows})")
+        if int(new_bound) < 0:
+            raise ValueError("ReconCurve.item: new_bound >= 0 expected")
+        if self._d2_new is None or self._d2_new.shape[0] < cloud.shape[0]:
+            self._d2_new = torch.empty(cloud.shape[0], dtype=torch.float32, device=cloud.device)
+        return _CurveItem(self, cloud, n_dev, row, int(new_bound))
+
+    def update(self, cloud, n_dev, row, new_bound):
+        """One update (the batch of one) -> rows[row] on the device."""
+        recon_curve_update_batch([self.item(cloud, n_dev, row, new_bound)])
+        return self.rows[row]
+
+    def raw(self, n):
+        """The first n rows on the host, numpy float64 [n, 6 + 2 T], in ONE device -> host copy."""
+        if not 0 <= int(n) <= self.n_rows:
+            raise ValueError(f"ReconCurve.raw: n outside [0, {self.n_rows}]")
+        return self.rows[:int(n)].cpu().numpy()
+
+    def curve(self, n):
+        """The first n rows as recon_metrics.summarise_curve's dict of lists (ratios formed on the host)."""
+        from . import recon_metrics
+        return recon_metrics.summarise_curve(self.raw(n), self.thresholds, self.cap)
+
+
+def recon_curve_update_batch(items):
+    """ReconCurve.update for several curves (items = [ReconCurve.item(...)]) in three launches whatever their number up to 16; more
+    go in chunks of 16.  Each item's results are bit for bit those of a call of its own.  No host synchronisation."""
+    import numpy as np
+    if not items:
+        return
+    for it in items:
+        if not isinstance(it, _CurveItem):
+            raise ValueError("recon_curve_update_batch: items made by ReconCurve.item expected")
+    dev = items[0][1].device
+    if any(it[1].device != dev for it in items):
+        raise ValueError("recon_curve_update_batch: the items of one call on one device expected")
+    if len({id(it[0]) for it in items}) != len(items):
+        raise ValueError("recon_curve_update_batch: a curve appears twice (its updates are ordered: one call each)")
+    if len(items) > 16:
+        for i in range(0, len(items), 16):
+            recon_curve_update_batch(items[i:i + 16])
+        return
+    n = len(items)
+    VP, LL, I = C.c_void_p, C.c_longlong, C.c_int
+    plans, cloud, count, seen, d2g, d2n, tot, row = [(VP * n)() for _ in range(8)]
+    G, T, capacity, bound = (I * n)(), (I * n)(), (LL * n)(), (LL * n)()
+    lo, hi = np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32)
+    cell, cap, th = np.zeros(n, np.float32), np.zeros(n, np.float32), np.zeros((n, 8), np.float32)
+    for i, (cv, pc, n_dev, r, nb) in enumerate(items):
+        plans[i], cloud[i], count[i], seen[i] = cv.plan.plan.data_ptr(), pc.data_ptr(), n_dev.data_ptr(), cv.seen.data_ptr()
+        d2g[i], d2n[i], tot[i], row[i] = cv.d2_gt.data_ptr(), cv._d2_new.data_ptr(), cv.totals.data_ptr(), cv.rows[r].data_ptr()
+        G[i], T[i], capacity[i], bound[i] = cv.G, len(cv.thresholds), pc.shape[0], nb
+        lo[i], hi[i], cell[i], cap[i] = list(cv.plan.lo), list(cv.plan.hi), cv.cell, cv.cap
+        th[i, :len(cv.thresholds)] = cv.thresholds
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        ws = _workspace_for("recon_curve", 16, lambda: L.nbp_recon_curve_workspace_bytes(16), dev)
+        rc = L.nbp_recon_curve_update_batch_f32(n, plans, G, lo.ctypes.data, hi.ctypes.data, cell.ctypes.data, cap.ctypes.data, cloud,
+                                                capacity, count, seen, d2g, d2n, tot, T, th.ctypes.data, row, bound, _lib.ptr(ws),
+                                                ws.numel(), _st())
+    _lib.check(rc, "nbp_recon_curve_update_batch_f32")

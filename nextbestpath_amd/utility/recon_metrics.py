@@ -40,16 +40,27 @@ def check_options(thresholds=DEFAULT_THRESHOLDS, cap=DEFAULT_CAP, cell=DEFAULT_C
 
 def option_spec(option):
     """The planning option `recon_metrics` -> None (off) or the keyword dict of hipops.ReconMetrics: None / False = off, True = the
-    defaults, a dict with any of `thresholds`, `cap`, `cell`."""
+    defaults, a dict with any of `thresholds`, `cap`, `cell` and `curve` (bool: the per-step curve as well; whoever passes the spec to
+    hipops.ReconMetrics strips that key first, metrics_kwargs)."""
     if option is None or option is False:
         return None
     if option is True:
         option = {}
-    if not isinstance(option, dict) or set(option) - {"thresholds", "cap", "cell"}:
-        raise ValueError("recon_metrics: None, True or a dict with the keys thresholds / cap / cell expected")
+    if not isinstance(option, dict) or set(option) - {"thresholds", "cap", "cell", "curve"}:
+        raise ValueError("recon_metrics: None, True or a dict with the keys thresholds / cap / cell / curve expected")
+    if not isinstance(option.get("curve", False), bool):
+        raise ValueError("recon_metrics: curve must be true or false")
     ts, cap, cell = check_options(option.get("thresholds", DEFAULT_THRESHOLDS), option.get("cap", DEFAULT_CAP),
                                   option.get("cell", DEFAULT_CELL))
-    return {"thresholds": ts, "cap": cap, "cell": cell}
+    spec = {"thresholds": ts, "cap": cap, "cell": cell}
+    if option.get("curve", False):  # the per-step curve (CurveReference / hipops.ReconCurve); the key is there only when it is on
+        spec["curve"] = True
+    return spec
+
+
+def metrics_kwargs(spec):
+    """A normalised spec without the keys that hipops.ReconMetrics / ReconCurve do not take (`curve`)."""
+    return {k: v for k, v in spec.items() if k != "curve"}
 
 
 def grown_box(bbox_lo, bbox_hi, cap):
@@ -164,3 +175,67 @@ def reference(cloud, gt, thresholds=DEFAULT_THRESHOLDS, cap=DEFAULT_CAP):
     acc_sums, acc_counts = stats_reference(nn_dist2_reference(cloud, gt, lo, hi, cap), ts)
     comp_sums, comp_counts = stats_reference(nn_dist2_reference(gt, cloud, lo, hi, cap), ts)
     return summarise(acc_sums, acc_counts, cloud.shape[0], comp_sums, comp_counts, gt.shape[0], ts, cap)
+
+
+# ---- the per-step curve: the same metrics after every step, updated incrementally
+class CurveReference:
+    """The definition of the per-step curve (numpy; the device path is hipops.ReconCurve).  The cloud is append-only and the GT
+    fixed, so both directions are incremental and equal the whole-cloud definition: a point's nearest GT distance never changes
+    (accuracy: each point is queried once, in the update that appends it; sums and counts accumulate), and the minimum over a union
+    is the minimum of the minima (completeness: a running per-GT-point minimum is lowered by the new points only).
+
+    State: d2_gt fp32 [G] in the GT's order (fl(cap cap) at the start), acc_sums float64 [2], acc_counts int64 [T], n_rec."""
+
+    def __init__(self, gt, thresholds=DEFAULT_THRESHOLDS, cap=DEFAULT_CAP, bbox=None):
+        self.thresholds, self.cap, _ = check_options(thresholds, cap)
+        self.gt = np.ascontiguousarray(np.asarray(gt, np.float32).reshape(-1, 3))
+        if self.gt.shape[0] < 1:
+            raise ValueError("recon metrics: an empty GT surface")
+        bbox = (self.gt.min(0), self.gt.max(0)) if bbox is None else bbox
+        self.lo, self.hi = grown_box(bbox[0], bbox[1], self.cap)       # exactly as reference() forms it
+        self.reset()
+
+    def reset(self):
+        T = len(self.thresholds)
+        self.d2_gt = np.full(self.gt.shape[0], np.float32(self.cap) * np.float32(self.cap), np.float32)
+        self.acc_sums, self.acc_counts, self.n_rec = np.zeros(2, np.float64), np.zeros(T, np.int64), 0
+        self.rows = []
+
+    def update(self, new_points):
+        """Appends `new_points` [n,3] (n = 0: the previous row again) -> the row: pack_raw's float64 vector [6 + 2 T]."""
+        new = np.asarray(new_points, np.float32).reshape(-1, 3)
+        if new.shape[0]:
+            sums, counts = stats_reference(nn_dist2_reference(new, self.gt, self.lo, self.hi, self.cap), self.thresholds)
+            self.acc_sums = self.acc_sums + sums
+            self.acc_counts = self.acc_counts + counts
+            self.n_rec += new.shape[0]
+            self.d2_gt = np.fmin(self.d2_gt, nn_dist2_reference(self.gt, new, self.lo, self.hi, self.cap))
+        row = pack_raw(self.acc_sums, self.acc_counts, self.n_rec, *stats_reference(self.d2_gt, self.thresholds), self.gt.shape[0])
+        self.rows.append(row)
+        return row
+
+
+def curve_auc(values, dx=1 / 40):
+    """long_term_utils.compute_auc's rule (the coverage `auc`: the trapezoid rule with step dx plus y[0] dx / 2; repeated here, this
+    module imports no torch) over a list; None where the list holds a None (a ratio without a denominator) or is empty."""
+    if not values or any(v is None for v in values):
+        return None
+    y = np.asarray(values, np.float64)
+    trap = getattr(np, "trapezoid", None) or np.trapz
+    return float(trap(y, dx=dx) + y[0] * dx / 2.0)
+
+
+def summarise_curve(rows, thresholds, cap, dx=1 / 40):
+    """Raw rows [n][6 + 2 T] -> a JSON-safe dict of lists, one entry per row, every entry from summarise_raw: n_points,
+    accuracy_mean, accuracy_rmse, completeness_mean, completeness_rmse, chamfer, thresholds = [{threshold, precision, recall,
+    fscore}] (each a list), and auc = {"recall": [per threshold], "fscore": [...]} over the rows.  None where a ratio has no
+    denominator, and for an AUC over a list that holds one; never a NaN."""
+    ts = [float(t) for t in thresholds]
+    rows = np.asarray(rows, np.float64).reshape(-1, RAW_HEAD + 2 * len(ts))
+    per = [summarise_raw(r, ts, cap) for r in rows]
+    out = {k: [p[k] for p in per] for k in ("n_points", "accuracy_mean", "accuracy_rmse", "completeness_mean", "completeness_rmse",
+                                            "chamfer")}
+    out["thresholds"] = [{"threshold": t, **{k: [p["thresholds"][i][k] for p in per] for k in ("precision", "recall", "fscore")}}
+                         for i, t in enumerate(ts)]
+    out["auc"] = {k: [curve_auc(block[k], dx) for block in out["thresholds"]] for k in ("recall", "fscore")}
+    return out
