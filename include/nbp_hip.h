@@ -14,7 +14,11 @@
  *    memory: scratch comes in through (ws, ws_bytes) sized by the matching *_workspace_bytes;
  *  - activations inside the network are NHWC fp32; the public tensors keep the reference's
  *    NCHW layout ([B,5,S,S] in, [B,8,S/4,S/4] and [B,1,S,S] out);
- *  - no exceptions cross the boundary, no global mutable state besides the explicit handle.
+ *  - no exceptions cross the boundary, no global mutable state besides the explicit handle;
+ *  - this project's own ctypes binding (nextbestpath_amd/_lib.py) reads its signatures from the declarations below, so a new
+ *    entry point is declared here, defined in csrc/, and is bound.  For that a declaration has the form
+ *    `<ret> nbp_<name>(<params>);` with int, unsigned, long long, unsigned long long, float, double, size_t (or a void return)
+ *    and pointers only: no other scalar type, array parameter or function pointer, and comments in the C form.
  */
 #ifndef NBP_HIP_H
 #define NBP_HIP_H
