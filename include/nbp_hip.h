@@ -1116,6 +1116,45 @@ int nbp_depth_noise_batch_f32(int n, const float* const* clean, float* const* ou
                               int H, int W, float sigma_base, float sigma_quad, float z_min, unsigned drop_thr, float edge_threshold,
                               void* stream);
 
+/* ---- Held-out view metrics (csrc/nbp_views.hip; the definition, which the kernels equal, is
+ * nextbestpath_amd/utility/view_metrics.py).  Not in the reference.  A point-splat render of a cloud [n][3] that is on
+ * the device from n_views cameras (cams_host [n_views][12]: R row-major then T, on the HOST; they travel as kernel arguments in
+ * chunks of 8), and its comparison with a mesh render of the same cameras.
+ *   nbp_views_splat_f32   keys [n_views][H][W] uint64: per pixel the smallest (float bits of v2) << 32 | point index over the points
+ *                         whose (2 radius + 1)^2 footprint, clipped to the image, holds the pixel; ~0 = empty.  A point takes part iff
+ *                         z_clip < v2 < z_far and its NDC coordinates are finite; its pixel is the inverse of the un-projection's NDC
+ *                         tables in fp32 (view_metrics.project, bit for bit).  n: host bound of the rows, and the int64 device counter
+ *                         where given (rows at or beyond it are never read).  The call sets the keys to ~0 first unless accumulate
+ *                         != 0; the merge is a 64-bit atomicMin, behind a plain load that skips it where the stored key is already
+ *                         lower (precheck != 0; 0 = every pixel goes to the atomic: the same bits).  A minimum is order-free: two
+ *                         runs give the same bits, and so does a cloud splatted in parts into the same keys -- each part at its
+ *                         own row positions in cloud3 (the index in a key is the row; there is no first-index argument: rows
+ *                         that are not part of a call are masked with NaN, or lie beyond its count).  One launch per 8 views.
+ *   nbp_views_resolve_f32 the rendered images: z_c [n_views][H][W] (-1 where empty), rgb_c [..][3] = cloud_rgb[index] (0 where
+ *                         empty), index int64 (-1 where empty); each output may be null.  n_cloud = rows of the cloud the keys were
+ *                         made from (and of cloud_rgb): a key whose index is at or beyond it reads as empty, never as an address.
+ *   nbp_views_stats_f64   resolve + classify + reduce in two launches of a fixed geometry (per-thread strided partials, a fixed tree
+ *                         in the block, one stored row per block, rows added in index order; no floating-point atomics: two runs give
+ *                         the same bits).  With gt = z_gt > -1 and z_gt < z_far, c = pixel not empty, dz = z_c - z_gt in fp32:
+ *                         counts6 [n_views][6] int64 = n_gt, n_c, n_hit (gt, c, |dz| <= tol), n_hole (gt, not c), n_leak (gt, c,
+ *                         dz > tol), n_floater (c and (not gt or dz < -tol)); sums3 [n_views][3] float64 over the hit pixels = sum
+ *                         |dz|, sum dz^2, squared colour error over the three channels (differences in float64 from the fp32 values;
+ *                         0 where cloud_rgb or rgb_gt is null).  ws: nbp_views_stats_workspace_bytes(n_views) (0 where it would fail).
+ * No allocation, no host synchronisation.  NBP_E_ARG: a null pointer, n_views < 1, H or W < 2, radius outside 0..4, a negative count,
+ * a tolerance that is negative or not finite, in the splat tan_half_fov <= 0, z_clip <= 0 or z_far <= z_clip, in the statistics
+ * (which take no z_clip) z_far <= 0; NBP_E_SHAPE: H W > 2^29, a cloud of 2^32 - 1 points or more (the key's
+ * low word is the index), more than 65535 views in the statistics, keys / index / counts6 / sums3 off the 8-byte grid; NBP_E_WS.
+ * Nothing is written on an error. */
+int nbp_views_splat_f32(const float* cloud3, long long n, const long long* n_dev_or_null, const float* cams_host, int n_views, int H,
+                        int W, int radius, float tan_half_fov, float z_clip, float z_far, int accumulate, int precheck,
+                        unsigned long long* keys, void* stream);
+int nbp_views_resolve_f32(const unsigned long long* keys, const float* cloud_rgb_or_null, long long n_cloud, int n_views, int H, int W,
+                          float* z_c_or_null, float* rgb_c_or_null, long long* index_or_null, void* stream);
+size_t nbp_views_stats_workspace_bytes(int n_views);
+int nbp_views_stats_f64(const unsigned long long* keys, const float* cloud_rgb_or_null, long long n_cloud, const float* z_gt,
+                        const float* rgb_gt_or_null, int n_views, int H, int W, float depth_tolerance, float z_far,
+                        long long* counts6, double* sums3, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

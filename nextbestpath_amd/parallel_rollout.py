@@ -5,7 +5,7 @@ runs them in nested loops on one GPU), so rank r takes runs r, r+W, r+2W, ... an
 collective is ONE all_gather of a padded fp32 tensor [runs_per_rank, n_poses + 3] holding
 (run id, final coverage, AUC, coverage curve) -- a few KB over RCCL/xGMI, latency bound (with the
 planning option `recon_metrics` on, a second one of float64 sums and counts: gather_reconstruction; with its `curve`, a third of the
-per-step rows: gather_reconstruction_curve).  One
+per-step rows: gather_reconstruction_curve; with the option `view_metrics`, one of the per-view counts and sums: gather_views).  One
 process per GPU; backend "nccl" (= RCCL on ROCm) with CUDA tensors, "gloo" on CPU-only hosts
 (that path is what the world_size-2 CPU tests exercise)."""
 from __future__ import annotations
@@ -154,3 +154,33 @@ def gather_reconstruction_curve(results, runs, rank, world, device, thresholds, 
     if rank != 0:
         return {}
     return {int(row[0]): recon_metrics.summarise_curve(row[1:].reshape(n_poses, per), thresholds, cap) for row in t if row[0] >= 0}
+
+
+def gather_views(results, runs, rank, world, device, options):
+    """The planning option `view_metrics`: all ranks call this behind gather_results, and only when the option is on.  The raw
+    float64 counts and sums of every run's held-out views (results[i]["views_raw"]: up to options["views"] rows of
+    utility/view_metrics.py::pack_raw's 9 numbers; a scene with fewer reachable poses has fewer) travel in ONE all_gather of a
+    padded float64 tensor [runs_per_rank, 2 + 9 views] (run id, number of views, rows; pad rows = -1) -- a gather of its own: the
+    others keep their shapes with the option off.  Rank 0 forms the ratios from them -> {run id: summarise_raw's dict with
+    `options` (view_metrics.resolved_options: the same for every run)}; the other ranks get {}."""
+    from .utility import view_metrics
+    rows, per, n_max = runs_per_rank(len(runs), world), view_metrics.RAW_WIDTH, int(options["views"])
+    width = 2 + n_max * per
+    t = np.full((rows, width), -1.0, np.float64)
+    for j, r in enumerate(results):
+        raw = np.asarray(r["views_raw"], np.float64).reshape(-1, per)
+        if raw.shape[0] > n_max:
+            raise ValueError(f"gather_views: a run with {raw.shape[0]} views, above the option's {n_max}")
+        t[j, 0], t[j, 1] = r["run_id"], raw.shape[0]
+        t[j, 2:2 + raw.size] = raw.reshape(-1)
+    collective = world > 1 or group_is_up()
+    if collective:
+        import torch.distributed as dist
+        local = torch.from_numpy(t).to(collective_device(device))
+        buf = [torch.empty_like(local) for _ in range(world)]
+        dist.all_gather(buf, local)
+        t = torch.stack(buf).cpu().numpy().reshape(-1, width)
+    if rank != 0:
+        return {}
+    return {int(row[0]): view_metrics.summarise_raw(row[2:2 + int(row[1]) * per].reshape(int(row[1]), per), options)
+            for row in t if row[0] >= 0}

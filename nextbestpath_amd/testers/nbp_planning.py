@@ -32,6 +32,7 @@ from ..utility import hipops
 from ..utility import depth_noise as noise_options
 from ..utility import recon_metrics as recon_options
 from ..utility import utils as hu
+from ..utility import view_metrics as view_options
 from ..utility.long_term_utils import LatticePlanner, compute_auc
 
 # Rollout.step: the step's forward on a stream of its own, behind the map stage by an event.  The reference runs the network at
@@ -56,7 +57,7 @@ class Rollout(lockstep.LockstepRollout):
     """One exploration rollout, steppable (bench.py times K consecutive ``step()`` calls)."""
 
     def __init__(self, params, nbp, camera, gt_scene_pc, mesh, mesh_for_check, y_bins, device, state=None, seed=0,
-                 grid=256, symmetry_ensemble=_UNSET, recon_metrics=None):
+                 grid=256, symmetry_ensemble=_UNSET, recon_metrics=None, view_metrics=None):
         self.params, self.nbp, self.camera, self.mesh, self.mesh_for_check = params, nbp, camera, mesh, mesh_for_check
         _set_symmetry_ensemble(nbp, params, symmetry_ensemble)
         self.y_bins, self.device = y_bins, device
@@ -92,6 +93,13 @@ class Rollout(lockstep.LockstepRollout):
             if self.recon_spec.get("curve"):    # ... with `curve`: the same metrics after every step, updated incrementally (pre)
                 self.recon_curve = hipops.ReconCurve(self.gt, self.bbox, **kw, plan=self.recon.plan)
         self._recon_default = None
+        # the planning option `view_metrics` (None = off: nothing is built or launched; True; a dict of utility/view_metrics.py): the
+        # coloured cloud rendered from held-out lattice poses against the mesh, once, at the rollout's end
+        self.view_spec = view_options.option_spec(view_metrics)
+        # where the rollout starts: the root of the held-out poses
+        self._start_ijk = None if camera.cam_idx is None else tuple(int(v) for v in camera.cam_idx[:3])
+        self.views = self._build_views(self.view_spec) if self.view_spec is not None else None
+        self._views_default = None
         self.path, self.path_record = [], 0
         self.collision_list, self.passable_list, self.idx_history = [], [], []
         self.step_seed = seed * 1_000_003
@@ -237,6 +245,33 @@ class Rollout(lockstep.LockstepRollout):
             rec = self._recon_default = hipops.ReconMetrics(self.gt, self.bbox, **recon_options.option_spec(True))
         rec.evaluate(self.st.cloud, self.st.cloud_count)
         return rec.raw() if raw else rec.summary()
+
+    def _build_views(self, spec):
+        """hipops.ViewMetrics of the held-out poses of `spec` (view_metrics.choose_views over the planner's lattice from the
+        rollout's start position), with the options it is made with as `.options`."""
+        cam, pl = self.camera, self.planner
+        opts = view_options.resolved_options(spec, cam.image_height, cam.image_width, self.params.zfar)
+        picks = view_options.choose_views(pl.nbrs, pl.mesh_hit, pl.node_index[self._start_ijk], opts["views"], opts["seed"])
+        cams = np.stack([cam.cam12_of_pose(cam.pose_from_idx((*pl.idx3_list[node], 2, heading))) for node, heading in picks])
+        vm = hipops.ViewMetrics(self.mesh, cams, opts["height"], opts["width"], radius=opts["radius"],
+                                depth_tolerance=opts["depth_tolerance"], z_far=opts["z_far"], ambient=cam.ambient,
+                                contrast=cam.contrast_factor, colours=cam.renders_colours)
+        vm.options = opts
+        return vm
+
+    def view_metrics(self, raw=False):
+        """Held-out view metrics of the WHOLE coloured cloud so far: the dict of utility/view_metrics.py::summarise_raw (the share of
+        the visible surface that is filled at the right depth, holes, leaks, floaters, depth error and PSNR, with the options used),
+        or with raw=True the float64 rows [views, 9] behind it (what travels between ranks).  Evaluated on the device
+        (hipops.ViewMetrics: splat and statistics, no host synchronisation), read back with one copy.  With the rollout's own
+        `view_metrics` option, or the defaults where it was built without one."""
+        self.finish()
+        vm = self.views or self._views_default
+        if vm is None:              # (kept apart from self.views: a rollout built with the option off keeps reporting as such)
+            vm = self._views_default = self._build_views(view_options.option_spec(True))
+        rgb = self.st.cloud_rgb if self.camera.renders_colours else None
+        vm.evaluate(self.st.cloud, rgb, self.st.cloud_count)
+        return vm.raw() if raw else vm.summary(vm.options)
 
     def reconstruction_curve(self, n, raw=False):
         """The per-step reconstruction curve (the option `recon_metrics` with `curve`): entry s is the metric of the WHOLE cloud as
@@ -500,6 +535,7 @@ def compute_nbp_trajectory(params, nbp, camera, gt_scene_pc, mesh, mesh_for_chec
 _test_config_ensemble = [_UNSET]
 _test_config_recon = [_UNSET]            # ... and its `recon_metrics` key, the same way
 _test_config_noise = [_UNSET]            # ... and its `depth_noise` key
+_test_config_views = [_UNSET]            # ... and its `view_metrics` key
 
 
 def load_params(path):
@@ -525,6 +561,7 @@ def load_params(path):
         _test_config_ensemble[0] = getattr(p, "symmetry_ensemble", _UNSET)
         _test_config_recon[0] = getattr(p, "recon_metrics", _UNSET)
         _test_config_noise[0] = getattr(p, "depth_noise", _UNSET)
+        _test_config_views[0] = getattr(p, "view_metrics", _UNSET)
     return p
 
 
@@ -540,7 +577,7 @@ def list_runs(dataset, params):
 
 
 def build_rollout(params, nbp, dataset, run, device, test_resolution=0.05, state=None, seed=0, grid=256, recon_metrics=None,
-                  depth_noise=None):
+                  depth_noise=None, view_metrics=None):
     """Scene + GT surface + camera + Rollout for one (scene, start pose) run (nbp_planning.py:414-492).  `depth_noise`: the camera's
     sensor model (utility/depth_noise.py; None = off, perfect depth)."""
     si, k = run
@@ -551,7 +588,8 @@ def build_rollout(params, nbp, dataset, run, device, test_resolution=0.05, state
     y_bins = sim_scene.y_bins_for(mesh.verts_host, 4)
     _, gt_dev = sim_scene.setup_gt_scene(params, settings, mesh, device, test_resolution, seed=seed)
     camera = setup_test_camera(params, mesh, settings.camera.start_positions[k], settings, device, seed=seed, depth_noise=depth_noise)
-    ro = Rollout(params, nbp, camera, gt_dev, mesh, mesh, y_bins, device, state, seed, grid, recon_metrics=recon_metrics)
+    ro = Rollout(params, nbp, camera, gt_dev, mesh, mesh, y_bins, device, state, seed, grid, recon_metrics=recon_metrics,
+                 view_metrics=view_metrics)
     ro.scene_name, ro.start = sd["scene_name"], k
     return ro
 
@@ -570,13 +608,17 @@ def _result(ro, n_poses):
             rows = ro.reconstruction_curve(n_poses, raw=True)
             res["reconstruction_curve"] = recon_options.summarise_curve(rows, ro.recon.thresholds, ro.recon.cap)
             res["reconstruction_curve_raw"] = rows.tolist()
+    if ro.views is not None:        # the option `view_metrics`: the whole coloured cloud from the held-out poses, once, at the end
+        raw = ro.view_metrics(raw=True)
+        res["views"] = view_options.summarise_raw(raw, ro.views.options)
+        res["views_raw"] = raw.tolist()                # the counts and sums behind the ratios (parallel_rollout.gather_views)
     return res
 
 
 def run_one(params, nbp, dataset, run, device, test_resolution=0.05, state=None, n_poses=N_POSES, seed=0, *, recon_metrics=None,
-            depth_noise=None):
+            depth_noise=None, view_metrics=None):
     ro = build_rollout(params, nbp, dataset, run, device, test_resolution, state, seed, recon_metrics=recon_metrics,
-                       depth_noise=depth_noise)
+                       depth_noise=depth_noise, view_metrics=view_metrics)
     nbp.eval()
     for _ in range(n_poses):
         ro.step()
@@ -585,7 +627,7 @@ def run_one(params, nbp, dataset, run, device, test_resolution=0.05, state=None,
 
 
 def run_many(params, nbp, dataset, runs, device, seeds, test_resolution=0.05, n_poses=N_POSES, rollouts_per_gpu=48,
-             grid=256, timing=None, *, recon_metrics=None, depth_noise=None):
+             grid=256, timing=None, *, recon_metrics=None, depth_noise=None, view_metrics=None):
     """Runs `runs` in lock-step groups of `rollouts_per_gpu` (MultiRollout); same results as run_one each.  `timing` (a dict)
     receives the wall-clock seconds of scene / GT-surface / camera setup and of the stepping (device-synchronised)."""
     import time
@@ -595,7 +637,7 @@ def run_many(params, nbp, dataset, runs, device, seeds, test_resolution=0.05, n_
         t0 = time.perf_counter()
         chunk = list(zip(runs[g0:g0 + rollouts_per_gpu], seeds[g0:g0 + rollouts_per_gpu]))
         ros = [build_rollout(params, nbp, dataset, run, device, test_resolution, None, seed, grid, recon_metrics=recon_metrics,
-                             depth_noise=depth_noise)
+                             depth_noise=depth_noise, view_metrics=view_metrics)
                for run, seed in chunk]
         multi = MultiRollout(ros, nbp, device)
         if timing is not None:
@@ -618,7 +660,7 @@ def test_nbp_planning(params_file, model_file, results_json_file, numGPU, test_s
                       use_perfect_depth_map=False, compute_collision=False, load_json=False, dataset_path=None,
                       nbp_weights=None, configs_dir=None, results_dir=None, n_poses=N_POSES, seed=8, torch_seed=9,
                       rollouts_per_gpu=48, grid_size=256, nbp_precision=None, symmetry_ensemble=_UNSET, recon_metrics=_UNSET,
-                      depth_noise=_UNSET):
+                      depth_noise=_UNSET, view_metrics=_UNSET):
     """Same arguments as the reference (nbp_planning.py:364-374); `grid_size` / `nbp_precision` select
     BASELINE.json configs[4] (512 grid at the same 0.3125 units per pixel, bf16 convolutions).  `symmetry_ensemble` (None = off, a
     name of utility/augment.py::ENSEMBLES or a list of op codes) is NBP.symmetry_ensemble of the loaded network; not given, it is
@@ -627,11 +669,15 @@ def test_nbp_planning(params_file, model_file, results_json_file, numGPU, test_s
     quality of every rollout's final cloud (utility/recon_metrics.py) to its record, next to coverage and auc, and with `curve` the same
     metrics after every step ("reconstruction_curve": lists over the steps, with their AUCs).  `depth_noise` (None =
     off: perfect depth; a dict of utility/depth_noise.py::option_spec; not given, the key of that name in the same file) puts the seeded
-    sensor model between the rasteriser and every consumer of depth, and the normalised spec into every record.  Under torchrun the flattened
+    sensor model between the rasteriser and every consumer of depth, and the normalised spec into every record.  `view_metrics` (None =
+    off, True = the defaults, or a dict of utility/view_metrics.py::option_spec; not given, the key of that name in the same file) adds
+    the held-out view metrics of every rollout's final coloured cloud ("views": the cloud rendered from lattice poses against the mesh,
+    with the options used) to its record.  Under torchrun the flattened
     (scene, start pose) runs are sharded round-robin over the ranks and the coverage curves are
     gathered with ONE all_gather over RCCL (backend "nccl" on ROCm; "gloo" on CPU-only hosts)."""
     import time
-    from ..parallel_rollout import gather_reconstruction, gather_reconstruction_curve, gather_results, init_distributed, shard
+    from ..parallel_rollout import (gather_reconstruction, gather_reconstruction_curve, gather_results, gather_views, init_distributed,
+                                     shard)
     t_start = time.perf_counter()
     here = os.path.dirname(os.path.abspath(__file__))
     configs_dir = configs_dir or os.path.join(here, "../../configs/macarons")
@@ -663,6 +709,9 @@ def test_nbp_planning(params_file, model_file, results_json_file, numGPU, test_s
     if depth_noise is _UNSET:
         depth_noise = None if _test_config_noise[0] is _UNSET else _test_config_noise[0]
     noise_spec = noise_options.option_spec(depth_noise)                       # (ValueError on anything but None or a dict of its keys)
+    if view_metrics is _UNSET:
+        view_metrics = None if _test_config_views[0] is _UNSET else _test_config_views[0]
+    view_spec = view_options.option_spec(view_metrics)                        # (ValueError on anything but None, True, a dict of its keys)
     dataset = sim_scene.SceneDataset(dataset_path, test_scenes)
     runs = list_runs(dataset, params)
     mine = shard(runs, rank, world)
@@ -670,7 +719,7 @@ def test_nbp_planning(params_file, model_file, results_json_file, numGPU, test_s
     with torch.no_grad():
         results = run_many(params, nbp, dataset, mine, device, [seed + 1000 * r[0] + r[1] for r in mine],
                            test_resolution, n_poses, rollouts_per_gpu, grid_size, timing=timing, recon_metrics=recon_spec,
-                           depth_noise=noise_spec)
+                           depth_noise=noise_spec, view_metrics=view_spec)
     for run, res in zip(mine, results):
         res["run_id"] = runs.index(run)
     t_gather = time.perf_counter()
@@ -687,6 +736,17 @@ def test_nbp_planning(params_file, model_file, results_json_file, numGPU, test_s
                 r.pop("reconstruction_curve_raw", None)
                 if rank == 0:
                     r["reconstruction_curve"] = curves[r["run_id"]]
+    if view_spec is not None:       # a float64 gather of its own: the raw counts and sums per view; the ratios are formed on rank 0
+        view_opts = view_options.resolved_options(view_spec, params.image_height, params.image_width, params.zfar)
+        for res in results:         # the gathered records all carry these: every rollout of this rank was evaluated with them
+            if res["views"]["options"] != view_opts:
+                raise RuntimeError(f"view_metrics: run {res['run_id']} was evaluated with {res['views']['options']}, not {view_opts}")
+        views = gather_views(results, runs, rank, world, device, view_opts)
+        for r in gathered:
+            r.pop("views", None)
+            r.pop("views_raw", None)
+            if rank == 0:
+                r["views"] = views[r["run_id"]]
     if rank == 0:
         out = {}
         for r in gathered:
@@ -698,6 +758,8 @@ def test_nbp_planning(params_file, model_file, results_json_file, numGPU, test_s
                     rec["reconstruction_curve"] = r["reconstruction_curve"]
             if noise_spec is not None:
                 rec["depth_noise"] = dict(noise_spec)
+            if view_spec is not None:
+                rec["views"] = r["views"]
             for key in ("X_cam_history", "V_cam_history"):      # histories of other ranks stay in their part files
                 if key in r:
                     rec[key] = r[key]

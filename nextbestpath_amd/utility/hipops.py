@@ -1248,3 +1248,169 @@ def recon_curve_update_batch(items):
                                                 capacity, count, seen, d2g, d2n, tot, T, th.ctypes.data, row, bound, _lib.ptr(ws),
                                                 ws.numel(), _st())
     _lib.check(rc, "nbp_recon_curve_update_batch_f32")
+
+
+# ---- held-out view metrics (csrc/nbp_views.hip; the definition of record is utility/view_metrics.py)
+def _view_cloud(name, cloud, cloud_rgb, n_dev):
+    _nn_points(name, cloud, "cloud")
+    _nn_count(name, n_dev, cloud.device)
+    if cloud_rgb is not None:
+        _nn_points(name, cloud_rgb, "cloud_rgb")
+        if cloud_rgb.device != cloud.device or cloud_rgb.shape[0] < cloud.shape[0]:
+            raise ValueError(f"{name}: cloud_rgb on the cloud's device with a row for each of its rows expected")
+
+
+def _view_keys(name, keys, V, H, W, device):
+    if (not isinstance(keys, torch.Tensor) or keys.dtype != torch.int64 or keys.device != device or tuple(keys.shape) != (V, H, W)
+            or not keys.is_contiguous()):
+        raise ValueError(f"{name}: keys must be a contiguous int64 [{V},{H},{W}] tensor on the cloud's device")
+
+
+def splat_cloud(cloud, cams, H, W, radius=1, n_dev=None, z_far=float("inf"), keys=None, accumulate=False, precheck=True,
+                tan_half_fov=TAN_HALF_FOV, z_clip=Z_CLIP):
+    """The splat alone -> keys int64 [V,H,W] (the bit pattern of view_metrics.splat's uint64 keys: -1 = empty): per pixel the
+    nearest point of cloud [n,3] (n_dev: int64 device counter; rows beyond it are never read) whose (2 radius + 1)^2 footprint
+    holds it, cams host [V,12].  keys with accumulate=True: lower an earlier result (a cloud splatted in parts gives the same bits
+    as at once, provided each part sits at its own rows of `cloud`: a key's index is the row, so rows outside a part are masked with
+    NaN or lie beyond n_dev); precheck=False sends every pixel to the atomic (the same bits; tools/bench_views.py measures both).  No host
+    synchronisation."""
+    _view_cloud("splat_cloud", cloud, None, n_dev)
+    keep, cam_ptr, V = _cam_arg(cams)
+    if V < 1:
+        raise ValueError("splat_cloud: at least one camera expected")
+    if accumulate and keys is None:
+        raise ValueError("splat_cloud: accumulate needs the keys of an earlier call")
+    if keys is None:
+        keys = torch.empty(V, int(H), int(W), dtype=torch.int64, device=cloud.device)
+    _view_keys("splat_cloud", keys, V, int(H), int(W), cloud.device)
+    with torch.cuda.device(cloud.device):
+        rc = _lib.lib().nbp_views_splat_f32(_lib.ptr(cloud), cloud.shape[0], _lib.ptr(n_dev), cam_ptr, V, int(H), int(W), int(radius),
+                                            tan_half_fov, float(z_clip), float(z_far), int(bool(accumulate)), int(bool(precheck)),
+                                            _lib.ptr(keys), _st())
+    _lib.check(rc, "nbp_views_splat_f32")
+    return keys
+
+
+def resolve_views(keys, cloud_rgb=None, n_cloud=None):
+    """keys int64 [V,H,W] -> (z [V,H,W] fp32, -1 where empty; rgb [V,H,W,3] = cloud_rgb[index], 0 where empty, or None; index
+    [V,H,W] int64, -1 where empty).  n_cloud: rows of the cloud the keys were made from (cloud_rgb's where given)."""
+    if not isinstance(keys, torch.Tensor) or not keys.is_cuda or keys.dim() != 3:
+        raise RuntimeError("resolve_views: the HIP path needs a cuda tensor [V,H,W] for keys (no CPU fallback)")
+    V, H, W = keys.shape
+    _view_keys("resolve_views", keys, V, H, W, keys.device)
+    if cloud_rgb is not None:
+        _nn_points("resolve_views", cloud_rgb, "cloud_rgb")
+    if n_cloud is None:
+        n_cloud = cloud_rgb.shape[0] if cloud_rgb is not None else (1 << 32) - 2
+    if cloud_rgb is not None:
+        n_cloud = min(int(n_cloud), cloud_rgb.shape[0])
+    z = torch.empty(V, H, W, dtype=torch.float32, device=keys.device)
+    index = torch.empty(V, H, W, dtype=torch.int64, device=keys.device)
+    rgb = torch.empty(V, H, W, 3, dtype=torch.float32, device=keys.device) if cloud_rgb is not None else None
+    with torch.cuda.device(keys.device):
+        rc = _lib.lib().nbp_views_resolve_f32(_lib.ptr(keys), _lib.ptr(cloud_rgb), int(n_cloud), V, H, W, _lib.ptr(z), _lib.ptr(rgb),
+                                              _lib.ptr(index), _st())
+    _lib.check(rc, "nbp_views_resolve_f32")
+    return z, rgb, index
+
+
+def render_cloud(cloud, cloud_rgb, cams, H, W, radius=1, n_dev=None, z_far=float("inf"), keys=None, accumulate=False):
+    """Point-splat render of the coloured cloud from cams host [V,12] -> (z [V,H,W] (-1 where empty), rgb [V,H,W,3] | None where
+    cloud_rgb is None, index [V,H,W] int64 (-1 where empty)): splat_cloud, then resolve_views.  `keys`: the key buffer to use (it
+    holds the splat afterwards); with accumulate=True its earlier content is lowered, not cleared."""
+    _view_cloud("render_cloud", cloud, cloud_rgb, n_dev)
+    keys = splat_cloud(cloud, cams, H, W, radius, n_dev, z_far, keys, accumulate)
+    return resolve_views(keys, cloud_rgb, cloud.shape[0])
+
+
+def view_stats(keys, cloud_rgb, z_gt, rgb_gt, depth_tolerance=1.0, z_far=float("inf"), n_cloud=None):
+    """Resolve + classify + reduce the keys of a splat against the mesh render (z_gt [V,H,W], rgb_gt [V,H,W,3] | None) of the same
+    cameras -> raw = (counts int64 [V,6] = n_gt, n_c, n_hit, n_hole, n_leak, n_floater; sums float64 [V,3] = sum |dz|, sum dz^2,
+    squared colour error over the hit pixels) on the device; view_metrics.raw_stats is the definition.  Two launches, no
+    floating-point atomics (two calls give the same bits), no host synchronisation."""
+    if not isinstance(keys, torch.Tensor) or not keys.is_cuda or keys.dim() != 3:
+        raise RuntimeError("view_stats: the HIP path needs a cuda tensor [V,H,W] for keys (no CPU fallback)")
+    V, H, W = keys.shape
+    dev = keys.device
+    _view_keys("view_stats", keys, V, H, W, dev)
+    if z_gt.dtype != torch.float32 or z_gt.device != dev or tuple(z_gt.shape) != (V, H, W) or not z_gt.is_contiguous():
+        raise ValueError("view_stats: z_gt must be a contiguous fp32 [V,H,W] tensor on the keys' device")
+    if rgb_gt is not None and (rgb_gt.dtype != torch.float32 or rgb_gt.device != dev or tuple(rgb_gt.shape) != (V, H, W, 3)
+                               or not rgb_gt.is_contiguous()):
+        raise ValueError("view_stats: rgb_gt must be a contiguous fp32 [V,H,W,3] tensor on the keys' device")
+    if cloud_rgb is not None:
+        _nn_points("view_stats", cloud_rgb, "cloud_rgb")
+    if n_cloud is None:
+        n_cloud = cloud_rgb.shape[0] if cloud_rgb is not None else (1 << 32) - 2
+    if cloud_rgb is not None:
+        n_cloud = min(int(n_cloud), cloud_rgb.shape[0])
+    L = _lib.lib()
+    counts = torch.empty(V, 6, dtype=torch.int64, device=dev)
+    sums = torch.empty(V, 3, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        ws = _workspace_for("view_stats", V, lambda: L.nbp_views_stats_workspace_bytes(V), dev)
+        rc = L.nbp_views_stats_f64(_lib.ptr(keys), _lib.ptr(cloud_rgb), int(n_cloud), _lib.ptr(z_gt), _lib.ptr(rgb_gt), V, H, W,
+                                   float(depth_tolerance), float(z_far), _lib.ptr(counts), _lib.ptr(sums), _lib.ptr(ws), ws.numel(),
+                                   _st())
+    _lib.check(rc, "nbp_views_stats_f64")
+    return counts, sums
+
+
+class ViewMetrics:
+    """Held-out view metrics of a coloured cloud against `mesh`, on the device (utility/view_metrics.py is the definition).  The
+    ground truth of the views (cams host [V,12]) is rendered ONCE, here, by the existing rasteriser: depth, and -- for a mesh with
+    vertex colours, unless colours=False -- colours with the ambient and contrast settings the rollout's camera renders its own
+    frames with, so that both colour images are the same quantity.  evaluate() splats the cloud and reduces; the key buffer
+    [V,H,W] belongs to the object.  ground_truth = (z_gt [V,H,W], rgb_gt [V,H,W,3] | None): images rendered elsewhere are taken
+    instead (mesh may then be None)."""
+
+    def __init__(self, mesh, cams, H, W, radius=1, depth_tolerance=1.0, z_far=float("inf"), ambient=0.85, contrast=1.0, colours=True,
+                 ground_truth=None):
+        from . import view_metrics
+        keep, _, V = _cam_arg(cams)
+        if V < 1:
+            raise ValueError("ViewMetrics: at least one camera expected")
+        if not 0 <= int(radius) <= view_metrics.MAX_RADIUS:
+            raise ValueError(f"ViewMetrics: radius outside 0..{view_metrics.MAX_RADIUS}")
+        self.cams, self.V, self.H, self.W = keep.copy(), V, int(H), int(W)
+        self.radius, self.depth_tolerance, self.z_far = int(radius), float(depth_tolerance), float(z_far)
+        if ground_truth is not None:
+            self.z_gt, self.rgb_gt = ground_truth
+            self.colours = self.rgb_gt is not None
+            if not isinstance(self.z_gt, torch.Tensor) or not self.z_gt.is_cuda or tuple(self.z_gt.shape) != (V, self.H, self.W):
+                raise ValueError("ViewMetrics: ground_truth z_gt must be a cuda tensor [V,H,W]")
+        else:
+            self.colours = bool(colours) and getattr(mesh, "colors", None) is not None
+            dev = mesh.verts.device
+            self.z_gt = torch.empty(V, self.H, self.W, dtype=torch.float32, device=dev)
+            self.rgb_gt = torch.empty(V, self.H, self.W, 3, dtype=torch.float32, device=dev) if self.colours else None
+            for v0 in range(0, V, 8):                  # the rasteriser takes 8 cameras per call
+                sl = slice(v0, min(v0 + 8, V))
+                if self.colours:
+                    raster_rgbz(mesh.verts, mesh.faces, mesh.colors, self.cams[sl], self.H, self.W, ambient, contrast,
+                                out_z=self.z_gt[sl], out_rgb=self.rgb_gt[sl])
+                else:                                  # (the colour render's depth: the same launch without the shading)
+                    raster_zface(mesh.verts, mesh.faces, self.cams[sl], self.H, self.W, out_z=self.z_gt[sl])
+        self.keys = torch.empty(V, self.H, self.W, dtype=torch.int64, device=self.z_gt.device)
+        self.result = None
+
+    def evaluate(self, cloud, cloud_rgb=None, n_dev=None):
+        """Enqueues the splat and the statistics on the current stream -> (counts int64 [V,6], sums float64 [V,3]) device tensors;
+        no host synchronisation.  cloud_rgb None (or a ground truth without colours): the depth half only.  Kept for raw()."""
+        _view_cloud("ViewMetrics.evaluate", cloud, cloud_rgb, n_dev)
+        splat_cloud(cloud, self.cams, self.H, self.W, self.radius, n_dev, self.z_far, self.keys)
+        rgb = cloud_rgb if self.colours else None
+        self.result = view_stats(self.keys, rgb, self.z_gt, self.rgb_gt if rgb is not None else None, self.depth_tolerance,
+                                 self.z_far, cloud.shape[0])
+        return self.result
+
+    def raw(self):
+        """The last evaluation's raw numbers on the host (ONE device -> host copy): view_metrics.pack_raw's float64 rows [V, 9]."""
+        if self.result is None:
+            raise RuntimeError("ViewMetrics: evaluate() first")
+        counts, sums = self.result
+        return torch.cat([counts.double(), sums], 1).cpu().numpy()
+
+    def summary(self, options=None):
+        from . import view_metrics
+        return view_metrics.summarise_raw(self.raw(), options)
