@@ -1155,6 +1155,27 @@ int nbp_views_stats_f64(const unsigned long long* keys, const float* cloud_rgb_o
                         const float* rgb_gt_or_null, int n_views, int H, int W, float depth_tolerance, float z_far,
                         long long* counts6, double* sums3, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- Frontier-based exploration as a policy behind the network's interface (csrc/nbp_frontier.hip; the definition, which the
+ * kernels equal bit for bit, is nextbestpath_amd/utility/frontier.py).  Not in the reference.  maps6 [B][6][S][S] fp32,
+ * S a multiple of 64, V = S / 4, W = S / 64.  Bit i of word w of a packed row is column 64 w + i.
+ *   nbp_frontier_workspace_bytes  what the policy call needs (5 B S W words; the mask call needs four of the five); 0 where the
+ *                                 call would fail.
+ *   nbp_frontier_mask_u64         frontier_bits [B][S][W]: the free pixels with an unknown edge neighbour (unknown = outside the
+ *                                 closing of `seen` by a (2 dilate + 1)-square); unknown_bits (same shape, may be null): the unknown
+ *                                 pixels.  Four launches.
+ *   nbp_frontier_policy_f32       out1 [B][8][V][V] = float(max(gain - distance_penalty max(|g0 - V/2|, |g1 - V/2|), 0)), gain = the
+ *                                 frontier pixels within `radius` of pixel (4 g0, 4 g1) in the 45-degree sector of the heading;
+ *                                 out2 [B][1][S][S] = 1 at the unknown pixels where unknown_obstacle != 0, else 0.  Both are written
+ *                                 completely.  Five launches (one more per 2^24 gain workgroups).
+ * No atomics, no hand-off between workgroups: two runs give the same bits.  No allocation, no host synchronisation; any B >= 1.
+ * NBP_E_ARG: a null pointer (but unknown_bits), B < 1, S < 1, radius outside 1..31, dilate outside 0..8, distance_penalty < 0;
+ * NBP_E_SHAPE: S % 64 != 0, frontier_bits / unknown_bits / ws off the 8-byte grid; NBP_E_WS.  Nothing is launched on an error. */
+size_t nbp_frontier_workspace_bytes(int B, int S);
+int nbp_frontier_mask_u64(const float* maps6, int B, int S, int dilate, unsigned long long* frontier_bits,
+                          unsigned long long* unknown_bits_or_null, void* ws, size_t ws_bytes, void* stream);
+int nbp_frontier_policy_f32(const float* maps6, int B, int S, int radius, int dilate, int unknown_obstacle, int distance_penalty,
+                            float* out1, float* out2, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -50,7 +50,17 @@ def _set_symmetry_ensemble(nbp, params, spec=_UNSET):
     if spec is _UNSET:
         spec = getattr(params, "symmetry_ensemble", _UNSET)
     if spec is not _UNSET:
-        nbp.symmetry_ensemble = spec
+        nbp.symmetry_ensemble = spec        # (a policy refuses anything but None: ValueError)
+
+
+def _wants_maps(nbp):
+    """Is `nbp` a policy that reads the six-channel map stack (testers/frontier_policy.py) and not the network input?"""
+    return getattr(nbp, "wants_maps6", False)
+
+
+def _policy_forward(policy, maps6):
+    """The policy branch of a step's forward: the planner's two inputs from the map stack [B,6,S,S].  Never entered with a network."""
+    return policy.forward_maps(maps6)
 
 
 class Rollout(lockstep.LockstepRollout):
@@ -180,13 +190,17 @@ class Rollout(lockstep.LockstepRollout):
         self.pose_i += 1
 
     def step(self):
-        static = getattr(self.nbp, "forward_static", None)
+        policy = _wants_maps(self.nbp)
+        static = None if policy else getattr(self.nbp, "forward_static", None)
         if static is not None and _STEP_OVERLAP and not self.nbp.training:
             return self._step_forward_on_its_own_stream(static)
         self.pre()
         with torch.no_grad():          # S9: one NBP forward per step (the reference also runs it without replanning, :252)
-            # net_in is a persistent tensor: the ~60 launches of a B = 1 forward replay as one hipGraph (bit-identical outputs)
-            out1, out2 = static(self.st.net_in) if static is not None else self.nbp(self.st.net_in)
+            if policy:                 # (in stream order: the map stack is one buffer, the next step's map stage clears it)
+                out1, out2 = _policy_forward(self.nbp, self.st.maps6[None])
+            else:
+                # net_in is a persistent tensor: the ~60 launches of a B = 1 forward replay as one hipGraph (bit-identical outputs)
+                out1, out2 = static(self.st.net_in) if static is not None else self.nbp(self.st.net_in)
         self.plan_enqueue(out1, out2)
         if self.need_replan:
             torch.cuda.current_stream().synchronize()
@@ -195,7 +209,10 @@ class Rollout(lockstep.LockstepRollout):
 
     def _step_forward_on_its_own_stream(self, static):
         """step() with the forward (the replayed hipGraph of this input buffer) on a side stream: same kernels, same inputs, same
-        results; only a replanning step waits for it."""
+        results; only a replanning step waits for it.  Networks only: a policy reads the map stack, which is not double-buffered,
+        so step() keeps it in stream order."""
+        if _wants_maps(self.nbp):
+            raise RuntimeError("a policy's forward stays in stream order (Rollout.step)")
         st = self.st
         ov = st.forward_overlap()
         slot = self.pose_i & 1
@@ -371,7 +388,10 @@ class MultiRollout:
                 out1, out2, rows = self._forward_replanning_only(gi)
             else:
                 with torch.no_grad():
-                    out1, out2 = self._forward(net_in)
+                    if _wants_maps(self.nbp):          # a policy gets the group's map stacks, not the network input
+                        out1, out2 = _policy_forward(self.nbp, self.maps6[gi])
+                    else:
+                        out1, out2 = self._forward(net_in)
             if self.batched:
                 self._plan_group(gi, out1, out2, rows)
             else:
@@ -536,6 +556,7 @@ _test_config_ensemble = [_UNSET]
 _test_config_recon = [_UNSET]            # ... and its `recon_metrics` key, the same way
 _test_config_noise = [_UNSET]            # ... and its `depth_noise` key
 _test_config_views = [_UNSET]            # ... and its `view_metrics` key
+_test_config_policy = [_UNSET]           # ... and its `policy` key
 
 
 def load_params(path):
@@ -562,6 +583,7 @@ def load_params(path):
         _test_config_recon[0] = getattr(p, "recon_metrics", _UNSET)
         _test_config_noise[0] = getattr(p, "depth_noise", _UNSET)
         _test_config_views[0] = getattr(p, "view_metrics", _UNSET)
+        _test_config_policy[0] = getattr(p, "policy", _UNSET)
     return p
 
 
@@ -598,6 +620,8 @@ def _result(ro, n_poses):
     res = {"scene": ro.scene_name, "start": ro.start, "coverage": ro.coverage_evolution(n_poses),
            "X_cam_history": ro.camera.X_cam_history.tolist(), "V_cam_history": ro.camera.V_cam_history.tolist(),
            "n_points": int(ro.st.cloud_count.item())}
+    if _wants_maps(ro.nbp):                            # the option `policy`: the normalised options the rollout was steered with
+        res["policy"] = dict(ro.nbp.options)
     if ro.camera.depth_noise is not None:              # the option `depth_noise`: the normalised spec the frames were made with
         res["depth_noise"] = dict(ro.camera.depth_noise)
     if ro.recon is not None:        # the option `recon_metrics`: the whole cloud once, at the rollout's end
@@ -615,8 +639,18 @@ def _result(ro, n_poses):
     return res
 
 
+def _policy_or(nbp, policy):
+    """The planning option `policy` (None / "nbp" = the network `nbp`; "frontier" or a dict of utility/frontier.py::option_spec; a
+    policy object passes through) -> what the rollouts evaluate."""
+    if _wants_maps(policy):
+        return policy
+    from .frontier_policy import make_policy
+    return make_policy(policy) or nbp
+
+
 def run_one(params, nbp, dataset, run, device, test_resolution=0.05, state=None, n_poses=N_POSES, seed=0, *, recon_metrics=None,
-            depth_noise=None, view_metrics=None):
+            depth_noise=None, view_metrics=None, policy=None):
+    nbp = _policy_or(nbp, policy)
     ro = build_rollout(params, nbp, dataset, run, device, test_resolution, state, seed, recon_metrics=recon_metrics,
                        depth_noise=depth_noise, view_metrics=view_metrics)
     nbp.eval()
@@ -627,11 +661,13 @@ def run_one(params, nbp, dataset, run, device, test_resolution=0.05, state=None,
 
 
 def run_many(params, nbp, dataset, runs, device, seeds, test_resolution=0.05, n_poses=N_POSES, rollouts_per_gpu=48,
-             grid=256, timing=None, *, recon_metrics=None, depth_noise=None, view_metrics=None):
+             grid=256, timing=None, *, recon_metrics=None, depth_noise=None, view_metrics=None, policy=None):
     """Runs `runs` in lock-step groups of `rollouts_per_gpu` (MultiRollout); same results as run_one each.  `timing` (a dict)
-    receives the wall-clock seconds of scene / GT-surface / camera setup and of the stepping (device-synchronised)."""
+    receives the wall-clock seconds of scene / GT-surface / camera setup and of the stepping (device-synchronised).  `policy`: as
+    in run_one (None = the network `nbp`)."""
     import time
     out = []
+    nbp = _policy_or(nbp, policy)
     nbp.eval()
     for g0 in range(0, len(runs), rollouts_per_gpu):
         t0 = time.perf_counter()
@@ -660,7 +696,7 @@ def test_nbp_planning(params_file, model_file, results_json_file, numGPU, test_s
                       use_perfect_depth_map=False, compute_collision=False, load_json=False, dataset_path=None,
                       nbp_weights=None, configs_dir=None, results_dir=None, n_poses=N_POSES, seed=8, torch_seed=9,
                       rollouts_per_gpu=48, grid_size=256, nbp_precision=None, symmetry_ensemble=_UNSET, recon_metrics=_UNSET,
-                      depth_noise=_UNSET, view_metrics=_UNSET):
+                      depth_noise=_UNSET, view_metrics=_UNSET, policy=_UNSET):
     """Same arguments as the reference (nbp_planning.py:364-374); `grid_size` / `nbp_precision` select
     BASELINE.json configs[4] (512 grid at the same 0.3125 units per pixel, bf16 convolutions).  `symmetry_ensemble` (None = off, a
     name of utility/augment.py::ENSEMBLES or a list of op codes) is NBP.symmetry_ensemble of the loaded network; not given, it is
@@ -672,7 +708,9 @@ def test_nbp_planning(params_file, model_file, results_json_file, numGPU, test_s
     sensor model between the rasteriser and every consumer of depth, and the normalised spec into every record.  `view_metrics` (None =
     off, True = the defaults, or a dict of utility/view_metrics.py::option_spec; not given, the key of that name in the same file) adds
     the held-out view metrics of every rollout's final coloured cloud ("views": the cloud rendered from lattice poses against the mesh,
-    with the options used) to its record.  Under torchrun the flattened
+    with the options used) to its record.  `policy` (None or "nbp" = the network; "frontier" or a dict of
+    utility/frontier.py::option_spec; not given, the key of that name in the same file) puts the frontier policy where the network
+    stands: no weights are loaded (`nbp_precision` given with it draws a warning), and every record gains "policy", the normalised options.  Under torchrun the flattened
     (scene, start pose) runs are sharded round-robin over the ranks and the coverage curves are
     gathered with ONE all_gather over RCCL (backend "nccl" on ROCm; "gloo" on CPU-only hosts)."""
     import time
@@ -688,18 +726,28 @@ def test_nbp_planning(params_file, model_file, results_json_file, numGPU, test_s
     device = torch.device("cuda", local_rank if world > 1 else numGPU)
     torch.cuda.set_device(device)
     random.seed(seed); np.random.seed(seed); torch.manual_seed(torch_seed)
-    nbp = NBP()
-    if nbp_weights and os.path.exists(nbp_weights):
-        ck = torch.load(nbp_weights, map_location="cpu")
-        nbp.load_state_dict(ck["model_state_dict"])
-    else:
-        from ..utility.synthetic import make_explorer_state_dict
-        print("[nbp] no checkpoint at", nbp_weights, "-> seeded synthetic weights")
-        nbp.load_state_dict(make_explorer_state_dict(torch_seed))
-    nbp.to(device).eval()
+    if policy is _UNSET:
+        policy = None if _test_config_policy[0] is _UNSET else _test_config_policy[0]
+    from .frontier_policy import make_policy
+    nbp = make_policy(policy)                                                 # (ValueError on anything but None, "nbp", "frontier", a dict)
+    policy_spec = None if nbp is None else dict(nbp.options)
     assert nbp_precision in (None, "fp32", "fp32_split", "bf16"), nbp_precision
-    if nbp_precision is not None:           # None: the model's default ("fp32_split")
-        nbp.conv_precision = nbp_precision
+    if nbp is not None and nbp_precision is not None:
+        import warnings
+        warnings.warn(f"policy {policy_spec['name']!r} runs no network: nbp_precision={nbp_precision!r} has no effect "
+                      "(nor have nbp_weights and model_file)", stacklevel=2)
+    if nbp is None:
+        nbp = NBP()
+        if nbp_weights and os.path.exists(nbp_weights):
+            ck = torch.load(nbp_weights, map_location="cpu")
+            nbp.load_state_dict(ck["model_state_dict"])
+        else:
+            from ..utility.synthetic import make_explorer_state_dict
+            print("[nbp] no checkpoint at", nbp_weights, "-> seeded synthetic weights")
+            nbp.load_state_dict(make_explorer_state_dict(torch_seed))
+        nbp.to(device).eval()
+        if nbp_precision is not None:           # None: the model's default ("fp32_split")
+            nbp.conv_precision = nbp_precision
     if symmetry_ensemble is _UNSET:
         symmetry_ensemble = None if _test_config_ensemble[0] is _UNSET else _test_config_ensemble[0]
     nbp.symmetry_ensemble = params.symmetry_ensemble = symmetry_ensemble      # (ValueError on anything but None, a name, op codes)
@@ -756,6 +804,8 @@ def test_nbp_planning(params_file, model_file, results_json_file, numGPU, test_s
                 rec["reconstruction"] = r["reconstruction"]
                 if recon_spec.get("curve"):
                     rec["reconstruction_curve"] = r["reconstruction_curve"]
+            if policy_spec is not None:
+                rec["policy"] = dict(policy_spec)
             if noise_spec is not None:
                 rec["depth_noise"] = dict(noise_spec)
             if view_spec is not None:

@@ -1414,3 +1414,43 @@ class ViewMetrics:
     def summary(self, options=None):
         from . import view_metrics
         return view_metrics.summarise_raw(self.raw(), options)
+
+
+# ---- frontier exploration as a policy (csrc/nbp_frontier.hip; the definition is utility/frontier.py)
+def _frontier_maps(name, maps6):
+    if maps6.dtype != torch.float32 or maps6.dim() != 4 or maps6.shape[1] != 6 or maps6.shape[2] != maps6.shape[3]:
+        raise ValueError(f"{name}: maps6 is fp32 [B,6,S,S]")
+    return maps6.shape[0], maps6.shape[2]
+
+
+def frontier_mask(maps6, dilate=2, want_unknown=False):
+    """maps6 [B,6,S,S] -> the packed frontier pixels, int64 [B,S,S/64] (bit i of word w of a row = column 64 w + i; read them as
+    uint64), or with want_unknown the pair (frontier, unknown).  Four launches."""
+    B, S = _frontier_maps("frontier_mask", maps6)
+    L = _lib.lib()
+    ws = _workspace_for("frontier", (B, S), lambda: L.nbp_frontier_workspace_bytes(B, S), maps6.device)
+    bits = torch.empty(B, S, max(S // 64, 1), dtype=torch.int64, device=maps6.device)
+    unknown = torch.empty_like(bits) if want_unknown else None
+    rc = L.nbp_frontier_mask_u64(_lib.ptr(maps6), B, S, int(dilate), _lib.ptr(bits), _lib.ptr(unknown), _lib.ptr(ws), ws.numel(), _st())
+    _lib.check(rc, "nbp_frontier_mask_u64")
+    return (bits, unknown) if want_unknown else bits
+
+
+def frontier_policy(maps6, radius=24, dilate=2, unknown="free", distance_penalty=0, out=None):
+    """maps6 [B,6,S,S] -> (out1 [B,8,V,V], out2 [B,1,S,S]) fp32, V = S / 4: the planner's two inputs from the accumulated maps
+    (utility/frontier.py::policy, bit for bit).  out = (out1, out2) to write into.  Five launches, no host synchronisation."""
+    B, S = _frontier_maps("frontier_policy", maps6)
+    if unknown not in ("free", "obstacle"):
+        raise ValueError(f"frontier_policy: unknown must be 'free' or 'obstacle', got {unknown!r}")
+    V, dev = S // 4, maps6.device
+    if out is None:
+        out = (torch.empty(B, 8, V, V, dtype=torch.float32, device=dev), torch.empty(B, 1, S, S, dtype=torch.float32, device=dev))
+    out1, out2 = out
+    if (out1.dtype, tuple(out1.shape)) != (torch.float32, (B, 8, V, V)) or (out2.dtype, tuple(out2.shape)) != (torch.float32, (B, 1, S, S)):
+        raise ValueError("frontier_policy: out is the pair fp32 [B,8,V,V], fp32 [B,1,S,S]")
+    L = _lib.lib()
+    ws = _workspace_for("frontier", (B, S), lambda: L.nbp_frontier_workspace_bytes(B, S), dev)
+    rc = L.nbp_frontier_policy_f32(_lib.ptr(maps6), B, S, int(radius), int(dilate), int(unknown == "obstacle"), int(distance_penalty),
+                                   _lib.ptr(out1), _lib.ptr(out2), _lib.ptr(ws), ws.numel(), _st())
+    _lib.check(rc, "nbp_frontier_policy_f32")
+    return out1, out2
