@@ -1176,6 +1176,30 @@ int nbp_frontier_mask_u64(const float* maps6, int B, int S, int dilate, unsigned
 int nbp_frontier_policy_f32(const float* maps6, int B, int S, int radius, int dilate, int unknown_obstacle, int distance_penalty,
                             float* out1, float* out2, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- Next-best-view by ray-cast information gain as a policy behind the network's interface (csrc/nbp_infogain.hip; the definition,
+ * which the kernels equal bit for bit, is nextbestpath_amd/utility/infogain.py).  Not in the reference.  maps6, S, V, W
+ * and the packed rows as for nbp_frontier_*; pack, dilate and erode are that path's launches.
+ *   nbp_infogain_workspace_bytes  what either call needs (4 B S W words); 0 where the call would fail.
+ *   nbp_infogain_policy_f32       out1 [B][8][V][V] = float(max(gain - distance_penalty max(|g0 - V/2|, |g1 - V/2|), 0)), gain = the
+ *                                 unknown pixels within `radius` of pixel (4 g0, 4 g1), in the 45-degree sector of the heading, that
+ *                                 a ray of the 8 `radius`-ray fan reaches from that pixel before a blocked pixel (occupied, or outside
+ *                                 the domain of rows and columns >= 1) or a diagonal step between two blocked corners stops it;
+ *                                 out2 [B][1][S][S] = 1 at the unknown pixels where unknown_obstacle != 0, else 0.  Both are written
+ *                                 completely.  Five launches; one wave per value cell.
+ *   nbp_infogain_visible_u64      the visible masks of chosen cells, to locate a gain mismatch: cells_host [n][3] = (b, g0, g1) in
+ *                                 HOST memory (read before the call returns); out [n][2 radius + 1] words, bit dx + radius of word
+ *                                 dy + radius = pixel (4 g0 + dy, 4 g1 + dx) is visible.  Three launches and one per 128 cells.
+ * Integer ORs in LDS only; no global atomics, no floating-point atomics, no hand-off between workgroups: two runs give the same bits.
+ * No allocation, no host synchronisation; any B >= 1.
+ * NBP_E_ARG: a null pointer, B < 1, S < 1, radius outside 1..31, dilate outside 0..8, distance_penalty < 0, n < 1, a cell with b outside
+ * 0..B-1 or g0, g1 outside 0..V-1; NBP_E_SHAPE: S % 64 != 0, out (of the visible call) / ws off the 8-byte grid; NBP_E_WS.  Nothing is
+ * launched on an error. */
+size_t nbp_infogain_workspace_bytes(int B, int S);
+int nbp_infogain_policy_f32(const float* maps6, int B, int S, int radius, int dilate, int unknown_obstacle, int distance_penalty,
+                            float* out1, float* out2, void* ws, size_t ws_bytes, void* stream);
+int nbp_infogain_visible_u64(const float* maps6, int B, int S, int radius, int dilate, const int* cells_host, int n,
+                             unsigned long long* out, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

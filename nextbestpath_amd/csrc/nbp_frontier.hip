@@ -15,7 +15,7 @@
 //             words and, where the window is not empty, eight popcounts; two shuffles add the four partial counts
 // The call reads 24 S^2 bytes per map and writes 5.5 S^2.  It is not yet at the bound that reading its input sets: measured at
 // four to five times a device copy of the same bytes, because five short launches depend on one another.
-#include "common.h"
+#include "nbp_internal.h"
 #include <mutex>
 
 namespace {
@@ -24,16 +24,15 @@ typedef unsigned long long u64;
 
 constexpr int FR_THREADS = 256;
 constexpr int FR_WAVES = FR_THREADS / 64;
-constexpr int FR_MAX_R = 31, FR_MAX_D = 8;
-constexpr int FR_ROWS = 2 * FR_MAX_R + 1;          // rows (and bits) of a sector mask
+constexpr int FR_MAX_R = NBP_FR_MAX_R, FR_MAX_D = NBP_FR_MAX_D;
+constexpr int FR_ROWS = NBP_FR_ROWS;               // rows (and bits) of a sector mask
 constexpr int FR_VC = 64, FR_PARTS = 4;            // value cells of a gain workgroup (one value row), lanes per cell
 constexpr int FR_GAIN_THREADS = FR_VC * FR_PARTS;
 constexpr int FR_LROWS = 2 * FR_MAX_R + 1;                        // 63 pixel rows ...
 constexpr int FR_LWORDS = 4 * FR_VC / 64 + 2;                     // ... of 4 words and one more on either side
 constexpr int FR_MAX_GRID = 1 << 20;
 
-// the columns lo..hi (as bits dx + R of a row's window) of sector h in row dy + R; lo > hi: none
-struct SectorRows { unsigned char lo[8][FR_ROWS], hi[8][FR_ROWS]; };
+typedef NbpSectorRows SectorRows;                  // (nbp_internal.h: one column interval per heading and row)
 
 // ---- pack: word g (of B S W, row-major over map, row, word) <- ballots over its 64 pixels
 __global__ __launch_bounds__(FR_THREADS) void frontier_pack_kernel(const float* __restrict__ maps6, long long n_words, int S, int W,
@@ -225,8 +224,10 @@ bool build_sector_rows(int R, SectorRows* out) {
     return true;
 }
 
+}  // namespace
+
 // ... built once per radius and process
-bool sector_rows(int R, SectorRows* out) {
+bool nbp_sector_rows(int R, NbpSectorRows* out) {
     static std::mutex lock;
     static SectorRows cache[FR_MAX_R + 1];
     static bool built[FR_MAX_R + 1] = {};
@@ -238,6 +239,8 @@ bool sector_rows(int R, SectorRows* out) {
     *out = cache[R];
     return true;
 }
+
+namespace {
 
 int check_shape(int B, int S) {
     NBP_RETURN_IF(B < 1 || S < 1, NBP_E_ARG);
@@ -252,16 +255,27 @@ int word_grid(long long n_words) {
     return (int)(g > FR_MAX_GRID ? FR_MAX_GRID : g);
 }
 
-// pack + dilate + erode + frontier words (+ out2): what the two entry points share.  ws holds the seen, occupied, near_d and
-// (unless the caller wants them) unknown words.
+}  // namespace
+
+void nbp_unknown_words_launch(const float* maps6, int B, int S, int dilate, u64* seen, u64* occ, u64* near_d, u64* unknown,
+                              hipStream_t stream) {
+    const int W = S / 64;
+    const size_t n = plane_words(B, S);
+    frontier_pack_kernel<<<word_grid((long long)n), FR_THREADS, 0, stream>>>(maps6, (long long)n, S, W, seen, occ);
+    frontier_dilate_kernel<<<nbp_ew_grid((long long)n, FR_THREADS), FR_THREADS, 0, stream>>>(seen, (long long)n, S, W, dilate, near_d);
+    frontier_erode_kernel<<<nbp_ew_grid((long long)n, FR_THREADS), FR_THREADS, 0, stream>>>(near_d, (long long)n, S, W, dilate, unknown);
+}
+
+namespace {
+
+// pack + dilate + erode (nbp_unknown_words_launch) + frontier words (+ out2): what the two entry points share.  ws holds the seen,
+// occupied, near_d and (unless the caller wants them) unknown words.
 int launch_mask(const float* maps6, int B, int S, int dilate, u64* ws, u64* frontier_bits, u64* unknown_bits, float* out2,
                 int unknown_obstacle, hipStream_t stream) {
     const int W = S / 64;
     const size_t n = plane_words(B, S);
     u64 *seen = ws, *occ = ws + n, *near_d = ws + 2 * n, *unknown = unknown_bits ? unknown_bits : ws + 3 * n;
-    frontier_pack_kernel<<<word_grid((long long)n), FR_THREADS, 0, stream>>>(maps6, (long long)n, S, W, seen, occ);
-    frontier_dilate_kernel<<<nbp_ew_grid((long long)n, FR_THREADS), FR_THREADS, 0, stream>>>(seen, (long long)n, S, W, dilate, near_d);
-    frontier_erode_kernel<<<nbp_ew_grid((long long)n, FR_THREADS), FR_THREADS, 0, stream>>>(near_d, (long long)n, S, W, dilate, unknown);
+    nbp_unknown_words_launch(maps6, B, S, dilate, seen, occ, near_d, unknown, stream);
     frontier_word_kernel<<<word_grid((long long)n), FR_THREADS, 0, stream>>>(seen, occ, unknown, (long long)n, S, W, frontier_bits, out2,
                                                                              unknown_obstacle);
     return nbp_launch_status();
@@ -296,7 +310,7 @@ extern "C" int nbp_frontier_policy_f32(const float* maps6, int B, int S, int rad
     NBP_RETURN_IF(((uintptr_t)ws & 7) != 0, NBP_E_SHAPE);
     NBP_RETURN_IF(ws_bytes < 5 * plane_words(B, S) * sizeof(u64), NBP_E_WS);
     SectorRows sectors;
-    NBP_RETURN_IF(!sector_rows(radius, &sectors), NBP_E_ARG);
+    NBP_RETURN_IF(!nbp_sector_rows(radius, &sectors), NBP_E_ARG);
     const int W = S / 64, V = S / 4;
     u64* bits = (u64*)ws + 4 * plane_words(B, S);
     rc = launch_mask(maps6, B, S, dilate, (u64*)ws, bits, nullptr, out2, unknown_obstacle != 0, (hipStream_t)stream);

@@ -129,3 +129,15 @@ int nbp_psi_gate_bf16_launch(const bf16_t* q, int F, const float* w_psi, const f
                              long long M, bf16_t* out, hipStream_t st);
 int nbp_final_1x1_bf16_launch(const bf16_t* in, int B, int H, int W, int C, const float* w_oc, int n_out,
                               const float* scale, const float* shift, int sigmoid, float* out_nchw, hipStream_t st);
+
+// bit-packed map planes (nbp_frontier.hip), shared with nbp_infogain.hip: W = S / 64 words per row, bit i of word w = column 64 w + i
+constexpr int NBP_FR_MAX_R = 31, NBP_FR_MAX_D = 8;
+constexpr int NBP_FR_ROWS = 2 * NBP_FR_MAX_R + 1;     // rows (and bits) of a sector mask
+// the columns lo..hi (as bits dx + R of a row's window) of sector h in row dy + R; lo > hi: none
+struct NbpSectorRows { unsigned char lo[8][NBP_FR_ROWS], hi[8][NBP_FR_ROWS]; };
+// the sector masks of radius R (1..31), built once per radius and process; false if a row's columns are not contiguous (they always are)
+bool nbp_sector_rows(int R, NbpSectorRows* out);
+// pack + dilate + erode, three launches in stream order: seen, occ (both cut to the domain of rows and columns >= 1), near_d and
+// unknown (the domain's pixels outside the closing of `seen` by `dilate`), each [B][S][W] words.  Arguments are the caller's to check.
+void nbp_unknown_words_launch(const float* maps6, int B, int S, int dilate, unsigned long long* seen, unsigned long long* occ,
+                              unsigned long long* near_d, unsigned long long* unknown, hipStream_t st);

@@ -640,7 +640,7 @@ def _result(ro, n_poses):
 
 
 def _policy_or(nbp, policy):
-    """The planning option `policy` (None / "nbp" = the network `nbp`; "frontier" or a dict of utility/frontier.py::option_spec; a
+    """The planning option `policy` (None / "nbp" = the network `nbp`; "frontier" / "infogain" or a dict of utility/frontier.py / infogain.py::option_spec; a
     policy object passes through) -> what the rollouts evaluate."""
     if _wants_maps(policy):
         return policy
@@ -708,8 +708,8 @@ def test_nbp_planning(params_file, model_file, results_json_file, numGPU, test_s
     sensor model between the rasteriser and every consumer of depth, and the normalised spec into every record.  `view_metrics` (None =
     off, True = the defaults, or a dict of utility/view_metrics.py::option_spec; not given, the key of that name in the same file) adds
     the held-out view metrics of every rollout's final coloured cloud ("views": the cloud rendered from lattice poses against the mesh,
-    with the options used) to its record.  `policy` (None or "nbp" = the network; "frontier" or a dict of
-    utility/frontier.py::option_spec; not given, the key of that name in the same file) puts the frontier policy where the network
+    with the options used) to its record.  `policy` (None or "nbp" = the network; "frontier" / "infogain" or a dict of
+    utility/frontier.py / infogain.py::option_spec; not given, the key of that name in the same file) puts that policy where the network
     stands: no weights are loaded (`nbp_precision` given with it draws a warning), and every record gains "policy", the normalised options.  Under torchrun the flattened
     (scene, start pose) runs are sharded round-robin over the ranks and the coverage curves are
     gathered with ONE all_gather over RCCL (backend "nccl" on ROCm; "gloo" on CPU-only hosts)."""
@@ -729,7 +729,7 @@ def test_nbp_planning(params_file, model_file, results_json_file, numGPU, test_s
     if policy is _UNSET:
         policy = None if _test_config_policy[0] is _UNSET else _test_config_policy[0]
     from .frontier_policy import make_policy
-    nbp = make_policy(policy)                                                 # (ValueError on anything but None, "nbp", "frontier", a dict)
+    nbp = make_policy(policy)                                                 # (ValueError on anything but None, "nbp", "frontier", "infogain", a dict)
     policy_spec = None if nbp is None else dict(nbp.options)
     assert nbp_precision in (None, "fp32", "fp32_split", "bf16"), nbp_precision
     if nbp is not None and nbp_precision is not None:

@@ -1454,3 +1454,43 @@ def frontier_policy(maps6, radius=24, dilate=2, unknown="free", distance_penalty
                                    _lib.ptr(out1), _lib.ptr(out2), _lib.ptr(ws), ws.numel(), _st())
     _lib.check(rc, "nbp_frontier_policy_f32")
     return out1, out2
+
+
+# ---- ray-cast information gain as a policy (csrc/nbp_infogain.hip; the definition is utility/infogain.py)
+def infogain_policy(maps6, radius=24, dilate=2, unknown="free", distance_penalty=0, out=None):
+    """maps6 [B,6,S,S] -> (out1 [B,8,V,V], out2 [B,1,S,S]) fp32, V = S / 4: the planner's two inputs from the accumulated maps
+    (utility/infogain.py::policy, bit for bit).  out = (out1, out2) to write into.  Five launches, no host synchronisation."""
+    B, S = _frontier_maps("infogain_policy", maps6)
+    if unknown not in ("free", "obstacle"):
+        raise ValueError(f"infogain_policy: unknown must be 'free' or 'obstacle', got {unknown!r}")
+    V, dev = S // 4, maps6.device
+    if out is None:
+        out = (torch.empty(B, 8, V, V, dtype=torch.float32, device=dev), torch.empty(B, 1, S, S, dtype=torch.float32, device=dev))
+    out1, out2 = out
+    if (out1.dtype, tuple(out1.shape)) != (torch.float32, (B, 8, V, V)) or (out2.dtype, tuple(out2.shape)) != (torch.float32, (B, 1, S, S)):
+        raise ValueError("infogain_policy: out is the pair fp32 [B,8,V,V], fp32 [B,1,S,S]")
+    L = _lib.lib()
+    ws = _workspace_for("infogain", (B, S), lambda: L.nbp_infogain_workspace_bytes(B, S), dev)
+    rc = L.nbp_infogain_policy_f32(_lib.ptr(maps6), B, S, int(radius), int(dilate), int(unknown == "obstacle"), int(distance_penalty),
+                                   _lib.ptr(out1), _lib.ptr(out2), _lib.ptr(ws), ws.numel(), _st())
+    _lib.check(rc, "nbp_infogain_policy_f32")
+    return out1, out2
+
+
+def infogain_visible(maps6, radius=24, dilate=2, cells=()):
+    """maps6 [B,6,S,S], cells [n,3] = (b, g0, g1) on the host -> the visible masks of those cells, int64 [n, 2 radius + 1] on the
+    device (bit dx + radius of word dy + radius = pixel (4 g0 + dy, 4 g1 + dx) is visible from the cell; read them as uint64):
+    utility/infogain.py::visible, packed.  To locate a gain mismatch."""
+    import numpy as np
+    B, S = _frontier_maps("infogain_visible", maps6)
+    cells = np.ascontiguousarray(np.asarray(cells, np.int32).reshape(-1, 3))
+    n, R = len(cells), int(radius)
+    out = torch.empty(n, 2 * max(R, 0) + 1, dtype=torch.int64, device=maps6.device)
+    if n == 0:
+        return out
+    L = _lib.lib()
+    ws = _workspace_for("infogain", (B, S), lambda: L.nbp_infogain_workspace_bytes(B, S), maps6.device)
+    rc = L.nbp_infogain_visible_u64(_lib.ptr(maps6), B, S, R, int(dilate), cells.ctypes.data, n, _lib.ptr(out),
+                                    _lib.ptr(ws), ws.numel(), _st())
+    _lib.check(rc, "nbp_infogain_visible_u64")
+    return out
