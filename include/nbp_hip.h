@@ -1116,6 +1116,27 @@ int nbp_depth_noise_batch_f32(int n, const float* const* clean, float* const* ou
                               int H, int W, float sigma_base, float sigma_quad, float z_min, unsigned drop_thr, float edge_threshold,
                               void* stream);
 
+/* ---- The depth-frame filter (csrc/nbp_depth_filter.hip; the definition, which the kernel equals bit for bit, is
+ * nextbestpath_amd/utility/depth_filter.py).  Not in the reference.  Raw [H][W] fp32 frames (z = -1: no return; a
+ * pixel is valid iff z > -1) -> filtered frames, in one pass that reads the raw frame only; every output value is an element of
+ * the input or -1.  Window: the (2 radius + 1)^2 - 1 neighbours inside the image; gate(c) = range_base + range_quad (c c), three
+ * fp32 operations.  Valid centre z: n = the valid neighbours with |z_q - z| <= gate(z); n < min_support -> -1; else, smooth != 0 ->
+ * the element of rank n / 2 of those neighbours and z (the median, the lower one of an even set); else z.  Invalid centre,
+ * fill_support > 0 and at least fill_support valid neighbours: m = their element of rank (count - 1) / 2, written iff every one of
+ * them has |v - m| <= gate(m); -1 otherwise.  Out of place: a raw frame that overlaps an output frame is NBP_E_ARG.  One launch
+ * (a 32 x 32 tile with its halo in LDS per workgroup), no workspace, no atomics.
+ *   nbp_depth_filter_f32        n (<= 65535) consecutive frames
+ *   nbp_depth_filter_batch_f32  n (<= 48: 12 items of <= 4 frames) frames, each with its own raw / out pointer (HOST arrays of n
+ *                               entries; they travel as kernel arguments)
+ * 16-byte accesses when W % 4 == 0 and every frame lies on the 16-byte grid, 4-byte accesses otherwise: any H, W >= 1.
+ * NBP_E_ARG: null pointer, n / H / W < 1, radius not 1 or 2, a negative or NaN range, both ranges 0, a support outside
+ * 0 .. (2 radius + 1)^2 - 1, overlapping frames; NBP_E_SHAPE: H W > 2^29 or more frames than the form takes.  Nothing is written
+ * on an error. */
+int nbp_depth_filter_f32(const float* raw, float* out, int n, int H, int W, int radius, float range_base, float range_quad,
+                         int smooth, int min_support, int fill_support, void* stream);
+int nbp_depth_filter_batch_f32(int n, const float* const* raw, float* const* out, int H, int W, int radius, float range_base,
+                               float range_quad, int smooth, int min_support, int fill_support, void* stream);
+
 /* ---- Held-out view metrics (csrc/nbp_views.hip; the definition, which the kernels equal, is
  * nextbestpath_amd/utility/view_metrics.py).  Not in the reference.  A point-splat render of a cloud [n][3] that is on
  * the device from n_views cameras (cams_host [n_views][12]: R row-major then T, on the HOST; they travel as kernel arguments in

@@ -18,6 +18,7 @@ import os
 import numpy as np
 import torch
 
+from ..utility import depth_filter as filter_options
 from ..utility import depth_noise as noise_options
 from ..utility import hipops
 
@@ -68,7 +69,8 @@ def camera_RT(X_cam, V_cam):
 class Camera:
     def __init__(self, x_min, x_max, pose_l, pose_w, pose_h, pose_n_elev, pose_n_azim, n_interpolation_steps,
                  zfar, image_height, image_width, device, gathering_factor=0.05, sensor_range=70.0, seed=0,
-                 ambient_light_intensity=0.85, contrast_factor=1.0, render_rgb=True, depth_noise=None):
+                 ambient_light_intensity=0.85, contrast_factor=1.0, render_rgb=True, depth_noise=None,
+                 depth_filter=None):
         self.x_min_arg = np.asarray(x_min, f32)
         self.x_min = self.x_min_arg + f32(3)             # mu:2230-2231 (kept for parity of attributes)
         self.x_max = np.asarray(x_max, f32) - f32(3)
@@ -109,6 +111,11 @@ class Camera:
         self.depth_noise = noise_options.option_spec(depth_noise)
         self._zclean_ring = None
         self._noise_seed = None if self.depth_noise is None else noise_options.word_seed(self.depth_noise, self.seed)
+        # the option `depth_filter` (None = off: nothing is allocated or launched, the paths above are as they are; a dict:
+        # utility/depth_filter.py::option_spec).  On: what the sensor delivers -- the noise launch's output, or the render when the
+        # noise is off -- goes to the same slot of _zraw_ring, and the filter launch behind it writes the depth ring's slot
+        self.depth_filter = filter_options.option_spec(depth_filter)
+        self._zraw_ring = None
         self._traj_dev = torch.zeros(512, 3, dtype=torch.float32, device=device)
         self._traj_n = 0
         self._overflow = torch.zeros(1, dtype=torch.int32, device=device)
@@ -259,13 +266,35 @@ class Camera:
             self._zclean_ring = torch.empty(16, self.image_height, self.image_width, dtype=torch.float32, device=self.device)
         return self._zclean_ring[slot:slot + n]
 
+    def _raw_slots(self, slot, n):
+        """Filter on: the slots of the raw ring, which hold the frames as the sensor delivered them (same numbering again)."""
+        if self._zraw_ring is None:
+            self._zraw_ring = torch.empty(16, self.image_height, self.image_width, dtype=torch.float32, device=self.device)
+        return self._zraw_ring[slot:slot + n]
+
+    def _render_slots(self, noisy, slot, n):
+        """Where the rasteriser writes the n frames of depth-ring slots `noisy`: the clean ring with the noise on, else the raw ring
+        with the filter on, else the depth ring itself."""
+        if self.depth_noise is not None:
+            return self._clean_slots(slot, n)
+        return noisy if self.depth_filter is None else self._raw_slots(slot, n)
+
     def noise_item(self, slot, n):
         """hipops.depth_noise_batch's item for the n frames rendered into clean slots slot.. and not committed yet: (clean frame
-        pointers, depth-ring frame pointers, word seed, frame ids = their numbers in this camera's capture order)."""
+        pointers, depth-ring frame pointers -- the raw ring's when the option `depth_filter` is on --, word seed, frame ids = their
+        numbers in this camera's capture order)."""
         hw4 = self.image_height * self.image_width * 4
-        c0, z0 = self._zclean_ring.data_ptr(), self._zbuf_ring.data_ptr()
+        c0 = self._zclean_ring.data_ptr()
+        z0 = (self._zbuf_ring if self.depth_filter is None else self._raw_slots(0, 16)).data_ptr()
         return ([c0 + k * hw4 for k in range(slot, slot + n)], [z0 + k * hw4 for k in range(slot, slot + n)], self._noise_seed,
                 [self.n_frames_captured + i for i in range(n)])
+
+    def filter_item(self, slot, n):
+        """hipops.depth_filter_batch's item for the n frames whose raw slots slot.. are (being) written and that are not committed
+        yet: (raw frame pointers, depth-ring frame pointers)."""
+        hw4 = self.image_height * self.image_width * 4
+        r0, z0 = self._raw_slots(0, 16).data_ptr(), self._zbuf_ring.data_ptr()
+        return [r0 + k * hw4 for k in range(slot, slot + n)], [z0 + k * hw4 for k in range(slot, slot + n)]
 
     def _commit(self, out, cams_host, slot):
         n = len(cams_host)
@@ -285,8 +314,8 @@ class Camera:
         assert self.deferred_colours(mesh)
         out, slot = self._reserve(len(cams_host))
         self._mesh = mesh
-        if self.depth_noise is not None:           # the render goes to the clean slots; the caller's noise launch fills `out`
-            out = self._clean_slots(slot, len(cams_host))
+        # with `depth_noise` or `depth_filter` on, the render goes to the clean or raw slots; the caller's launches fill `out`
+        out = self._render_slots(out, slot, len(cams_host))
         return out, self._zface_slots(slot, len(cams_host)), slot
 
     def _zface_slots(self, slot, n):
@@ -295,8 +324,8 @@ class Camera:
         return self._zface_ring[slot:slot + n]
 
     def capture_commit(self, out, cams_host, slot):
-        if self.depth_noise is not None:           # (`out` were the clean slots: the frames are the depth ring's)
-            out = self._zbuf_ring[slot:slot + len(cams_host)]
+        if self.depth_noise is not None or self.depth_filter is not None:      # (`out` were the clean or raw slots: the frames
+            out = self._zbuf_ring[slot:slot + len(cams_host)]                  # are the depth ring's)
         self._commit(out, cams_host, slot)
 
     def capture_images(self, mesh, cams_host):
@@ -304,7 +333,7 @@ class Camera:
         n = len(cams_host)
         noisy, slot = self._reserve(n)
         self._mesh = mesh
-        out = noisy if self.depth_noise is None else self._clean_slots(slot, n)
+        out = self._render_slots(noisy, slot, n)
         if self.deferred_colours(mesh):
             # depth AND the nearest face per pixel: the colours of the reference's renderer (mu:2743-2763) are a pure
             # function of (face, pixel, camera, mesh), so they are evaluated where they are consumed -- for the ~5 % of
@@ -320,8 +349,11 @@ class Camera:
         else:
             hipops.raster_zbuf(mesh.verts, mesh.faces, cams_host, self.image_height, self.image_width, bin_cap=mesh.bin_cap,
                                out=out, overflow=self._overflow)
-        if self.depth_noise is not None:           # same stream, behind the render: clean slot -> depth-ring slot
-            hipops.depth_noise(out, noisy, self._noise_seed, self.n_frames_captured, self.depth_noise)
+        if self.depth_noise is not None:           # same stream, behind the render: clean slot -> depth-ring (or raw) slot
+            raw = noisy if self.depth_filter is None else self._raw_slots(slot, n)
+            hipops.depth_noise(out, raw, self._noise_seed, self.n_frames_captured, self.depth_noise)
+        if self.depth_filter is not None:          # behind both: raw slot -> depth-ring slot
+            hipops.depth_filter(self._raw_slots(slot, n), noisy, self.depth_filter)
         self._commit(noisy, cams_host, slot)
         return noisy
 
@@ -341,13 +373,18 @@ class Camera:
         """The 4 interpolated updates + captures of nbp_planning.py:269-274 with ONE raster launch."""
         return self.capture_images(mesh, self.move_poses(next_idx))
 
-    def frames_batch(self, which, clean=False):
+    def frames_batch(self, which, clean=False, raw=False):
         """Stacks frames by negative offsets (e.g. [-1] = current, [-5,-4,-3,-2] = supervision batch):
         (depth [n,H,W] device, cams [n,12] HOST -- cameras travel as kernel arguments).  clean=True: the frames as rendered, before
-        the option `depth_noise` (the same frames when it is off)."""
+        the option `depth_noise` (the same frames when it is off).  raw=True: the frames as the sensor delivered them, before the
+        option `depth_filter` (the same frames as the default when it is off)."""
         sel = [self.frames[w] for w in which]
         slots = [s[2] for s in sel]
-        ring = self._zclean_ring if clean and self.depth_noise is not None else self._zbuf_ring
+        ring = self._zbuf_ring
+        if clean and self.depth_noise is not None:
+            ring = self._zclean_ring
+        elif (clean or raw) and self.depth_filter is not None:      # (noise off: the render IS what the sensor delivered)
+            ring = self._zraw_ring
         if all(b == a + 1 for a, b in zip(slots, slots[1:])):
             z = ring[slots[0]:slots[0] + len(slots)]                     # consecutive ring slots: a view, no copy kernel
         else:

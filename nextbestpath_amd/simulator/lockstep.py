@@ -106,16 +106,18 @@ def _concurrent_streams(device, n, tries=24, cycles=300_000, against=(), priorit
     return chosen, {"streams_tested": tested, "concurrent": ok}
 
 
-def setup_test_camera(params, mesh, start_cam_idx, settings, device, seed=0, depth_noise=None):
+def setup_test_camera(params, mesh, start_cam_idx, settings, device, seed=0, depth_noise=None, depth_filter=None):
     """macarons/testers/scene.py:410-488: build the camera, step to the first collision-free
     neighbour of the start pose, capture, then walk to the start pose capturing 4 frames.  `depth_noise`: the camera's option of
-    that name (None = off), set before these captures: they are frames 0..4 of its noise sequence."""
+    that name (None = off), set before these captures: they are frames 0..4 of its noise sequence.  `depth_filter`: the camera's
+    option of that name (None = off): these captures pass through it too."""
     cam = Camera(settings.camera.x_min, settings.camera.x_max, settings.camera.pose_l, settings.camera.pose_w,
                  settings.camera.pose_h, settings.camera.pose_n_elev, settings.camera.pose_n_azim,
                  params.n_interpolation_steps, params.zfar, params.image_height, params.image_width, device,
                  params.gathering_factor, params.sensor_range, seed=seed,
                  ambient_light_intensity=getattr(params, "ambient_light_intensity", 0.85),
-                 contrast_factor=getattr(settings.camera, "contrast_factor", 1.0), depth_noise=depth_noise)
+                 contrast_factor=getattr(settings.camera, "contrast_factor", 1.0), depth_noise=depth_noise,
+                 depth_filter=depth_filter)
     start = tuple(int(v) for v in start_cam_idx)
     neigh = cam.get_neighboring_poses(start)
     segs = torch.from_numpy(np.stack([np.concatenate([cam.pose_from_idx(n)[:3], cam.pose_from_idx(start)[:3]])
@@ -226,7 +228,8 @@ def render_moves(grp, next_idx):
     rendered in ONE rasteriser call when every camera defers its colours, else one call per rollout (identical frames).  Cameras
     with the option `depth_noise` render into their clean slots (capture_begin hands those out); ONE noise launch per spec over all
     their new frames follows the render (a frame's noise depends on its camera's seed, its id and the pixel only: the same frames
-    as alone)."""
+    as alone).  Cameras with the option `depth_filter` get ONE filter launch per spec behind that, from their raw slots into the
+    depth ring (a frame's filtered value depends on that frame only)."""
     p0 = grp[0].params
     moves = [r.camera.move_poses(idx) for r, idx in zip(grp, next_idx)]
     if not all(r.camera.deferred_colours(r.mesh) for r in grp):
@@ -242,5 +245,11 @@ def render_moves(grp, next_idx):
             noisy.setdefault(tuple(sorted(r.camera.depth_noise.items())), []).append(r.camera.noise_item(slot, len(cams)))
     for spec, items in noisy.items():
         hipops.depth_noise_batch(items, dict(spec), p0.image_height, p0.image_width)
+    filtered = {}                                  # the same for the option `depth_filter`, behind the noise: raw slot -> depth ring
+    for r, cams, (_, _, slot) in zip(grp, moves, pend):
+        if r.camera.depth_filter is not None:
+            filtered.setdefault(tuple(sorted(r.camera.depth_filter.items())), []).append(r.camera.filter_item(slot, len(cams)))
+    for spec, items in filtered.items():
+        hipops.depth_filter_batch(items, dict(spec), p0.image_height, p0.image_width)
     for r, cams, (out, _, slot) in zip(grp, moves, pend):
         r.camera.capture_commit(out, cams, slot)

@@ -29,6 +29,7 @@ from ..simulator import lockstep
 from ..simulator import scene as sim_scene
 from ..simulator.lockstep import N_POSES, RolloutState, _concurrent_streams, _settle_gc, setup_test_camera  # noqa: F401
 from ..utility import hipops
+from ..utility import depth_filter as filter_options
 from ..utility import depth_noise as noise_options
 from ..utility import recon_metrics as recon_options
 from ..utility import utils as hu
@@ -555,6 +556,7 @@ def compute_nbp_trajectory(params, nbp, camera, gt_scene_pc, mesh, mesh_for_chec
 _test_config_ensemble = [_UNSET]
 _test_config_recon = [_UNSET]            # ... and its `recon_metrics` key, the same way
 _test_config_noise = [_UNSET]            # ... and its `depth_noise` key
+_test_config_filter = [_UNSET]           # ... and its `depth_filter` key
 _test_config_views = [_UNSET]            # ... and its `view_metrics` key
 _test_config_policy = [_UNSET]           # ... and its `policy` key
 
@@ -582,6 +584,7 @@ def load_params(path):
         _test_config_ensemble[0] = getattr(p, "symmetry_ensemble", _UNSET)
         _test_config_recon[0] = getattr(p, "recon_metrics", _UNSET)
         _test_config_noise[0] = getattr(p, "depth_noise", _UNSET)
+        _test_config_filter[0] = getattr(p, "depth_filter", _UNSET)
         _test_config_views[0] = getattr(p, "view_metrics", _UNSET)
         _test_config_policy[0] = getattr(p, "policy", _UNSET)
     return p
@@ -599,9 +602,10 @@ def list_runs(dataset, params):
 
 
 def build_rollout(params, nbp, dataset, run, device, test_resolution=0.05, state=None, seed=0, grid=256, recon_metrics=None,
-                  depth_noise=None, view_metrics=None):
+                  depth_noise=None, view_metrics=None, depth_filter=None):
     """Scene + GT surface + camera + Rollout for one (scene, start pose) run (nbp_planning.py:414-492).  `depth_noise`: the camera's
-    sensor model (utility/depth_noise.py; None = off, perfect depth)."""
+    sensor model (utility/depth_noise.py; None = off, perfect depth).  `depth_filter`: the camera's frame filter behind it
+    (utility/depth_filter.py; None = off)."""
     si, k = run
     sd = dataset[si]
     settings = sim_scene.Settings(sd["settings"], params.scene_scale_factor)
@@ -609,7 +613,8 @@ def build_rollout(params, nbp, dataset, run, device, test_resolution=0.05, state
                                 params.scene_scale_factor, device)
     y_bins = sim_scene.y_bins_for(mesh.verts_host, 4)
     _, gt_dev = sim_scene.setup_gt_scene(params, settings, mesh, device, test_resolution, seed=seed)
-    camera = setup_test_camera(params, mesh, settings.camera.start_positions[k], settings, device, seed=seed, depth_noise=depth_noise)
+    camera = setup_test_camera(params, mesh, settings.camera.start_positions[k], settings, device, seed=seed, depth_noise=depth_noise,
+                               depth_filter=depth_filter)
     ro = Rollout(params, nbp, camera, gt_dev, mesh, mesh, y_bins, device, state, seed, grid, recon_metrics=recon_metrics,
                  view_metrics=view_metrics)
     ro.scene_name, ro.start = sd["scene_name"], k
@@ -624,6 +629,8 @@ def _result(ro, n_poses):
         res["policy"] = dict(ro.nbp.options)
     if ro.camera.depth_noise is not None:              # the option `depth_noise`: the normalised spec the frames were made with
         res["depth_noise"] = dict(ro.camera.depth_noise)
+    if ro.camera.depth_filter is not None:             # the option `depth_filter`: the normalised spec the frames went through
+        res["depth_filter"] = dict(ro.camera.depth_filter)
     if ro.recon is not None:        # the option `recon_metrics`: the whole cloud once, at the rollout's end
         raw = ro.reconstruction_metrics(raw=True)
         res["reconstruction"] = recon_options.summarise_raw(raw, ro.recon.thresholds, ro.recon.cap)
@@ -649,10 +656,10 @@ def _policy_or(nbp, policy):
 
 
 def run_one(params, nbp, dataset, run, device, test_resolution=0.05, state=None, n_poses=N_POSES, seed=0, *, recon_metrics=None,
-            depth_noise=None, view_metrics=None, policy=None):
+            depth_noise=None, view_metrics=None, policy=None, depth_filter=None):
     nbp = _policy_or(nbp, policy)
     ro = build_rollout(params, nbp, dataset, run, device, test_resolution, state, seed, recon_metrics=recon_metrics,
-                       depth_noise=depth_noise, view_metrics=view_metrics)
+                       depth_noise=depth_noise, view_metrics=view_metrics, depth_filter=depth_filter)
     nbp.eval()
     for _ in range(n_poses):
         ro.step()
@@ -661,7 +668,7 @@ def run_one(params, nbp, dataset, run, device, test_resolution=0.05, state=None,
 
 
 def run_many(params, nbp, dataset, runs, device, seeds, test_resolution=0.05, n_poses=N_POSES, rollouts_per_gpu=48,
-             grid=256, timing=None, *, recon_metrics=None, depth_noise=None, view_metrics=None, policy=None):
+             grid=256, timing=None, *, recon_metrics=None, depth_noise=None, view_metrics=None, policy=None, depth_filter=None):
     """Runs `runs` in lock-step groups of `rollouts_per_gpu` (MultiRollout); same results as run_one each.  `timing` (a dict)
     receives the wall-clock seconds of scene / GT-surface / camera setup and of the stepping (device-synchronised).  `policy`: as
     in run_one (None = the network `nbp`)."""
@@ -673,7 +680,7 @@ def run_many(params, nbp, dataset, runs, device, seeds, test_resolution=0.05, n_
         t0 = time.perf_counter()
         chunk = list(zip(runs[g0:g0 + rollouts_per_gpu], seeds[g0:g0 + rollouts_per_gpu]))
         ros = [build_rollout(params, nbp, dataset, run, device, test_resolution, None, seed, grid, recon_metrics=recon_metrics,
-                             depth_noise=depth_noise, view_metrics=view_metrics)
+                             depth_noise=depth_noise, view_metrics=view_metrics, depth_filter=depth_filter)
                for run, seed in chunk]
         multi = MultiRollout(ros, nbp, device)
         if timing is not None:
@@ -696,7 +703,7 @@ def test_nbp_planning(params_file, model_file, results_json_file, numGPU, test_s
                       use_perfect_depth_map=False, compute_collision=False, load_json=False, dataset_path=None,
                       nbp_weights=None, configs_dir=None, results_dir=None, n_poses=N_POSES, seed=8, torch_seed=9,
                       rollouts_per_gpu=48, grid_size=256, nbp_precision=None, symmetry_ensemble=_UNSET, recon_metrics=_UNSET,
-                      depth_noise=_UNSET, view_metrics=_UNSET, policy=_UNSET):
+                      depth_noise=_UNSET, view_metrics=_UNSET, policy=_UNSET, depth_filter=_UNSET):
     """Same arguments as the reference (nbp_planning.py:364-374); `grid_size` / `nbp_precision` select
     BASELINE.json configs[4] (512 grid at the same 0.3125 units per pixel, bf16 convolutions).  `symmetry_ensemble` (None = off, a
     name of utility/augment.py::ENSEMBLES or a list of op codes) is NBP.symmetry_ensemble of the loaded network; not given, it is
@@ -705,7 +712,9 @@ def test_nbp_planning(params_file, model_file, results_json_file, numGPU, test_s
     quality of every rollout's final cloud (utility/recon_metrics.py) to its record, next to coverage and auc, and with `curve` the same
     metrics after every step ("reconstruction_curve": lists over the steps, with their AUCs).  `depth_noise` (None =
     off: perfect depth; a dict of utility/depth_noise.py::option_spec; not given, the key of that name in the same file) puts the seeded
-    sensor model between the rasteriser and every consumer of depth, and the normalised spec into every record.  `view_metrics` (None =
+    sensor model between the rasteriser and every consumer of depth, and the normalised spec into every record.  `depth_filter` (None =
+    off; a dict of utility/depth_filter.py::option_spec; not given, the key of that name in the same file) puts the frame filter (gated
+    median, speckle rejection, hole filling) behind the sensor, and its normalised spec into every record.  `view_metrics` (None =
     off, True = the defaults, or a dict of utility/view_metrics.py::option_spec; not given, the key of that name in the same file) adds
     the held-out view metrics of every rollout's final coloured cloud ("views": the cloud rendered from lattice poses against the mesh,
     with the options used) to its record.  `policy` (None or "nbp" = the network; "frontier" / "infogain" or a dict of
@@ -757,6 +766,9 @@ def test_nbp_planning(params_file, model_file, results_json_file, numGPU, test_s
     if depth_noise is _UNSET:
         depth_noise = None if _test_config_noise[0] is _UNSET else _test_config_noise[0]
     noise_spec = noise_options.option_spec(depth_noise)                       # (ValueError on anything but None or a dict of its keys)
+    if depth_filter is _UNSET:
+        depth_filter = None if _test_config_filter[0] is _UNSET else _test_config_filter[0]
+    filter_spec = filter_options.option_spec(depth_filter)                    # (ValueError on anything but None or a dict of its keys)
     if view_metrics is _UNSET:
         view_metrics = None if _test_config_views[0] is _UNSET else _test_config_views[0]
     view_spec = view_options.option_spec(view_metrics)                        # (ValueError on anything but None, True, a dict of its keys)
@@ -767,7 +779,7 @@ def test_nbp_planning(params_file, model_file, results_json_file, numGPU, test_s
     with torch.no_grad():
         results = run_many(params, nbp, dataset, mine, device, [seed + 1000 * r[0] + r[1] for r in mine],
                            test_resolution, n_poses, rollouts_per_gpu, grid_size, timing=timing, recon_metrics=recon_spec,
-                           depth_noise=noise_spec, view_metrics=view_spec)
+                           depth_noise=noise_spec, view_metrics=view_spec, depth_filter=filter_spec)
     for run, res in zip(mine, results):
         res["run_id"] = runs.index(run)
     t_gather = time.perf_counter()
@@ -808,6 +820,8 @@ def test_nbp_planning(params_file, model_file, results_json_file, numGPU, test_s
                 rec["policy"] = dict(policy_spec)
             if noise_spec is not None:
                 rec["depth_noise"] = dict(noise_spec)
+            if filter_spec is not None:
+                rec["depth_filter"] = dict(filter_spec)
             if view_spec is not None:
                 rec["views"] = r["views"]
             for key in ("X_cam_history", "V_cam_history"):      # histories of other ranks stay in their part files

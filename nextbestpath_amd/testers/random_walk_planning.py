@@ -48,7 +48,7 @@ class RandomWalkRollout:
 
     def _partial(self, which, seed, clean=False):
         """compute_partial_point_cloud of frames `which` into the scratch cloud -> (points view, device count).  clean=True: of
-        the frames before the camera's option `depth_noise` (the same frames when it is off)."""
+        the frames before the camera's options `depth_noise` and `depth_filter` (the same frames when they are off)."""
         depth, cams = self.camera.frames_batch(which, clean=clean)
         self.part_count.zero_()
         hipops.unproject_append(depth, None, cams, self.part, self.part_count, self.params.gathering_factor,
@@ -81,7 +81,7 @@ class RandomWalkRollout:
         self.covered_scene.fill_cells(self.part, n_dev=self.part_count)
         cov, _ = self.gt_scene.scene_coverage(self.covered_scene, surface_epsilon=self.eps)
         self.coverage_evolution.append(cov)
-        # the same frame through the depth path (perfect, or the camera's `depth_noise`) -> surface scene + full cloud (:118-136)
+        # the same frame through the depth path (perfect, or the camera's `depth_noise` / `depth_filter`) -> surface scene + full cloud (:118-136)
         depth, cams = self._partial([-1], self.seed + 11 * pose_i + 3)
         self.surface_scene.fill_cells(self.part, n_dev=self.part_count)
         self._append_full()
@@ -121,16 +121,19 @@ def compute_random_walk_trajectory(params, macarons, camera, gt_scene, surface_s
 
 def test_random_walk_planning(params_file, model_file, results_json_file, numGPU, test_scenes, test_resolution=0.05,
                               use_perfect_depth_map=True, compute_collision=False, load_json=False, dataset_path=None,
-                              configs_dir=None, results_dir=None, n_poses=200, seed=8, depth_noise=None):
+                              configs_dir=None, results_dir=None, n_poses=200, seed=8, depth_noise=None, depth_filter=None):
     """Same arguments as the reference (random_walk_planning.py:402-411): every (scene, start pose) of the dataset is
     rolled out and {scene: {start: {coverage, X_cam_history, V_cam_history}}} is written as JSON.  `model_file` (the
     MACARONS weights) is not loaded: perfect depth, or the seeded sensor model `depth_noise` (utility/depth_noise.py; None = off), whose
-    normalised spec then joins every record."""
+    normalised spec then joins every record; `depth_filter` (utility/depth_filter.py; None = off) puts the frame filter behind the
+    sensor, and its normalised spec into every record.  The "true coverage" reads the clean frames either way."""
     import json
     import os
+    from ..utility.depth_filter import option_spec as filter_option_spec
     from ..utility.depth_noise import option_spec
     from .nbp_planning import load_params, setup_test_camera
     noise_spec = option_spec(depth_noise)
+    filter_spec = filter_option_spec(depth_filter)
     here = os.path.dirname(os.path.abspath(__file__))
     configs_dir = configs_dir or os.path.join(here, "../../configs/macarons")
     results_dir = results_dir or os.path.join(here, "../../data")
@@ -149,13 +152,16 @@ def test_random_walk_planning(params_file, model_file, results_json_file, numGPU
         for k, start in enumerate(settings.camera.start_positions):
             s = seed + 1000 * si + k
             gt_scene, covered, surface, proxy = sim_scene.setup_test_scenes(params, settings, mesh, device, test_resolution, seed=s)
-            camera = setup_test_camera(params, mesh, start, settings, device, seed=s, depth_noise=noise_spec)
+            camera = setup_test_camera(params, mesh, start, settings, device, seed=s, depth_noise=noise_spec,
+                                       depth_filter=filter_spec)
             cov, X, V, *_ = compute_random_walk_trajectory(params, None, camera, gt_scene, surface, proxy, covered, mesh, device,
                                                            test_resolution, use_perfect_depth_map, compute_collision, n_poses,
                                                            seed=s)
             results[sd["scene_name"]][str(k)] = {"coverage": cov, "X_cam_history": X.tolist(), "V_cam_history": V.tolist()}
             if noise_spec is not None:
                 results[sd["scene_name"]][str(k)]["depth_noise"] = dict(noise_spec)
+            if filter_spec is not None:
+                results[sd["scene_name"]][str(k)]["depth_filter"] = dict(filter_spec)
     os.makedirs(results_dir, exist_ok=True)
     with open(path, "w") as fh:
         json.dump(results, fh)

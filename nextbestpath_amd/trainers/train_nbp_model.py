@@ -854,7 +854,8 @@ def run_training_nbp(params):
                                          n_poses=getattr(params, "n_collect_poses", 100),
                                          n_gt_points=getattr(params, "n_gt_surface_points", 50000),
                                          rollouts_per_gpu=getattr(params, "collect_rollouts_per_gpu", 1),
-                                         depth_noise=getattr(params, "collect_depth_noise", None))
+                                         depth_noise=getattr(params, "collect_depth_noise", None),
+                                         depth_filter=getattr(params, "collect_depth_filter", None))
         print(f"[rank {rank}] epoch {epoch}: collected {n} records ({env.entries()} in the store)")
         if epoch == 0:
             validation = nu.store_validation_data(env, getattr(params, "n_validation", 1200), keep_compact=True)

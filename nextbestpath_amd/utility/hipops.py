@@ -575,6 +575,57 @@ def depth_noise_batch(items, spec, H=None, W=None):
     _lib.check(rc, "nbp_depth_noise_batch_f32")
 
 
+# ---- the depth-frame filter (csrc/nbp_depth_filter.hip; the definition is utility/depth_filter.py)
+def _filter_args(spec):
+    from . import depth_filter as df
+    spec = df.option_spec(spec)
+    if spec is None:
+        raise ValueError("depth_filter: a spec is needed (None means off: nothing to launch)")
+    return (spec["radius"], spec["range_base"], spec["range_quad"], int(spec["smooth"]), spec["min_support"], spec["fill_support"])
+
+
+def depth_filter(raw, out, spec):
+    """The filter on raw [n,H,W] (or [H,W]) fp32 -> out (same shape, another buffer), frame by frame; spec:
+    depth_filter.option_spec's dict.  One launch.  Returns out."""
+    if raw.dtype != torch.float32 or out.dtype != torch.float32 or raw.shape != out.shape or raw.dim() not in (2, 3):
+        raise ValueError("depth_filter: raw and out are fp32 [n,H,W] (or [H,W]) of one shape")
+    n = raw.shape[0] if raw.dim() == 3 else 1
+    H, W = raw.shape[-2:]
+    rc = _lib.lib().nbp_depth_filter_f32(_lib.ptr(raw), _lib.ptr(out), n, H, W, *_filter_args(spec), _st())
+    _lib.check(rc, "nbp_depth_filter_f32")
+    return out
+
+
+def depth_filter_batch(items, spec, H=None, W=None):
+    """depth_filter for several cameras in one launch.  items = [(raw frames, out frames)]: per item up to 4 frames, each an [H,W]
+    fp32 tensor or a device pointer (then H and W are needed), which need not be adjacent in memory.  More than 12 items go in
+    chunks of 12."""
+    if len(items) > 12:
+        for i in range(0, len(items), 12):
+            depth_filter_batch(items[i:i + 12], spec, H, W)
+        return
+    args = _filter_args(spec)
+    ra, ou = [], []
+    for raw, out in items:
+        if not (1 <= len(raw) <= 4 and len(out) == len(raw)):
+            raise ValueError("depth_filter_batch: an item has 1 to 4 raw frames and as many output frames")
+        for r, o in zip(raw, out):
+            for t in (r, o):
+                if not isinstance(t, int):
+                    if t.dtype != torch.float32 or t.dim() != 2 or not t.is_contiguous() or (H is not None and tuple(t.shape) != (H, W)):
+                        raise ValueError("depth_filter_batch: frames are contiguous fp32 [H,W] tensors of one shape")
+                    H, W = t.shape
+            ra.append(r if isinstance(r, int) else r.data_ptr())
+            ou.append(o if isinstance(o, int) else o.data_ptr())
+    n = len(ra)
+    if n == 0:
+        return
+    if H is None or W is None:
+        raise ValueError("depth_filter_batch: frames given as pointers need H and W")
+    rc = _lib.lib().nbp_depth_filter_batch_f32(n, (C.c_void_p * n)(*ra), (C.c_void_p * n)(*ou), int(H), int(W), *args, _st())
+    _lib.check(rc, "nbp_depth_filter_batch_f32")
+
+
 def carve_update(proxy_pts, depth, mask, cam12_host, zfar, fov_range, tol, score_threshold, n_inside, n_behind, occ,
                  out_of_field, tan_half_fov=TAN_HALF_FOV):
     """A20 (macarons_utils.py:2849-2949, 3329-3363): in-place update of the per-proxy-point carving state."""

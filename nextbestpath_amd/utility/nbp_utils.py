@@ -797,7 +797,8 @@ class CollectionGroup:
 
 def trajectory_collection(params, current_epoch, dataset, db_env, pc2img_size, value_map_size, prediction_range, nbp,
                           coverage_after_trajectory, memory, device, folder_img_path=None, rank=0, world=1, n_poses=100,
-                          n_gt_points=None, rollouts_per_gpu=1, timing=None, replay_format=None, depth_noise=None):
+                          n_gt_points=None, rollouts_per_gpu=1, timing=None, replay_format=None, depth_noise=None,
+                          depth_filter=None):
     """ref :470-852.  `dataset` is a simulator.scene.SceneDataset; with world > 1 each rank collects the scenes
     rank, rank + world, ... into its own store (collection is embarrassingly parallel).
     rollouts_per_gpu = K > 1: up to K of the rank's scenes in lock-step (CollectionGroup); the store receives the same records in
@@ -805,10 +806,14 @@ def trajectory_collection(params, current_epoch, dataset, db_env, pc2img_size, v
     replay_format: "reference" (the reference's record bytes) or "compact" (utility/replay_codec.py: the same record, its images
     encoded on the device before they leave it); None = params.replay_format, "reference" when the config does not name one.
     depth_noise: the cameras' sensor model (utility/depth_noise.py::option_spec; None = off, perfect depth): what the collecting policy
-    sees and un-projects is the noisy depth, while the labels, slices of the mesh, do not change."""
+    sees and un-projects is the noisy depth, while the labels, slices of the mesh, do not change.
+    depth_filter: the cameras' frame filter behind the sensor (utility/depth_filter.py::option_spec; None = off); the labels do not
+    change with it either."""
     nbp.eval()
+    from .depth_filter import option_spec as filter_option_spec
     from .depth_noise import option_spec
     noise_spec = option_spec(depth_noise)
+    filter_spec = filter_option_spec(depth_filter)
     replay_format = check_replay_format(getattr(params, "replay_format", "reference") if replay_format is None else replay_format)
 
     def make(si):
@@ -820,7 +825,7 @@ def trajectory_collection(params, current_epoch, dataset, db_env, pc2img_size, v
         seed = 7919 * current_epoch + si
         _, gt_dev = sim_scene.setup_gt_scene(params, settings, mesh, device, 0.05, seed=seed, n_points=n_gt_points)
         camera = lockstep.setup_test_camera(params, mesh, settings.camera.start_positions[0], settings, device, seed=seed,
-                                            depth_noise=noise_spec)
+                                            depth_noise=noise_spec, depth_filter=filter_spec)
         return CollectionRollout(params, nbp, camera, gt_dev, mesh, y_bins, device, db_env, seed,
                                  pc2img_size[0], value_map_size[0], prediction_range, replay_format=replay_format)
 
