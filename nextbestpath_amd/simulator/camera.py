@@ -13,6 +13,7 @@ and azimuth wrap :2590-2632, look-at :940-957 (pytorch3d look_at_view_transform 
 """
 from __future__ import annotations
 
+import collections
 import os
 
 import numpy as np
@@ -66,7 +67,52 @@ def camera_RT(X_cam, V_cam):
     return hit[1], (-(X @ hit[0])).astype(f32)
 
 
+class FrameRings:
+    """The camera's named frame rings [16,H,W(,3)], each allocated on first use: `rings` holds the ones that exist."""
+
+    KINDS = {"depth": ((), torch.float32), "clean": ((), torch.float32), "raw": ((), torch.float32),
+             "zface": ((), torch.int64), "rgb": ((3,), torch.float32)}          # name -> (trailing shape, dtype)
+
+    def __init__(self, height, width, device):
+        self.shape, self.device, self.rings, self._addr = (16, height, width), device, {}, {}
+
+    def _ring(self, name):
+        ring = self.rings.get(name)
+        if ring is None:
+            tail, dtype = self.KINDS[name]
+            ring = self.rings[name] = torch.empty(*self.shape, *tail, dtype=dtype, device=self.device)
+            self._addr[name] = (ring.data_ptr(), ring.stride(0) * ring.element_size())
+        return ring
+
+    def slots(self, name, slot, n):
+        return self._ring(name)[slot:slot + n]
+
+    def view(self, name, slots):
+        ring = self._ring(name)
+        if all(b == a + 1 for a, b in zip(slots, slots[1:])):
+            return ring[slots[0]:slots[0] + len(slots)]                 # consecutive ring slots: a view, no copy kernel
+        return torch.stack([ring[k] for k in slots])
+
+    def pointers(self, name, slots):
+        """One device address per frame (the ring's frames are contiguous, 16-byte aligned)."""
+        self._ring(name)
+        base, step = self._addr[name]
+        return [base + k * step for k in slots]
+
+
+def _ring_property(name):
+    return property(lambda self: self._rings.rings.get(name))              # None until the ring exists
+
+
+# one stage of the sensor chain behind the render: `kind` ("noise" / "filter") reads ring `src` and writes the same slots of ring
+# `dst`; `key` is the spec as a hashable (the lock-step render groups cameras by it)
+Stage = collections.namedtuple("Stage", "kind src dst spec key")
+
+
 class Camera:
+    _zbuf_ring, _zclean_ring, _zraw_ring = _ring_property("depth"), _ring_property("clean"), _ring_property("raw")
+    _zface_ring, _rgb_ring = _ring_property("zface"), _ring_property("rgb")
+
     def __init__(self, x_min, x_max, pose_l, pose_w, pose_h, pose_n_elev, pose_n_azim, n_interpolation_steps,
                  zfar, image_height, image_width, device, gathering_factor=0.05, sensor_range=70.0, seed=0,
                  ambient_light_intensity=0.85, contrast_factor=1.0, render_rgb=True, depth_noise=None,
@@ -84,8 +130,7 @@ class Camera:
         self.seed = int(seed)
         self.ambient, self.contrast_factor = float(ambient_light_intensity), float(contrast_factor)
         self.render_rgb = render_rgb
-        self._rgb_ring = None
-        self._zface_ring = None
+        self._rings = FrameRings(self.image_height, self.image_width, device)
         self._mesh = None
         self.l_step = self.h_step = 3
         # ---- lattice (mu:2295-2320); flat order = cartesian product order (i, j, k, e, a)
@@ -103,19 +148,24 @@ class Camera:
         self.visited = set()
         self.n_frames_captured = 0
         self.frames = []                                # last frames: (zbuf [H,W] device view, cam12 host row)
-        self._zbuf_ring = None
         self._cursor = 0
-        # the option `depth_noise` (None = off: nothing is allocated or launched; a dict: utility/depth_noise.py::option_spec).  On:
-        # the rasteriser renders into _zclean_ring, the noise launch behind it writes the same slot of _zbuf_ring, which every
-        # consumer reads; frame ids count this camera's captures, the words' seed mixes the spec's seed with the camera's
+        # the options `depth_noise` and `depth_filter` (None = off: nothing is allocated or launched; a dict: option_spec of
+        # utility/depth_noise.py / depth_filter.py) make the sensor chain, decided here once: the rasteriser renders into the first
+        # stage's source ring, each stage's launch behind it, on the same stream, writes the same slot of its destination, and every
+        # consumer reads the depth ring.  Noise: frame ids count this camera's captures, the words' seed mixes the spec's seed with
+        # the camera's.  Filter: it reads what the sensor delivered -- the noise launch's output, or the render when the noise is off
         self.depth_noise = noise_options.option_spec(depth_noise)
-        self._zclean_ring = None
-        self._noise_seed = None if self.depth_noise is None else noise_options.word_seed(self.depth_noise, self.seed)
-        # the option `depth_filter` (None = off: nothing is allocated or launched, the paths above are as they are; a dict:
-        # utility/depth_filter.py::option_spec).  On: what the sensor delivers -- the noise launch's output, or the render when the
-        # noise is off -- goes to the same slot of _zraw_ring, and the filter launch behind it writes the depth ring's slot
         self.depth_filter = filter_options.option_spec(depth_filter)
-        self._zraw_ring = None
+        self._noise_seed = None if self.depth_noise is None else noise_options.word_seed(self.depth_noise, self.seed)
+        self.chain = []
+        if self.depth_noise is not None:
+            self.chain.append(Stage("noise", "clean", "depth" if self.depth_filter is None else "raw", self.depth_noise,
+                                    tuple(sorted(self.depth_noise.items()))))
+        if self.depth_filter is not None:
+            self.chain.append(Stage("filter", "raw", "depth", self.depth_filter, tuple(sorted(self.depth_filter.items()))))
+        self.stages = {st.kind: st for st in self.chain}
+        self._render_ring = self.chain[0].src if self.chain else "depth"
+        self._raw_ring = self.stages["filter"].src if "filter" in self.stages else "depth"
         self._traj_dev = torch.zeros(512, 3, dtype=torch.float32, device=device)
         self._traj_n = 0
         self._overflow = torch.zeros(1, dtype=torch.int32, device=device)
@@ -246,55 +296,31 @@ class Camera:
         self.update_camera(start_cam_idx)
 
     # ------------------------------------------------------------------ rendering (device resident frames)
-    def _ring(self):
-        if self._zbuf_ring is None:
-            self._zbuf_ring = torch.empty(16, self.image_height, self.image_width, dtype=torch.float32,
-                                          device=self.device)
-        return self._zbuf_ring
-
     def _reserve(self, n):
-        ring = self._ring()
+        """n slots of every ring, all rings numbered alike -> (the depth ring's, which the frames become; the render target's; first
+        slot)."""
         if self._cursor + n > 16:                       # explicit cursor: the 8 newest frames stay intact
             self._cursor = 0
         slot = self._cursor
         self._cursor += n
-        return ring[slot:slot + n], slot
+        depth = self._rings.slots("depth", slot, n)
+        return depth, (self._rings.slots(self._render_ring, slot, n) if self.chain else depth), slot
 
-    def _clean_slots(self, slot, n):
-        """Noise on: the slots of the clean ring that the rasteriser renders into (same numbering as the depth ring's)."""
-        if self._zclean_ring is None:
-            self._zclean_ring = torch.empty(16, self.image_height, self.image_width, dtype=torch.float32, device=self.device)
-        return self._zclean_ring[slot:slot + n]
-
-    def _raw_slots(self, slot, n):
-        """Filter on: the slots of the raw ring, which hold the frames as the sensor delivered them (same numbering again)."""
-        if self._zraw_ring is None:
-            self._zraw_ring = torch.empty(16, self.image_height, self.image_width, dtype=torch.float32, device=self.device)
-        return self._zraw_ring[slot:slot + n]
-
-    def _render_slots(self, noisy, slot, n):
-        """Where the rasteriser writes the n frames of depth-ring slots `noisy`: the clean ring with the noise on, else the raw ring
-        with the filter on, else the depth ring itself."""
-        if self.depth_noise is not None:
-            return self._clean_slots(slot, n)
-        return noisy if self.depth_filter is None else self._raw_slots(slot, n)
+    def stage_item(self, stage, slot, n):
+        """The batched launch's item (hipops.depth_noise_batch / depth_filter_batch) of `stage` for the n frames of slots slot..,
+        which are rendered and not committed yet: (source frame pointers, destination frame pointers), and for the noise (word
+        seed, frame ids = their numbers in this camera's capture order) behind them."""
+        slots = range(slot, slot + n)
+        item = (self._rings.pointers(stage.src, slots), self._rings.pointers(stage.dst, slots))
+        if stage.kind == "noise":
+            item += (self._noise_seed, [self.n_frames_captured + i for i in range(n)])
+        return item
 
     def noise_item(self, slot, n):
-        """hipops.depth_noise_batch's item for the n frames rendered into clean slots slot.. and not committed yet: (clean frame
-        pointers, depth-ring frame pointers -- the raw ring's when the option `depth_filter` is on --, word seed, frame ids = their
-        numbers in this camera's capture order)."""
-        hw4 = self.image_height * self.image_width * 4
-        c0 = self._zclean_ring.data_ptr()
-        z0 = (self._zbuf_ring if self.depth_filter is None else self._raw_slots(0, 16)).data_ptr()
-        return ([c0 + k * hw4 for k in range(slot, slot + n)], [z0 + k * hw4 for k in range(slot, slot + n)], self._noise_seed,
-                [self.n_frames_captured + i for i in range(n)])
+        return self.stage_item(self.stages["noise"], slot, n)
 
     def filter_item(self, slot, n):
-        """hipops.depth_filter_batch's item for the n frames whose raw slots slot.. are (being) written and that are not committed
-        yet: (raw frame pointers, depth-ring frame pointers)."""
-        hw4 = self.image_height * self.image_width * 4
-        r0, z0 = self._raw_slots(0, 16).data_ptr(), self._zbuf_ring.data_ptr()
-        return [r0 + k * hw4 for k in range(slot, slot + n)], [z0 + k * hw4 for k in range(slot, slot + n)]
+        return self.stage_item(self.stages["filter"], slot, n)
 
     def _commit(self, out, cams_host, slot):
         n = len(cams_host)
@@ -312,50 +338,42 @@ class Camera:
         """First half of capture_images for a batched render of several cameras (hipops.raster_zface_batch): reserves the ring
         slots and returns (out_z, out_zface, slot); capture_commit registers the frames once the launch is enqueued."""
         assert self.deferred_colours(mesh)
-        out, slot = self._reserve(len(cams_host))
+        n = len(cams_host)
+        _, out, slot = self._reserve(n)
         self._mesh = mesh
-        # with `depth_noise` or `depth_filter` on, the render goes to the clean or raw slots; the caller's launches fill `out`
-        out = self._render_slots(out, slot, len(cams_host))
-        return out, self._zface_slots(slot, len(cams_host)), slot
-
-    def _zface_slots(self, slot, n):
-        if self._zface_ring is None:
-            self._zface_ring = torch.empty(16, self.image_height, self.image_width, dtype=torch.int64, device=self.device)
-        return self._zface_ring[slot:slot + n]
+        # with a sensor chain the render goes to its first source ring; the caller's launches fill the depth ring's slots
+        return out, self._rings.slots("zface", slot, n), slot
 
     def capture_commit(self, out, cams_host, slot):
-        if self.depth_noise is not None or self.depth_filter is not None:      # (`out` were the clean or raw slots: the frames
-            out = self._zbuf_ring[slot:slot + len(cams_host)]                  # are the depth ring's)
-        self._commit(out, cams_host, slot)
+        """(`out` is capture_begin's render target: the frames are the depth ring's, whichever ring that was.)"""
+        self._commit(self._rings.slots("depth", slot, len(cams_host)) if self.chain else out, cams_host, slot)
 
     def capture_images(self, mesh, cams_host):
         """Rasterises len(cams_host) frames in one launch; cams_host [n,12] fp32 (R row-major, T)."""
         n = len(cams_host)
-        noisy, slot = self._reserve(n)
+        depth, out, slot = self._reserve(n)
         self._mesh = mesh
-        out = self._render_slots(noisy, slot, n)
         if self.deferred_colours(mesh):
             # depth AND the nearest face per pixel: the colours of the reference's renderer (mu:2743-2763) are a pure
             # function of (face, pixel, camera, mesh), so they are evaluated where they are consumed -- for the ~5 % of
             # pixels the un-projection keeps (colour_source), or as whole images on request (frames_rgb)
             hipops.raster_zface(mesh.verts, mesh.faces, cams_host, self.image_height, self.image_width, out_z=out,
-                                out_zface=self._zface_slots(slot, n))
+                                out_zface=self._rings.slots("zface", slot, n))
         elif self.render_rgb and getattr(mesh, "colors", None) is not None:
             # a contrast change needs every pixel's luminance: eager colour render, colours in a ring beside the depths
-            if self._rgb_ring is None:
-                self._rgb_ring = torch.empty(16, self.image_height, self.image_width, 3, dtype=torch.float32, device=self.device)
             hipops.raster_rgbz(mesh.verts, mesh.faces, mesh.colors, cams_host, self.image_height, self.image_width,
-                               self.ambient, self.contrast_factor, out_z=out, out_rgb=self._rgb_ring[slot:slot + n])
+                               self.ambient, self.contrast_factor, out_z=out, out_rgb=self._rings.slots("rgb", slot, n))
         else:
             hipops.raster_zbuf(mesh.verts, mesh.faces, cams_host, self.image_height, self.image_width, bin_cap=mesh.bin_cap,
                                out=out, overflow=self._overflow)
-        if self.depth_noise is not None:           # same stream, behind the render: clean slot -> depth-ring (or raw) slot
-            raw = noisy if self.depth_filter is None else self._raw_slots(slot, n)
-            hipops.depth_noise(out, raw, self._noise_seed, self.n_frames_captured, self.depth_noise)
-        if self.depth_filter is not None:          # behind both: raw slot -> depth-ring slot
-            hipops.depth_filter(self._raw_slots(slot, n), noisy, self.depth_filter)
-        self._commit(noisy, cams_host, slot)
-        return noisy
+        for st in self.chain:                      # same stream, behind the render: each stage from its source slots to its destination's
+            src, dst = self._rings.slots(st.src, slot, n), self._rings.slots(st.dst, slot, n)
+            if st.kind == "noise":
+                hipops.depth_noise(src, dst, self._noise_seed, self.n_frames_captured, st.spec)
+            else:
+                hipops.depth_filter(src, dst, st.spec)
+        self._commit(depth, cams_host, slot)
+        return depth
 
     def capture_image(self, mesh):
         cam = np.concatenate([self.R_cam.reshape(-1), self.T_cam.reshape(-1)]).astype(f32)
@@ -379,42 +397,31 @@ class Camera:
         the option `depth_noise` (the same frames when it is off).  raw=True: the frames as the sensor delivered them, before the
         option `depth_filter` (the same frames as the default when it is off)."""
         sel = [self.frames[w] for w in which]
-        slots = [s[2] for s in sel]
-        ring = self._zbuf_ring
-        if clean and self.depth_noise is not None:
-            ring = self._zclean_ring
-        elif (clean or raw) and self.depth_filter is not None:      # (noise off: the render IS what the sensor delivered)
-            ring = self._zraw_ring
-        if all(b == a + 1 for a, b in zip(slots, slots[1:])):
-            z = ring[slots[0]:slots[0] + len(slots)]                     # consecutive ring slots: a view, no copy kernel
-        else:
-            z = torch.stack([ring[k] for k in slots])
-        return z, np.stack([s[1] for s in sel]).astype(f32)
+        # (clean with the noise off: the render IS what the sensor delivered; either with its stage off: the depth ring)
+        name = self._render_ring if clean else self._raw_ring if raw else "depth"
+        return self._rings.view(name, [s[2] for s in sel]), np.stack([s[1] for s in sel]).astype(f32)
 
-    def _ring_view(self, ring, which):
-        slots = [self.frames[w][2] for w in which]
-        if all(b == a + 1 for a, b in zip(slots, slots[1:])):
-            return ring[slots[0]:slots[0] + len(slots)]
-        return torch.stack([ring[k] for k in slots])
+    def _slots(self, which):
+        return [self.frames[w][2] for w in which]
 
     def frames_rgb(self, which):
         """Colour images of the same frames [n,H,W,3] (None when the camera renders depth only)."""
         if self._zface_ring is not None:
             m = self._mesh
             cams = np.stack([self.frames[w][1] for w in which]).astype(f32)
-            return hipops.shade_image(self._ring_view(self._zface_ring, which), m.verts, m.faces, m.colors, cams, self.ambient)
+            return hipops.shade_image(self._rings.view("zface", self._slots(which)), m.verts, m.faces, m.colors, cams, self.ambient)
         if self._rgb_ring is None:
             return None
-        return self._ring_view(self._rgb_ring, which)
+        return self._rings.view("rgb", self._slots(which))
 
     def colour_source(self, which):
         """Keyword arguments that make hipops.unproject_append carry the colours of these frames: {} when the camera renders
         depth only, shade=(nearest faces, mesh, ambient) in the deferred form, rgb=images after an eager colour render."""
         if self._zface_ring is not None:
             m = self._mesh
-            return {"shade": (self._ring_view(self._zface_ring, which), m.verts, m.faces, m.colors, self.ambient)}
+            return {"shade": (self._rings.view("zface", self._slots(which)), m.verts, m.faces, m.colors, self.ambient)}
         if self._rgb_ring is not None:
-            return {"rgb": self._ring_view(self._rgb_ring, which)}
+            return {"rgb": self._rings.view("rgb", self._slots(which))}
         return {}
 
     def ring_frames(self, which, colours):
@@ -422,18 +429,16 @@ class Camera:
         (depth frame pointers, cams host [F,12], shade), shade = (nearest-face frame pointers, verts, faces, vertex colours, ambient)
         when `colours` are wanted and this camera defers them, else None.  None when the frames are not ring slots or the camera
         renders colours eagerly (those travel as whole images: the single call)."""
-        if self._zbuf_ring is None or self._rgb_ring is not None:
+        rings = self._rings.rings
+        if "depth" not in rings or "rgb" in rings:
             return None
-        slots = [self.frames[w][2] for w in which]
-        hw4 = self.image_height * self.image_width * 4
-        z0 = self._zbuf_ring.data_ptr()
-        depth = [z0 + k * hw4 for k in slots]                  # (the ring's frames are [H,W] fp32, 16-byte aligned)
+        slots = self._slots(which)
+        depth = self._rings.pointers("depth", slots)
         cams = np.stack([self.frames[w][1] for w in which]).astype(f32)
         shade = None
-        if colours and self._zface_ring is not None:
+        if colours and "zface" in rings:
             m = self._mesh
-            f0 = self._zface_ring.data_ptr()
-            shade = ([f0 + 2 * k * hw4 for k in slots], m.verts, m.faces, m.colors, self.ambient)
+            shade = (self._rings.pointers("zface", slots), m.verts, m.faces, m.colors, self.ambient)
         return depth, cams, shade
 
     @property

@@ -226,10 +226,10 @@ def unproject_group(grp, frames, colours):
 def render_moves(grp, next_idx):
     """Every rollout of a group moves to its next lattice index (next_idx[i]): the 4 interpolated frames of all the moves are
     rendered in ONE rasteriser call when every camera defers its colours, else one call per rollout (identical frames).  Cameras
-    with the option `depth_noise` render into their clean slots (capture_begin hands those out); ONE noise launch per spec over all
-    their new frames follows the render (a frame's noise depends on its camera's seed, its id and the pixel only: the same frames
-    as alone).  Cameras with the option `depth_filter` get ONE filter launch per spec behind that, from their raw slots into the
-    depth ring (a frame's filtered value depends on that frame only)."""
+    with a sensor chain render into its first source slots (capture_begin hands those out); behind the render, stage kind by stage
+    kind in chain order, ONE launch per spec over all the new frames of the cameras with that stage (a group shares one spec unless
+    a caller mixes rollouts).  The same frames as alone: a frame's noise depends on its camera's seed, its id and the pixel only,
+    its filtered value on that frame only."""
     p0 = grp[0].params
     moves = [r.camera.move_poses(idx) for r, idx in zip(grp, next_idx)]
     if not all(r.camera.deferred_colours(r.mesh) for r in grp):
@@ -239,17 +239,13 @@ def render_moves(grp, next_idx):
     pend = [r.camera.capture_begin(r.mesh, cams) for r, cams in zip(grp, moves)]
     hipops.raster_zface_batch([(r, r.mesh.verts, r.mesh.faces, cams, out, zf) for r, cams, (out, zf, _) in zip(grp, moves, pend)],
                               p0.image_height, p0.image_width, len(moves[0]))
-    noisy = {}                                     # spec -> items (a group shares one spec unless a caller mixes rollouts)
-    for r, cams, (_, _, slot) in zip(grp, moves, pend):
-        if r.camera.depth_noise is not None:
-            noisy.setdefault(tuple(sorted(r.camera.depth_noise.items())), []).append(r.camera.noise_item(slot, len(cams)))
-    for spec, items in noisy.items():
-        hipops.depth_noise_batch(items, dict(spec), p0.image_height, p0.image_width)
-    filtered = {}                                  # the same for the option `depth_filter`, behind the noise: raw slot -> depth ring
-    for r, cams, (_, _, slot) in zip(grp, moves, pend):
-        if r.camera.depth_filter is not None:
-            filtered.setdefault(tuple(sorted(r.camera.depth_filter.items())), []).append(r.camera.filter_item(slot, len(cams)))
-    for spec, items in filtered.items():
-        hipops.depth_filter_batch(items, dict(spec), p0.image_height, p0.image_width)
+    for kind, launch in {"noise": hipops.depth_noise_batch, "filter": hipops.depth_filter_batch}.items():
+        by_spec = {}                               # spec key -> (spec, items), in first-appearance order
+        for r, cams, (_, _, slot) in zip(grp, moves, pend):
+            stage = r.camera.stages.get(kind)
+            if stage is not None:
+                by_spec.setdefault(stage.key, (stage.spec, []))[1].append(r.camera.stage_item(stage, slot, len(cams)))
+        for spec, items in by_spec.values():
+            launch(items, spec, p0.image_height, p0.image_width)
     for r, cams, (out, _, slot) in zip(grp, moves, pend):
         r.camera.capture_commit(out, cams, slot)

@@ -19,6 +19,7 @@ import json
 import os
 import random
 import time
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -28,7 +29,7 @@ from ..networks.nbp_model import NBP
 from ..simulator import lockstep
 from ..simulator import scene as sim_scene
 from ..simulator.lockstep import N_POSES, RolloutState, _concurrent_streams, _settle_gc, setup_test_camera  # noqa: F401
-from ..utility import hipops
+from ..utility import augment, hipops
 from ..utility import depth_filter as filter_options
 from ..utility import depth_noise as noise_options
 from ..utility import recon_metrics as recon_options
@@ -551,14 +552,10 @@ def compute_nbp_trajectory(params, nbp, camera, gt_scene_pc, mesh, mesh_for_chec
     return coverage_evolution, camera.X_cam_history, camera.V_cam_history, ro.st.cloud[:n_cloud], colors
 
 
-# the `symmetry_ensemble` key of the configs/test/ file load_params read last (a file with the NBP options: `nbp_weights`); the entry
-# script passes test_nbp_planning the options it knows by keyword, and this one reaches it here
-_test_config_ensemble = [_UNSET]
-_test_config_recon = [_UNSET]            # ... and its `recon_metrics` key, the same way
-_test_config_noise = [_UNSET]            # ... and its `depth_noise` key
-_test_config_filter = [_UNSET]           # ... and its `depth_filter` key
-_test_config_views = [_UNSET]            # ... and its `view_metrics` key
-_test_config_policy = [_UNSET]           # ... and its `policy` key
+# the option keys of the configs/test/ file load_params read last (a file with the NBP options: `nbp_weights`), each _UNSET where the
+# file has none; the entry script passes test_nbp_planning the options it knows by keyword, and these reach it here.  In the order
+# in which resolve_options checks them
+_test_config = dict.fromkeys(("policy", "symmetry_ensemble", "recon_metrics", "depth_noise", "depth_filter", "view_metrics"), _UNSET)
 
 
 def load_params(path):
@@ -581,12 +578,8 @@ def load_params(path):
     for k, v in flat(raw, {}).items():
         setattr(p, k, v)
     if hasattr(p, "nbp_weights"):
-        _test_config_ensemble[0] = getattr(p, "symmetry_ensemble", _UNSET)
-        _test_config_recon[0] = getattr(p, "recon_metrics", _UNSET)
-        _test_config_noise[0] = getattr(p, "depth_noise", _UNSET)
-        _test_config_filter[0] = getattr(p, "depth_filter", _UNSET)
-        _test_config_views[0] = getattr(p, "view_metrics", _UNSET)
-        _test_config_policy[0] = getattr(p, "policy", _UNSET)
+        for key in _test_config:
+            _test_config[key] = getattr(p, key, _UNSET)
     return p
 
 
@@ -621,16 +614,50 @@ def build_rollout(params, nbp, dataset, run, device, test_resolution=0.05, state
     return ro
 
 
+def run_tags(policy_spec, noise_spec, filter_spec):
+    """The entries that every record of a run carries for the options `policy`, `depth_noise` and `depth_filter`: those that are on
+    (a normalised spec, not None), in that order, each a copy of its spec."""
+    tags = {"policy": policy_spec, "depth_noise": noise_spec, "depth_filter": filter_spec}
+    return {key: dict(spec) for key, spec in tags.items() if spec is not None}
+
+
+def resolve_options(**given):
+    """The planning options of a test run (_test_config's keys) as one record.  An option not given (or _UNSET) is the key of that
+    name in the configs/test/ file load_params read last, None = off where that file has none; each then goes through its own
+    make_policy / option_spec, in _test_config's order: a bad combination raises the first bad option's ValueError.  The record has
+    the normalised spec (or None) under each option's name -- `policy` is the policy object, None = the network, with its options
+    as `policy_spec`; `symmetry_ensemble` stays as given, checked here as its setter will -- and `rollout`, the keywords of
+    build_rollout / run_one / run_many among them."""
+    from .frontier_policy import make_policy
+    opts = SimpleNamespace()
+
+    def ensemble(spec):
+        if opts.policy is not None:
+            opts.policy.symmetry_ensemble = spec           # (a policy refuses anything but None)
+        else:
+            augment.check_ensemble(spec)
+        return spec
+
+    normalise = {"policy": make_policy, "symmetry_ensemble": ensemble, "recon_metrics": recon_options.option_spec,
+                 "depth_noise": noise_options.option_spec, "depth_filter": filter_options.option_spec,
+                 "view_metrics": view_options.option_spec}
+    if set(given) - set(normalise):
+        raise TypeError(f"resolve_options: unknown options {sorted(set(given) - set(normalise))}")
+    for key in _test_config:
+        value = given.get(key, _UNSET)
+        value = _test_config[key] if value is _UNSET else value
+        setattr(opts, key, normalise[key](None if value is _UNSET else value))
+    opts.policy_spec = None if opts.policy is None else dict(opts.policy.options)
+    opts.rollout = {key: getattr(opts, key) for key in ("recon_metrics", "depth_noise", "view_metrics", "depth_filter")}
+    return opts
+
+
 def _result(ro, n_poses):
     res = {"scene": ro.scene_name, "start": ro.start, "coverage": ro.coverage_evolution(n_poses),
            "X_cam_history": ro.camera.X_cam_history.tolist(), "V_cam_history": ro.camera.V_cam_history.tolist(),
            "n_points": int(ro.st.cloud_count.item())}
-    if _wants_maps(ro.nbp):                            # the option `policy`: the normalised options the rollout was steered with
-        res["policy"] = dict(ro.nbp.options)
-    if ro.camera.depth_noise is not None:              # the option `depth_noise`: the normalised spec the frames were made with
-        res["depth_noise"] = dict(ro.camera.depth_noise)
-    if ro.camera.depth_filter is not None:             # the option `depth_filter`: the normalised spec the frames went through
-        res["depth_filter"] = dict(ro.camera.depth_filter)
+    # the options `policy`, `depth_noise`, `depth_filter` that are on: the normalised specs the rollout was steered and its frames made with
+    res.update(run_tags(ro.nbp.options if _wants_maps(ro.nbp) else None, ro.camera.depth_noise, ro.camera.depth_filter))
     if ro.recon is not None:        # the option `recon_metrics`: the whole cloud once, at the rollout's end
         raw = ro.reconstruction_metrics(raw=True)
         res["reconstruction"] = recon_options.summarise_raw(raw, ro.recon.thresholds, ro.recon.cap)
@@ -658,8 +685,8 @@ def _policy_or(nbp, policy):
 def run_one(params, nbp, dataset, run, device, test_resolution=0.05, state=None, n_poses=N_POSES, seed=0, *, recon_metrics=None,
             depth_noise=None, view_metrics=None, policy=None, depth_filter=None):
     nbp = _policy_or(nbp, policy)
-    ro = build_rollout(params, nbp, dataset, run, device, test_resolution, state, seed, recon_metrics=recon_metrics,
-                       depth_noise=depth_noise, view_metrics=view_metrics, depth_filter=depth_filter)
+    options = dict(recon_metrics=recon_metrics, depth_noise=depth_noise, view_metrics=view_metrics, depth_filter=depth_filter)
+    ro = build_rollout(params, nbp, dataset, run, device, test_resolution, state, seed, **options)
     nbp.eval()
     for _ in range(n_poses):
         ro.step()
@@ -674,14 +701,13 @@ def run_many(params, nbp, dataset, runs, device, seeds, test_resolution=0.05, n_
     in run_one (None = the network `nbp`)."""
     import time
     out = []
+    options = dict(recon_metrics=recon_metrics, depth_noise=depth_noise, view_metrics=view_metrics, depth_filter=depth_filter)
     nbp = _policy_or(nbp, policy)
     nbp.eval()
     for g0 in range(0, len(runs), rollouts_per_gpu):
         t0 = time.perf_counter()
         chunk = list(zip(runs[g0:g0 + rollouts_per_gpu], seeds[g0:g0 + rollouts_per_gpu]))
-        ros = [build_rollout(params, nbp, dataset, run, device, test_resolution, None, seed, grid, recon_metrics=recon_metrics,
-                             depth_noise=depth_noise, view_metrics=view_metrics, depth_filter=depth_filter)
-               for run, seed in chunk]
+        ros = [build_rollout(params, nbp, dataset, run, device, test_resolution, None, seed, grid, **options) for run, seed in chunk]
         multi = MultiRollout(ros, nbp, device)
         if timing is not None:
             torch.cuda.synchronize(device)
@@ -735,11 +761,9 @@ def test_nbp_planning(params_file, model_file, results_json_file, numGPU, test_s
     device = torch.device("cuda", local_rank if world > 1 else numGPU)
     torch.cuda.set_device(device)
     random.seed(seed); np.random.seed(seed); torch.manual_seed(torch_seed)
-    if policy is _UNSET:
-        policy = None if _test_config_policy[0] is _UNSET else _test_config_policy[0]
-    from .frontier_policy import make_policy
-    nbp = make_policy(policy)                                                 # (ValueError on anything but None, "nbp", "frontier", "infogain", a dict)
-    policy_spec = None if nbp is None else dict(nbp.options)
+    opts = resolve_options(policy=policy, symmetry_ensemble=symmetry_ensemble, recon_metrics=recon_metrics, depth_noise=depth_noise,
+                           depth_filter=depth_filter, view_metrics=view_metrics)
+    nbp, policy_spec, recon_spec, view_spec = opts.policy, opts.policy_spec, opts.recon_metrics, opts.view_metrics
     assert nbp_precision in (None, "fp32", "fp32_split", "bf16"), nbp_precision
     if nbp is not None and nbp_precision is not None:
         import warnings
@@ -757,29 +781,14 @@ def test_nbp_planning(params_file, model_file, results_json_file, numGPU, test_s
         nbp.to(device).eval()
         if nbp_precision is not None:           # None: the model's default ("fp32_split")
             nbp.conv_precision = nbp_precision
-    if symmetry_ensemble is _UNSET:
-        symmetry_ensemble = None if _test_config_ensemble[0] is _UNSET else _test_config_ensemble[0]
-    nbp.symmetry_ensemble = params.symmetry_ensemble = symmetry_ensemble      # (ValueError on anything but None, a name, op codes)
-    if recon_metrics is _UNSET:
-        recon_metrics = None if _test_config_recon[0] is _UNSET else _test_config_recon[0]
-    recon_spec = recon_options.option_spec(recon_metrics)                     # (ValueError on anything but None, True, a dict)
-    if depth_noise is _UNSET:
-        depth_noise = None if _test_config_noise[0] is _UNSET else _test_config_noise[0]
-    noise_spec = noise_options.option_spec(depth_noise)                       # (ValueError on anything but None or a dict of its keys)
-    if depth_filter is _UNSET:
-        depth_filter = None if _test_config_filter[0] is _UNSET else _test_config_filter[0]
-    filter_spec = filter_options.option_spec(depth_filter)                    # (ValueError on anything but None or a dict of its keys)
-    if view_metrics is _UNSET:
-        view_metrics = None if _test_config_views[0] is _UNSET else _test_config_views[0]
-    view_spec = view_options.option_spec(view_metrics)                        # (ValueError on anything but None, True, a dict of its keys)
+    nbp.symmetry_ensemble = params.symmetry_ensemble = opts.symmetry_ensemble
     dataset = sim_scene.SceneDataset(dataset_path, test_scenes)
     runs = list_runs(dataset, params)
     mine = shard(runs, rank, world)
     timing = {"load_s": time.perf_counter() - t_start}          # parameters, weights (packed on first use), dataset listing
     with torch.no_grad():
         results = run_many(params, nbp, dataset, mine, device, [seed + 1000 * r[0] + r[1] for r in mine],
-                           test_resolution, n_poses, rollouts_per_gpu, grid_size, timing=timing, recon_metrics=recon_spec,
-                           depth_noise=noise_spec, view_metrics=view_spec, depth_filter=filter_spec)
+                           test_resolution, n_poses, rollouts_per_gpu, grid_size, timing=timing, **opts.rollout)
     for run, res in zip(mine, results):
         res["run_id"] = runs.index(run)
     t_gather = time.perf_counter()
@@ -816,12 +825,7 @@ def test_nbp_planning(params_file, model_file, results_json_file, numGPU, test_s
                 rec["reconstruction"] = r["reconstruction"]
                 if recon_spec.get("curve"):
                     rec["reconstruction_curve"] = r["reconstruction_curve"]
-            if policy_spec is not None:
-                rec["policy"] = dict(policy_spec)
-            if noise_spec is not None:
-                rec["depth_noise"] = dict(noise_spec)
-            if filter_spec is not None:
-                rec["depth_filter"] = dict(filter_spec)
+            rec.update(run_tags(policy_spec, opts.depth_noise, opts.depth_filter))
             if view_spec is not None:
                 rec["views"] = r["views"]
             for key in ("X_cam_history", "V_cam_history"):      # histories of other ranks stay in their part files

@@ -131,7 +131,7 @@ def test_random_walk_planning(params_file, model_file, results_json_file, numGPU
     import os
     from ..utility.depth_filter import option_spec as filter_option_spec
     from ..utility.depth_noise import option_spec
-    from .nbp_planning import load_params, setup_test_camera
+    from .nbp_planning import load_params, run_tags, setup_test_camera
     noise_spec = option_spec(depth_noise)
     filter_spec = filter_option_spec(depth_filter)
     here = os.path.dirname(os.path.abspath(__file__))
@@ -157,11 +157,8 @@ def test_random_walk_planning(params_file, model_file, results_json_file, numGPU
             cov, X, V, *_ = compute_random_walk_trajectory(params, None, camera, gt_scene, surface, proxy, covered, mesh, device,
                                                            test_resolution, use_perfect_depth_map, compute_collision, n_poses,
                                                            seed=s)
-            results[sd["scene_name"]][str(k)] = {"coverage": cov, "X_cam_history": X.tolist(), "V_cam_history": V.tolist()}
-            if noise_spec is not None:
-                results[sd["scene_name"]][str(k)]["depth_noise"] = dict(noise_spec)
-            if filter_spec is not None:
-                results[sd["scene_name"]][str(k)]["depth_filter"] = dict(filter_spec)
+            results[sd["scene_name"]][str(k)] = {"coverage": cov, "X_cam_history": X.tolist(), "V_cam_history": V.tolist(),
+                                                 **run_tags(None, noise_spec, filter_spec)}
     os.makedirs(results_dir, exist_ok=True)
     with open(path, "w") as fh:
         json.dump(results, fh)

@@ -520,6 +520,27 @@ def raster_zface_batch(items, H, W, n_frames, tan_half_fov=TAN_HALF_FOV, z_clip=
     _lib.check(rc, "nbp_raster_zface_batch_f32")
 
 
+def _frame_pointers(who, what, items, H, W):
+    """The frame lists of a batched sensor launch's items, checked -> (source pointers, output pointers, H, W), frame by frame.
+    items = [(source frames, output frames, per-frame ids | None)]: 1 to 4 frames per item, lists of one length, each frame a
+    contiguous fp32 [H,W] tensor of the one shape or a device pointer (then H and W are needed).  `who` names the caller in the
+    messages, `what` its source frames."""
+    src, dst = [], []
+    for fr, out, ids in items:
+        if not (1 <= len(fr) <= 4 and len(out) == len(fr) and (ids is None or len(ids) == len(fr))):
+            raise ValueError(f"{who}: an item has 1 to 4 {what} frames and as many output frames" + (" and frame ids" if ids is not None else ""))
+        for t in (t for pair in zip(fr, out) for t in pair):
+            if not isinstance(t, int):
+                if t.dtype != torch.float32 or t.dim() != 2 or not t.is_contiguous() or (H is not None and tuple(t.shape) != (H, W)):
+                    raise ValueError(f"{who}: frames are contiguous fp32 [H,W] tensors of one shape")
+                H, W = t.shape
+        src += [t if isinstance(t, int) else t.data_ptr() for t in fr]
+        dst += [t if isinstance(t, int) else t.data_ptr() for t in out]
+    if src and (H is None or W is None):
+        raise ValueError(f"{who}: frames given as pointers need H and W")
+    return src, dst, H, W
+
+
 # ---- the depth-sensor noise model (csrc/nbp_depth_noise.hip; the definition is utility/depth_noise.py)
 def _noise_args(spec):
     from . import depth_noise as dn
@@ -551,25 +572,12 @@ def depth_noise_batch(items, spec, H=None, W=None):
             depth_noise_batch(items[i:i + 12], spec, H, W)
         return
     args = _noise_args(spec)
-    cl, ou, seeds, ids = [], [], [], []
-    for clean, out, seed, frames in items:
-        if not (1 <= len(clean) <= 4 and len(out) == len(clean) and len(frames) == len(clean)):
-            raise ValueError("depth_noise_batch: an item has 1 to 4 clean frames and as many output frames and frame ids")
-        for c, o, f in zip(clean, out, frames):
-            for t in (c, o):
-                if not isinstance(t, int):
-                    if t.dtype != torch.float32 or t.dim() != 2 or not t.is_contiguous() or (H is not None and tuple(t.shape) != (H, W)):
-                        raise ValueError("depth_noise_batch: frames are contiguous fp32 [H,W] tensors of one shape")
-                    H, W = t.shape
-            cl.append(c if isinstance(c, int) else c.data_ptr())
-            ou.append(o if isinstance(o, int) else o.data_ptr())
-            seeds.append(int(seed) & 0xFFFFFFFF)
-            ids.append(int(f) & 0xFFFFFFFF)
+    cl, ou, H, W = _frame_pointers("depth_noise_batch", "clean", [(clean, out, frames) for clean, out, _, frames in items], H, W)
     n = len(cl)
     if n == 0:
         return
-    if H is None or W is None:
-        raise ValueError("depth_noise_batch: frames given as pointers need H and W")
+    seeds = [int(seed) & 0xFFFFFFFF for _, _, seed, frames in items for _ in frames]
+    ids = [int(f) & 0xFFFFFFFF for *_, frames in items for f in frames]
     rc = _lib.lib().nbp_depth_noise_batch_f32(n, (C.c_void_p * n)(*cl), (C.c_void_p * n)(*ou), (C.c_uint * n)(*seeds), (C.c_uint * n)(*ids),
                                               int(H), int(W), *args, _st())
     _lib.check(rc, "nbp_depth_noise_batch_f32")
@@ -605,23 +613,10 @@ def depth_filter_batch(items, spec, H=None, W=None):
             depth_filter_batch(items[i:i + 12], spec, H, W)
         return
     args = _filter_args(spec)
-    ra, ou = [], []
-    for raw, out in items:
-        if not (1 <= len(raw) <= 4 and len(out) == len(raw)):
-            raise ValueError("depth_filter_batch: an item has 1 to 4 raw frames and as many output frames")
-        for r, o in zip(raw, out):
-            for t in (r, o):
-                if not isinstance(t, int):
-                    if t.dtype != torch.float32 or t.dim() != 2 or not t.is_contiguous() or (H is not None and tuple(t.shape) != (H, W)):
-                        raise ValueError("depth_filter_batch: frames are contiguous fp32 [H,W] tensors of one shape")
-                    H, W = t.shape
-            ra.append(r if isinstance(r, int) else r.data_ptr())
-            ou.append(o if isinstance(o, int) else o.data_ptr())
+    ra, ou, H, W = _frame_pointers("depth_filter_batch", "raw", [(raw, out, None) for raw, out in items], H, W)
     n = len(ra)
     if n == 0:
         return
-    if H is None or W is None:
-        raise ValueError("depth_filter_batch: frames given as pointers need H and W")
     rc = _lib.lib().nbp_depth_filter_batch_f32(n, (C.c_void_p * n)(*ra), (C.c_void_p * n)(*ou), int(H), int(W), *args, _st())
     _lib.check(rc, "nbp_depth_filter_batch_f32")
 

@@ -329,9 +329,9 @@ def test_test_config_key_resolves_like_depth_noise(tmp_path):
     try:
         path.write_text(json.dumps({"nbp_weights": "none", "depth_filter": spec}))
         tp.load_params(str(path))
-        assert tp._test_config_filter[0] == spec
+        assert tp._test_config["depth_filter"] == spec
         path.write_text(json.dumps({"nbp_weights": "none"}))
         tp.load_params(str(path))
-        assert tp._test_config_filter[0] is tp._UNSET
+        assert tp._test_config["depth_filter"] is tp._UNSET
     finally:
-        tp._test_config_filter[0] = tp._UNSET
+        tp._test_config["depth_filter"] = tp._UNSET

@@ -165,7 +165,7 @@ def test_the_test_config_key_reaches_the_driver(tmp_path):
     with_key.write_text(json.dumps({"_network": {"nbp_weights": "w.pth", "symmetry_ensemble": [0, 6]}}))
     without.write_text(json.dumps({"_network": {"nbp_weights": "w.pth"}}))
     other.write_text(json.dumps({"_rollout": {"image_height": 4}}))
-    assert tp.load_params(str(with_key)).symmetry_ensemble == [0, 6] and tp._test_config_ensemble[0] == [0, 6]
+    assert tp.load_params(str(with_key)).symmetry_ensemble == [0, 6] and tp._test_config["symmetry_ensemble"] == [0, 6]
     tp.load_params(str(other))                                   # not a test config: the record stays
-    assert tp._test_config_ensemble[0] == [0, 6]
-    assert not hasattr(tp.load_params(str(without)), "symmetry_ensemble") and tp._test_config_ensemble[0] is tp._UNSET
+    assert tp._test_config["symmetry_ensemble"] == [0, 6]
+    assert not hasattr(tp.load_params(str(without)), "symmetry_ensemble") and tp._test_config["symmetry_ensemble"] is tp._UNSET
