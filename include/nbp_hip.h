@@ -1221,6 +1221,50 @@ int nbp_infogain_policy_f32(const float* maps6, int B, int S, int radius, int di
 int nbp_infogain_visible_u64(const float* maps6, int B, int S, int radius, int dilate, const int* cells_host, int n,
                              unsigned long long* out, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- TSDF fusion of depth frames, and the fused surface cloud (csrc/nbp_tsdf.hip; the definition, which the kernels equal bit for
+ * bit, is nextbestpath_amd/utility/tsdf.py).  Not in the reference.  A volume is int32 [nx][ny][nz][2] on the device:
+ * voxel (i, j, k), linear index (i ny + j) nz + k, holds (S, W) = (sum of quantised signed distances, number of observations); its
+ * centre on axis a is lo_a + (f32(i_a) + 0.5) voxel.  lo_host [3], the cameras ([.][12]: R row-major then T) and the pointer tables
+ * are HOST memory, read before the call returns; they travel as kernel arguments.
+ *   nbp_tsdf_integrate_f32        n (<= 65535) [H][W] fp32 frames into ONE volume: consecutive in depth_or_null, or each at its own
+ *                                 address frames_host_or_null[n] (exactly one of the two is given); cams_host [n][12].  A frame
+ *                                 updates a voxel iff the centre projects (view_metrics.project with this z_clip and tan_half_fov)
+ *                                 onto a pixel of the image whose depth d has d > -1 (a NaN has not) and d <= max_depth, and sdf = d -
+ *                                 v2 >= -trunc: S += (int) rint(min(sdf, trunc) (127 / trunc)), W += 1.  One launch per 4 frames.
+ *   nbp_tsdf_integrate_batch_f32  n_items (<= 12) volumes, item i with its own vols_host[i], lo_host [i][3], voxel_host[i],
+ *                                 dims_host [i][3] = nx, ny, nz, trunc_host[i], max_depth_host[i] and n_frames_host[i] (1..4) frames
+ *                                 frames_host [i][4] with cams_host [i][4][12], all frames [H][W].  ONE launch; each volume gets the
+ *                                 bits of a call of its own.
+ *                                 A thread owns a voxel, loads (S, W) once, loops over the launch's frames in registers and stores
+ *                                 once, and only where a frame updated it.  No atomics: integer sums with one owner, so frames in any
+ *                                 order or grouping give the same bits.
+ *   nbp_tsdf_extract_f32          the fused surface cloud, points [.][3] in the order (linear index, axis 0, 1, 2): voxel and its
+ *                                 neighbour one step up the axis both usable (W >= min_weight and |S| < 127 W) and (S0 < 0) != (S1 <
+ *                                 0) -> the voxel's centre with (D0 / (D0 - D1)) voxel added on that axis, D = f32(S) / f32(W).
+ *                                 total (int64, device) receives the number of points whatever the capacity; the first `capacity`
+ *                                 rows are written, nothing beyond them (capacity 0: points may be null, the count alone).  Three
+ *                                 launches (count per run of voxels, scan, emit); ws: nbp_tsdf_extract_workspace_bytes(nx ny nz)
+ *                                 (0 where the call would fail).
+ *   nbp_tsdf_stats_i64            counts2 (int64 [2], device) = #(W > 0), #usable.  Two launches of a fixed geometry; ws:
+ *                                 nbp_tsdf_stats_workspace_bytes().
+ * No allocation, no host synchronisation; two runs give the same bytes.  NBP_E_ARG: a null pointer, n / n_items / a frame count / a
+ * dimension / H / W < 1, voxel, trunc, tan_half_fov or z_clip not positive and finite, lo not finite, max_depth not positive (it may
+ * be infinite), min_weight < 1, capacity < 0, both or neither of depth and frames_host, a frame (or the extraction's points, total or
+ * workspace) that overlaps a volume, two overlapping volumes in one batch; NBP_E_SHAPE: more than 2^28 voxels, H W > 2^29, more frames
+ * or items than the form takes, a volume, total or counts2 off the 8-byte grid; NBP_E_WS.  Nothing is written on an error. */
+int nbp_tsdf_integrate_f32(int* vol, const float* lo_host, float voxel, int nx, int ny, int nz, const float* depth_or_null,
+                           const float* const* frames_host_or_null, int n, const float* cams_host, int H, int W, float tan_half_fov,
+                           float z_clip, float trunc, float max_depth, void* stream);
+int nbp_tsdf_integrate_batch_f32(int n_items, int* const* vols_host, const float* lo_host, const float* voxel_host, const int* dims_host,
+                                 const float* trunc_host, const float* max_depth_host, const int* n_frames_host,
+                                 const float* const* frames_host, const float* cams_host, int H, int W, float tan_half_fov,
+                                 float z_clip, void* stream);
+size_t nbp_tsdf_extract_workspace_bytes(long long n_voxels);
+int nbp_tsdf_extract_f32(const int* vol, const float* lo_host, float voxel, int nx, int ny, int nz, int min_weight,
+                         float* points_or_null, long long capacity, long long* total, void* ws, size_t ws_bytes, void* stream);
+size_t nbp_tsdf_stats_workspace_bytes(void);
+int nbp_tsdf_stats_i64(const int* vol, long long n_voxels, int min_weight, long long* counts2, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,7 +5,7 @@ runs them in nested loops on one GPU), so rank r takes runs r, r+W, r+2W, ... an
 collective is ONE all_gather of a padded fp32 tensor [runs_per_rank, n_poses + 3] holding
 (run id, final coverage, AUC, coverage curve) -- a few KB over RCCL/xGMI, latency bound (with the
 planning option `recon_metrics` on, a second one of float64 sums and counts: gather_reconstruction; with its `curve`, a third of the
-per-step rows: gather_reconstruction_curve; with the option `view_metrics`, one of the per-view counts and sums: gather_views).  One
+per-step rows: gather_reconstruction_curve; with the option `view_metrics`, one of the per-view counts and sums: gather_views; with the option `fusion`, one of the fused cloud's sums and counts: gather_fusion).  One
 process per GPU; backend "nccl" (= RCCL on ROCm) with CUDA tensors, "gloo" on CPU-only hosts
 (that path is what the world_size-2 CPU tests exercise)."""
 from __future__ import annotations
@@ -154,6 +154,32 @@ def gather_reconstruction_curve(results, runs, rank, world, device, thresholds, 
     if rank != 0:
         return {}
     return {int(row[0]): recon_metrics.summarise_curve(row[1:].reshape(n_poses, per), thresholds, cap) for row in t if row[0] >= 0}
+
+
+def gather_fusion(results, runs, rank, world, device, thresholds, cap, options=None):
+    """The planning option `fusion`: all ranks call this behind gather_results, and only when the option is on.  The raw float64
+    numbers of every run's fused cloud (results[i]["fusion_raw"], utility/tsdf.py::pack_raw: the reconstruction metrics' sums and
+    counts, then observed_voxels, usable_voxels, frames) travel in ONE all_gather of a padded float64 tensor [runs_per_rank, 1 + 6
+    + 2 T + 3] (run id first; pad rows = -1) -- a gather of its own: the others keep their shapes with the option off.  Rank 0
+    forms the ratios with recon_metrics.summarise_raw (through tsdf.summarise_raw, which adds the counts and `options`) -> {run id:
+    the record's "fusion" block}; the other ranks get {}."""
+    from .utility import recon_metrics, tsdf
+    rows = runs_per_rank(len(runs), world)
+    width = 1 + recon_metrics.RAW_HEAD + 2 * len(thresholds) + len(tsdf.RAW_TAIL)
+    t = np.full((rows, width), -1.0, np.float64)
+    for j, r in enumerate(results):
+        t[j, 0] = r["run_id"]
+        t[j, 1:] = np.asarray(r["fusion_raw"], np.float64)
+    collective = world > 1 or group_is_up()
+    if collective:
+        import torch.distributed as dist
+        local = torch.from_numpy(t).to(collective_device(device))
+        buf = [torch.empty_like(local) for _ in range(world)]
+        dist.all_gather(buf, local)
+        t = torch.stack(buf).cpu().numpy().reshape(-1, width)
+    if rank != 0:
+        return {}
+    return {int(row[0]): tsdf.summarise_raw(row[1:], thresholds, cap, options) for row in t if row[0] >= 0}
 
 
 def gather_views(results, runs, rank, world, device, options):

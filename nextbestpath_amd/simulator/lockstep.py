@@ -182,6 +182,15 @@ class LockstepRollout:
         st.frames_appended += len(which)
         if filing:
             st.frames_filed += len(which)
+        fusion = getattr(self, "fusion", None)     # (option `fusion`: the same frames and cameras into the rollout's TSDF volume)
+        if fusion is not None:
+            fusion.integrate(depth, cams)
+
+    def fusion_item(self, depth, cams):
+        """The arguments of hipops.tsdf_integrate_batch for the frames this rollout un-projects (ring-slot pointers and their
+        cameras), or None where the rollout has no `fusion` (the planning option of that name is off)."""
+        fusion = getattr(self, "fusion", None)
+        return None if fusion is None else fusion.item(depth, cams)
 
     def unproject_item(self, frames, colours):
         """Arguments of hipops.unproject_append_batch for `frames` of this rollout; None when its camera cannot take part in the
@@ -218,6 +227,10 @@ def unproject_group(grp, frames, colours):
         hipops.unproject_append_batch(items, p0.image_height, p0.image_width, n, p0.gathering_factor, p0.sensor_range)
         for r in grp:
             r.st.frames_appended += n
+        # the option `fusion`: exactly these frames, with these cameras, into each rollout's TSDF volume, in ONE call (a launch per 12)
+        fused = [f for f in (r.fusion_item(it[1], it[2]) for r, it in zip(grp, items)) if f is not None]
+        if fused:
+            hipops.tsdf_integrate_batch(fused, p0.image_height, p0.image_width)
     else:
         for r in grp:
             r.unproject(frames, colours)

@@ -33,6 +33,7 @@ from ..utility import augment, hipops
 from ..utility import depth_filter as filter_options
 from ..utility import depth_noise as noise_options
 from ..utility import recon_metrics as recon_options
+from ..utility import tsdf as fusion_options
 from ..utility import utils as hu
 from ..utility import view_metrics as view_options
 from ..utility.long_term_utils import LatticePlanner, compute_auc
@@ -69,7 +70,7 @@ class Rollout(lockstep.LockstepRollout):
     """One exploration rollout, steppable (bench.py times K consecutive ``step()`` calls)."""
 
     def __init__(self, params, nbp, camera, gt_scene_pc, mesh, mesh_for_check, y_bins, device, state=None, seed=0,
-                 grid=256, symmetry_ensemble=_UNSET, recon_metrics=None, view_metrics=None):
+                 grid=256, symmetry_ensemble=_UNSET, recon_metrics=None, view_metrics=None, fusion=None):
         self.params, self.nbp, self.camera, self.mesh, self.mesh_for_check = params, nbp, camera, mesh, mesh_for_check
         _set_symmetry_ensemble(nbp, params, symmetry_ensemble)
         self.y_bins, self.device = y_bins, device
@@ -112,6 +113,13 @@ class Rollout(lockstep.LockstepRollout):
         self._start_ijk = None if camera.cam_idx is None else tuple(int(v) for v in camera.cam_idx[:3])
         self.views = self._build_views(self.view_spec) if self.view_spec is not None else None
         self._views_default = None
+        # the planning option `fusion` (None = off: nothing is allocated, launched, gathered or written; True; a dict of
+        # utility/tsdf.py): every frame the rollout un-projects also goes into a TSDF volume over the GT bounds, an observer like
+        # recon_metrics -- nothing of the step reads it -- whose fused surface cloud is judged once, at the rollout's end
+        self.fusion_spec = fusion_options.option_spec(fusion)
+        self.fusion = None
+        if self.fusion_spec is not None:
+            self.fusion = hipops.TSDFVolume(self.bbox, fusion_options.resolved_options(self.fusion_spec, params.sensor_range), device)
         self.path, self.path_record = [], 0
         self.collision_list, self.passable_list, self.idx_history = [], [], []
         self.step_seed = seed * 1_000_003
@@ -291,6 +299,30 @@ class Rollout(lockstep.LockstepRollout):
         rgb = self.st.cloud_rgb if self.camera.renders_colours else None
         vm.evaluate(self.st.cloud, rgb, self.st.cloud_count)
         return vm.raw() if raw else vm.summary(vm.options)
+
+    def fused_cloud(self):
+        """(points fp32 [n,3] on the device, n): the surface cloud of the rollout's TSDF volume (the option `fusion`), in
+        utility/tsdf.py::extract's order.  Reads the point count back: for the rollout's end, not for the step."""
+        if self.fusion is None:
+            raise RuntimeError("fused_cloud: the rollout was built without the option `fusion`")
+        self.finish()
+        return self.fusion.extract()
+
+    def fusion_metrics(self, raw=False):
+        """Reconstruction quality of the FUSED cloud against the GT surface, by the metrics that judge the raw cloud
+        (hipops.ReconMetrics with the rollout's `recon_metrics` option, or that option's defaults): utility/tsdf.py::summarise_raw's
+        dict -- recon_metrics.summarise's entries (n_points = the fused points) with observed_voxels, usable_voxels, frames and the
+        volume's options -- or with raw=True the float64 vector behind it (tsdf.pack_raw: what travels between ranks)."""
+        points, n = self.fused_cloud()
+        rec = self.recon or self._recon_default
+        if rec is None:
+            rec = self._recon_default = hipops.ReconMetrics(self.gt, self.bbox, **recon_options.option_spec(True))
+        if n == 0:                  # (the metrics' kernels take a buffer of at least one row; the device count says none is valid)
+            points = torch.zeros(1, 3, dtype=torch.float32, device=self.device)
+        rec.evaluate(points, torch.full((1,), n, dtype=torch.int64, device=self.device))
+        st = self.fusion.stats()
+        row = fusion_options.pack_raw(rec.raw(), st["observed_voxels"], st["usable_voxels"], self.fusion.frames)
+        return row if raw else fusion_options.summarise_raw(row, rec.thresholds, rec.cap, self.fusion.options)
 
     def reconstruction_curve(self, n, raw=False):
         """The per-step reconstruction curve (the option `recon_metrics` with `curve`): entry s is the metric of the WHOLE cloud as
@@ -555,7 +587,8 @@ def compute_nbp_trajectory(params, nbp, camera, gt_scene_pc, mesh, mesh_for_chec
 # the option keys of the configs/test/ file load_params read last (a file with the NBP options: `nbp_weights`), each _UNSET where the
 # file has none; the entry script passes test_nbp_planning the options it knows by keyword, and these reach it here.  In the order
 # in which resolve_options checks them
-_test_config = dict.fromkeys(("policy", "symmetry_ensemble", "recon_metrics", "depth_noise", "depth_filter", "view_metrics"), _UNSET)
+_test_config = dict.fromkeys(("policy", "symmetry_ensemble", "recon_metrics", "depth_noise", "depth_filter", "view_metrics", "fusion"),
+                            _UNSET)
 
 
 def load_params(path):
@@ -595,10 +628,10 @@ def list_runs(dataset, params):
 
 
 def build_rollout(params, nbp, dataset, run, device, test_resolution=0.05, state=None, seed=0, grid=256, recon_metrics=None,
-                  depth_noise=None, view_metrics=None, depth_filter=None):
+                  depth_noise=None, view_metrics=None, depth_filter=None, fusion=None):
     """Scene + GT surface + camera + Rollout for one (scene, start pose) run (nbp_planning.py:414-492).  `depth_noise`: the camera's
     sensor model (utility/depth_noise.py; None = off, perfect depth).  `depth_filter`: the camera's frame filter behind it
-    (utility/depth_filter.py; None = off)."""
+    (utility/depth_filter.py; None = off).  `fusion`: the rollout's TSDF volume (utility/tsdf.py; None = off)."""
     si, k = run
     sd = dataset[si]
     settings = sim_scene.Settings(sd["settings"], params.scene_scale_factor)
@@ -609,7 +642,7 @@ def build_rollout(params, nbp, dataset, run, device, test_resolution=0.05, state
     camera = setup_test_camera(params, mesh, settings.camera.start_positions[k], settings, device, seed=seed, depth_noise=depth_noise,
                                depth_filter=depth_filter)
     ro = Rollout(params, nbp, camera, gt_dev, mesh, mesh, y_bins, device, state, seed, grid, recon_metrics=recon_metrics,
-                 view_metrics=view_metrics)
+                 view_metrics=view_metrics, fusion=fusion)
     ro.scene_name, ro.start = sd["scene_name"], k
     return ro
 
@@ -627,7 +660,7 @@ def resolve_options(**given):
     make_policy / option_spec, in _test_config's order: a bad combination raises the first bad option's ValueError.  The record has
     the normalised spec (or None) under each option's name -- `policy` is the policy object, None = the network, with its options
     as `policy_spec`; `symmetry_ensemble` stays as given, checked here as its setter will -- and `rollout`, the keywords of
-    build_rollout / run_one / run_many among them."""
+    build_rollout / run_one / run_many among them (`fusion` only where it is on: off is those functions' default)."""
     from .frontier_policy import make_policy
     opts = SimpleNamespace()
 
@@ -640,7 +673,7 @@ def resolve_options(**given):
 
     normalise = {"policy": make_policy, "symmetry_ensemble": ensemble, "recon_metrics": recon_options.option_spec,
                  "depth_noise": noise_options.option_spec, "depth_filter": filter_options.option_spec,
-                 "view_metrics": view_options.option_spec}
+                 "view_metrics": view_options.option_spec, "fusion": fusion_options.option_spec}
     if set(given) - set(normalise):
         raise TypeError(f"resolve_options: unknown options {sorted(set(given) - set(normalise))}")
     for key in _test_config:
@@ -649,6 +682,8 @@ def resolve_options(**given):
         setattr(opts, key, normalise[key](None if value is _UNSET else value))
     opts.policy_spec = None if opts.policy is None else dict(opts.policy.options)
     opts.rollout = {key: getattr(opts, key) for key in ("recon_metrics", "depth_noise", "view_metrics", "depth_filter")}
+    if opts.fusion is not None:
+        opts.rollout["fusion"] = opts.fusion
     return opts
 
 
@@ -670,6 +705,11 @@ def _result(ro, n_poses):
         raw = ro.view_metrics(raw=True)
         res["views"] = view_options.summarise_raw(raw, ro.views.options)
         res["views_raw"] = raw.tolist()                # the counts and sums behind the ratios (parallel_rollout.gather_views)
+    if ro.fusion is not None:       # the option `fusion`: the TSDF volume's surface cloud by the reconstruction metrics, once, at the end
+        raw = ro.fusion_metrics(raw=True)
+        rec = ro.recon or ro._recon_default
+        res["fusion"] = fusion_options.summarise_raw(raw, rec.thresholds, rec.cap, ro.fusion.options)
+        res["fusion_raw"] = raw.tolist()               # the sums and counts behind the ratios (parallel_rollout.gather_fusion)
     return res
 
 
@@ -683,9 +723,10 @@ def _policy_or(nbp, policy):
 
 
 def run_one(params, nbp, dataset, run, device, test_resolution=0.05, state=None, n_poses=N_POSES, seed=0, *, recon_metrics=None,
-            depth_noise=None, view_metrics=None, policy=None, depth_filter=None):
+            depth_noise=None, view_metrics=None, policy=None, depth_filter=None, fusion=None):
     nbp = _policy_or(nbp, policy)
-    options = dict(recon_metrics=recon_metrics, depth_noise=depth_noise, view_metrics=view_metrics, depth_filter=depth_filter)
+    options = dict(recon_metrics=recon_metrics, depth_noise=depth_noise, view_metrics=view_metrics, depth_filter=depth_filter,
+                   fusion=fusion)
     ro = build_rollout(params, nbp, dataset, run, device, test_resolution, state, seed, **options)
     nbp.eval()
     for _ in range(n_poses):
@@ -695,13 +736,15 @@ def run_one(params, nbp, dataset, run, device, test_resolution=0.05, state=None,
 
 
 def run_many(params, nbp, dataset, runs, device, seeds, test_resolution=0.05, n_poses=N_POSES, rollouts_per_gpu=48,
-             grid=256, timing=None, *, recon_metrics=None, depth_noise=None, view_metrics=None, policy=None, depth_filter=None):
+             grid=256, timing=None, *, recon_metrics=None, depth_noise=None, view_metrics=None, policy=None, depth_filter=None,
+             fusion=None):
     """Runs `runs` in lock-step groups of `rollouts_per_gpu` (MultiRollout); same results as run_one each.  `timing` (a dict)
     receives the wall-clock seconds of scene / GT-surface / camera setup and of the stepping (device-synchronised).  `policy`: as
     in run_one (None = the network `nbp`)."""
     import time
     out = []
-    options = dict(recon_metrics=recon_metrics, depth_noise=depth_noise, view_metrics=view_metrics, depth_filter=depth_filter)
+    options = dict(recon_metrics=recon_metrics, depth_noise=depth_noise, view_metrics=view_metrics, depth_filter=depth_filter,
+                   fusion=fusion)
     nbp = _policy_or(nbp, policy)
     nbp.eval()
     for g0 in range(0, len(runs), rollouts_per_gpu):
@@ -729,7 +772,7 @@ def test_nbp_planning(params_file, model_file, results_json_file, numGPU, test_s
                       use_perfect_depth_map=False, compute_collision=False, load_json=False, dataset_path=None,
                       nbp_weights=None, configs_dir=None, results_dir=None, n_poses=N_POSES, seed=8, torch_seed=9,
                       rollouts_per_gpu=48, grid_size=256, nbp_precision=None, symmetry_ensemble=_UNSET, recon_metrics=_UNSET,
-                      depth_noise=_UNSET, view_metrics=_UNSET, policy=_UNSET, depth_filter=_UNSET):
+                      depth_noise=_UNSET, view_metrics=_UNSET, policy=_UNSET, depth_filter=_UNSET, fusion=_UNSET):
     """Same arguments as the reference (nbp_planning.py:364-374); `grid_size` / `nbp_precision` select
     BASELINE.json configs[4] (512 grid at the same 0.3125 units per pixel, bf16 convolutions).  `symmetry_ensemble` (None = off, a
     name of utility/augment.py::ENSEMBLES or a list of op codes) is NBP.symmetry_ensemble of the loaded network; not given, it is
@@ -745,12 +788,15 @@ def test_nbp_planning(params_file, model_file, results_json_file, numGPU, test_s
     the held-out view metrics of every rollout's final coloured cloud ("views": the cloud rendered from lattice poses against the mesh,
     with the options used) to its record.  `policy` (None or "nbp" = the network; "frontier" / "infogain" or a dict of
     utility/frontier.py / infogain.py::option_spec; not given, the key of that name in the same file) puts that policy where the network
-    stands: no weights are loaded (`nbp_precision` given with it draws a warning), and every record gains "policy", the normalised options.  Under torchrun the flattened
+    stands: no weights are loaded (`nbp_precision` given with it draws a warning), and every record gains "policy", the normalised options.
+    `fusion` (None = off, True = the defaults, or a dict of utility/tsdf.py::option_spec; not given, the key of that name in the same
+    file) integrates every frame a rollout un-projects into a TSDF volume and adds "fusion" to its record: the fused surface cloud
+    by the reconstruction metrics (with `recon_metrics`' options, or its defaults), the voxel counts and the options.  Under torchrun the flattened
     (scene, start pose) runs are sharded round-robin over the ranks and the coverage curves are
     gathered with ONE all_gather over RCCL (backend "nccl" on ROCm; "gloo" on CPU-only hosts)."""
     import time
-    from ..parallel_rollout import (gather_reconstruction, gather_reconstruction_curve, gather_results, gather_views, init_distributed,
-                                     shard)
+    from ..parallel_rollout import (gather_fusion, gather_reconstruction, gather_reconstruction_curve, gather_results, gather_views,
+                                     init_distributed, shard)
     t_start = time.perf_counter()
     here = os.path.dirname(os.path.abspath(__file__))
     configs_dir = configs_dir or os.path.join(here, "../../configs/macarons")
@@ -762,7 +808,7 @@ def test_nbp_planning(params_file, model_file, results_json_file, numGPU, test_s
     torch.cuda.set_device(device)
     random.seed(seed); np.random.seed(seed); torch.manual_seed(torch_seed)
     opts = resolve_options(policy=policy, symmetry_ensemble=symmetry_ensemble, recon_metrics=recon_metrics, depth_noise=depth_noise,
-                           depth_filter=depth_filter, view_metrics=view_metrics)
+                           depth_filter=depth_filter, view_metrics=view_metrics, fusion=fusion)
     nbp, policy_spec, recon_spec, view_spec = opts.policy, opts.policy_spec, opts.recon_metrics, opts.view_metrics
     assert nbp_precision in (None, "fp32", "fp32_split", "bf16"), nbp_precision
     if nbp is not None and nbp_precision is not None:
@@ -816,6 +862,15 @@ def test_nbp_planning(params_file, model_file, results_json_file, numGPU, test_s
             r.pop("views_raw", None)
             if rank == 0:
                 r["views"] = views[r["run_id"]]
+    if opts.fusion is not None:     # a float64 gather of its own: the fused cloud's raw sums and counts; the ratios are formed on rank 0
+        fusion_opts = fusion_options.resolved_options(opts.fusion, params.sensor_range)
+        fusion_recon = recon_spec or recon_options.option_spec(True)
+        fused = gather_fusion(results, runs, rank, world, device, fusion_recon["thresholds"], fusion_recon["cap"], fusion_opts)
+        for r in gathered:
+            r.pop("fusion", None)
+            r.pop("fusion_raw", None)
+            if rank == 0:
+                r["fusion"] = fused[r["run_id"]]
     if rank == 0:
         out = {}
         for r in gathered:
@@ -828,6 +883,8 @@ def test_nbp_planning(params_file, model_file, results_json_file, numGPU, test_s
             rec.update(run_tags(policy_spec, opts.depth_noise, opts.depth_filter))
             if view_spec is not None:
                 rec["views"] = r["views"]
+            if opts.fusion is not None:
+                rec["fusion"] = r["fusion"]
             for key in ("X_cam_history", "V_cam_history"):      # histories of other ranks stay in their part files
                 if key in r:
                     rec[key] = r[key]

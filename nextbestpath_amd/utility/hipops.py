@@ -1540,3 +1540,183 @@ def infogain_visible(maps6, radius=24, dilate=2, cells=()):
                                     _lib.ptr(ws), ws.numel(), _st())
     _lib.check(rc, "nbp_infogain_visible_u64")
     return out
+
+
+# ---- TSDF fusion of depth frames (csrc/nbp_tsdf.hip; the definition is utility/tsdf.py)
+def _tsdf_volume(name, vol):
+    if not isinstance(vol, torch.Tensor) or not vol.is_cuda:
+        raise RuntimeError(f"{name}: the HIP path needs a cuda tensor for the volume (no CPU fallback)")
+    if vol.dim() != 4 or vol.shape[3] != 2 or vol.dtype != torch.int32 or not vol.is_contiguous() or vol.numel() == 0:
+        raise ValueError(f"{name}: the volume must be a contiguous int32 [nx,ny,nz,2] tensor")
+    return tuple(int(d) for d in vol.shape[:3])
+
+
+def _tsdf_frames(name, depth, device, H, W):
+    """depth: fp32 [n,H,W] or [H,W] (consecutive frames), or a list of [H,W] tensors / device pointers (then H and W are needed)
+    -> (base pointer | None, pointer list | None, n, H, W)."""
+    if isinstance(depth, torch.Tensor):
+        if not depth.is_cuda:
+            raise RuntimeError(f"{name}: the HIP path needs cuda tensors for the frames (no CPU fallback)")
+        if depth.dtype != torch.float32 or depth.dim() not in (2, 3) or not depth.is_contiguous() or depth.device != device:
+            raise ValueError(f"{name}: frames are contiguous fp32 [n,H,W] (or [H,W]) on the volume's device")
+        return depth.data_ptr(), None, (depth.shape[0] if depth.dim() == 3 else 1), int(depth.shape[-2]), int(depth.shape[-1])
+    ptrs = []
+    for t in depth:
+        if isinstance(t, int):
+            ptrs.append(t)
+            continue
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError(f"{name}: the HIP path needs cuda tensors for the frames (no CPU fallback)")
+        if t.dtype != torch.float32 or t.dim() != 2 or not t.is_contiguous() or t.device != device or (H is not None and tuple(t.shape) != (H, W)):
+            raise ValueError(f"{name}: frames are contiguous fp32 [H,W] tensors of one shape on the volume's device")
+        H, W = int(t.shape[0]), int(t.shape[1])
+        ptrs.append(t.data_ptr())
+    if ptrs and (H is None or W is None):
+        raise ValueError(f"{name}: frames given as pointers need H and W")
+    return None, ptrs, len(ptrs), H, W
+
+
+def tsdf_integrate(vol, lo, voxel, depth, cams, trunc, max_depth, H=None, W=None, tan_half_fov=TAN_HALF_FOV, z_clip=Z_CLIP):
+    """Integrates n depth frames into ONE volume int32 [nx,ny,nz,2] (in place; tsdf.integrate frame by frame, bit for bit, in any
+    order).  depth: fp32 [n,H,W] / [H,W], or a list of [H,W] tensors or device pointers (with H, W); cams host [n,12].  One launch
+    per 4 frames, no host synchronisation.  Returns vol."""
+    dims = _tsdf_volume("tsdf_integrate", vol)
+    base, ptrs, n, H, W = _tsdf_frames("tsdf_integrate", depth, vol.device, H, W)
+    keep, cam_ptr, n_cams = _cam_arg(cams)
+    if n < 1 or n_cams != n:
+        raise ValueError(f"tsdf_integrate: {n} frames with {n_cams} cameras")
+    lo3 = (C.c_float * 3)(*[float(v) for v in lo])
+    table = None if ptrs is None else (C.c_void_p * n)(*ptrs)
+    with torch.cuda.device(vol.device):
+        rc = _lib.lib().nbp_tsdf_integrate_f32(_lib.ptr(vol), lo3, float(voxel), *dims, base, table, n, cam_ptr, H, W, float(tan_half_fov),
+                                               float(z_clip), float(trunc), float(max_depth), _st())
+    _lib.check(rc, "nbp_tsdf_integrate_f32")
+    return vol
+
+
+def tsdf_integrate_batch(items, H=None, W=None, tan_half_fov=TAN_HALF_FOV, z_clip=Z_CLIP):
+    """tsdf_integrate for several volumes in ONE launch.  items = [(vol, lo, voxel, trunc, max_depth, frames, cams host [F,12])]
+    (TSDFVolume.item makes them): per item its own volume and geometry and 1 to 4 frames, each an [H,W] fp32 tensor or a device
+    pointer (then H and W are needed), which need not be adjacent in memory.  Each volume gets the bits of a call of its own.  More
+    than 12 items go in chunks of 12."""
+    import numpy as np
+    if len(items) > 12:
+        for i in range(0, len(items), 12):
+            tsdf_integrate_batch(items[i:i + 12], H, W, tan_half_fov, z_clip)
+        return
+    n = len(items)
+    if n == 0:
+        return
+    dev = items[0][0].device if isinstance(items[0][0], torch.Tensor) else None
+    vols, frames, nf = (C.c_void_p * n)(), (C.c_void_p * (4 * n))(), (C.c_int * n)()
+    lo, voxel, dims = np.zeros((n, 3), np.float32), np.zeros(n, np.float32), np.zeros((n, 3), np.int32)
+    trunc, max_depth, cams = np.zeros(n, np.float32), np.zeros(n, np.float32), np.zeros((n, 4, 12), np.float32)
+    for i, (vol, lo_i, voxel_i, trunc_i, max_depth_i, fr, cam) in enumerate(items):
+        dims[i] = _tsdf_volume("tsdf_integrate_batch", vol)
+        if vol.device != dev:
+            raise ValueError("tsdf_integrate_batch: the items of one call on one device expected")
+        _, ptrs, k, H, W = _tsdf_frames("tsdf_integrate_batch", list(fr), dev, H, W)
+        cam = np.asarray(cam, np.float32).reshape(-1, 12)
+        if not 1 <= k <= 4 or cam.shape[0] != k:
+            raise ValueError("tsdf_integrate_batch: an item has 1 to 4 frames and as many cameras")
+        vols[i], nf[i], lo[i], voxel[i], trunc[i], max_depth[i] = vol.data_ptr(), k, lo_i, voxel_i, trunc_i, max_depth_i
+        cams[i, :k] = cam
+        for f in range(k):
+            frames[4 * i + f] = ptrs[f]
+    with torch.cuda.device(dev):
+        rc = _lib.lib().nbp_tsdf_integrate_batch_f32(n, vols, lo.ctypes.data, voxel.ctypes.data, dims.ctypes.data, trunc.ctypes.data,
+                                                     max_depth.ctypes.data, nf, frames, cams.ctypes.data, int(H), int(W),
+                                                     float(tan_half_fov), float(z_clip), _st())
+    _lib.check(rc, "nbp_tsdf_integrate_batch_f32")
+
+
+def tsdf_extract(vol, lo, voxel, min_weight=1, out=None):
+    """The fused surface cloud of a volume, in tsdf.extract's order -> (points fp32 [.,3], total int64 [1] on the device).  `out`
+    given (fp32 [capacity,3]): its first min(total, capacity) rows are written and nothing beyond them, with no host
+    synchronisation.  out=None: the points are counted first, the total is read back (the ONE host synchronisation of this path:
+    it belongs to the evaluation at a rollout's end) and exactly total rows are returned."""
+    dims = _tsdf_volume("tsdf_extract", vol)
+    n_vox = dims[0] * dims[1] * dims[2]
+    if out is not None and (not isinstance(out, torch.Tensor) or out.device != vol.device or out.dtype != torch.float32
+                            or out.dim() != 2 or out.shape[1] != 3 or not out.is_contiguous()):
+        raise ValueError("tsdf_extract: out must be a contiguous fp32 [capacity,3] tensor on the volume's device")
+    L = _lib.lib()
+    lo3 = (C.c_float * 3)(*[float(v) for v in lo])
+    total = torch.zeros(1, dtype=torch.int64, device=vol.device)
+
+    def call(points, capacity):
+        with torch.cuda.device(vol.device):
+            ws = _workspace_for("tsdf_extract", n_vox, lambda: L.nbp_tsdf_extract_workspace_bytes(n_vox), vol.device)
+            rc = L.nbp_tsdf_extract_f32(_lib.ptr(vol), lo3, float(voxel), *dims, int(min_weight), _lib.ptr(points), capacity,
+                                        _lib.ptr(total), _lib.ptr(ws), ws.numel(), _st())
+        _lib.check(rc, "nbp_tsdf_extract_f32")
+
+    if out is not None:
+        call(out if out.shape[0] else None, out.shape[0])
+        return out, total
+    call(None, 0)
+    n = int(total.item())
+    out = torch.empty(n, 3, dtype=torch.float32, device=vol.device)
+    if n:
+        call(out, n)
+    return out, total
+
+
+def tsdf_stats(vol, min_weight=1):
+    """int64 [2] on the device: the voxels with W > 0, the usable voxels (tsdf.stats).  Two launches, no host synchronisation."""
+    dims = _tsdf_volume("tsdf_stats", vol)
+    L = _lib.lib()
+    counts = torch.empty(2, dtype=torch.int64, device=vol.device)
+    with torch.cuda.device(vol.device):
+        ws = _workspace_for("tsdf_stats", 0, L.nbp_tsdf_stats_workspace_bytes, vol.device)
+        rc = L.nbp_tsdf_stats_i64(_lib.ptr(vol), dims[0] * dims[1] * dims[2], int(min_weight), _lib.ptr(counts), _lib.ptr(ws), ws.numel(),
+                                  _st())
+    _lib.check(rc, "nbp_tsdf_stats_i64")
+    return counts
+
+
+class TSDFVolume:
+    """The TSDF volume of one rollout on the device (utility/tsdf.py is the definition): int32 [nx,ny,nz,2] over bbox = (lo, hi) of
+    the GT grown by trunc.  spec: tsdf.option_spec's dict with max_depth resolved (tsdf.resolved_options); it is `.options`.
+    `frames` counts the frames integrated so far (on the host)."""
+
+    def __init__(self, bbox, spec, device):
+        from . import tsdf
+        spec = tsdf.option_spec(spec)
+        if spec is None or "max_depth" not in spec:
+            raise ValueError("TSDFVolume: a spec with max_depth is needed (tsdf.resolved_options; None means off: nothing to build)")
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("TSDFVolume: the HIP path needs a cuda device (no CPU fallback)")
+        self.options = spec
+        lo, dims = tsdf.volume_geometry(bbox, spec)
+        self.lo, self.dims = [float(v) for v in lo], tuple(int(d) for d in dims)
+        self.voxel, self.trunc, self.max_depth, self.min_weight = spec["voxel"], spec["trunc"], spec["max_depth"], spec["min_weight"]
+        self.vol = torch.zeros(*self.dims, 2, dtype=torch.int32, device=device)
+        self.frames = 0
+
+    def reset(self):
+        """An empty volume again.  Enqueue-only."""
+        self.vol.zero_()
+        self.frames = 0
+
+    def integrate(self, depth, cams, H=None, W=None):
+        """`depth` (tsdf_integrate's forms) with cams host [n,12] into the volume: one call, no host synchronisation."""
+        tsdf_integrate(self.vol, self.lo, self.voxel, depth, cams, self.trunc, self.max_depth, H, W)
+        self.frames += len(cams)
+
+    def item(self, frames, cams):
+        """The arguments of tsdf_integrate_batch for 1 to 4 frames (a list of [H,W] tensors or device pointers) of this volume.
+        Making an item counts its frames: an item is made to be launched."""
+        self.frames += len(cams)
+        return (self.vol, self.lo, self.voxel, self.trunc, self.max_depth, frames, cams)
+
+    def extract(self):
+        """(points fp32 [n,3] on the device, n): the fused surface cloud.  Reads the count back (one host synchronisation)."""
+        points, total = tsdf_extract(self.vol, self.lo, self.voxel, self.min_weight)
+        return points, points.shape[0]
+
+    def stats(self):
+        """{"observed_voxels", "usable_voxels"} on the host (one device -> host copy)."""
+        observed, usable = tsdf_stats(self.vol, self.min_weight).tolist()
+        return {"observed_voxels": int(observed), "usable_voxels": int(usable)}
