@@ -19,7 +19,9 @@ enum { NBP_TILE_AUTO = 0, NBP_TILE_128x128 = 1, NBP_TILE_256x64 = 2, NBP_TILE_25
        NBP_TILE_SPLIT_GATE = 19 };      // nbp_split.hip: the attention gates' 1x1 GEMM over [g | x] (gate1x1_h2_kernel)
       //  // nbp_split.hip: 8 x 32 pixels x 128 channels (32-pixel-wide layers with N % 128 == 0)
 struct TileInfo { int bm, bn; };
-struct ConvPlan { int tile; int split_k; int chunks_per_split; };
+// finish (nbp_plan_conv_split): the last split-K slice runs as a launch of its own that adds the earlier slices' partial sums in its
+// epilogue and writes final values (no reduce launch)
+struct ConvPlan { int tile; int split_k; int chunks_per_split; int finish; };
 
 // fp32 path (nbp_conv.hip)
 // kernel arguments of the fp32-activation convolutions (nbp_conv.hip, nbp_split.hip)
@@ -78,8 +80,9 @@ int nbp_pack_upconv_weight_split_launch(const float* w_oihw, int N, int C, void*
 // head != null offers the one-channel sigmoid head that alone consumes a 64-channel layer: out1[m] = sigmoid((out[m,:] . w) * scale[0]
 // + shift[0]); *headed tells whether the launch wrote it INSTEAD of `out` -- if not, the caller runs nbp_final_1x1_f32 as before
 struct ConvHead { const float* w; const float* scale; const float* shift; float* out; };
-// pool_out != null offers the 2x2 max-pool of the output(s) [B,H/2,W/2,N]; *pooled tells whether the launch wrote it (only
-// without split-K) -- if not, the caller runs nbp_maxpool2_nhwc_f32 as before
+// pool_out != null offers the 2x2 max-pool of the output(s) [B,H/2,W/2,N]; *pooled tells whether the launch wrote it (in the
+// epilogue of a launch that writes final values -- no split-K, or the finishing launch of a sliced plan -- or in the split-K
+// reduce of a one-problem launch) -- if not, the caller runs nbp_maxpool2_nhwc_f32 as before
 int nbp_conv_split_launch_g(const ConvOperandsSplit& o, const ConvOperandsSplit* o2, int C0, int C1, int ups, int B, int H, int W,
                             int ksize, int N, int relu, int split_k, void* ws, size_t ws_bytes, hipStream_t st,
                             float* const* pool_out = nullptr, int* pooled = nullptr, const struct ConvHead* head = nullptr,

@@ -108,13 +108,17 @@ struct SplitOps {
     const float* psi0;
 };
 struct SplitArgs {
-    SplitOps g[2];              // blockIdx.z >= split_k: the second problem of a grouped launch
+    SplitOps g[2];              // blockIdx.z >= slices: the second problem of a grouped launch
     int C0, C1, ups, H, W, Hs, Ws, N, relu;
     long long M;
     int split_k, chunks_total, chunks_per_split;       // in 16-channel chunks
     unsigned bytes0, bytes1, bytesw;
     float* partial;             // split-K scratch [group][split][M][N]
     int groups, xcd_remap;
+    // A launch runs the slices slice0 .. slice0 + slices - 1 of the layer's split_k (all of them: 0, split_k).  finish (the FIN
+    // instantiations; slice0 == split_k - 1, slices == 1): the launch adds the partial sums an EARLIER launch on the same stream left
+    // in `partial` to its own slice and writes final values -- no reduce launch follows
+    int slice0, slices, finish;
 };
 
 // ------------------------------------------------------------------ 3x3 convolution from LDS-resident fp16 planes
@@ -156,18 +160,26 @@ __device__ unsigned nbp_dbg_n;
 // low-resolution tile, plain output (no parity scatter, no 2 x 2 sum pass).  a.H / a.W = the low-resolution output, a.Hs / a.Ws = dout.
 // ONE (training's "fp16" precision): one piece per operand, hi = fp16(s x) -- the halo and the weight planes hold hi alone (one plane,
 // [k half][..] without the [hi|lo] level) and every tap-product is ONE MFMA; scales, staging order, split-K and epilogue as above.
-// (ONE leads the parameter list: a kernel symbol ends in the same <..., PH, BS, P2, DG> as before the one-piece form existed)
-template <bool ONE, int TW, int TM, int TN, bool PH, bool BS = false, bool P2 = false, bool DG = false>
+// (FIN and ONE lead the parameter list: a kernel symbol ends in the same <..., PH, BS, P2, DG> as before either form existed)
+// FIN: the launch that FINISHES a split-K sum.  It runs the layer's last slice alone, after the launch of the slices before it has
+// completed (stream order is the hand-off, as it is for the reduce launch), and its epilogue loads the earlier slices' partial sums of
+// its own outputs -- each lane the addresses the same lane position of the earlier launch wrote -- adds them in slice order, its own
+// accumulators last (the reduce kernel's order: the same bits), and goes on as a launch that writes final values does: scale / shift,
+// ReLU, max |out|, the 2x2 max-pool.  The last slice's partial sums are never written or read back and no reduce launch runs.
+template <bool FIN, bool ONE, int TW, int TM, int TN, bool PH, bool BS = false, bool P2 = false, bool DG = false>
 __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv3x3_halo_h2_kernel(SplitArgs a) {
     static_assert(!P2 || PH, "two-parity form: up_conv layers");
     static_assert(!DG || (PH && !BS && !P2), "data gradient of an up_conv layer: the one-parity tap structure");
+    static_assert(!FIN || (!BS && !DG), "finishing launches: the inference forms");
     constexpr bool PHO = PH && !DG;                            // the launch writes one output parity of the full-resolution image
     int zs = blockIdx.z;
     const int py = PHO ? (P2 ? zs & 1 : (zs >> 1) & 1) : 0, px = (PHO && !P2) ? zs & 1 : 0;
     if (PHO) zs >>= (P2 ? 1 : 2);
-    const int zslice = zs;                                     // partial-sum slice: group * split_k + split
-    const SplitOps& o = zs >= a.split_k ? a.g[1] : a.g[0];
-    if (zs >= a.split_k) zs -= a.split_k;
+    const int zgroup = zs >= a.slices ? 1 : 0;                 // zs = group * (slices of this launch) + slice of this launch
+    const SplitOps& o = zgroup ? a.g[1] : a.g[0];
+    if (zgroup) zs -= a.slices;
+    zs += a.slice0;                                            // the layer's slice
+    const int zslice = zgroup * a.split_k + zs;                // partial-sum plane: group * split_k + slice
     constexpr int ROWS = PH ? 2 : 3, TPR = PH ? 2 : 3, TAPS = ROWS * TPR;      // filter rows = stages per chunk; taps per row
     constexpr int BN = TN * 32, NB = BN / 64;
     constexpr int RPB = 32 / TW, TH = 4 * TM * RPB;            // image rows per 32-pixel row block; tile height (16)
@@ -475,7 +487,7 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     }
 
     // ---- epilogue (A = pixels, B = weights): col n = lane & 31, pixel of the row block = (r&3) + 8 (r>>2) + 4 (lane>>5)
-    const bool final_out = (a.split_k == 1);
+    const bool final_out = FIN || a.split_k == 1;
     float* outp = final_out ? o.out : a.partial + (long long)zslice * a.M * a.N;
     float mx = 0.f;
     // The output stores go through a buffer resource at the tile's first element: the lane's part of the address is ONE 32-bit offset
@@ -487,7 +499,30 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     const long long erem = (a.M * a.N - e0) * 4;
     const __amdgpu_buffer_rsrc_t rso = __builtin_amdgcn_make_buffer_rsrc(outp + e0, 0, erem < 0x7fffffffll ? (int)erem : 0x7fffffff, 0x00020000);
     const unsigned vout = (unsigned)(((TM * wave * RPB * PS * a.W + 4 * khalf * PS) * a.N + (lane & 31)) * 4);
-    constexpr bool HEADABLE = !PH && TN == 2;              // 64 columns = all channels of the head's input in one wave
+    constexpr bool HEADABLE = !PH && TN == 2 && !FIN;      // 64 columns = all channels of the head's input in one wave
+    // FIN: the earlier slices' planes of this group, from the tile's first element; what is left of a plane bounds its resource, so
+    // a wrong index reads zeros (a wrong number in the tests), never another allocation
+    const float* const prev0 = FIN ? a.partial + (long long)zgroup * a.split_k * a.M * a.N + e0 : nullptr;
+    const int prev_bytes = erem < 0x7fffffffll ? (int)erem : 0x7fffffff;
+    const int nprev = a.slice0;                                // >= 1 in a finishing launch
+    // wave-uniform part of an output's offset from the tile's first element (parity, column block j, row block i, register r; the
+    // lane's part is vout)
+    auto soff_of = [&](int pq, int j, int i, int r) {
+        const int q = (r & 3) + 8 * (r >> 2);
+        return (unsigned)((((i * RPB + q / TW) * PS * a.W + (q % TW) * PS + (PHO ? (P2 ? pq : px) : 0)) * a.N + j * 32) * 4);
+    };
+    auto plane = [&](int s) {
+        return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(prev0 + (long long)s * a.M * a.N), 0, prev_bytes, 0x00020000);
+    };
+    auto load_slice = [&](__amdgpu_buffer_rsrc_t rs, float (&dst)[16], int pq, int j, int i) {      // a register block's 16 loads together
+#pragma unroll
+        for (int r = 0; r < 16; ++r) dst[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, vout, soff_of(pq, j, i, r), 0));
+    };
+    const __amdgpu_buffer_rsrc_t rp0 = plane(0);
+    float pre[16];                                             // FIN: slice 0 of the register block that is finished next
+    // later slices in flight per register block: two where the 240 registers of two resident waves allow (tools/kernel_budget.py)
+    constexpr int SPB = (TW == 16 && TM == 2 && !PH) ? 1 : 2;
+    if constexpr (FIN) load_slice(rp0, pre, 0, 0, 0);
     const bool head = HEADABLE && final_out && o.head_out;
     const bool bn_stats = BS && final_out && o.bn_part;
     double* const bsh = reinterpret_cast<double*>(ldsb);       // [wave][BN columns][sum | sum of squares]: the stage buffers are dead
@@ -506,7 +541,6 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     for (int pq = 0; pq < NPAR; ++pq)
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
-        const int pxe = P2 ? pq : px;                          // the column parity these accumulators belong to
         const int n = n0 + j * 32 + (lane & 31);
         float sc = 1.f, sh = 0.f;
         if (final_out) { sc = o.scale[n]; sh = o.shift[n]; }
@@ -514,11 +548,34 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
         float vals[TM][16];
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
+            float prev[FIN ? 16 : 1];
+            if constexpr (FIN) {
+                // prev = ((p0 + p1) + ...) + p_(nprev - 1) of this register block's outputs.  Slice 0 was loaded while the block before
+                // this one was finished; the next block's loads go out now.  The slices after slice 0 (plans of three slices or more)
+                // are loaded SPB at a time and added in slice order (a serial load-add chain costs one memory round trip per slice)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) prev[r] = pre[r];
+                const int ni = i + 1 < TM ? i + 1 : 0, nj = ni ? j : (j + 1 < TN ? j + 1 : 0), npq = (ni || nj) ? pq : pq + 1;
+                if (npq < NPAR) load_slice(rp0, pre, npq, nj, ni);
+                for (int s = 1; s < nprev; s += SPB) {
+                    float u[SPB][16];
+#pragma unroll
+                    for (int t = 0; t < SPB; ++t)
+                        if (s + t < nprev) load_slice(plane(s + t), u[t], pq, j, i);       // (wave-uniform)
+#pragma unroll
+                    for (int t = 0; t < SPB; ++t)
+                        if (s + t < nprev) {
+#pragma unroll
+                            for (int r = 0; r < 16; ++r) prev[r] += u[t][r];
+                        }
+                }
+            }
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int q = (r & 3) + 8 * (r >> 2);
-                const unsigned soff = (unsigned)((((i * RPB + q / TW) * PS * a.W + (q % TW) * PS + (PHO ? pxe : 0)) * a.N + j * 32) * 4);
-                float v = ldexpf(accs[pq][i][j][r], einv) * sc + sh;
+                const unsigned soff = soff_of(pq, j, i, r);
+                float v;
+                if constexpr (FIN) v = fmaf(prev[r] + ldexpf(accs[pq][i][j][r], einv), sc, sh);        // (the reduce kernels' fmaf)
+                else v = ldexpf(accs[pq][i][j][r], einv) * sc + sh;
                 if (final_out && a.relu) v = fmaxf(v, 0.f);
                 mx = fmaxf(mx, fabsf(v));
                 if (!head) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rso, vout, soff, 0);
@@ -1340,7 +1397,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_split_kernel(const float* _
             const f32x4 sh = *reinterpret_cast<const f32x4*>(shift + n);
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                v[e] = v[e] * sc[e] + sh[e];          // the partial sums already carry 1 / (s_x s_w)
+                v[e] = fmaf(v[e], sc[e], sh[e]);      // the partial sums already carry 1 / (s_x s_w); (one rounding, as in a finishing launch)
                 if (relu) v[e] = fmaxf(v[e], 0.f);
                 mx = fmaxf(mx, fabsf(v[e]));
             }
@@ -1395,7 +1452,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_pool_kernel(const float* __
         for (int k = 0; k < 4; ++k) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                float r = v[k][e] * sc[e] + sh[e];
+                float r = fmaf(v[k][e], sc[e], sh[e]);
                 if (relu) r = fmaxf(r, 0.f);
                 mx = fmaxf(mx, fabsf(r));
                 v[k][e] = r;
@@ -1696,11 +1753,11 @@ int split_tile_width(int H, int W, int N, int ksize) {
     return 0;
 }
 
-template <int TW, int TM, int TN, bool PH, bool BS = false, bool P2 = false, bool DG = false, bool ONE = false>
+template <int TW, int TM, int TN, bool PH, bool BS = false, bool P2 = false, bool DG = false, bool ONE = false, bool FIN = false>
 int launch_h2(const SplitArgs& a, hipStream_t st, int tile) {
-    {
+    if (!FIN) {     // (a finishing launch runs under the tile id of the launch before it: the row's symbol stays that instantiation)
         char nm[96];
-        snprintf(nm, sizeof(nm), "conv3x3_halo_h2_kernel<%s, %d, %d, %d, %s, %s, %s, %s>", ONE ? "true" : "false", TW, TM, TN, PH ? "true" : "false",
+        snprintf(nm, sizeof(nm), "conv3x3_halo_h2_kernel<false, %s, %d, %d, %d, %s, %s, %s, %s>", ONE ? "true" : "false", TW, TM, TN, PH ? "true" : "false",
                  BS ? "true" : "false", P2 ? "true" : "false", DG ? "true" : "false");
         nbp_note_kernel_symbol(tile, nm);
     }
@@ -1710,7 +1767,7 @@ int launch_h2(const SplitArgs& a, hipStream_t st, int tile) {
     constexpr size_t smem = 2 * NPL * (size_t)RS + 2 * (size_t)(PH ? 4 : 6) * NPL * NB * 1024 * (P2 ? 2 : 1) + (PH ? 0 : (HPIX * 4 + 15) / 16 * 16);      // (+ psi of the halo pixels)
     static bool attr_set = false;
     if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_halo_h2_kernel<ONE, TW, TM, TN, PH, BS, P2, DG>),
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_halo_h2_kernel<FIN, ONE, TW, TM, TN, PH, BS, P2, DG>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
         if (e != hipSuccess) return (int)e;
         attr_set = true;
@@ -1718,14 +1775,22 @@ int launch_h2(const SplitArgs& a, hipStream_t st, int tile) {
     // PH: tiles of the low-resolution image, four parities in blockIdx.z (fastest); DG: a.M counts the low-resolution output itself
     constexpr bool PHO = PH && !DG;
     NBP_RETURN_IF((long long)(2 * TH + 2) * a.W * a.N * 4 >= (1ll << 31), NBP_E_SHAPE);      // a tile's outputs within 32-bit offsets of its first
-    dim3 grid((unsigned)(a.M / (PHO ? 4 : 1) / (TH * TW)), (unsigned)(a.N / (TN * 32)), (unsigned)(a.split_k * a.groups * (PHO ? (P2 ? 2 : 4) : 1)));
-    conv3x3_halo_h2_kernel<ONE, TW, TM, TN, PH, BS, P2, DG><<<grid, 256, smem, st>>>(a);
+    NBP_RETURN_IF(a.slices < 1 || a.slice0 < 0 || a.slice0 + a.slices > a.split_k, NBP_E_ARG);
+    NBP_RETURN_IF(FIN != (a.finish != 0) || (FIN && (a.slices != 1 || a.slice0 < 1 || !a.partial)), NBP_E_ARG);
+    dim3 grid((unsigned)(a.M / (PHO ? 4 : 1) / (TH * TW)), (unsigned)(a.N / (TN * 32)), (unsigned)(a.slices * a.groups * (PHO ? (P2 ? 2 : 4) : 1)));
+    conv3x3_halo_h2_kernel<FIN, ONE, TW, TM, TN, PH, BS, P2, DG><<<grid, 256, smem, st>>>(a);
     return nbp_launch_status();
 }
 // the same instantiation in the two-piece (one == 0) or the one-piece form
 template <int TW, int TM, int TN, bool PH, bool BS = false, bool P2 = false, bool DG = false>
 int launch_h2o(const SplitArgs& a, hipStream_t st, int tile, int one) {
     return one ? launch_h2<TW, TM, TN, PH, BS, P2, DG, true>(a, st, tile) : launch_h2<TW, TM, TN, PH, BS, P2, DG, false>(a, st, tile);
+}
+// an inference launch (no batch statistics, no data gradient) of the slices a.slice0 .. + a.slices - 1; a.finish: the FIN instantiation
+template <int TW, int TM, int TN, bool PH, bool P2 = false>
+int launch_h2f(const SplitArgs& a, hipStream_t st, int tile, int one) {
+    if (!a.finish) return launch_h2o<TW, TM, TN, PH, false, P2>(a, st, tile, one);
+    return one ? launch_h2<TW, TM, TN, PH, false, P2, false, true, true>(a, st, tile) : launch_h2<TW, TM, TN, PH, false, P2, false, false, true>(a, st, tile);
 }
 
 }  // namespace
@@ -1780,8 +1845,23 @@ static bool half_rows_for_tail(long long workgroups) {
     return rem > 0 && rem <= 160;
 }
 
+// Finishing launch (conv3x3_halo_h2_kernel<FIN>): a layer with slices runs as TWO convolution launches, the slices before the last
+// and then the last one alone, which adds the earlier partial sums in its epilogue and writes the layer -- one slice's write and
+// read and the whole reduce launch less, for one more launch tail.  The tail is what decides: the second launch must fill the
+// device on its own, so the rule takes the eval planner's plans (request 0) whose last slice has at least
+// NBP_SPLIT_FINISH_MIN_WGS workgroups (512 = one full round of two per CU).  NBP_SPLIT_FINISH: 0 = never (the reduce launch),
+// 1 = the rule, 2 = every sliced launch, explicit split_k requests included (the tests' A/B: bit-identical either way).
+// Launches that take BatchNorm statistics never finish (the launcher clears it).
+static int finish_by_rule(int request, int split_k, long long last_slice_wgs) {
+    static const int mode = nbp_tune_int("NBP_SPLIT_FINISH", 1);
+    static const int min_wgs = nbp_tune_int("NBP_SPLIT_FINISH_MIN_WGS", 512);
+    if (split_k < 2 || mode <= 0) return 0;
+    if (mode >= 2) return 1;
+    return request == 0 && last_slice_wgs >= min_wgs ? 1 : 0;
+}
+
 ConvPlan nbp_plan_conv_split(long long M, int N, int chunks_total, int split_k, int groups, int H, int W, int ksize, int ups) {
-    ConvPlan p{0, 1, chunks_total};
+    ConvPlan p{0, 1, chunks_total, 0};
     constexpr int min_blocks = 256;           // split-K workgroup target: one workgroup per CU
     if (ups && !((H | W) & 1)) {
         const int twu = split_tile_width(H / 2, W / 2, N, ksize);
@@ -1800,6 +1880,7 @@ ConvPlan nbp_plan_conv_split(long long M, int N, int chunks_total, int split_k, 
             p.split_k = (int)nbp_cdiv(cc, per); p.chunks_per_split = per;
             const bool r8t = r8 || half_rows_for_tail((M / 4 / (16 * twu)) * (N / (twu == 32 ? 64 : 128)) * groups * 4 * p.split_k);
             p.tile = r8t ? NBP_TILE_SPLIT_UP_R8 : NBP_TILE_SPLIT_UP;
+            p.finish = finish_by_rule(split_k, p.split_k, blocks * (r8t ? 2 : 1));
             return p;
         }
     }
@@ -1832,6 +1913,7 @@ ConvPlan nbp_plan_conv_split(long long M, int N, int chunks_total, int split_k, 
     // (full-height plans of 32-pixel-wide layers with N % 128 == 0 run 8 x 32 pixels x 128 channels: its own tile id, so that a
     // per-layer timing table and a profile's kernel rows name the same instantiation)
     p.tile = r8t ? NBP_TILE_SPLIT_HALO_R8 : (tw == 32 && N % 128 == 0) ? NBP_TILE_SPLIT_HALO_128 : NBP_TILE_SPLIT_HALO_64;
+    p.finish = finish_by_rule(split_k, p.split_k, blocks * (r8t ? 2 : 1));
     return p;
 }
 
@@ -1876,7 +1958,9 @@ int nbp_conv_split_launch_g(const ConvOperandsSplit& o, const ConvOperandsSplit*
     const bool wide = p.tile == NBP_TILE_SPLIT_HALO_128;      // 8 x 32 pixels x 128 channels
     const int th = (r8 || wide) ? 8 : 16;
     a.split_k = p.split_k; a.chunks_per_split = p.chunks_per_split;
+    a.slice0 = 0; a.slices = p.split_k; a.finish = 0;
     a.chunks_total = (C0 + C1) / 16;
+    const bool finish = p.finish && p.split_k > 1 && !bn_part;      // the last slice as a launch of its own that writes the layer
     const int tw = ph ? split_tile_width(H / 2, W / 2, N, ksize) : split_tile_width(H, W, N, ksize);
     if (ph) {
         NBP_RETURN_IF(C1 != 0, NBP_E_SHAPE);
@@ -1889,7 +1973,8 @@ int nbp_conv_split_launch_g(const ConvOperandsSplit& o, const ConvOperandsSplit*
         a.bytesw = (unsigned)bwu;
     }
     {
-        const long long ptiles = a.M / (ph ? 4 : 1) / (th * tw), nbk = N / ((tw == 32 && !wide) ? 64 : 128);      // = the launch's grid
+        // = the launch's grid (x, y): the same for the two launches of a finishing plan, which differ in z alone
+        const long long ptiles = a.M / (ph ? 4 : 1) / (th * tw), nbk = N / ((tw == 32 && !wide) ? 64 : 128);
         const long long tiles = ptiles * nbk;
         // bytes that cross the fabric: mode 1 = 8 x weights + activations, mode 2 = weights + min(nbk, 8) x activations
         const double wb = (double)(C0 + C1) * (ph ? 16 : 9) * N * 4, ab = (double)a.M / (ups ? 4 : 1) * (C0 + C1) * 4;
@@ -1908,10 +1993,11 @@ int nbp_conv_split_launch_g(const ConvOperandsSplit& o, const ConvOperandsSplit*
     }
     // the max-pool that follows an encoder block rides in the epilogue when the launch writes final values (no split-K)
     static const int allow_pool = nbp_tune_int("NBP_CONV_POOL", 1);
-    const bool with_pool = allow_pool && pool_out && pool_out[0] && (groups == 1 || pool_out[1]) && p.split_k == 1 && !ph && !ups &&
+    // (or the finishing launch of a sliced one)
+    const bool with_pool = allow_pool && pool_out && pool_out[0] && (groups == 1 || pool_out[1]) && (p.split_k == 1 || finish) && !ph && !ups &&
                            !((H | W) & 1);
     // ... and in the split-K reduce otherwise (one problem per launch: the encoder's layers)
-    const bool pool_in_reduce = allow_pool && pool_out && pool_out[0] && groups == 1 && p.split_k > 1 && !ph && !ups && !((H | W) & 1);
+    const bool pool_in_reduce = allow_pool && pool_out && pool_out[0] && groups == 1 && p.split_k > 1 && !finish && !ph && !ups && !((H | W) & 1);
     if (pooled) *pooled = with_pool || pool_in_reduce;
     if (with_pool || pool_in_reduce)
         for (int g = 0; g < groups; ++g) a.g[g].pool_out = pool_out[g];
@@ -1936,16 +2022,28 @@ int nbp_conv_split_launch_g(const ConvOperandsSplit& o, const ConvOperandsSplit*
     // up_conv layers on full-height 32-pixel-wide tiles: both column parities in one workgroup of half the height (same workgroup
     // count, one staged halo for two parities).  The 16-pixel-wide levels keep one parity per workgroup (the two-parity form measured
     // 7 % slower per launch there: 619 against 577 us at B = 24); round 3's one-parity 16 x 32 form (120 B of scratch per lane) is gone.
-    int rc = (ph && !r8 && tw == 32) ? launch_h2o<32, 2, 2, true, false, true>(a, st, p.tile, one)
-           : r8 ? (ph ? (tw == 32 ? launch_h2o<32, 2, 2, true>(a, st, p.tile, one) : launch_h2o<16, 1, 4, true>(a, st, p.tile, one))
-                      : (tw == 32 ? launch_h2o<32, 2, 2, false>(a, st, p.tile, one) : launch_h2o<16, 1, 4, false>(a, st, p.tile, one)))
-           : ph ? launch_h2o<16, 2, 4, true>(a, st, p.tile, one)
+    auto launch = [&](const SplitArgs& a) {      // (the instantiation is the same for both launches of a finishing plan, FIN apart)
+        return (ph && !r8 && tw == 32) ? launch_h2f<32, 2, 2, true, true>(a, st, p.tile, one)
+           : r8 ? (ph ? (tw == 32 ? launch_h2f<32, 2, 2, true>(a, st, p.tile, one) : launch_h2f<16, 1, 4, true>(a, st, p.tile, one))
+                      : (tw == 32 ? launch_h2f<32, 2, 2, false>(a, st, p.tile, one) : launch_h2f<16, 1, 4, false>(a, st, p.tile, one)))
+           : ph ? launch_h2f<16, 2, 4, true>(a, st, p.tile, one)
                 // 32-pixel-wide levels: 8 x 32 pixels x 128 channels where the layer has them (round 5) -- the same workgroup count, MFMAs
                 // per stage and sums in the same order as 16 x 32 x 64, but a 10 x 34 halo staged per 128 output channels instead of an
                 // 18 x 34 one per 64: 44 % less halo traffic, splitting and LDS writes per output (every N % 128 == 0 layer 1.4 - 2.7 %
                 // faster at B = 24, the forward 9.46 -> 9.38 ms; profiles/r05/tile_8x32x128.txt)
-                : (tw == 32 ? (wide ? launch_h2o<32, 2, 4, false>(a, st, p.tile, one) : launch_h2o<32, 4, 2, false>(a, st, p.tile, one))
-                            : launch_h2o<16, 2, 4, false>(a, st, p.tile, one));
+                : (tw == 32 ? (wide ? launch_h2f<32, 2, 4, false>(a, st, p.tile, one) : launch_h2f<32, 4, 2, false>(a, st, p.tile, one))
+                            : launch_h2f<16, 2, 4, false>(a, st, p.tile, one));
+    };
+    if (finish) {
+        // slices 0 .. k - 2 leave their partial sums in the workspace as ever (the last slice's plane stays unwritten); the last slice
+        // follows in stream order, adds them in its epilogue and writes the layer
+        a.slices = p.split_k - 1;
+        int rc = launch(a);
+        if (rc) return rc;
+        a.slice0 = p.split_k - 1; a.slices = 1; a.finish = 1;
+        return launch(a);
+    }
+    int rc = launch(a);
     if (rc) return rc;
     if (p.split_k > 1) {
         const long long MN = a.M * N;
@@ -2083,6 +2181,7 @@ int nbp_upconv_dgrad_split_launch(const float* dy, int N, int B, int H, int W, c
     if (sk > a.chunks_total) sk = a.chunks_total;
     a.chunks_per_split = (int)nbp_cdiv(a.chunks_total, sk);
     a.split_k = (int)nbp_cdiv(a.chunks_total, a.chunks_per_split);
+    a.slice0 = 0; a.slices = a.split_k; a.finish = 0;
     a.xcd_remap = blocks >= 8 ? 1 : 0;
     a.partial = nullptr;
     if (a.split_k > 1) {

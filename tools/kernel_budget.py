@@ -78,13 +78,14 @@ def main():
                 bad.append(f"{name} left the step budget: {r}")
     bad += [f"{g}: no such kernel (renamed?)" for g in GUARDED if g not in seen]
     lines.append("")
-    lines.append(f"inference instantiations of conv3x3_halo_h2_kernel<ONE, TW, TM, TN, PH, BS, P2, DG> (two-piece, no batch statistics, no data gradient; "
+    lines.append(f"inference instantiations of conv3x3_halo_h2_kernel<FIN, ONE, TW, TM, TN, PH, BS, P2, DG> (two-piece, no batch statistics, no data gradient; "
                  f"limit: {CONV_VGPRS} allocated)")
     lines.append(f"{'instantiation':72s} {'VGPRs':>6s} {'alloc':>6s} {'scratch':>8s} {'LDS B':>7s}")
     n_conv = 0
     for name, r in sorted(resource_usage(os.path.join(nbuild.CSRC, "nbp_split.hip")).items()):
-        m = re.match(r"conv3x3_halo_h2_kernel<(\w+), (\d+), (\d+), (\d+), (\w+), (\w+), (\w+), (\w+)>", name)
-        if not m or m.group(1) != "false" or m.group(6) != "false" or m.group(8) != "false":
+        # <FIN, ONE, TW, TM, TN, PH, BS, P2, DG>: FIN = the launch that finishes a split-K sum, an inference form like the plain one
+        m = re.match(r"conv3x3_halo_h2_kernel<(\w+), (\w+), (\d+), (\d+), (\d+), (\w+), (\w+), (\w+), (\w+)>", name)
+        if not m or m.group(2) != "false" or m.group(7) != "false" or m.group(9) != "false":
             continue
         n_conv += 1
         total = r["vgprs"] + r.get("agprs", 0)
