@@ -1077,6 +1077,38 @@ int nbp_recon_curve_update_batch_f32(int n, const void* const* plans, const int*
                                      float* const* d2_new, void* const* totals, const int* T, const float* thresholds_host,
                                      double* const* row, const long long* new_bound, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- Cloud-to-mesh accuracy (csrc/nbp_surface.hip).  Not in the reference: the exact truncated squared distance
+ * from a point to the GT MESH, fp32, through a uniform grid of triangles.  The definition of record is
+ * nextbestpath_amd/utility/surface_metrics.py (point_triangle_d2, mesh_dist2_reference), which the kernels equal bit for bit; the
+ * summary of the distances is nbp_recon_stats_f64.  Host binding: hipops.MeshPlan / mesh_dist2 / SurfaceMetrics.
+ *   d2[i] = min(cap2, min over the PARTICIPATING triangles of point_triangle_d2(q_i, a, b, c)),  cap2 = fl(cap cap).
+ * verts3 [V][3] fp32, faces3 [F][3] int32; a triangle participates iff its indices are inside [0, V) and its three vertices lie
+ * inside the box (lo <= v <= hi, fp32; a NaN or an infinity is outside).  The grid is the nearest-neighbour grid above (lo_host /
+ * hi_host / cell, cells of 1.001 cell, the same limits); a triangle is registered in every cell between the cells of its bounding
+ * box's corners.  The number of (triangle, cell) pairs is known on the device only, so a plan is built in two calls:
+ *   nbp_mesh_plan_count_f32   counts and scans into `plan` (nbp_mesh_plan_bytes; ws: nbp_mesh_plan_workspace_bytes), copies the
+ *                             participating triangles' vertices there, and leaves totals2_dev [2] int64 = (pairs, participating
+ *                             triangles) on the device: the caller reads the first back -- the one host synchronisation of this
+ *                             path, at setup -- and allocates `entries` int32 [pairs] (at least one element)
+ *   nbp_mesh_plan_fill_i32    writes the pairs' triangle indices into entries; nothing at or beyond entry_capacity is written.
+ *                             NBP_E_SHAPE: entry_capacity > 2^31 - 1
+ *   nbp_mesh_dist2_planned_f32  one launch: the query walks the shells of cells around its unclamped cell and stops after shell r
+ *                             once best <= fl(r cell)^2; the box term of point_triangle_d2 makes that exit exact for triangles of
+ *                             any size (the file's header).  Q / Q_dev_or_null as above; a query more than ceil(cap / cell) cells
+ *                             outside the grid, or with a NaN, gets cap2 without a memory access.  No atomics on the output.
+ * No allocation; no host synchronisation inside the library.  NBP_E_ARG / NBP_E_SHAPE / NBP_E_WS as for nbp_nn_*; totals2_dev off the
+ * 8-byte grid is NBP_E_SHAPE.  The size queries return 0 where the call would fail.  F = 0, V = 0 and Q = 0 are legal. */
+size_t nbp_mesh_plan_bytes(const float* lo_host, const float* hi_host, float cell, long long F);
+size_t nbp_mesh_plan_workspace_bytes(const float* lo_host, const float* hi_host, float cell);
+int nbp_mesh_plan_count_f32(const float* verts3, long long V, const int* faces3, long long F, const float* lo_host,
+                            const float* hi_host, float cell, void* plan, size_t plan_bytes, long long* totals2_dev, void* ws,
+                            size_t ws_bytes, void* stream);
+int nbp_mesh_plan_fill_i32(const float* verts3, long long V, const int* faces3, long long F, const float* lo_host,
+                           const float* hi_host, float cell, const void* plan, int* entries, long long entry_capacity, void* ws,
+                           size_t ws_bytes, void* stream);
+int nbp_mesh_dist2_planned_f32(const void* plan, const int* entries, const float* lo_host, const float* hi_host, float cell,
+                               float cap, const float* q3, long long Q, const long long* Q_dev_or_null, float* d2, void* stream);
+
 /* ---- The replay store's container in LMDB's on-disk format (csrc/nbp_mdb.cpp; host only).  The reference keeps its experience
  * records in an LMDB environment (next_best_path/trainers/train_nbp_model.py:61-63 lmdb.open(path, map_size);
  * next_best_path/utility/nbp_utils.py:32-141: txn.put per record, ordered cursors, txn.delete of the validation records).  liblmdb is

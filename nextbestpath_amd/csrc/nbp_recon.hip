@@ -36,10 +36,7 @@
 // above with r = R).  The slot -> GT index map is the fourth component of the plan's float4 (its bits; the query never reads it).
 // The summaries follow in two launches of the stats geometry above: d2_gt in full, the step's own distances into the running
 // float64 totals by one thread.  The watermark `seen` moves in the last launch only (the first two read it).
-#include "nbp_grid.h"
-
-#include <math.h>
-#include <stddef.h>
+#include "nbp_nn_grid.h"
 
 #pragma clang fp contract(off)
 
@@ -48,14 +45,9 @@ namespace {
 constexpr int NN_LANES = 8;                      // lanes per query: the 8 rim columns of shell 1 at once
 constexpr int NN_UNROLL = 4;                     // points of a run in flight together (coverage_mark_body: one per iteration
                                                  // is a chain of dependent round trips)
-constexpr int NN_MAX_AXIS = 2048;                // cells per axis for which the early exit is proven (see above)
 constexpr int STATS_BLOCKS = 256, STATS_THREADS = 256, STATS_WAVES = STATS_THREADS / 64;
 constexpr int STATS_MAX_T = 8;
 constexpr int STATS_ROW = 2 + STATS_MAX_T;       // 8-byte words of a block's row: two float64 sums, then the counts
-
-struct Box { float hi[3]; };
-
-static size_t al256(size_t b) { return (b + 255) / 256 * 256; }
 
 // ---- sort
 __global__ __launch_bounds__(256) void nn_bin_kernel(const float* __restrict__ t, const long long* __restrict__ n_dev, long long n_host,
@@ -435,26 +427,7 @@ __global__ __launch_bounds__(64) void curve_final_kernel(const CurveBatch b) {
     }
 }
 
-// ---- host
-// The grid over the caller's box [lo, hi]: cells 1.001 w wide (inv), one cell on an axis with hi == lo.
-int nn_grid(const float* lo, const float* hi, float w, Grid* g, Box* bx, size_t* ncell) {
-    size_t n = 1;
-    for (int a = 0; a < 3; ++a) {
-        g->lo[a] = lo[a];
-        bx->hi[a] = hi[a];
-        const double ext = (double)hi[a] - (double)lo[a];
-        if (!(ext >= 0) || !(ext / (double)w < (double)NN_MAX_AXIS * 65536.0)) return ext >= 0 ? NBP_E_SHAPE : NBP_E_ARG;
-        const long long na = (long long)(ext / (double)w) + 1;
-        if (na > NN_MAX_AXIS) return NBP_E_SHAPE;
-        g->n[a] = (int)na;
-        n *= (size_t)na;
-    }
-    g->inv = (float)(1.0 / ((double)w * 1.001));
-    if (n > (size_t)1 << 28) return NBP_E_SHAPE;
-    *ncell = n;
-    return 0;
-}
-
+// ---- host (the grid over the caller's box and the argument checks: nbp_nn_grid.h)
 void nn_plan_carve(void* plan, size_t ncell, int** start, float4** sorted) {
     char* p = (char*)(((uintptr_t)plan + 255) / 256 * 256);
     *start = (int*)p; p += al256((ncell + 1) * 4);
@@ -501,10 +474,6 @@ int nn_query(const void* plan, const Grid& g, size_t ncell, float cap, float w, 
     nn_query_kernel<<<nbp_ew_grid(Q * NN_LANES, 256), 256, 0, st>>>(q3, Q_dev, Q, g, R, w, cap2, sorted, start, d2);
     return nbp_launch_status();
 }
-
-bool nn_args_ok(const float* lo, const float* hi, float w) { return lo && hi && w > 0 && isfinite(w); }
-// cap > 0 and at most 2^24 cells: the shell index and the cell coordinates stay inside int and exact in float
-bool nn_cap_ok(float cap, float w) { return cap > 0 && isfinite(cap) && (double)cap / (double)w <= 16777216.0; }
 
 }  // namespace
 

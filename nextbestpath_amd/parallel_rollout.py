@@ -5,7 +5,8 @@ runs them in nested loops on one GPU), so rank r takes runs r, r+W, r+2W, ... an
 collective is ONE all_gather of a padded fp32 tensor [runs_per_rank, n_poses + 3] holding
 (run id, final coverage, AUC, coverage curve) -- a few KB over RCCL/xGMI, latency bound (with the
 planning option `recon_metrics` on, a second one of float64 sums and counts: gather_reconstruction; with its `curve`, a third of the
-per-step rows: gather_reconstruction_curve; with the option `view_metrics`, one of the per-view counts and sums: gather_views; with the option `fusion`, one of the fused cloud's sums and counts: gather_fusion).  One
+per-step rows: gather_reconstruction_curve; with the option `view_metrics`, one of the per-view counts and sums: gather_views; with the option `fusion`, one of the fused cloud's sums and counts: gather_fusion; with the option `surface_metrics`, one of both
+clouds' sums and counts against the mesh: gather_surface).  One
 process per GPU; backend "nccl" (= RCCL on ROCm) with CUDA tensors, "gloo" on CPU-only hosts
 (that path is what the world_size-2 CPU tests exercise)."""
 from __future__ import annotations
@@ -180,6 +181,32 @@ def gather_fusion(results, runs, rank, world, device, thresholds, cap, options=N
     if rank != 0:
         return {}
     return {int(row[0]): tsdf.summarise_raw(row[1:], thresholds, cap, options) for row in t if row[0] >= 0}
+
+
+def gather_surface(results, runs, rank, world, device, spec):
+    """The planning option `surface_metrics`: all ranks call this behind gather_results, and only when the option is on.  The raw
+    float64 numbers of every run's cloud-to-mesh accuracy (results[i]["surface_raw"], utility/surface_metrics.py::pack_record: the
+    raw cloud's sums, size and counts, the fused cloud's, has_fused and the mesh's three counts) travel in ONE all_gather of a padded
+    float64 tensor [runs_per_rank, 1 + 2 (3 + T) + 4] (run id first; pad rows = -1) -- a gather of its own: the others keep their
+    shapes with the option off.  spec: the normalised options (surface_metrics.option_spec).  Rank 0 forms the ratios with
+    surface_metrics.summarise_record -> {run id: the record's "surface" block}; the other ranks get {}."""
+    from .utility import surface_metrics
+    rows = runs_per_rank(len(runs), world)
+    width = 1 + 2 * (surface_metrics.RAW_HEAD + len(spec["thresholds"])) + len(surface_metrics.RECORD_TAIL)
+    t = np.full((rows, width), -1.0, np.float64)
+    for j, r in enumerate(results):
+        t[j, 0] = r["run_id"]
+        t[j, 1:] = np.asarray(r["surface_raw"], np.float64)
+    collective = world > 1 or group_is_up()
+    if collective:
+        import torch.distributed as dist
+        local = torch.from_numpy(t).to(collective_device(device))
+        buf = [torch.empty_like(local) for _ in range(world)]
+        dist.all_gather(buf, local)
+        t = torch.stack(buf).cpu().numpy().reshape(-1, width)
+    if rank != 0:
+        return {}
+    return {int(row[0]): surface_metrics.summarise_record(row[1:], spec) for row in t if row[0] >= 0}
 
 
 def gather_views(results, runs, rank, world, device, options):

@@ -33,6 +33,7 @@ from ..utility import augment, hipops
 from ..utility import depth_filter as filter_options
 from ..utility import depth_noise as noise_options
 from ..utility import recon_metrics as recon_options
+from ..utility import surface_metrics as surface_options
 from ..utility import tsdf as fusion_options
 from ..utility import utils as hu
 from ..utility import view_metrics as view_options
@@ -70,7 +71,7 @@ class Rollout(lockstep.LockstepRollout):
     """One exploration rollout, steppable (bench.py times K consecutive ``step()`` calls)."""
 
     def __init__(self, params, nbp, camera, gt_scene_pc, mesh, mesh_for_check, y_bins, device, state=None, seed=0,
-                 grid=256, symmetry_ensemble=_UNSET, recon_metrics=None, view_metrics=None, fusion=None):
+                 grid=256, symmetry_ensemble=_UNSET, recon_metrics=None, view_metrics=None, fusion=None, surface_metrics=None):
         self.params, self.nbp, self.camera, self.mesh, self.mesh_for_check = params, nbp, camera, mesh, mesh_for_check
         _set_symmetry_ensemble(nbp, params, symmetry_ensemble)
         self.y_bins, self.device = y_bins, device
@@ -120,6 +121,12 @@ class Rollout(lockstep.LockstepRollout):
         self.fusion = None
         if self.fusion_spec is not None:
             self.fusion = hipops.TSDFVolume(self.bbox, fusion_options.resolved_options(self.fusion_spec, params.sensor_range), device)
+        # the planning option `surface_metrics` (None = off: nothing is built, launched, gathered or written; True; a dict of
+        # utility/surface_metrics.py): the cloud's accuracy against the GT MESH, not the GT sample, once, at the rollout's end; the
+        # mesh's triangle grid is built here (one read-back of its size)
+        self.surface_spec = surface_options.option_spec(surface_metrics)
+        self.surface = None if self.surface_spec is None else hipops.SurfaceMetrics(mesh, **self.surface_spec)
+        self._surface_default = None
         self.path, self.path_record = [], 0
         self.collision_list, self.passable_list, self.idx_history = [], [], []
         self.step_seed = seed * 1_000_003
@@ -308,12 +315,13 @@ class Rollout(lockstep.LockstepRollout):
         self.finish()
         return self.fusion.extract()
 
-    def fusion_metrics(self, raw=False):
+    def fusion_metrics(self, raw=False, fused=None):
         """Reconstruction quality of the FUSED cloud against the GT surface, by the metrics that judge the raw cloud
         (hipops.ReconMetrics with the rollout's `recon_metrics` option, or that option's defaults): utility/tsdf.py::summarise_raw's
         dict -- recon_metrics.summarise's entries (n_points = the fused points) with observed_voxels, usable_voxels, frames and the
-        volume's options -- or with raw=True the float64 vector behind it (tsdf.pack_raw: what travels between ranks)."""
-        points, n = self.fused_cloud()
+        volume's options -- or with raw=True the float64 vector behind it (tsdf.pack_raw: what travels between ranks).  `fused`:
+        what fused_cloud() returned, where the caller has extracted it already."""
+        points, n = self.fused_cloud() if fused is None else fused
         rec = self.recon or self._recon_default
         if rec is None:
             rec = self._recon_default = hipops.ReconMetrics(self.gt, self.bbox, **recon_options.option_spec(True))
@@ -323,6 +331,29 @@ class Rollout(lockstep.LockstepRollout):
         st = self.fusion.stats()
         row = fusion_options.pack_raw(rec.raw(), st["observed_voxels"], st["usable_voxels"], self.fusion.frames)
         return row if raw else fusion_options.summarise_raw(row, rec.thresholds, rec.cap, self.fusion.options)
+
+    def surface_metrics(self, raw=False, fused=None):
+        """Accuracy of the WHOLE cloud so far against the surface of the GT mesh (exact point-to-triangle distances, no GT sample
+        in between), and with the option `fusion` of the fused cloud too: utility/surface_metrics.py::summarise_record's dict
+        {"cloud": n_points, cap, accuracy_mean, accuracy_rmse, thresholds = [{threshold, precision}]; "fused": the same (only with
+        fusion); "mesh": {faces, faces_used, entries}; "options"}, or with raw=True the float64 vector behind it (pack_record: what
+        travels between ranks).  Evaluated on the device (hipops.SurfaceMetrics), read back with one copy per cloud.  `fused`: what
+        fused_cloud() returned, where the caller has extracted it already.  With the rollout's own `surface_metrics` option, or the
+        defaults where it was built without one."""
+        self.finish()
+        sm = self.surface or self._surface_default
+        if sm is None:              # (kept apart from self.surface: a rollout built with the option off keeps reporting as such)
+            sm = self._surface_default = hipops.SurfaceMetrics(self.mesh, **surface_options.option_spec(True))
+        sm.evaluate(self.st.cloud, self.st.cloud_count)
+        cloud_raw, fused_raw = sm.raw(), None
+        if self.fusion is not None:
+            points, n = self.fused_cloud() if fused is None else fused
+            if n == 0:              # (the kernels take a buffer of at least one row; the device count says none is valid)
+                points = torch.zeros(1, 3, dtype=torch.float32, device=self.device)
+            sm.evaluate(points, torch.full((1,), n, dtype=torch.int64, device=self.device))
+            fused_raw = sm.raw()
+        row = surface_options.pack_record(cloud_raw, fused_raw, sm.mesh_block())
+        return row if raw else surface_options.summarise_record(row, {"thresholds": sm.thresholds, "cap": sm.cap, "cell": sm.cell})
 
     def reconstruction_curve(self, n, raw=False):
         """The per-step reconstruction curve (the option `recon_metrics` with `curve`): entry s is the metric of the WHOLE cloud as
@@ -587,8 +618,8 @@ def compute_nbp_trajectory(params, nbp, camera, gt_scene_pc, mesh, mesh_for_chec
 # the option keys of the configs/test/ file load_params read last (a file with the NBP options: `nbp_weights`), each _UNSET where the
 # file has none; the entry script passes test_nbp_planning the options it knows by keyword, and these reach it here.  In the order
 # in which resolve_options checks them
-_test_config = dict.fromkeys(("policy", "symmetry_ensemble", "recon_metrics", "depth_noise", "depth_filter", "view_metrics", "fusion"),
-                            _UNSET)
+_test_config = dict.fromkeys(("policy", "symmetry_ensemble", "recon_metrics", "depth_noise", "depth_filter", "view_metrics", "fusion",
+                             "surface_metrics"), _UNSET)
 
 
 def load_params(path):
@@ -628,10 +659,11 @@ def list_runs(dataset, params):
 
 
 def build_rollout(params, nbp, dataset, run, device, test_resolution=0.05, state=None, seed=0, grid=256, recon_metrics=None,
-                  depth_noise=None, view_metrics=None, depth_filter=None, fusion=None):
+                  depth_noise=None, view_metrics=None, depth_filter=None, fusion=None, surface_metrics=None):
     """Scene + GT surface + camera + Rollout for one (scene, start pose) run (nbp_planning.py:414-492).  `depth_noise`: the camera's
     sensor model (utility/depth_noise.py; None = off, perfect depth).  `depth_filter`: the camera's frame filter behind it
-    (utility/depth_filter.py; None = off).  `fusion`: the rollout's TSDF volume (utility/tsdf.py; None = off)."""
+    (utility/depth_filter.py; None = off).  `fusion`: the rollout's TSDF volume (utility/tsdf.py; None = off).  `surface_metrics`: the
+    cloud's accuracy against the mesh (utility/surface_metrics.py; None = off)."""
     si, k = run
     sd = dataset[si]
     settings = sim_scene.Settings(sd["settings"], params.scene_scale_factor)
@@ -642,7 +674,7 @@ def build_rollout(params, nbp, dataset, run, device, test_resolution=0.05, state
     camera = setup_test_camera(params, mesh, settings.camera.start_positions[k], settings, device, seed=seed, depth_noise=depth_noise,
                                depth_filter=depth_filter)
     ro = Rollout(params, nbp, camera, gt_dev, mesh, mesh, y_bins, device, state, seed, grid, recon_metrics=recon_metrics,
-                 view_metrics=view_metrics, fusion=fusion)
+                 view_metrics=view_metrics, fusion=fusion, surface_metrics=surface_metrics)
     ro.scene_name, ro.start = sd["scene_name"], k
     return ro
 
@@ -660,7 +692,8 @@ def resolve_options(**given):
     make_policy / option_spec, in _test_config's order: a bad combination raises the first bad option's ValueError.  The record has
     the normalised spec (or None) under each option's name -- `policy` is the policy object, None = the network, with its options
     as `policy_spec`; `symmetry_ensemble` stays as given, checked here as its setter will -- and `rollout`, the keywords of
-    build_rollout / run_one / run_many among them (`fusion` only where it is on: off is those functions' default)."""
+    build_rollout / run_one / run_many among them (`fusion` and `surface_metrics` only where they are on: off is those functions'
+    default)."""
     from .frontier_policy import make_policy
     opts = SimpleNamespace()
 
@@ -673,7 +706,8 @@ def resolve_options(**given):
 
     normalise = {"policy": make_policy, "symmetry_ensemble": ensemble, "recon_metrics": recon_options.option_spec,
                  "depth_noise": noise_options.option_spec, "depth_filter": filter_options.option_spec,
-                 "view_metrics": view_options.option_spec, "fusion": fusion_options.option_spec}
+                 "view_metrics": view_options.option_spec, "fusion": fusion_options.option_spec,
+                 "surface_metrics": surface_options.option_spec}
     if set(given) - set(normalise):
         raise TypeError(f"resolve_options: unknown options {sorted(set(given) - set(normalise))}")
     for key in _test_config:
@@ -684,6 +718,8 @@ def resolve_options(**given):
     opts.rollout = {key: getattr(opts, key) for key in ("recon_metrics", "depth_noise", "view_metrics", "depth_filter")}
     if opts.fusion is not None:
         opts.rollout["fusion"] = opts.fusion
+    if opts.surface_metrics is not None:
+        opts.rollout["surface_metrics"] = opts.surface_metrics
     return opts
 
 
@@ -705,11 +741,17 @@ def _result(ro, n_poses):
         raw = ro.view_metrics(raw=True)
         res["views"] = view_options.summarise_raw(raw, ro.views.options)
         res["views_raw"] = raw.tolist()                # the counts and sums behind the ratios (parallel_rollout.gather_views)
+    fused = None                    # the fused cloud is extracted once per record, whichever metrics judge it
     if ro.fusion is not None:       # the option `fusion`: the TSDF volume's surface cloud by the reconstruction metrics, once, at the end
-        raw = ro.fusion_metrics(raw=True)
+        fused = ro.fused_cloud() if ro.surface is not None else None
+        raw = ro.fusion_metrics(raw=True, fused=fused)
         rec = ro.recon or ro._recon_default
         res["fusion"] = fusion_options.summarise_raw(raw, rec.thresholds, rec.cap, ro.fusion.options)
         res["fusion_raw"] = raw.tolist()               # the sums and counts behind the ratios (parallel_rollout.gather_fusion)
+    if ro.surface is not None:      # the option `surface_metrics`: the whole cloud (and the fused one) against the GT mesh, once, at the end
+        raw = ro.surface_metrics(raw=True, fused=fused)
+        res["surface"] = surface_options.summarise_record(raw, ro.surface_spec)
+        res["surface_raw"] = raw.tolist()              # the sums and counts behind the ratios (parallel_rollout.gather_surface)
     return res
 
 
@@ -723,10 +765,10 @@ def _policy_or(nbp, policy):
 
 
 def run_one(params, nbp, dataset, run, device, test_resolution=0.05, state=None, n_poses=N_POSES, seed=0, *, recon_metrics=None,
-            depth_noise=None, view_metrics=None, policy=None, depth_filter=None, fusion=None):
+            depth_noise=None, view_metrics=None, policy=None, depth_filter=None, fusion=None, surface_metrics=None):
     nbp = _policy_or(nbp, policy)
     options = dict(recon_metrics=recon_metrics, depth_noise=depth_noise, view_metrics=view_metrics, depth_filter=depth_filter,
-                   fusion=fusion)
+                   fusion=fusion, surface_metrics=surface_metrics)
     ro = build_rollout(params, nbp, dataset, run, device, test_resolution, state, seed, **options)
     nbp.eval()
     for _ in range(n_poses):
@@ -737,14 +779,14 @@ def run_one(params, nbp, dataset, run, device, test_resolution=0.05, state=None,
 
 def run_many(params, nbp, dataset, runs, device, seeds, test_resolution=0.05, n_poses=N_POSES, rollouts_per_gpu=48,
              grid=256, timing=None, *, recon_metrics=None, depth_noise=None, view_metrics=None, policy=None, depth_filter=None,
-             fusion=None):
+             fusion=None, surface_metrics=None):
     """Runs `runs` in lock-step groups of `rollouts_per_gpu` (MultiRollout); same results as run_one each.  `timing` (a dict)
     receives the wall-clock seconds of scene / GT-surface / camera setup and of the stepping (device-synchronised).  `policy`: as
     in run_one (None = the network `nbp`)."""
     import time
     out = []
     options = dict(recon_metrics=recon_metrics, depth_noise=depth_noise, view_metrics=view_metrics, depth_filter=depth_filter,
-                   fusion=fusion)
+                   fusion=fusion, surface_metrics=surface_metrics)
     nbp = _policy_or(nbp, policy)
     nbp.eval()
     for g0 in range(0, len(runs), rollouts_per_gpu):
@@ -772,7 +814,8 @@ def test_nbp_planning(params_file, model_file, results_json_file, numGPU, test_s
                       use_perfect_depth_map=False, compute_collision=False, load_json=False, dataset_path=None,
                       nbp_weights=None, configs_dir=None, results_dir=None, n_poses=N_POSES, seed=8, torch_seed=9,
                       rollouts_per_gpu=48, grid_size=256, nbp_precision=None, symmetry_ensemble=_UNSET, recon_metrics=_UNSET,
-                      depth_noise=_UNSET, view_metrics=_UNSET, policy=_UNSET, depth_filter=_UNSET, fusion=_UNSET):
+                      depth_noise=_UNSET, view_metrics=_UNSET, policy=_UNSET, depth_filter=_UNSET, fusion=_UNSET,
+                      surface_metrics=_UNSET):
     """Same arguments as the reference (nbp_planning.py:364-374); `grid_size` / `nbp_precision` select
     BASELINE.json configs[4] (512 grid at the same 0.3125 units per pixel, bf16 convolutions).  `symmetry_ensemble` (None = off, a
     name of utility/augment.py::ENSEMBLES or a list of op codes) is NBP.symmetry_ensemble of the loaded network; not given, it is
@@ -791,12 +834,15 @@ def test_nbp_planning(params_file, model_file, results_json_file, numGPU, test_s
     stands: no weights are loaded (`nbp_precision` given with it draws a warning), and every record gains "policy", the normalised options.
     `fusion` (None = off, True = the defaults, or a dict of utility/tsdf.py::option_spec; not given, the key of that name in the same
     file) integrates every frame a rollout un-projects into a TSDF volume and adds "fusion" to its record: the fused surface cloud
-    by the reconstruction metrics (with `recon_metrics`' options, or its defaults), the voxel counts and the options.  Under torchrun the flattened
+    by the reconstruction metrics (with `recon_metrics`' options, or its defaults), the voxel counts and the options.
+    `surface_metrics` (None = off, True = the defaults, or a dict with thresholds / cap / cell of utility/surface_metrics.py::option_spec;
+    not given, the key of that name in the same file) adds "surface" to every record: the accuracy of the whole cloud, and with `fusion`
+    of the fused cloud, against the surface of the GT mesh itself (exact point-to-triangle distances).  Under torchrun the flattened
     (scene, start pose) runs are sharded round-robin over the ranks and the coverage curves are
     gathered with ONE all_gather over RCCL (backend "nccl" on ROCm; "gloo" on CPU-only hosts)."""
     import time
-    from ..parallel_rollout import (gather_fusion, gather_reconstruction, gather_reconstruction_curve, gather_results, gather_views,
-                                     init_distributed, shard)
+    from ..parallel_rollout import (gather_fusion, gather_reconstruction, gather_reconstruction_curve, gather_results, gather_surface,
+                                     gather_views, init_distributed, shard)
     t_start = time.perf_counter()
     here = os.path.dirname(os.path.abspath(__file__))
     configs_dir = configs_dir or os.path.join(here, "../../configs/macarons")
@@ -808,7 +854,7 @@ def test_nbp_planning(params_file, model_file, results_json_file, numGPU, test_s
     torch.cuda.set_device(device)
     random.seed(seed); np.random.seed(seed); torch.manual_seed(torch_seed)
     opts = resolve_options(policy=policy, symmetry_ensemble=symmetry_ensemble, recon_metrics=recon_metrics, depth_noise=depth_noise,
-                           depth_filter=depth_filter, view_metrics=view_metrics, fusion=fusion)
+                           depth_filter=depth_filter, view_metrics=view_metrics, fusion=fusion, surface_metrics=surface_metrics)
     nbp, policy_spec, recon_spec, view_spec = opts.policy, opts.policy_spec, opts.recon_metrics, opts.view_metrics
     assert nbp_precision in (None, "fp32", "fp32_split", "bf16"), nbp_precision
     if nbp is not None and nbp_precision is not None:
@@ -871,6 +917,13 @@ def test_nbp_planning(params_file, model_file, results_json_file, numGPU, test_s
             r.pop("fusion_raw", None)
             if rank == 0:
                 r["fusion"] = fused[r["run_id"]]
+    if opts.surface_metrics is not None:    # a float64 gather of its own: both clouds' raw sums and counts; the ratios are formed on rank 0
+        surface = gather_surface(results, runs, rank, world, device, opts.surface_metrics)
+        for r in gathered:
+            r.pop("surface", None)
+            r.pop("surface_raw", None)
+            if rank == 0:
+                r["surface"] = surface[r["run_id"]]
     if rank == 0:
         out = {}
         for r in gathered:
@@ -885,6 +938,8 @@ def test_nbp_planning(params_file, model_file, results_json_file, numGPU, test_s
                 rec["views"] = r["views"]
             if opts.fusion is not None:
                 rec["fusion"] = r["fusion"]
+            if opts.surface_metrics is not None:
+                rec["surface"] = r["surface"]
             for key in ("X_cam_history", "V_cam_history"):      # histories of other ranks stay in their part files
                 if key in r:
                     rec[key] = r[key]

@@ -1171,6 +1171,113 @@ class ReconMetrics:
         return recon_metrics.summarise_raw(self.raw(), self.thresholds, self.cap)
 
 
+# ---- cloud-to-mesh accuracy (csrc/nbp_surface.hip; the definition of record is utility/surface_metrics.py)
+class MeshPlan:
+    """The triangles of a mesh inside `box` = (lo, hi) registered once in the grid of `cell`-wide cells (nbp_mesh_plan_count_f32 /
+    nbp_mesh_plan_fill_i32); `dist2` then costs one launch.  verts fp32 [V,3], faces int32 [F,3] on the device.  Construction reads
+    the number of (triangle, cell) pairs back: the ONE host synchronisation of this path, at setup.  `entries` = that number,
+    `faces_used` = the triangles that take part (surface_metrics.participating)."""
+
+    def __init__(self, verts, faces, box, cell=1.0):
+        _nn_points("MeshPlan", verts, "verts")
+        if not isinstance(faces, torch.Tensor) or not faces.is_cuda:
+            raise RuntimeError("MeshPlan: the HIP path needs a cuda tensor for faces (no CPU fallback)")
+        if faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype != torch.int32 or not faces.is_contiguous():
+            raise ValueError("MeshPlan: faces must be a contiguous int32 [n,3] tensor")
+        if faces.device != verts.device:
+            raise ValueError("MeshPlan: verts and faces on one device expected")
+        L = _lib.lib()
+        dev = verts.device
+        self.verts, self.faces, self.cell, self.V, self.F = verts, faces, float(cell), verts.shape[0], faces.shape[0]
+        self.lo, self.hi = _nn_box(box)
+        with torch.cuda.device(dev):
+            nplan = L.nbp_mesh_plan_bytes(self.lo, self.hi, self.cell, self.F)
+            nws = L.nbp_mesh_plan_workspace_bytes(self.lo, self.hi, self.cell)
+            # (a zero size: the count call names the reason)
+            self.plan = torch.empty(max(nplan, 256), dtype=torch.uint8, device=dev)
+            ws = torch.empty(max(nws, 256), dtype=torch.uint8, device=dev)
+            totals = torch.empty(2, dtype=torch.int64, device=dev)
+            args = (_lib.ptr(verts), self.V, _lib.ptr(faces), self.F, self.lo, self.hi, self.cell, _lib.ptr(self.plan))
+            rc = L.nbp_mesh_plan_count_f32(*args, nplan, _lib.ptr(totals), _lib.ptr(ws), nws, _st())
+            _lib.check(rc, "nbp_mesh_plan_count_f32")
+            self.entries, self.faces_used = (int(v) for v in totals.tolist())          # the host synchronisation
+            fits = self.entries <= 0x7fffffff     # (beyond: no list is allocated, and the fill call names the reason)
+            self.entry_list = torch.empty(max(self.entries, 1) if fits else 1, dtype=torch.int32, device=dev)
+            rc = L.nbp_mesh_plan_fill_i32(*args, _lib.ptr(self.entry_list), self.entries, _lib.ptr(ws), nws, _st())
+        _lib.check(rc, "nbp_mesh_plan_fill_i32")
+
+    def dist2(self, query, cap, n_query_dev=None, out=None):
+        """Truncated exact squared distances to the mesh -> fp32 [Q] on the device: out[i] = min(cap^2, min over the plan's triangles
+        of point_triangle_d2(q_i, ...)), bit for bit surface_metrics.mesh_dist2_reference.  n_query_dev: int64 device counter (rows
+        beyond it are never read, entries of out beyond it never written).  One launch, no host synchronisation."""
+        _nn_points("MeshPlan.dist2", query, "query")
+        if query.device != self.plan.device:
+            raise ValueError("MeshPlan.dist2: query on the plan's device expected")
+        _nn_count("MeshPlan.dist2", n_query_dev, query.device)
+        Q = query.shape[0]
+        out = _nn_out("MeshPlan.dist2", out, Q, query.device)
+        with torch.cuda.device(query.device):
+            rc = _lib.lib().nbp_mesh_dist2_planned_f32(_lib.ptr(self.plan), _lib.ptr(self.entry_list), self.lo, self.hi, self.cell,
+                                                       float(cap), _lib.ptr(query), Q, _lib.ptr(n_query_dev), _lib.ptr(out), _st())
+        _lib.check(rc, "nbp_mesh_dist2_planned_f32")
+        return out
+
+
+def mesh_dist2(query, verts, faces, box, cap, cell=1.0, n_query_dev=None, out=None):
+    """MeshPlan(verts, faces, box, cell).dist2(query, cap, ...): the plan built for one call (its build synchronises with the host)."""
+    return MeshPlan(verts, faces, box, cell).dist2(query, cap, n_query_dev=n_query_dev, out=out)
+
+
+class SurfaceMetrics:
+    """Accuracy of a cloud against the surface of a mesh (not a sample of it), on the device: the mean and RMS truncated distance to
+    the nearest triangle and the share of points within each threshold (utility/surface_metrics.py).  mesh: an object with verts
+    fp32 [V,3] and faces int32 [F,3] on the device and verts_host (simulator/scene.py::DeviceMesh); the triangles are registered
+    once, inside the vertex bounds grown by `cap` (surface_metrics.mesh_box)."""
+
+    def __init__(self, mesh, thresholds=None, cap=5.0, cell=1.0):
+        from . import surface_metrics
+        thresholds = surface_metrics.DEFAULT_THRESHOLDS if thresholds is None else thresholds
+        self.thresholds, self.cap, self.cell = surface_metrics.check_options(thresholds, cap, cell)
+        lo, hi = surface_metrics.mesh_box(mesh.verts_host, self.cap)
+        self.box = (lo.tolist(), hi.tolist())
+        self.plan = MeshPlan(mesh.verts, mesh.faces, self.box, self.cell)
+        self.result = None
+
+    def evaluate(self, cloud, n_dev=None):
+        """Enqueues the distances and their summary on the current stream -> dict of device tensors (sums float64 [2], counts int64
+        [T], n_points int64 [1]); no host synchronisation.  Kept for summary() / raw()."""
+        _nn_points("SurfaceMetrics.evaluate", cloud, "cloud")
+        dev, N = cloud.device, cloud.shape[0]
+        # the distances are scratch of the stream (consumed by the summary enqueued right behind them)
+        d2 = _workspace("surface_d2_cloud", 4 * max(N, 1), dev)[:4 * N].view(torch.float32)
+        self.plan.dist2(cloud, self.cap, n_query_dev=n_dev, out=d2)
+        sums, counts = recon_stats(d2, self.thresholds, n_dev)
+        if n_dev is None:
+            n_points = torch.full((1,), N, dtype=torch.int64, device=dev)
+        else:
+            n_points = n_dev.reshape(1).clamp(0, N)          # (a copy: the counter may move on)
+        self.result = {"sums": sums, "counts": counts, "n_points": n_points}
+        return self.result
+
+    def raw(self):
+        """The last evaluation's raw numbers on the host (ONE device -> host copy): surface_metrics.pack_raw's float64 vector."""
+        from . import surface_metrics
+        if self.result is None:
+            raise RuntimeError("SurfaceMetrics: evaluate() first")
+        r = self.result
+        flat = torch.cat([r["sums"], r["n_points"].double(), r["counts"].double()]).cpu().numpy()
+        return surface_metrics.pack_raw(flat[0:2], flat[3:], flat[2])
+
+    def summary(self):
+        """The last evaluation as the dict of surface_metrics.summarise_raw (ratios formed on the host from the raw sums and counts)."""
+        from . import surface_metrics
+        return surface_metrics.summarise_raw(self.raw(), self.thresholds, self.cap)
+
+    def mesh_block(self):
+        """The record's "mesh" entry: the triangles of the mesh, those that take part, and the grid's (triangle, cell) pairs."""
+        return {"faces": self.plan.F, "faces_used": self.plan.faces_used, "entries": self.plan.entries}
+
+
 _CurveItem = collections.namedtuple("_CurveItem", "curve cloud n_dev row new_bound")      # what ReconCurve.item hands out
 
 

@@ -1,0 +1,453 @@
+"""GPU: the cloud-to-mesh accuracy metrics (csrc/nbp_surface.hip through hipops.MeshPlan / mesh_dist2 / SurfaceMetrics and the rollout
+driver's `surface_metrics` option) against their numpy definition (utility/surface_metrics.py).
+
+Every distance must equal the brute force BIT FOR BIT: the kernel evaluates the definition's fp32 expression on a subset of the
+triangles that provably holds the minimum.  Brute force stays at or below ~1 k x 5 k point-triangle pairs per case."""
+import json
+import os
+import types
+
+import numpy as np
+import pytest
+import torch
+
+import surface_cases as cases
+from nextbestpath_amd.utility import recon_metrics as rm
+from nextbestpath_amd.utility import surface_metrics as sm
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+f32 = np.float32
+SENTINEL = f32(-7.0)
+
+
+def _dev(a, dtype=torch.float32):
+    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda", dtype)
+
+
+def _count(n):
+    return torch.tensor([n], dtype=torch.int64, device="cuda")
+
+
+def _soup(tri):
+    tri = np.asarray(tri, f32).reshape(-1, 3, 3)
+    return tri.reshape(-1, 3), np.arange(3 * len(tri), dtype=np.int32).reshape(-1, 3)
+
+
+# ---- the meshes.  Each returns verts, faces, lo, hi; the grids' dimensions (7 x 5 x 3 cells at cell 1 and the like) are multiples
+# of nothing in the launch geometry (8 lanes per query, 256 threads, waves of 64)
+def _mesh_one():
+    return (*_soup([[[1.2, 0.7, 0.4], [4.9, 3.1, 1.0], [2.2, 3.9, 2.6]]]), [0, 0, 0], [6.5, 4.2, 2.9])
+
+
+def _mesh_seven():
+    v, f = cases.random_mesh(31, 7, 5.0, 2.0)
+    return v, f, [-2.5, -2.5, -2.5], [8.1, 7.3, 7.9]
+
+
+def _mesh_300():
+    v, f = cases.random_mesh(32, 300, 10.0, 1.5)
+    return v, f, [-1.5, -1.5, -1.5], [11.3, 9.4, 7.2]               # some triangles reach outside: dropped
+
+
+def _mesh_whole_grid():
+    return (*_soup([[[0, 0, 0], [6.4, 0, 4.3], [0, 5.2, 4.3]]]), [0, 0, 0], [6.4, 5.2, 4.3])       # its box IS the grid: 7 x 6 x 5 cells
+
+
+def _mesh_single_cells():
+    rng = np.random.default_rng(33)
+    o = (rng.integers(0, 6, (120, 1, 3)) + 0.5) * 1.001             # cell centres of cell = 1
+    return (*_soup(o + rng.uniform(-0.05, 0.05, (120, 3, 3))), [0, 0, 0], [6.2, 6.2, 6.2])
+
+
+def _mesh_straddlers():
+    rng = np.random.default_rng(34)
+    tri = []
+    for _ in range(40):                                              # across one cell face: 2 cells
+        o = (rng.integers(1, 20, 3) + np.array([0.0, 0.5, 0.5])) * 1.001
+        tri.append(o + rng.uniform(-0.1, 0.1, (3, 3)))
+    for _ in range(25):                                              # a run of 20 cells along one axis, thin in the others
+        o = (rng.integers(1, 3, 3) + 0.5) * 1.001
+        axis = rng.integers(0, 3)
+        t = o + rng.uniform(-0.1, 0.1, (3, 3))
+        t[1, axis] += 19.0
+        t[2, axis] += 9.5
+        tri.append(t)
+    for _ in range(6):                                               # 20 x 3 cells and more: registered by the wave together
+        t = np.array([2.5, 2.5, 2.5]) * 1.001 + rng.uniform(-0.1, 0.1, (3, 3))
+        t[1, 0] += 19.0
+        t[2, 1] += 2.0 + rng.uniform(0, 6)
+        tri.append(t)
+    return (*_soup(tri), [0, 0, 0], [23.3, 22.9, 22.4])
+
+
+def _mesh_slivers_degenerates():
+    rng = np.random.default_rng(35)
+    fam = cases.families(rng, 60)
+    tri = []
+    for name in ("sliver", "degenerate", "small"):
+        p, a, b, c = fam[name]
+        tri.append(np.stack([a, b, c], 1).astype(np.float64) / 4.0 + 8.0)        # into [0, 16]^3, sizes / 4
+    return (*_soup(np.concatenate(tri)), [-1, -1, -1], [17.2, 17.2, 17.2])
+
+
+def _mesh_duplicates():
+    v, f = cases.random_mesh(36, 80, 6.0, 1.5)
+    return v, np.concatenate([f, f[:30], f[10:20]]).astype(np.int32), [-2, -2, -2], [8.5, 8.5, 8.5]
+
+
+def _mesh_dropped():
+    v, f = cases.random_mesh(37, 40, 6.0, 1.0)
+    lo, hi = [-1.5, -1.5, -1.5], [7.7, 7.7, 7.7]
+    v[3 * 5] = [7.7 + 1e-3, 3, 3]                                    # one vertex outside the box, by a little and by a lot
+    v[3 * 6 + 1] = [3, -40, 3]
+    v[3 * 7 + 2] = [np.nan, 3, 3]                                    # a NaN vertex, an infinite one
+    v[3 * 8] = [3, np.inf, 3]
+    v[3 * 9] = hi                                                    # ON the box's corner: inside
+    f = np.concatenate([f, [[0, 1, 120]], [[-1, 1, 2]], [[0, 2 ** 31 - 1, 2]]]).astype(np.int32)     # indices out of range
+    return v, f, lo, hi
+
+
+def _mesh_empty():
+    v, f = cases.random_mesh(38, 9, 4.0, 1.0)
+    return v + f32(100), f, [0, 0, 0], [5.5, 4.5, 3.5]              # everything outside the box
+
+
+def _mesh_no_faces():
+    v, f = cases.random_mesh(39, 3, 4.0, 1.0)
+    return v, f[:0], [0, 0, 0], [5.5, 4.5, 3.5]
+
+
+MESHES = {"one": _mesh_one, "seven": _mesh_seven, "300": _mesh_300, "whole_grid": _mesh_whole_grid, "single_cells": _mesh_single_cells,
+          "straddlers": _mesh_straddlers, "slivers_degenerates": _mesh_slivers_degenerates, "duplicates": _mesh_duplicates,
+          "dropped": _mesh_dropped, "empty": _mesh_empty, "no_faces": _mesh_no_faces}
+
+# (mesh, cell, cap, Q): cap below one cell and of many cells, cell 0.5 / 1 / 2, Q = 1 / 65 / 1000
+DIST_CASES = [
+    ("one", 1.0, 5.0, 1000), ("one", 0.5, 0.3, 65), ("one", 2.0, 1.0, 1), ("seven", 1.0, 1.0, 1000), ("seven", 2.0, 5.0, 65),
+    ("seven", 0.5, 5.0, 1000), ("300", 1.0, 5.0, 1000), ("300", 0.5, 0.3, 1000), ("300", 2.0, 1.0, 65), ("300", 1.0, 0.3, 1),
+    ("whole_grid", 1.0, 5.0, 1000), ("whole_grid", 0.5, 1.0, 1000), ("whole_grid", 2.0, 0.3, 65),
+    ("single_cells", 1.0, 0.3, 1000), ("single_cells", 1.0, 5.0, 1000), ("straddlers", 1.0, 5.0, 1000), ("straddlers", 2.0, 1.0, 1000),
+    ("straddlers", 0.5, 0.3, 1000), ("slivers_degenerates", 1.0, 5.0, 1000), ("slivers_degenerates", 0.5, 1.0, 1000),
+    ("duplicates", 1.0, 5.0, 1000), ("duplicates", 2.0, 0.3, 65), ("dropped", 1.0, 5.0, 1000), ("dropped", 0.5, 1.0, 65),
+    ("empty", 1.0, 5.0, 65), ("no_faces", 1.0, 1.0, 65),
+]
+
+
+@pytest.mark.parametrize("name,cell,cap,Q", DIST_CASES)
+def test_mesh_dist2_is_the_brute_force_minimum(hip, name, cell, cap, Q):
+    """MeshPlan.dist2 == mesh_dist2_reference bit for bit; a second call gives the same bits; mesh_dist2 agrees; a device count
+    below Q leaves the tail untouched; the plan's counts are the definition's."""
+    from nextbestpath_amd.utility import hipops
+    verts, faces, lo, hi = MESHES[name]()
+    q = cases.queries(DIST_CASES.index((name, cell, cap, Q)), verts, faces, lo, hi, cap, cell, Q)
+    want = sm.mesh_dist2_reference(q, verts, faces, lo, hi, cap)
+    cap2 = f32(cap) * f32(cap)
+    assert want.max() <= cap2
+    used, entries = sm.plan_counts(verts, faces, lo, hi, cell)
+    if name in ("empty", "no_faces"):
+        assert used == 0 and entries == 0 and np.all(want == cap2)
+    elif Q >= 65:
+        assert (want < cap2).any() and (want == cap2).any() and np.count_nonzero(want == 0) >= 2
+    vd, fd, qd = _dev(verts), _dev(faces, torch.int32), _dev(q)
+    plan = hipops.MeshPlan(vd, fd, (lo, hi), cell)
+    assert (plan.faces_used, plan.entries) == (used, entries)
+    runs = []
+    for _ in range(2):
+        out = torch.full((Q,), float(SENTINEL), dtype=torch.float32, device="cuda")
+        assert plan.dist2(qd, cap, out=out) is out
+        runs.append(out.cpu().numpy())
+    bad = np.flatnonzero(runs[0].view(np.uint32) != want.view(np.uint32))
+    assert bad.size == 0, (bad[:5], runs[0][bad[:5]], want[bad[:5]], q[bad[:5]])
+    assert np.array_equal(runs[0].view(np.uint32), runs[1].view(np.uint32))
+    assert np.array_equal(hipops.mesh_dist2(qd, vd, fd, (lo, hi), cap, cell).cpu().numpy().view(np.uint32), want.view(np.uint32))
+    # a device count below Q: rows beyond it are never read (NaN there would not matter, a surface point would) or written
+    n = Q - min(Q, 7)
+    out = torch.full((Q,), float(SENTINEL), dtype=torch.float32, device="cuda")
+    plan.dist2(qd, cap, n_query_dev=_count(n), out=out)
+    got = out.cpu().numpy()
+    assert np.array_equal(got[:n].view(np.uint32), want[:n].view(np.uint32)) and np.all(got[n:] == SENTINEL)
+
+
+def test_plan_counts_of_known_meshes(hip):
+    from nextbestpath_amd.utility import hipops
+    verts, faces, lo, hi = _mesh_whole_grid()
+    plan = hipops.MeshPlan(_dev(verts), _dev(faces, torch.int32), (lo, hi), 1.0)
+    assert (plan.F, plan.faces_used, plan.entries) == (1, 1, 7 * 6 * 5)
+    verts, faces, lo, hi = _mesh_dropped()
+    plan = hipops.MeshPlan(_dev(verts), _dev(faces, torch.int32), (lo, hi), 1.0)
+    assert plan.F == 43 and plan.faces_used == 40 - 4
+    verts, faces, lo, hi = _mesh_single_cells()
+    plan = hipops.MeshPlan(_dev(verts), _dev(faces, torch.int32), (lo, hi), 1.0)
+    assert plan.faces_used == plan.entries == 120
+
+
+def _raw_plan(hip, verts, faces, lo, hi, cell):
+    """The two build calls by hand -> (plan bytes tensor, total pairs, the fill call as a function of (entries tensor, capacity))."""
+    import ctypes as C
+    vd, fd = _dev(verts), _dev(faces, torch.int32)
+    lo3, hi3 = (C.c_float * 3)(*lo), (C.c_float * 3)(*hi)
+    nplan, nws = hip.nbp_mesh_plan_bytes(lo3, hi3, cell, len(faces)), hip.nbp_mesh_plan_workspace_bytes(lo3, hi3, cell)
+    assert nplan > 0 and nws > 0
+    plan, ws = torch.empty(nplan, dtype=torch.uint8, device="cuda"), torch.empty(nws, dtype=torch.uint8, device="cuda")
+    totals = torch.empty(2, dtype=torch.int64, device="cuda")
+    head = (vd.data_ptr(), len(verts), fd.data_ptr(), len(faces), lo3, hi3, cell, plan.data_ptr())
+
+    def count(plan_bytes=nplan, ws_bytes=nws, totals_ptr=None):
+        return hip.nbp_mesh_plan_count_f32(*head, plan_bytes, totals.data_ptr() if totals_ptr is None else totals_ptr, ws.data_ptr(),
+                                           ws_bytes, None)
+
+    def fill(entries, capacity, ws_bytes=nws):
+        return hip.nbp_mesh_plan_fill_i32(*head, entries.data_ptr(), capacity, ws.data_ptr(), ws_bytes, None)
+
+    return count, fill, totals, (vd, fd, plan, ws)
+
+
+def test_entry_capacity_below_the_total_writes_nothing_beyond_it(hip):
+    verts, faces, lo, hi = _mesh_straddlers()
+    count, fill, totals, keep = _raw_plan(hip, verts, faces, lo, hi, 1.0)
+    assert count() == 0
+    total, used = totals.tolist()
+    assert (used, total) == sm.plan_counts(verts, faces, lo, hi, 1.0) and used == len(faces) and total > 500
+    for capacity in (total, total // 2, 1, 0):
+        entries = torch.full((total + 64,), -1, dtype=torch.int32, device="cuda")
+        assert fill(entries, capacity) == 0
+        got = entries.cpu().numpy()
+        assert np.all(got[capacity:] == -1), capacity
+        assert np.all((got[:capacity] >= 0) & (got[:capacity] < len(faces))), capacity       # every position below it has one owner
+    full = torch.full((total,), -1, dtype=torch.int32, device="cuda")
+    assert fill(full, total) == 0
+    keep_, c0, c1 = sm.cell_ranges(verts, faces, lo, hi, 1.0)
+    assert np.array_equal(np.bincount(full.cpu().numpy(), minlength=len(faces)), np.prod(c1 - c0 + 1, axis=1))
+
+
+def test_refusals(hip):
+    from nextbestpath_amd import _lib
+    from nextbestpath_amd.utility import hipops
+    verts, faces, lo, hi = _mesh_seven()
+    vd, fd, qd = _dev(verts), _dev(faces, torch.int32), torch.zeros(4, 3, device="cuda")
+    with pytest.raises(_lib.NbpHipError, match="NBP_E_SHAPE"):
+        hipops.MeshPlan(vd, fd, ([0, 0, 0], [700, 700, 700]), 1.0)               # 701^3 > 2^28 cells
+    with pytest.raises(_lib.NbpHipError, match="NBP_E_SHAPE"):
+        hipops.MeshPlan(vd, fd, ([0, 0, 0], [3000, 1, 1]), 1.0)                  # an axis beyond the proven 2048 cells
+    with pytest.raises(_lib.NbpHipError, match="NBP_E_ARG"):
+        hipops.MeshPlan(vd, fd, ([0, 0, 0], [1, -1, 1]), 1.0)
+    with pytest.raises(_lib.NbpHipError, match="NBP_E_ARG"):
+        hipops.MeshPlan(vd, fd, (lo, hi), 0.0)
+    plan = hipops.MeshPlan(vd, fd, (lo, hi), 1.0)
+    for cap in (0.0, -1.0, float("nan"), float("inf")):
+        with pytest.raises(_lib.NbpHipError, match="NBP_E_ARG"):
+            plan.dist2(qd, cap)
+    assert plan.dist2(qd[:0], 1.0).shape == (0,)
+    # no CPU fallback, and the argument checks of the nearest-neighbour path
+    with pytest.raises(RuntimeError):
+        hipops.MeshPlan(vd.cpu(), fd, (lo, hi), 1.0)
+    with pytest.raises(RuntimeError):
+        hipops.MeshPlan(vd, fd.cpu(), (lo, hi), 1.0)
+    with pytest.raises(RuntimeError):
+        plan.dist2(qd.cpu(), 1.0)
+    with pytest.raises(RuntimeError):
+        hipops.mesh_dist2(qd.cpu(), vd, fd, (lo, hi), 1.0)
+    with pytest.raises(ValueError):
+        hipops.MeshPlan(vd, fd.long(), (lo, hi), 1.0)
+    with pytest.raises(ValueError):
+        plan.dist2(qd.double(), 1.0)
+    with pytest.raises(ValueError):
+        plan.dist2(qd, 1.0, n_query_dev=torch.zeros(1, dtype=torch.int32, device="cuda"))
+    with pytest.raises(ValueError):
+        plan.dist2(qd, 1.0, out=torch.zeros(3, device="cuda"))
+    mesh = types.SimpleNamespace(verts=vd, faces=fd, verts_host=verts)
+    with pytest.raises(ValueError, match="surface metrics"):
+        hipops.SurfaceMetrics(mesh, thresholds=(6.0,), cap=5.0)                   # above the cap
+    with pytest.raises(RuntimeError):
+        hipops.SurfaceMetrics(mesh).evaluate(qd.cpu())
+    with pytest.raises(RuntimeError, match="evaluate"):
+        hipops.SurfaceMetrics(mesh).raw()
+    # the C entry points: workspace, plan and capacity
+    count, fill, totals, keep = _raw_plan(hip, verts, faces, lo, hi, 1.0)
+    assert count(plan_bytes=64) == -2 and count(ws_bytes=64) == -2               # NBP_E_WS
+    assert count(totals_ptr=totals.data_ptr() + 4) == -3                         # NBP_E_SHAPE: off the 8-byte grid
+    assert count() == 0
+    entries = torch.zeros(8, dtype=torch.int32, device="cuda")
+    assert fill(entries, 2 ** 31) == -3                                          # NBP_E_SHAPE: more than 2^31 - 1 entries
+    assert fill(entries, -1) == -1 and fill(entries, 8, ws_bytes=64) == -2
+    import ctypes as C
+    assert hip.nbp_mesh_plan_bytes((C.c_float * 3)(0, 0, 0), (C.c_float * 3)(3000, 1, 1), 1.0, 5) == 0
+    assert hip.nbp_mesh_plan_workspace_bytes((C.c_float * 3)(0, 0, 0), (C.c_float * 3)(1, 1, 1), 0.0) == 0
+
+
+# ---- the metrics object
+@pytest.fixture(scope="module")
+def box():
+    """A cube of side 10 in right triangles of leg 0.5 (4 800 faces), 3 000 points exactly on it, and a 2 000-point GT sample."""
+    from nextbestpath_amd.simulator.scene import sample_gt_surface
+    verts, faces = cases.box_mesh(10.0, 0.5, origin=(-3.0, 1.0, 2.0))
+    points = cases.points_on_mesh(51, verts, faces, 3000)
+    gt = sample_gt_surface(verts, faces, 2000, verts.min(0), verts.max(0), seed=52)
+    return verts, faces, points, gt
+
+
+def _mesh_of(verts, faces):
+    return types.SimpleNamespace(verts=_dev(verts), faces=_dev(faces, torch.int32), verts_host=verts)
+
+
+def test_surface_metrics_raw_equals_the_definition(hip, box):
+    from nextbestpath_amd.utility import hipops
+    verts, faces, points, _ = box
+    rng = np.random.default_rng(53)
+    cloud = np.concatenate([points[:1500], points[1500:2200] + rng.normal(0, 0.2, (700, 3)).astype(f32),
+                            rng.uniform(-12, 18, (300, 3)).astype(f32)]).astype(f32)
+    ths, cap = (0.05, 0.1, 0.25, 1.0), 3.0
+    buf = torch.full((4000, 3), float("nan"), device="cuda")                    # a rollout's buffer: capacity beyond the count
+    buf[:len(cloud)] = _dev(cloud)
+    buf[len(cloud):len(cloud) + 300] = _dev(points[:300])                       # ... with would-be perfect points in the tail
+    m = hipops.SurfaceMetrics(_mesh_of(verts, faces), ths, cap, 1.0)
+    assert m.mesh_block() == {"faces": 4800, "faces_used": 4800, "entries": sm.plan_counts(verts, faces, *sm.mesh_box(verts, cap), 1.0)[1]}
+    res = m.evaluate(buf, _count(len(cloud)))
+    assert res["sums"].dtype == torch.float64 and res["counts"].dtype == torch.int64 and res["sums"].is_cuda
+    raw = m.raw()
+    d2 = m.plan.dist2(_dev(cloud), cap).cpu().numpy()
+    lo, hi = sm.mesh_box(verts, cap)
+    assert np.array_equal(d2.view(np.uint32), sm.mesh_dist2_reference(cloud, verts, faces, lo, hi, cap).view(np.uint32))
+    sums, counts = rm.stats_reference(d2, ths)
+    want = sm.pack_raw(sums, counts, len(cloud))
+    print(raw, want)
+    assert np.array_equal(raw[2:], want[2:])                                     # n and the counts: exact
+    assert 0 < counts[0] < counts[-1] < len(cloud)
+    # both add 2 500 non-negative float64 terms, in different orders: each sum is within n 2^-53 relative of the exact one
+    assert np.all(np.abs(raw[:2] - want[:2]) <= 2 * len(cloud) * 2.0 ** -53 * want[:2])
+    m.evaluate(buf, _count(len(cloud)))
+    assert np.array_equal(m.raw().view(np.uint64), raw.view(np.uint64))          # two evaluations: the same bits
+    got, ref = m.summary(), sm.reference(cloud, verts, faces, ths, cap)
+    assert got["n_points"] == ref["n_points"] == len(cloud) and got["thresholds"] == ref["thresholds"]
+    assert abs(got["accuracy_mean"] - ref["accuracy_mean"]) <= 1e-10 * ref["accuracy_mean"]
+    json.dumps(got, allow_nan=False)
+    m.evaluate(buf, _count(0))                                                   # an empty cloud: None, never NaN
+    assert m.summary() == sm.reference(cloud[:0], verts, faces, ths, cap)
+    m.evaluate(_dev(cloud))                                                      # the host length alone
+    assert np.array_equal(m.raw()[2:], want[2:])
+
+
+def test_points_on_the_surface_score_zero_against_the_mesh_and_not_against_a_sample(hip, box):
+    """The point of the feature.  Points exactly on the mesh: the distance to the SURFACE is zero to rounding, the distance to a
+    2 000-point sample of that surface (600 square units: neighbours ~0.55 apart) is the sample's spacing."""
+    from nextbestpath_amd.utility import hipops
+    verts, faces, points, gt = box
+    lo, hi = rm.grown_box(gt.min(0), gt.max(0), 5.0)
+    floor_numpy = float(np.sqrt(rm.nn_dist2_reference(points, gt, lo, hi, 5.0).astype(np.float64)).mean())
+    assert floor_numpy > 0.05                                                    # the numpy reference alone says so
+    pd = _dev(points)
+    m = hipops.SurfaceMetrics(_mesh_of(verts, faces))
+    m.evaluate(pd)
+    surface = m.summary()
+    r = hipops.ReconMetrics(_dev(gt), (gt.min(0).tolist(), gt.max(0).tolist()))
+    r.evaluate(pd)
+    sample = r.summary()
+    print(surface["accuracy_mean"], sample["accuracy_mean"], floor_numpy)
+    assert surface["accuracy_mean"] < 1e-4 and surface["thresholds"][0] == {"threshold": 0.05, "precision": 1.0}
+    assert sample["accuracy_mean"] > 0.05 and abs(sample["accuracy_mean"] - floor_numpy) < 1e-9
+
+
+# ---- the driver
+@pytest.fixture(scope="module")
+def dataset(tmp_path_factory):
+    from nextbestpath_amd.simulator.mesh import make_maze_scene
+    d = tmp_path_factory.mktemp("synth")
+    make_maze_scene(str(d / "maze_00"), seed=0, cells=8, size=4.8, height=1.2, tess=0.3)
+    return str(d)
+
+
+def _net():
+    from nextbestpath_amd.networks.nbp_model import NBP
+    from nextbestpath_amd.utility.synthetic import make_explorer_state_dict
+    net = NBP()
+    net.load_state_dict(make_explorer_state_dict(9))
+    return net.cuda().eval()
+
+
+def _small_params():
+    """The default parameters with a thin GT surface and a thin cloud, so that the numpy brute force over the rollout's whole cloud
+    and the mesh's 4 000 triangles takes seconds."""
+    from nextbestpath_amd.testers import nbp_planning as tp
+    params = tp.load_params(os.path.join(ROOT, "configs/macarons/macarons_default_training_config.json"))
+    params.n_gt_surface_points = 3000
+    params.gathering_factor = 0.001
+    return params
+
+
+OPTS = {"thresholds": [0.05, 0.5, 1.0], "cap": 4.0}
+STEPS = 3
+
+
+def _rollout(dataset, **options):
+    from nextbestpath_amd.simulator import scene as sc
+    from nextbestpath_amd.testers import nbp_planning as tp
+    params, ds, net = _small_params(), sc.SceneDataset(dataset), _net()
+    with torch.no_grad():
+        ro = tp.build_rollout(params, net, ds, tp.list_runs(ds, params)[0], torch.device("cuda"), seed=5, **options)
+        for _ in range(STEPS):
+            ro.step()
+        ro.finish()
+        res = tp._result(ro, STEPS)
+    n = int(ro.st.cloud_count.item())
+    return ro, res, ro.st.cloud[:n].cpu().numpy()
+
+
+def _assert_cloud_block(got, want):
+    assert set(got) == set(want) == {"n_points", "cap", "accuracy_mean", "accuracy_rmse", "thresholds"}
+    assert got["n_points"] == want["n_points"] and got["cap"] == want["cap"] and got["thresholds"] == want["thresholds"]
+    for key in ("accuracy_mean", "accuracy_rmse"):
+        assert abs(got[key] - want[key]) <= 1e-10 * abs(want[key]), (key, got[key], want[key])
+
+
+def test_rollout_option_off_and_on(hip, dataset, nbp_weights, monkeypatch):
+    from nextbestpath_amd import parallel_rollout as pr
+    from nextbestpath_amd.utility import hipops
+    built = []
+    real = hipops.MeshPlan
+    monkeypatch.setattr(hipops, "MeshPlan", lambda *a, **k: built.append(1) or real(*a, **k))
+    off_ro, off, off_cloud = _rollout(dataset)
+    assert not built and off_ro.surface is None and off_ro.surface_spec is None          # nothing is built: no plan
+    assert sorted(off) == ["V_cam_history", "X_cam_history", "coverage", "n_points", "scene", "start"]
+    on_ro, on, cloud = _rollout(dataset, surface_metrics=OPTS)
+    assert len(built) == 1 and sorted(set(on) - set(off)) == ["surface", "surface_raw"]
+    # the option is an observer: trajectory, coverage and cloud keep their bits
+    assert on["coverage"] == off["coverage"] and on["X_cam_history"] == off["X_cam_history"] and on["V_cam_history"] == off["V_cam_history"]
+    assert on["n_points"] == off["n_points"] == len(cloud) > 500 and np.array_equal(cloud.view(np.uint32), off_cloud.view(np.uint32))
+    block = on["surface"]
+    assert sorted(block) == ["cloud", "mesh", "options"] and block["options"] == {"thresholds": [0.05, 0.5, 1.0], "cap": 4.0, "cell": 1.0}
+    mesh = on_ro.mesh
+    want = sm.reference(cloud, mesh.verts_host, mesh.faces_host, OPTS["thresholds"], OPTS["cap"])
+    print(block["cloud"], want)
+    _assert_cloud_block(block["cloud"], want)
+    assert 0 < want["accuracy_mean"] < 0.5
+    lo, hi = sm.mesh_box(mesh.verts_host, OPTS["cap"])
+    used, entries = sm.plan_counts(mesh.verts_host, mesh.faces_host, lo, hi, 1.0)
+    assert block["mesh"] == {"faces": len(mesh.faces_host), "faces_used": used, "entries": entries}
+    json.dumps(block, allow_nan=False)
+    # what travels between ranks gives the same block
+    on["run_id"] = 0
+    assert pr.gather_surface([on], [(0, 0)], 0, 1, torch.device("cuda"), sm.option_spec(OPTS)) == {0: block}
+    # the public method works on a rollout built without the option, with the defaults, and leaves its record as it was
+    dflt = off_ro.surface_metrics()
+    assert len(built) == 2 and dflt["options"] == {"thresholds": [0.05, 0.1, 0.25, 0.5, 1.0], "cap": 5.0, "cell": 1.0}
+    assert dflt["cloud"]["n_points"] == len(off_cloud) and "fused" not in dflt and off_ro.surface is None
+
+
+def test_rollout_with_fusion_reports_the_fused_cloud_too(hip, dataset, nbp_weights, monkeypatch):
+    from nextbestpath_amd.utility import hipops
+    extracts = []
+    real = hipops.TSDFVolume.extract
+    monkeypatch.setattr(hipops.TSDFVolume, "extract", lambda self: extracts.append(1) or real(self))
+    ro, res, cloud = _rollout(dataset, surface_metrics=OPTS, fusion=True)
+    assert len(extracts) == 1                                                    # once per record, not once per metric
+    block = res["surface"]
+    assert sorted(block) == ["cloud", "fused", "mesh", "options"] and "fusion" in res
+    mesh = ro.mesh
+    _assert_cloud_block(block["cloud"], sm.reference(cloud, mesh.verts_host, mesh.faces_host, OPTS["thresholds"], OPTS["cap"]))
+    points, n = ro.fused_cloud()
+    assert n == block["fused"]["n_points"] == res["fusion"]["n_points"] > 100
+    _assert_cloud_block(block["fused"], sm.reference(points.cpu().numpy(), mesh.verts_host, mesh.faces_host, OPTS["thresholds"],
+                                                     OPTS["cap"]))
+    assert ro.surface_metrics() == block
+    json.dumps(block, allow_nan=False)
