@@ -489,7 +489,9 @@ int nbp_unproject_append_f32(const float* depth, const unsigned char* mask_or_nu
  * nearest face through each pixel centre (perspective-correct, faces clipped at z_clip), -1 where
  * no face.  Faces are binned in two levels (8x8-pixel tiles inside 64x64-pixel coarse tiles) into lists with room for
  * every face: no face is ever dropped (the reference renders with max_faces_per_bin = 500000,
- * macarons/testers/scene.py:440-446).  bin_cap and overflow_flag are kept for ABI compatibility and ignored. */
+ * macarons/testers/scene.py:440-446).  bin_cap and overflow_flag are kept for ABI compatibility and ignored.
+ * Every rasteriser entry point (zbuf, rgbz, zface, zface_batch) returns NBP_E_ARG for z_clip <= 0: depths are merged by atomicMin on
+ * their bit patterns, which orders positive floats only. */
 size_t nbp_raster_workspace_bytes(int n_faces, int n_frames, int H, int W, int bin_cap);
 int nbp_raster_zbuf_f32(const float* verts, int n_verts, const int* faces, int n_faces,
                         const float* cams12_host, int n_frames, int H, int W, float tan_half_fov,

@@ -1105,6 +1105,7 @@ static int raster_launch(const float* verts, int n_verts, const int* faces, int 
                          unsigned long long* zface_out = nullptr) {
     NBP_RETURN_IF(!verts || !faces || !cams12_host || !zbuf || !ws, NBP_E_ARG);
     NBP_RETURN_IF(n_verts < 3 || n_faces < 1 || n_frames < 1 || n_frames > MAX_CAMS || H < 1 || W < 1, NBP_E_ARG);
+    NBP_RETURN_IF(!(z_clip > 0.f), NBP_E_ARG);                           // atomicMin on the bit pattern orders positive depths only
     const int tiles_x = (int)nbp_cdiv(W, TILE), tiles_y = (int)nbp_cdiv(H, TILE);
     NBP_RETURN_IF(tiles_x > 256 || tiles_y > 256, NBP_E_SHAPE);          // fine-tile coordinates are packed in 8 bits
     NBP_RETURN_IF(ws_bytes < raster_ws_bytes(n_faces, n_frames, H, W, rgb != nullptr && !zface_out), NBP_E_WS);
@@ -1261,6 +1262,7 @@ extern "C" int nbp_raster_zface_batch_f32(int n, const float* const* verts, cons
     NBP_RETURN_IF(n < 1 || n > STEP_BATCH || !verts || !n_verts || !faces || !n_faces || !cams12_host || !zbuf || !zface || !ws || !ws_bytes,
                   NBP_E_ARG);
     NBP_RETURN_IF(n_frames < 1 || n_frames > 4 || H < 1 || W < 1, NBP_E_ARG);
+    NBP_RETURN_IF(!(z_clip > 0.f), NBP_E_ARG);                           // (as raster_launch)
     const int tiles_x = (int)nbp_cdiv(W, TILE), tiles_y = (int)nbp_cdiv(H, TILE);
     NBP_RETURN_IF(tiles_x > 256 || tiles_y > 256, NBP_E_SHAPE);
     hipStream_t st = (hipStream_t)stream;
