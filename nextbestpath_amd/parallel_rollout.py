@@ -2,11 +2,11 @@
 
 Each (scene, start pose) rollout is independent (next_best_path/testers/nbp_planning.py:414-467
 runs them in nested loops on one GPU), so rank r takes runs r, r+W, r+2W, ... and the only
-collective is ONE all_gather of a padded fp32 tensor [runs_per_rank, n_poses + 3] holding
-(run id, final coverage, AUC, coverage curve) -- a few KB over RCCL/xGMI, latency bound (with the
-planning option `recon_metrics` on, a second one of float64 sums and counts: gather_reconstruction; with its `curve`, a third of the
-per-step rows: gather_reconstruction_curve; with the option `view_metrics`, one of the per-view counts and sums: gather_views; with the option `fusion`, one of the fused cloud's sums and counts: gather_fusion; with the option `surface_metrics`, one of both
-clouds' sums and counts against the mesh: gather_surface).  One
+collectives are all_gathers of padded, fixed-width rows (run id first; pad rows = -1), a few KB over RCCL/xGMI, latency bound:
+ONE of an fp32 tensor [runs_per_rank, n_poses + 3] holding (run id, final coverage, AUC, coverage curve) -- gather_results -- and
+one of float64 sums and counts behind it for every record block that is on (testers/record_blocks.py; gather_reconstruction,
+gather_reconstruction_curve, gather_views, gather_fusion, gather_surface), from which rank 0 forms the ratios.  A block that is
+off causes no collective, so every other gather keeps its shape.  One
 process per GPU; backend "nccl" (= RCCL on ROCm) with CUDA tensors, "gloo" on CPU-only hosts
 (that path is what the world_size-2 CPU tests exercise)."""
 from __future__ import annotations
@@ -80,19 +80,23 @@ def pack_results(results, runs, n_poses, rows):
     return t
 
 
+def all_rows(local, world, device):
+    """The half that every gather shares: this rank's padded rows (a numpy array [rows, width]) -> all ranks' rows [world rows, width]
+    in rank order, through ONE all_gather on the collective's device where there is a process group (a 1-rank group still goes
+    through the backend); without one, the rows themselves.  The dtype travels as it is."""
+    if not (world > 1 or group_is_up()):
+        return local
+    import torch.distributed as dist
+    mine = torch.from_numpy(local).to(collective_device(device))
+    buf = [torch.empty_like(mine) for _ in range(world)]
+    dist.all_gather(buf, mine)
+    return torch.stack(buf).cpu().numpy().reshape(-1, local.shape[1])
+
+
 def gather_results(results, runs, rank, world, device, n_poses):
     """All ranks call this; every rank gets the list of {run_id, coverage, final, auc, scene, start}
     in run order (only the coverage metrics travel; pose histories stay in the per-rank results)."""
-    rows = runs_per_rank(len(runs), world)
-    collective = world > 1 or group_is_up()          # a 1-rank process group still goes through the backend
-    local = torch.from_numpy(pack_results(results, runs, n_poses, rows)).to(collective_device(device) if collective else device)
-    if collective:
-        import torch.distributed as dist
-        buf = [torch.empty_like(local) for _ in range(world)]
-        dist.all_gather(buf, local)
-        allt = torch.stack(buf).cpu().numpy().reshape(-1, n_poses + 3)
-    else:
-        allt = local.cpu().numpy()
+    allt = all_rows(pack_results(results, runs, n_poses, runs_per_rank(len(runs), world)), world, device)
     by_id = {int(r["run_id"]): r for r in results}
     out = []
     for row in allt:
@@ -106,134 +110,78 @@ def gather_results(results, runs, rank, world, device, n_poses):
     return out
 
 
-def gather_reconstruction(results, runs, rank, world, device, thresholds, cap):
-    """The planning option `recon_metrics`: all ranks call this behind gather_results.  The raw float64 sums and counts of every
-    run's reconstruction metrics (results[i]["reconstruction_raw"], utility/recon_metrics.py::pack_raw) travel in ONE all_gather
-    of a padded float64 tensor [runs_per_rank, 1 + 6 + 2 T] (run id first; pad rows = -1) -- a gather of its own, so that the
-    coverage gather keeps its shape with the option off.  Rank 0 forms the ratios from them -> {run id: metrics dict}; the other
-    ranks get {}."""
-    from .utility import recon_metrics
-    rows = runs_per_rank(len(runs), world)
-    width = 1 + recon_metrics.RAW_HEAD + 2 * len(thresholds)
+def pack_raw_rows(results, rows, raw_key, width, per=None):
+    """Local results -> padded float64 [rows, width]: the run id, then the run's raw numbers results[i][raw_key], which fill the row
+    exactly; with `per`, the run id, the number of `per`-wide records the run has, and those records, as many as fit or fewer.
+    Whatever is left, and every pad row, is -1.  Raw numbers that do not fit the width are a ValueError."""
+    head = 1 if per is None else 2
     t = np.full((rows, width), -1.0, np.float64)
     for j, r in enumerate(results):
+        raw = np.asarray(r[raw_key], np.float64).reshape(-1)
+        if raw.size > width - head or (raw.size != width - head if per is None else raw.size % per):
+            raise ValueError(f"{raw_key}: run {r['run_id']} has {raw.size} numbers, its row holds {width - head}"
+                             + ("" if per is None else f" in records of {per}"))
         t[j, 0] = r["run_id"]
-        t[j, 1:] = np.asarray(r["reconstruction_raw"], np.float64)
-    collective = world > 1 or group_is_up()
-    if collective:
-        import torch.distributed as dist
-        local = torch.from_numpy(t).to(collective_device(device))
-        buf = [torch.empty_like(local) for _ in range(world)]
-        dist.all_gather(buf, local)
-        t = torch.stack(buf).cpu().numpy().reshape(-1, width)
+        if per is not None:
+            t[j, 1] = raw.size // per
+        t[j, head:head + raw.size] = raw
+    return t
+
+
+def gather_raw(results, runs, rank, world, device, raw_key, width, summarise, per=None):
+    """The float64 gather of one record block: all ranks call it behind gather_results, and only when the block is on.  Every
+    run's raw sums and counts (results[i][raw_key]) travel in ONE all_gather of pack_raw_rows' tensor [runs_per_rank, width] -- a
+    gather of its own, so that the others keep their shapes with the block off.  Rank 0 forms the ratios from them -> {run id:
+    summarise(raw)}, raw as the run's vector (with `per`: as its records [n, per]); the other ranks get {}."""
+    t = all_rows(pack_raw_rows(results, runs_per_rank(len(runs), world), raw_key, width, per), world, device)
     if rank != 0:
         return {}
-    return {int(row[0]): recon_metrics.summarise_raw(row[1:], thresholds, cap) for row in t if row[0] >= 0}
+    if per is None:
+        return {int(row[0]): summarise(row[1:]) for row in t if row[0] >= 0}
+    return {int(row[0]): summarise(row[2:2 + int(row[1]) * per].reshape(int(row[1]), per)) for row in t if row[0] >= 0}
+
+
+def gather_reconstruction(results, runs, rank, world, device, thresholds, cap):
+    """The planning option `recon_metrics`: utility/recon_metrics.py::pack_raw's 6 + 2 T numbers per run -> {run id: summarise_raw's
+    dict}."""
+    from .utility import recon_metrics
+    width = 1 + recon_metrics.RAW_HEAD + 2 * len(thresholds)
+    return gather_raw(results, runs, rank, world, device, "reconstruction_raw", width,
+                      lambda raw: recon_metrics.summarise_raw(raw, thresholds, cap))
 
 
 def gather_reconstruction_curve(results, runs, rank, world, device, thresholds, cap, n_poses):
-    """The planning option `recon_metrics` with `curve`: all ranks call this behind gather_reconstruction.  The raw rows of every
-    run's per-step curve (results[i]["reconstruction_curve_raw"]: n_poses rows of pack_raw's 6 + 2 T numbers) travel in ONE
-    all_gather of a padded float64 tensor [runs_per_rank, 1 + n_poses (6 + 2 T)] (run id first; pad rows = -1) -- a gather of its
-    own: the other two keep their shapes with the curve off.  Rank 0 forms the ratios -> {run id: summarise_curve's dict}; the
-    other ranks get {}."""
+    """The planning option `recon_metrics` with `curve`: n_poses rows of pack_raw's 6 + 2 T numbers per run -> {run id:
+    summarise_curve's dict}."""
     from .utility import recon_metrics
-    rows = runs_per_rank(len(runs), world)
     per = recon_metrics.RAW_HEAD + 2 * len(thresholds)
-    width = 1 + n_poses * per
-    t = np.full((rows, width), -1.0, np.float64)
-    for j, r in enumerate(results):
-        t[j, 0] = r["run_id"]
-        t[j, 1:] = np.asarray(r["reconstruction_curve_raw"], np.float64).reshape(n_poses * per)
-    collective = world > 1 or group_is_up()
-    if collective:
-        import torch.distributed as dist
-        local = torch.from_numpy(t).to(collective_device(device))
-        buf = [torch.empty_like(local) for _ in range(world)]
-        dist.all_gather(buf, local)
-        t = torch.stack(buf).cpu().numpy().reshape(-1, width)
-    if rank != 0:
-        return {}
-    return {int(row[0]): recon_metrics.summarise_curve(row[1:].reshape(n_poses, per), thresholds, cap) for row in t if row[0] >= 0}
+    return gather_raw(results, runs, rank, world, device, "reconstruction_curve_raw", 1 + n_poses * per,
+                      lambda raw: recon_metrics.summarise_curve(raw.reshape(n_poses, per), thresholds, cap))
 
 
 def gather_fusion(results, runs, rank, world, device, thresholds, cap, options=None):
-    """The planning option `fusion`: all ranks call this behind gather_results, and only when the option is on.  The raw float64
-    numbers of every run's fused cloud (results[i]["fusion_raw"], utility/tsdf.py::pack_raw: the reconstruction metrics' sums and
-    counts, then observed_voxels, usable_voxels, frames) travel in ONE all_gather of a padded float64 tensor [runs_per_rank, 1 + 6
-    + 2 T + 3] (run id first; pad rows = -1) -- a gather of its own: the others keep their shapes with the option off.  Rank 0
-    forms the ratios with recon_metrics.summarise_raw (through tsdf.summarise_raw, which adds the counts and `options`) -> {run id:
-    the record's "fusion" block}; the other ranks get {}."""
+    """The planning option `fusion`: utility/tsdf.py::pack_raw's numbers per run (the reconstruction metrics' 6 + 2 T of the fused
+    cloud, then observed_voxels, usable_voxels, frames) -> {run id: tsdf.summarise_raw's dict, with `options`}."""
     from .utility import recon_metrics, tsdf
-    rows = runs_per_rank(len(runs), world)
     width = 1 + recon_metrics.RAW_HEAD + 2 * len(thresholds) + len(tsdf.RAW_TAIL)
-    t = np.full((rows, width), -1.0, np.float64)
-    for j, r in enumerate(results):
-        t[j, 0] = r["run_id"]
-        t[j, 1:] = np.asarray(r["fusion_raw"], np.float64)
-    collective = world > 1 or group_is_up()
-    if collective:
-        import torch.distributed as dist
-        local = torch.from_numpy(t).to(collective_device(device))
-        buf = [torch.empty_like(local) for _ in range(world)]
-        dist.all_gather(buf, local)
-        t = torch.stack(buf).cpu().numpy().reshape(-1, width)
-    if rank != 0:
-        return {}
-    return {int(row[0]): tsdf.summarise_raw(row[1:], thresholds, cap, options) for row in t if row[0] >= 0}
+    return gather_raw(results, runs, rank, world, device, "fusion_raw", width,
+                      lambda raw: tsdf.summarise_raw(raw, thresholds, cap, options))
 
 
 def gather_surface(results, runs, rank, world, device, spec):
-    """The planning option `surface_metrics`: all ranks call this behind gather_results, and only when the option is on.  The raw
-    float64 numbers of every run's cloud-to-mesh accuracy (results[i]["surface_raw"], utility/surface_metrics.py::pack_record: the
-    raw cloud's sums, size and counts, the fused cloud's, has_fused and the mesh's three counts) travel in ONE all_gather of a padded
-    float64 tensor [runs_per_rank, 1 + 2 (3 + T) + 4] (run id first; pad rows = -1) -- a gather of its own: the others keep their
-    shapes with the option off.  spec: the normalised options (surface_metrics.option_spec).  Rank 0 forms the ratios with
-    surface_metrics.summarise_record -> {run id: the record's "surface" block}; the other ranks get {}."""
+    """The planning option `surface_metrics`: utility/surface_metrics.py::pack_record's 2 (3 + T) + 4 numbers per run (the raw
+    cloud's, the fused cloud's, has_fused and the mesh's counts) -> {run id: summarise_record's dict}.  spec: the normalised options."""
     from .utility import surface_metrics
-    rows = runs_per_rank(len(runs), world)
     width = 1 + 2 * (surface_metrics.RAW_HEAD + len(spec["thresholds"])) + len(surface_metrics.RECORD_TAIL)
-    t = np.full((rows, width), -1.0, np.float64)
-    for j, r in enumerate(results):
-        t[j, 0] = r["run_id"]
-        t[j, 1:] = np.asarray(r["surface_raw"], np.float64)
-    collective = world > 1 or group_is_up()
-    if collective:
-        import torch.distributed as dist
-        local = torch.from_numpy(t).to(collective_device(device))
-        buf = [torch.empty_like(local) for _ in range(world)]
-        dist.all_gather(buf, local)
-        t = torch.stack(buf).cpu().numpy().reshape(-1, width)
-    if rank != 0:
-        return {}
-    return {int(row[0]): surface_metrics.summarise_record(row[1:], spec) for row in t if row[0] >= 0}
+    return gather_raw(results, runs, rank, world, device, "surface_raw", width,
+                      lambda raw: surface_metrics.summarise_record(raw, spec))
 
 
 def gather_views(results, runs, rank, world, device, options):
-    """The planning option `view_metrics`: all ranks call this behind gather_results, and only when the option is on.  The raw
-    float64 counts and sums of every run's held-out views (results[i]["views_raw"]: up to options["views"] rows of
-    utility/view_metrics.py::pack_raw's 9 numbers; a scene with fewer reachable poses has fewer) travel in ONE all_gather of a
-    padded float64 tensor [runs_per_rank, 2 + 9 views] (run id, number of views, rows; pad rows = -1) -- a gather of its own: the
-    others keep their shapes with the option off.  Rank 0 forms the ratios from them -> {run id: summarise_raw's dict with
-    `options` (view_metrics.resolved_options: the same for every run)}; the other ranks get {}."""
+    """The planning option `view_metrics`: up to options["views"] rows of utility/view_metrics.py::pack_raw's 9 numbers per run (a
+    scene with fewer reachable poses has fewer: the row carries the count behind the run id) -> {run id: summarise_raw's dict with
+    `options` (view_metrics.resolved_options: the same for every run)}.  More views than the option's are a ValueError."""
     from .utility import view_metrics
-    rows, per, n_max = runs_per_rank(len(runs), world), view_metrics.RAW_WIDTH, int(options["views"])
-    width = 2 + n_max * per
-    t = np.full((rows, width), -1.0, np.float64)
-    for j, r in enumerate(results):
-        raw = np.asarray(r["views_raw"], np.float64).reshape(-1, per)
-        if raw.shape[0] > n_max:
-            raise ValueError(f"gather_views: a run with {raw.shape[0]} views, above the option's {n_max}")
-        t[j, 0], t[j, 1] = r["run_id"], raw.shape[0]
-        t[j, 2:2 + raw.size] = raw.reshape(-1)
-    collective = world > 1 or group_is_up()
-    if collective:
-        import torch.distributed as dist
-        local = torch.from_numpy(t).to(collective_device(device))
-        buf = [torch.empty_like(local) for _ in range(world)]
-        dist.all_gather(buf, local)
-        t = torch.stack(buf).cpu().numpy().reshape(-1, width)
-    if rank != 0:
-        return {}
-    return {int(row[0]): view_metrics.summarise_raw(row[2:2 + int(row[1]) * per].reshape(int(row[1]), per), options)
-            for row in t if row[0] >= 0}
+    per = view_metrics.RAW_WIDTH
+    return gather_raw(results, runs, rank, world, device, "views_raw", 2 + int(options["views"]) * per,
+                      lambda raw: view_metrics.summarise_raw(raw, options), per=per)

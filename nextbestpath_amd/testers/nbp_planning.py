@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from .. import parallel_rollout
 from ..networks.nbp_model import NBP
 from ..simulator import lockstep
 from ..simulator import scene as sim_scene
@@ -38,6 +39,7 @@ from ..utility import tsdf as fusion_options
 from ..utility import utils as hu
 from ..utility import view_metrics as view_options
 from ..utility.long_term_utils import LatticePlanner, compute_auc
+from . import record_blocks
 
 # Rollout.step: the step's forward on a stream of its own, behind the map stage by an event.  The reference runs the network at
 # every step and reads its output only when it replans (nbp_planning.py:166 / :252): a step that does not replan goes on to the move
@@ -106,14 +108,13 @@ class Rollout(lockstep.LockstepRollout):
             self.recon = hipops.ReconMetrics(self.gt, self.bbox, **kw)
             if self.recon_spec.get("curve"):    # ... with `curve`: the same metrics after every step, updated incrementally (pre)
                 self.recon_curve = hipops.ReconCurve(self.gt, self.bbox, **kw, plan=self.recon.plan)
-        self._recon_default = None
+        self._defaults = {}                 # metrics objects built for a direct call on a rollout without the option (_metrics)
         # the planning option `view_metrics` (None = off: nothing is built or launched; True; a dict of utility/view_metrics.py): the
         # coloured cloud rendered from held-out lattice poses against the mesh, once, at the rollout's end
         self.view_spec = view_options.option_spec(view_metrics)
         # where the rollout starts: the root of the held-out poses
         self._start_ijk = None if camera.cam_idx is None else tuple(int(v) for v in camera.cam_idx[:3])
         self.views = self._build_views(self.view_spec) if self.view_spec is not None else None
-        self._views_default = None
         # the planning option `fusion` (None = off: nothing is allocated, launched, gathered or written; True; a dict of
         # utility/tsdf.py): every frame the rollout un-projects also goes into a TSDF volume over the GT bounds, an observer like
         # recon_metrics -- nothing of the step reads it -- whose fused surface cloud is judged once, at the rollout's end
@@ -126,7 +127,6 @@ class Rollout(lockstep.LockstepRollout):
         # mesh's triangle grid is built here (one read-back of its size)
         self.surface_spec = surface_options.option_spec(surface_metrics)
         self.surface = None if self.surface_spec is None else hipops.SurfaceMetrics(mesh, **self.surface_spec)
-        self._surface_default = None
         self.path, self.path_record = [], 0
         self.collision_list, self.passable_list, self.idx_history = [], [], []
         self.step_seed = seed * 1_000_003
@@ -267,6 +267,25 @@ class Rollout(lockstep.LockstepRollout):
         state waits in its constructor, so a loop over step() that never calls finish() is safe as well."""
         self._wait_forwards()
 
+    def _metrics(self, name):
+        """The rollout's own metrics object `name` ("recon", "views", "surface"), or, where it was built with that option off, one
+        with the option's defaults: made at the first call and kept apart from self.<name>, so that the rollout keeps reporting the
+        option as off."""
+        build = {"recon": lambda: hipops.ReconMetrics(self.gt, self.bbox, **recon_options.option_spec(True)),
+                 "views": lambda: self._build_views(view_options.option_spec(True)),
+                 "surface": lambda: hipops.SurfaceMetrics(self.mesh, **surface_options.option_spec(True))}
+        if getattr(self, name) is None and name not in self._defaults:
+            self._defaults[name] = build[name]()
+        return getattr(self, name) or self._defaults[name]
+
+    def _counted(self, fused):
+        """(points, n) of fused_cloud() -> (points, n as a device count) for the metrics' kernels, which take a buffer of at least
+        one row: an empty cloud goes as one dummy row, and the count says that none is valid."""
+        points, n = fused
+        if n == 0:
+            points = torch.zeros(1, 3, dtype=torch.float32, device=self.device)
+        return points, torch.full((1,), n, dtype=torch.int64, device=self.device)
+
     def reconstruction_metrics(self, raw=False):
         """Reconstruction quality of the WHOLE cloud so far (no sub-sampling) against the GT surface: the dict of
         utility/recon_metrics.py::summarise (accuracy, completeness, Chamfer distance, precision / recall / F-score per threshold),
@@ -274,9 +293,7 @@ class Rollout(lockstep.LockstepRollout):
         device (hipops.ReconMetrics: both nearest-neighbour directions and their summaries, no host synchronisation), read back
         with one copy.  With the rollout's own `recon_metrics` option, or the defaults where it was built without one."""
         self.finish()
-        rec = self.recon or self._recon_default
-        if rec is None:             # (kept apart from self.recon: a rollout built with the option off keeps reporting as such)
-            rec = self._recon_default = hipops.ReconMetrics(self.gt, self.bbox, **recon_options.option_spec(True))
+        rec = self._metrics("recon")
         rec.evaluate(self.st.cloud, self.st.cloud_count)
         return rec.raw() if raw else rec.summary()
 
@@ -300,9 +317,7 @@ class Rollout(lockstep.LockstepRollout):
         (hipops.ViewMetrics: splat and statistics, no host synchronisation), read back with one copy.  With the rollout's own
         `view_metrics` option, or the defaults where it was built without one."""
         self.finish()
-        vm = self.views or self._views_default
-        if vm is None:              # (kept apart from self.views: a rollout built with the option off keeps reporting as such)
-            vm = self._views_default = self._build_views(view_options.option_spec(True))
+        vm = self._metrics("views")
         rgb = self.st.cloud_rgb if self.camera.renders_colours else None
         vm.evaluate(self.st.cloud, rgb, self.st.cloud_count)
         return vm.raw() if raw else vm.summary(vm.options)
@@ -321,13 +336,9 @@ class Rollout(lockstep.LockstepRollout):
         dict -- recon_metrics.summarise's entries (n_points = the fused points) with observed_voxels, usable_voxels, frames and the
         volume's options -- or with raw=True the float64 vector behind it (tsdf.pack_raw: what travels between ranks).  `fused`:
         what fused_cloud() returned, where the caller has extracted it already."""
-        points, n = self.fused_cloud() if fused is None else fused
-        rec = self.recon or self._recon_default
-        if rec is None:
-            rec = self._recon_default = hipops.ReconMetrics(self.gt, self.bbox, **recon_options.option_spec(True))
-        if n == 0:                  # (the metrics' kernels take a buffer of at least one row; the device count says none is valid)
-            points = torch.zeros(1, 3, dtype=torch.float32, device=self.device)
-        rec.evaluate(points, torch.full((1,), n, dtype=torch.int64, device=self.device))
+        fused = self.fused_cloud() if fused is None else fused
+        rec = self._metrics("recon")
+        rec.evaluate(*self._counted(fused))
         st = self.fusion.stats()
         row = fusion_options.pack_raw(rec.raw(), st["observed_voxels"], st["usable_voxels"], self.fusion.frames)
         return row if raw else fusion_options.summarise_raw(row, rec.thresholds, rec.cap, self.fusion.options)
@@ -341,16 +352,11 @@ class Rollout(lockstep.LockstepRollout):
         fused_cloud() returned, where the caller has extracted it already.  With the rollout's own `surface_metrics` option, or the
         defaults where it was built without one."""
         self.finish()
-        sm = self.surface or self._surface_default
-        if sm is None:              # (kept apart from self.surface: a rollout built with the option off keeps reporting as such)
-            sm = self._surface_default = hipops.SurfaceMetrics(self.mesh, **surface_options.option_spec(True))
+        sm = self._metrics("surface")
         sm.evaluate(self.st.cloud, self.st.cloud_count)
         cloud_raw, fused_raw = sm.raw(), None
         if self.fusion is not None:
-            points, n = self.fused_cloud() if fused is None else fused
-            if n == 0:              # (the kernels take a buffer of at least one row; the device count says none is valid)
-                points = torch.zeros(1, 3, dtype=torch.float32, device=self.device)
-            sm.evaluate(points, torch.full((1,), n, dtype=torch.int64, device=self.device))
+            sm.evaluate(*self._counted(self.fused_cloud() if fused is None else fused))
             fused_raw = sm.raw()
         row = surface_options.pack_record(cloud_raw, fused_raw, sm.mesh_block())
         return row if raw else surface_options.summarise_record(row, {"thresholds": sm.thresholds, "cap": sm.cap, "cell": sm.cell})
@@ -658,12 +664,24 @@ def list_runs(dataset, params):
     return runs
 
 
-def build_rollout(params, nbp, dataset, run, device, test_resolution=0.05, state=None, seed=0, grid=256, recon_metrics=None,
-                  depth_noise=None, view_metrics=None, depth_filter=None, fusion=None, surface_metrics=None):
-    """Scene + GT surface + camera + Rollout for one (scene, start pose) run (nbp_planning.py:414-492).  `depth_noise`: the camera's
-    sensor model (utility/depth_noise.py; None = off, perfect depth).  `depth_filter`: the camera's frame filter behind it
-    (utility/depth_filter.py; None = off).  `fusion`: the rollout's TSDF volume (utility/tsdf.py; None = off).  `surface_metrics`: the
-    cloud's accuracy against the mesh (utility/surface_metrics.py; None = off)."""
+# the options of a test run that build_rollout / run_one / run_many take by keyword (None = off): the camera's, and the rollout's observers
+CAMERA_OPTIONS = ("depth_noise", "depth_filter")
+OBSERVER_OPTIONS = tuple(dict.fromkeys(block.option for block in record_blocks.BLOCKS))
+
+
+def _known_options(who, options):
+    """A name among `options` that is neither the camera's nor an observer's is a TypeError, as an unknown keyword is."""
+    unknown = sorted(set(options) - set(CAMERA_OPTIONS + OBSERVER_OPTIONS))
+    if unknown:
+        raise TypeError(f"{who}() got an unexpected keyword argument {unknown[0]!r}")
+
+
+def build_rollout(params, nbp, dataset, run, device, test_resolution=0.05, state=None, seed=0, grid=256, **options):
+    """Scene + GT surface + camera + Rollout for one (scene, start pose) run (nbp_planning.py:414-492).  `options` (each None = off):
+    the camera's `depth_noise` (the sensor model, utility/depth_noise.py) and `depth_filter` (the frame filter behind it,
+    utility/depth_filter.py), and the rollout's observers `recon_metrics`, `view_metrics`, `fusion`, `surface_metrics`
+    (Rollout.__init__)."""
+    _known_options("build_rollout", options)
     si, k = run
     sd = dataset[si]
     settings = sim_scene.Settings(sd["settings"], params.scene_scale_factor)
@@ -671,10 +689,10 @@ def build_rollout(params, nbp, dataset, run, device, test_resolution=0.05, state
                                 params.scene_scale_factor, device)
     y_bins = sim_scene.y_bins_for(mesh.verts_host, 4)
     _, gt_dev = sim_scene.setup_gt_scene(params, settings, mesh, device, test_resolution, seed=seed)
-    camera = setup_test_camera(params, mesh, settings.camera.start_positions[k], settings, device, seed=seed, depth_noise=depth_noise,
-                               depth_filter=depth_filter)
-    ro = Rollout(params, nbp, camera, gt_dev, mesh, mesh, y_bins, device, state, seed, grid, recon_metrics=recon_metrics,
-                 view_metrics=view_metrics, fusion=fusion, surface_metrics=surface_metrics)
+    camera = setup_test_camera(params, mesh, settings.camera.start_positions[k], settings, device, seed=seed,
+                               **{key: value for key, value in options.items() if key in CAMERA_OPTIONS})
+    ro = Rollout(params, nbp, camera, gt_dev, mesh, mesh, y_bins, device, state, seed, grid,
+                 **{key: value for key, value in options.items() if key in OBSERVER_OPTIONS})
     ro.scene_name, ro.start = sd["scene_name"], k
     return ro
 
@@ -728,31 +746,21 @@ def _result(ro, n_poses):
            "X_cam_history": ro.camera.X_cam_history.tolist(), "V_cam_history": ro.camera.V_cam_history.tolist(),
            "n_points": int(ro.st.cloud_count.item())}
     # the options `policy`, `depth_noise`, `depth_filter` that are on: the normalised specs the rollout was steered and its frames made with
-    res.update(run_tags(ro.nbp.options if _wants_maps(ro.nbp) else None, ro.camera.depth_noise, ro.camera.depth_filter))
-    if ro.recon is not None:        # the option `recon_metrics`: the whole cloud once, at the rollout's end
-        raw = ro.reconstruction_metrics(raw=True)
-        res["reconstruction"] = recon_options.summarise_raw(raw, ro.recon.thresholds, ro.recon.cap)
-        res["reconstruction_raw"] = raw.tolist()       # the sums and counts behind the ratios (parallel_rollout.gather_reconstruction)
-        if ro.recon_curve is not None:                 # ... with `curve`: the same metrics per step (gather_reconstruction_curve)
-            rows = ro.reconstruction_curve(n_poses, raw=True)
-            res["reconstruction_curve"] = recon_options.summarise_curve(rows, ro.recon.thresholds, ro.recon.cap)
-            res["reconstruction_curve_raw"] = rows.tolist()
-    if ro.views is not None:        # the option `view_metrics`: the whole coloured cloud from the held-out poses, once, at the end
-        raw = ro.view_metrics(raw=True)
-        res["views"] = view_options.summarise_raw(raw, ro.views.options)
-        res["views_raw"] = raw.tolist()                # the counts and sums behind the ratios (parallel_rollout.gather_views)
-    fused = None                    # the fused cloud is extracted once per record, whichever metrics judge it
-    if ro.fusion is not None:       # the option `fusion`: the TSDF volume's surface cloud by the reconstruction metrics, once, at the end
-        fused = ro.fused_cloud() if ro.surface is not None else None
-        raw = ro.fusion_metrics(raw=True, fused=fused)
-        rec = ro.recon or ro._recon_default
-        res["fusion"] = fusion_options.summarise_raw(raw, rec.thresholds, rec.cap, ro.fusion.options)
-        res["fusion_raw"] = raw.tolist()               # the sums and counts behind the ratios (parallel_rollout.gather_fusion)
-    if ro.surface is not None:      # the option `surface_metrics`: the whole cloud (and the fused one) against the GT mesh, once, at the end
-        raw = ro.surface_metrics(raw=True, fused=fused)
-        res["surface"] = surface_options.summarise_record(raw, ro.surface_spec)
-        res["surface_raw"] = raw.tolist()              # the sums and counts behind the ratios (parallel_rollout.gather_surface)
-    return res
+    tags = run_tags(ro.nbp.options if _wants_maps(ro.nbp) else None, ro.camera.depth_noise, ro.camera.depth_filter)
+    # the blocks of the observers that are on (record_blocks.BLOCKS), each measured once, at the rollout's end: the block, and the raw
+    # sums and counts behind its ratios (what parallel_rollout's gathers carry); formed with what the rollout was made with.
+    # `made` / `size` stand where collect_records has opts / params: a field that a Block.context of record_blocks.py starts
+    # to read belongs here too (tests/test_record_blocks_host.py runs every context on both, on the CPU)
+    made = SimpleNamespace(recon_metrics=ro.recon_spec, view_metrics=ro.view_spec, fusion=ro.fusion_spec, surface_metrics=ro.surface_spec)
+    size = SimpleNamespace(image_height=ro.camera.image_height, image_width=ro.camera.image_width, zfar=ro.params.zfar,
+                           sensor_range=ro.params.sensor_range)
+    fused = None if ro.fusion is None else ro.fused_cloud()      # extracted once per record, however many blocks judge it
+
+    def entries(block):
+        raw = block.measure(ro, n_poses, fused)
+        return {block.key: block.summarise(raw, *block.context(made, size, n_poses)), block.key + "_raw": raw.tolist()}
+
+    return record_blocks.fill(res, record_blocks.blocks_on(made), entries, tags)
 
 
 def _policy_or(nbp, policy):
@@ -764,11 +772,10 @@ def _policy_or(nbp, policy):
     return make_policy(policy) or nbp
 
 
-def run_one(params, nbp, dataset, run, device, test_resolution=0.05, state=None, n_poses=N_POSES, seed=0, *, recon_metrics=None,
-            depth_noise=None, view_metrics=None, policy=None, depth_filter=None, fusion=None, surface_metrics=None):
+def run_one(params, nbp, dataset, run, device, test_resolution=0.05, state=None, n_poses=N_POSES, seed=0, *, policy=None, **options):
+    """`policy`: None = the network `nbp` (_policy_or); `options`: build_rollout's."""
+    _known_options("run_one", options)
     nbp = _policy_or(nbp, policy)
-    options = dict(recon_metrics=recon_metrics, depth_noise=depth_noise, view_metrics=view_metrics, depth_filter=depth_filter,
-                   fusion=fusion, surface_metrics=surface_metrics)
     ro = build_rollout(params, nbp, dataset, run, device, test_resolution, state, seed, **options)
     nbp.eval()
     for _ in range(n_poses):
@@ -778,15 +785,13 @@ def run_one(params, nbp, dataset, run, device, test_resolution=0.05, state=None,
 
 
 def run_many(params, nbp, dataset, runs, device, seeds, test_resolution=0.05, n_poses=N_POSES, rollouts_per_gpu=48,
-             grid=256, timing=None, *, recon_metrics=None, depth_noise=None, view_metrics=None, policy=None, depth_filter=None,
-             fusion=None, surface_metrics=None):
+             grid=256, timing=None, *, policy=None, **options):
     """Runs `runs` in lock-step groups of `rollouts_per_gpu` (MultiRollout); same results as run_one each.  `timing` (a dict)
-    receives the wall-clock seconds of scene / GT-surface / camera setup and of the stepping (device-synchronised).  `policy`: as
-    in run_one (None = the network `nbp`)."""
+    receives the wall-clock seconds of scene / GT-surface / camera setup and of the stepping (device-synchronised).  `policy` and
+    `options`: as in run_one."""
     import time
     out = []
-    options = dict(recon_metrics=recon_metrics, depth_noise=depth_noise, view_metrics=view_metrics, depth_filter=depth_filter,
-                   fusion=fusion, surface_metrics=surface_metrics)
+    _known_options("run_many", options)
     nbp = _policy_or(nbp, policy)
     nbp.eval()
     for g0 in range(0, len(runs), rollouts_per_gpu):
@@ -810,39 +815,64 @@ def run_many(params, nbp, dataset, runs, device, seeds, test_resolution=0.05, n_
     return out
 
 
+def collect_records(results, runs, mine, rank, world, device, opts, params, n_poses, scene_names):
+    """The tail of a test run, behind run_many: all ranks call this with their own `results` (of the runs `mine` = shard(runs, rank,
+    world), in that order) and the options record `opts` (resolve_options).  The coverage curves travel in gather_results, and the raw
+    float64 numbers of every block that is on (record_blocks.BLOCKS) in a gather of their own each.  -> (gathered, out): every rank's
+    list of gather_results, on rank 0 with each block formed from the gathered row in place of the locally formed one, on the other
+    ranks without the blocks; and the dict that goes into the result JSON {scene name: {start: record}} (`scene_names`: by scene
+    index), None off rank 0."""
+    for run, res in zip(mine, results):
+        res["run_id"] = runs.index(run)
+    gathered = parallel_rollout.gather_results(results, runs, rank, world, device, n_poses)
+    blocks = record_blocks.blocks_on(opts)
+    for block in blocks:
+        ctx = block.context(opts, params, n_poses)              # (from opts, params and n_poses alone: the same on every rank)
+        if block.check is not None:
+            for res in results:
+                block.check(res, *ctx)
+        formed = getattr(parallel_rollout, block.gather)(results, runs, rank, world, device, *ctx)      # {} off rank 0
+        for r in gathered:
+            r.pop(block.key, None)
+            r.pop(block.key + "_raw", None)
+            if rank == 0:
+                r[block.key] = formed[r["run_id"]]
+    if rank != 0:
+        return gathered, None
+    out = {}
+    tags = run_tags(opts.policy_spec, opts.depth_noise, opts.depth_filter)
+    for r in gathered:
+        si, k = runs[r["run_id"]]
+        rec = record_blocks.fill({"coverage": r["coverage"], "auc": r["auc"]}, blocks, lambda block: {block.key: r[block.key]},
+                                 {key: dict(spec) for key, spec in tags.items()})
+        for key in ("X_cam_history", "V_cam_history"):          # histories of other ranks stay in their part files
+            if key in r:
+                rec[key] = r[key]
+        out.setdefault(scene_names[si], {})[str(k)] = rec
+    return gathered, out
+
+
 def test_nbp_planning(params_file, model_file, results_json_file, numGPU, test_scenes, test_resolution=0.05,
                       use_perfect_depth_map=False, compute_collision=False, load_json=False, dataset_path=None,
                       nbp_weights=None, configs_dir=None, results_dir=None, n_poses=N_POSES, seed=8, torch_seed=9,
-                      rollouts_per_gpu=48, grid_size=256, nbp_precision=None, symmetry_ensemble=_UNSET, recon_metrics=_UNSET,
-                      depth_noise=_UNSET, view_metrics=_UNSET, policy=_UNSET, depth_filter=_UNSET, fusion=_UNSET,
-                      surface_metrics=_UNSET):
+                      rollouts_per_gpu=48, grid_size=256, nbp_precision=None, **options):
     """Same arguments as the reference (nbp_planning.py:364-374); `grid_size` / `nbp_precision` select
-    BASELINE.json configs[4] (512 grid at the same 0.3125 units per pixel, bf16 convolutions).  `symmetry_ensemble` (None = off, a
-    name of utility/augment.py::ENSEMBLES or a list of op codes) is NBP.symmetry_ensemble of the loaded network; not given, it is
-    the key of that name in the configs/test/ file load_params read last (absent there: off).  `recon_metrics` (None = off, True =
-    the defaults, or a dict with thresholds / cap / cell / curve; not given, the key of that name in the same file) adds the reconstruction
-    quality of every rollout's final cloud (utility/recon_metrics.py) to its record, next to coverage and auc, and with `curve` the same
-    metrics after every step ("reconstruction_curve": lists over the steps, with their AUCs).  `depth_noise` (None =
-    off: perfect depth; a dict of utility/depth_noise.py::option_spec; not given, the key of that name in the same file) puts the seeded
-    sensor model between the rasteriser and every consumer of depth, and the normalised spec into every record.  `depth_filter` (None =
-    off; a dict of utility/depth_filter.py::option_spec; not given, the key of that name in the same file) puts the frame filter (gated
-    median, speckle rejection, hole filling) behind the sensor, and its normalised spec into every record.  `view_metrics` (None =
-    off, True = the defaults, or a dict of utility/view_metrics.py::option_spec; not given, the key of that name in the same file) adds
-    the held-out view metrics of every rollout's final coloured cloud ("views": the cloud rendered from lattice poses against the mesh,
-    with the options used) to its record.  `policy` (None or "nbp" = the network; "frontier" / "infogain" or a dict of
-    utility/frontier.py / infogain.py::option_spec; not given, the key of that name in the same file) puts that policy where the network
-    stands: no weights are loaded (`nbp_precision` given with it draws a warning), and every record gains "policy", the normalised options.
-    `fusion` (None = off, True = the defaults, or a dict of utility/tsdf.py::option_spec; not given, the key of that name in the same
-    file) integrates every frame a rollout un-projects into a TSDF volume and adds "fusion" to its record: the fused surface cloud
-    by the reconstruction metrics (with `recon_metrics`' options, or its defaults), the voxel counts and the options.
-    `surface_metrics` (None = off, True = the defaults, or a dict with thresholds / cap / cell of utility/surface_metrics.py::option_spec;
-    not given, the key of that name in the same file) adds "surface" to every record: the accuracy of the whole cloud, and with `fusion`
-    of the fused cloud, against the surface of the GT mesh itself (exact point-to-triangle distances).  Under torchrun the flattened
-    (scene, start pose) runs are sharded round-robin over the ranks and the coverage curves are
-    gathered with ONE all_gather over RCCL (backend "nccl" on ROCm; "gloo" on CPU-only hosts)."""
+    BASELINE.json configs[4] (512 grid at the same 0.3125 units per pixel, bf16 convolutions).  `options`: the planning options
+    (resolve_options; an unknown name is a TypeError).  Each is None = off, or what its option_spec takes; not given, it is the key of
+    that name in the configs/test/ file load_params read last (absent there: off):
+      `policy`             frontier_policy.make_policy (utility/frontier.py / infogain.py::option_spec): stands where the network does, "policy" in every record
+      `symmetry_ensemble`  utility/augment.py::ENSEMBLES (a name, or a list of op codes): NBP.symmetry_ensemble of the loaded network
+      `recon_metrics`      utility/recon_metrics.py::option_spec: "reconstruction", and with `curve` "reconstruction_curve", in every record
+      `depth_noise`        utility/depth_noise.py::option_spec: the seeded sensor model behind the rasteriser, its spec in every record
+      `depth_filter`       utility/depth_filter.py::option_spec: the frame filter behind the sensor, its spec in every record
+      `view_metrics`       utility/view_metrics.py::option_spec: "views" in every record
+      `fusion`             utility/tsdf.py::option_spec: a TSDF volume of every frame, "fusion" in every record (judged with `recon_metrics`' options, or its defaults)
+      `surface_metrics`    utility/surface_metrics.py::option_spec: "surface" in every record
+    With a policy no weights are loaded (`nbp_precision` given with it draws a warning).  Under torchrun the flattened (scene, start
+    pose) runs are sharded round-robin over the ranks; the coverage curves are gathered with ONE all_gather over RCCL (backend
+    "nccl" on ROCm; "gloo" on CPU-only hosts), and each record block that is on with one more (collect_records)."""
     import time
-    from ..parallel_rollout import (gather_fusion, gather_reconstruction, gather_reconstruction_curve, gather_results, gather_surface,
-                                     gather_views, init_distributed, shard)
+    from ..parallel_rollout import init_distributed, shard
     t_start = time.perf_counter()
     here = os.path.dirname(os.path.abspath(__file__))
     configs_dir = configs_dir or os.path.join(here, "../../configs/macarons")
@@ -853,9 +883,8 @@ def test_nbp_planning(params_file, model_file, results_json_file, numGPU, test_s
     device = torch.device("cuda", local_rank if world > 1 else numGPU)
     torch.cuda.set_device(device)
     random.seed(seed); np.random.seed(seed); torch.manual_seed(torch_seed)
-    opts = resolve_options(policy=policy, symmetry_ensemble=symmetry_ensemble, recon_metrics=recon_metrics, depth_noise=depth_noise,
-                           depth_filter=depth_filter, view_metrics=view_metrics, fusion=fusion, surface_metrics=surface_metrics)
-    nbp, policy_spec, recon_spec, view_spec = opts.policy, opts.policy_spec, opts.recon_metrics, opts.view_metrics
+    opts = resolve_options(**options)
+    nbp, policy_spec = opts.policy, opts.policy_spec
     assert nbp_precision in (None, "fp32", "fp32_split", "bf16"), nbp_precision
     if nbp is not None and nbp_precision is not None:
         import warnings
@@ -881,69 +910,10 @@ def test_nbp_planning(params_file, model_file, results_json_file, numGPU, test_s
     with torch.no_grad():
         results = run_many(params, nbp, dataset, mine, device, [seed + 1000 * r[0] + r[1] for r in mine],
                            test_resolution, n_poses, rollouts_per_gpu, grid_size, timing=timing, **opts.rollout)
-    for run, res in zip(mine, results):
-        res["run_id"] = runs.index(run)
     t_gather = time.perf_counter()
-    gathered = gather_results(results, runs, rank, world, device, n_poses)
-    if recon_spec is not None:      # a second, float64 gather of the raw sums and counts; the ratios are formed on rank 0
-        recon = gather_reconstruction(results, runs, rank, world, device, recon_spec["thresholds"], recon_spec["cap"])
-        for r in gathered:
-            r.pop("reconstruction_raw", None)
-            if rank == 0:
-                r["reconstruction"] = recon[r["run_id"]]
-        if recon_spec.get("curve"):                    # a third gather: the per-step rows
-            curves = gather_reconstruction_curve(results, runs, rank, world, device, recon_spec["thresholds"], recon_spec["cap"], n_poses)
-            for r in gathered:
-                r.pop("reconstruction_curve_raw", None)
-                if rank == 0:
-                    r["reconstruction_curve"] = curves[r["run_id"]]
-    if view_spec is not None:       # a float64 gather of its own: the raw counts and sums per view; the ratios are formed on rank 0
-        view_opts = view_options.resolved_options(view_spec, params.image_height, params.image_width, params.zfar)
-        for res in results:         # the gathered records all carry these: every rollout of this rank was evaluated with them
-            if res["views"]["options"] != view_opts:
-                raise RuntimeError(f"view_metrics: run {res['run_id']} was evaluated with {res['views']['options']}, not {view_opts}")
-        views = gather_views(results, runs, rank, world, device, view_opts)
-        for r in gathered:
-            r.pop("views", None)
-            r.pop("views_raw", None)
-            if rank == 0:
-                r["views"] = views[r["run_id"]]
-    if opts.fusion is not None:     # a float64 gather of its own: the fused cloud's raw sums and counts; the ratios are formed on rank 0
-        fusion_opts = fusion_options.resolved_options(opts.fusion, params.sensor_range)
-        fusion_recon = recon_spec or recon_options.option_spec(True)
-        fused = gather_fusion(results, runs, rank, world, device, fusion_recon["thresholds"], fusion_recon["cap"], fusion_opts)
-        for r in gathered:
-            r.pop("fusion", None)
-            r.pop("fusion_raw", None)
-            if rank == 0:
-                r["fusion"] = fused[r["run_id"]]
-    if opts.surface_metrics is not None:    # a float64 gather of its own: both clouds' raw sums and counts; the ratios are formed on rank 0
-        surface = gather_surface(results, runs, rank, world, device, opts.surface_metrics)
-        for r in gathered:
-            r.pop("surface", None)
-            r.pop("surface_raw", None)
-            if rank == 0:
-                r["surface"] = surface[r["run_id"]]
+    gathered, out = collect_records(results, runs, mine, rank, world, device, opts, params, n_poses,
+                                    [dataset[si]["scene_name"] for si in range(len(dataset))])
     if rank == 0:
-        out = {}
-        for r in gathered:
-            si, k = runs[r["run_id"]]
-            rec = {"coverage": r["coverage"], "auc": r["auc"]}
-            if recon_spec is not None:
-                rec["reconstruction"] = r["reconstruction"]
-                if recon_spec.get("curve"):
-                    rec["reconstruction_curve"] = r["reconstruction_curve"]
-            rec.update(run_tags(policy_spec, opts.depth_noise, opts.depth_filter))
-            if view_spec is not None:
-                rec["views"] = r["views"]
-            if opts.fusion is not None:
-                rec["fusion"] = r["fusion"]
-            if opts.surface_metrics is not None:
-                rec["surface"] = r["surface"]
-            for key in ("X_cam_history", "V_cam_history"):      # histories of other ranks stay in their part files
-                if key in r:
-                    rec[key] = r[key]
-            out.setdefault(dataset[si]["scene_name"], {})[str(k)] = rec
         os.makedirs(results_dir, exist_ok=True)
         with open(os.path.join(results_dir, results_json_file), "w") as fh:
             json.dump(out, fh)

@@ -312,10 +312,17 @@ def test_option_reaches_every_driver():
     cfg = json.load(open(os.path.join(ROOT, "configs/nbp/nbp_default_training_config.json")))["_nbp"]
     assert "collect_depth_filter" in cfg and cfg["collect_depth_filter"] is None
     assert 'depth_filter=getattr(params, "collect_depth_filter", None)' in inspect.getsource(train_nbp_model)
-    for fn in (nu.trajectory_collection, Camera.__init__, lockstep.setup_test_camera, tp.build_rollout, tp.run_one, tp.run_many,
-               rw.test_random_walk_planning):
+    for fn in (nu.trajectory_collection, Camera.__init__, lockstep.setup_test_camera, rw.test_random_walk_planning):
         assert inspect.signature(fn).parameters["depth_filter"].default is None, fn
-    assert inspect.signature(tp.test_nbp_planning).parameters["depth_filter"].default is tp._UNSET
+    # the planning drivers take their options as **options, checked against the known names: the camera's are handed to the camera
+    for fn in (tp.build_rollout, tp.run_one, tp.run_many, tp.test_nbp_planning):
+        assert inspect.signature(fn).parameters["options"].kind is inspect.Parameter.VAR_KEYWORD, fn
+    assert "depth_filter" in tp.CAMERA_OPTIONS and "depth_filter" in tp._test_config
+    spec = {"range_base": 0.5}
+    assert tp._known_options("run_one", {"depth_filter": spec}) is None
+    for fn in (tp.build_rollout, tp.run_one, tp.run_many):
+        with pytest.raises(TypeError, match="depth_blur"):        # (before anything is built: the other arguments are never read)
+            fn(*[None] * 6, depth_filter=spec, depth_blur={})
     assert inspect.signature(Camera.frames_batch).parameters["raw"].default is False
     assert callable(hipops.depth_filter) and callable(hipops.depth_filter_batch) and callable(Camera.filter_item)
 
