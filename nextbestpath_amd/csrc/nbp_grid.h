@@ -1,12 +1,25 @@
-// nbp_grid.h -- uniform point grid shared by the coverage metric (nbp_planner.hip) and the scene store
-// (nbp_scene.hip): cell lookup and the chip-wide exclusive scan of per-cell counts.  Included inside each
-// translation unit (everything is in an anonymous namespace); not part of the C ABI.
+// nbp_grid.h -- uniform point grid shared by the coverage metric (nbp_planner.hip), the scene store (nbp_scene.hip) and the
+// shell-walk grids (nbp_nn_grid.h): cell lookup, the chip-wide exclusive scan of per-cell counts and two host helpers.  Included
+// inside each translation unit (everything is in an anonymous namespace); not part of the C ABI.
 #pragma once
 #include "common.h"
+
+#include <math.h>
 
 namespace {
 
 struct Grid { float lo[3]; float inv; int n[3]; };
+
+// (host) a carved buffer's size, rounded up to the 256-byte alignment of the next one
+size_t al256(size_t b) { return (b + 255) / 256 * 256; }
+
+// (host) Largest float x with sqrtf(x) < thr (thr > 0 finite): the squared-distance form of `distance < thr`.
+float sq_below(float thr) {
+    float x = thr * thr;
+    while (sqrtf(x) >= thr) x = nextafterf(x, 0.f);
+    while (sqrtf(nextafterf(x, INFINITY)) < thr) x = nextafterf(x, INFINITY);
+    return x;
+}
 
 __device__ __forceinline__ int grid_cell(const Grid& g, float x, float y, float z, int* ijk) {
     int i = (int)floorf((x - g.lo[0]) * g.inv), j = (int)floorf((y - g.lo[1]) * g.inv), k = (int)floorf((z - g.lo[2]) * g.inv);

@@ -1,6 +1,7 @@
-// nbp_nn_grid.h -- the host side of the shell-walk grids: the grid over a caller's box and the argument checks that the
-// nearest-neighbour plan (nbp_recon.hip) and the triangle plan (nbp_surface.hip) share, so that both walk the SAME cells and the
-// early exit's proof (nbp_recon.hip's header) covers both.  Included inside each translation unit; not part of the C ABI.
+// nbp_nn_grid.h -- the host side of the shell-walk grids: the grid over a caller's box, the argument checks and the carving of a
+// plan and of its build scratch that the nearest-neighbour plan (nbp_recon.hip) and the triangle plan (nbp_surface.hip) share, so
+// that both walk the SAME cells and the early exit's proof (nbp_shell_walk.h's header, beside the walk) covers both.  Included
+// inside each translation unit; not part of the C ABI.
 #pragma once
 #include "nbp_grid.h"
 
@@ -9,33 +10,54 @@
 
 namespace {
 
-constexpr int NN_MAX_AXIS = 2048;                // cells per axis for which the early exit is proven (nbp_recon.hip's header)
+constexpr int NN_MAX_AXIS = 2048;                // cells per axis for which the early exit is proven (nbp_shell_walk.h's header)
 
 struct Box { float hi[3]; };
-
-static size_t al256(size_t b) { return (b + 255) / 256 * 256; }
-
-// The grid over the caller's box [lo, hi]: cells 1.001 w wide (inv), one cell on an axis with hi == lo.
-int nn_grid(const float* lo, const float* hi, float w, Grid* g, Box* bx, size_t* ncell) {
-    size_t n = 1;
-    for (int a = 0; a < 3; ++a) {
-        g->lo[a] = lo[a];
-        bx->hi[a] = hi[a];
-        const double ext = (double)hi[a] - (double)lo[a];
-        if (!(ext >= 0) || !(ext / (double)w < (double)NN_MAX_AXIS * 65536.0)) return ext >= 0 ? NBP_E_SHAPE : NBP_E_ARG;
-        const long long na = (long long)(ext / (double)w) + 1;
-        if (na > NN_MAX_AXIS) return NBP_E_SHAPE;
-        g->n[a] = (int)na;
-        n *= (size_t)na;
-    }
-    g->inv = (float)(1.0 / ((double)w * 1.001));
-    if (n > (size_t)1 << 28) return NBP_E_SHAPE;
-    *ncell = n;
-    return 0;
-}
+struct BoxGrid { Grid g; Box bx; size_t ncell; };
 
 bool nn_args_ok(const float* lo, const float* hi, float w) { return lo && hi && w > 0 && isfinite(w); }
 // cap > 0 and at most 2^24 cells: the shell index and the cell coordinates stay inside int and exact in float
 bool nn_cap_ok(float cap, float w) { return cap > 0 && isfinite(cap) && (double)cap / (double)w <= 16777216.0; }
+// a count of points, triangles or vertices that indexes as an int
+bool nn_count_ok(long long n) { return n >= 0 && n <= 0x7fffffffll; }
+
+// The checked grid of an entry point over the caller's box [lo, hi]: cells 1.001 w wide (inv), one cell on an axis with hi == lo.
+// NBP_E_ARG unless nn_args_ok, then NBP_E_ARG or NBP_E_SHAPE by the extents.  The entry's other NBP_E_ARG checks stand before it,
+// its NBP_E_WS checks after it.
+int nn_grid(const float* lo, const float* hi, float w, BoxGrid* b) {
+    if (!nn_args_ok(lo, hi, w)) return NBP_E_ARG;
+    size_t n = 1;
+    for (int a = 0; a < 3; ++a) {
+        b->g.lo[a] = lo[a];
+        b->bx.hi[a] = hi[a];
+        const double ext = (double)hi[a] - (double)lo[a];
+        if (!(ext >= 0) || !(ext / (double)w < (double)NN_MAX_AXIS * 65536.0)) return ext >= 0 ? NBP_E_SHAPE : NBP_E_ARG;
+        const long long na = (long long)(ext / (double)w) + 1;
+        if (na > NN_MAX_AXIS) return NBP_E_SHAPE;
+        b->g.n[a] = (int)na;
+        n *= (size_t)na;
+    }
+    b->g.inv = (float)(1.0 / ((double)w * 1.001));
+    if (n > (size_t)1 << 28) return NBP_E_SHAPE;
+    b->ncell = n;
+    return 0;
+}
+
+// A plan: `start` [ncell + 1], then the payload (sorted points, or triangles' vertices) as float4.
+void nn_plan_carve(const void* plan, size_t ncell, int** start, float4** payload) {
+    char* p = (char*)(((uintptr_t)plan + 255) / 256 * 256);
+    *start = (int*)p; p += al256((ncell + 1) * 4);
+    *payload = (float4*)p;
+}
+size_t nn_plan_size(size_t ncell, size_t payload_bytes) { return 256 + al256((ncell + 1) * 4) + al256(payload_bytes); }
+
+// A build's scratch: the per-cell counts and the scan's tile sums; returns what follows them (the caller's own tail).
+char* nn_scratch_carve(void* ws, size_t ncell, int** count, int** tsum) {
+    char* p = (char*)(((uintptr_t)ws + 255) / 256 * 256);
+    *count = (int*)p; p += al256(ncell * 4);
+    *tsum = (int*)p; p += al256((ncell / SCAN_TILE + 1) * 4);
+    return p;
+}
+size_t nn_scratch_bytes(size_t ncell) { return 256 + al256(ncell * 4) + al256((ncell / SCAN_TILE + 1) * 4); }
 
 }  // namespace

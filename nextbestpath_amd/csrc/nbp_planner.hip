@@ -415,8 +415,6 @@ static int coverage_grid(const float* bbox_lo, const float* bbox_hi, float thr, 
     return 0;
 }
 
-static size_t al256(size_t b) { return (b + 255) / 256 * 256; }
-
 // the grid of a coverage PLAN: cells of thr / PLAN_R (coverage_mark_body), over the GT box grown by thr
 static int coverage_plan_grid(const float* bbox_lo, const float* bbox_hi, float thr, Grid* g, size_t* ncell) {
     size_t n = 1;
@@ -480,14 +478,6 @@ extern "C" int nbp_coverage_count_f32(const float* gt3, int G, const float* pc3,
 }
 
 // ---- planned coverage (one GT grid per rollout)
-// Largest float x with sqrtf(x) < thr (thr > 0 finite): the squared-distance form of `distance < thr`.
-static float sq_below(float thr) {
-    float x = thr * thr;
-    while (sqrtf(x) >= thr) x = nextafterf(x, 0.f);
-    while (sqrtf(nextafterf(x, INFINITY)) < thr) x = nextafterf(x, INFINITY);
-    return x;
-}
-
 static void plan_carve(void* plan, size_t ncell, int G, int** start, float4** sorted, unsigned** stamp) {
     char* p = (char*)(((uintptr_t)plan + 255) / 256 * 256);
     *start = (int*)p; p += al256((ncell + 1) * 4);

@@ -3,22 +3,10 @@
 // record is nextbestpath_amd/utility/recon_metrics.py).  Not in the reference.
 //
 // Nearest neighbour.  The targets inside the caller's box are counting-sorted into a uniform grid (bin, grid_exclusive_scan,
-// scatter to float4 -- the coverage plan's three steps).  One launch over the queries follows: NN_LANES lanes per query walk the
-// shells of cells at Chebyshev cell distance r = 0, 1, ..., R = ceil(cap / w) around the query's UNCLAMPED cell.  k is the fastest
-// cell index, so the z cells of an (x, y) column are one contiguous run of the sorted array: a column on the rim of the shell's
-// square is one run over its 2 r + 1 cells (two loads of `start`), a column inside the square contributes its two end cells.
-//
-// Why the walk may stop after shell r once best <= fl(r w)^2, and after shell R whatever it found.  Cells are 1.001 w wide.  A
-// target in a cell that shells 0..r do not hold differs from the query's cell by at least r + 1 on some axis, so their cell
-// coordinates u = fl(fl(x - lo) inv) differ by more than r there.  u carries a relative error below 2^-23, i.e. below n 2^-23
-// cells on an axis of n cells; with n <= NN_MAX_AXIS = 2048 (more is NBP_E_SHAPE) the two errors together stay below 0.0005 cells
-// (plus r 2^-23 for a query r cells outside the grid), so for r >= 1 the real separation on that axis exceeds (r - 0.0005) 1.001 w
-// > r w by a margin of 4e-4 relative, which dwarfs the 2^-24 roundings of e = fl(t - q), fl(e e) and fl(r w).  Rounding is
-// monotone, so the pair's fp32 squared distance
-// ((ex ex + ey ey) + ez ez) >= fl(e e) > fl(r w)^2 >= best: it cannot lower the minimum.  (r = 0: best <= 0 is a minimum already.)
-// After shell R every unvisited target is farther than R w >= cap: its squared distance exceeds cap2.  So the result is the
-// brute-force minimum over all in-box targets, bit for bit, and -- a minimum being blind to the order of its operands -- the
-// atomicAdd slot order inside a cell does not show: two runs give the same bits.  No atomics touch the output.
+// scatter to float4 -- the coverage plan's three steps).  One launch over the queries follows: nbp_shell_walk.h's walk over the
+// shells of cells around the query's unclamped cell, NN_LANES lanes per query, a run of cells being a run of the sorted array.  Its
+// header proves that the result is the brute-force minimum over all in-box targets, bit for bit; and -- a minimum being blind to
+// the order of its operands -- the atomicAdd slot order inside a cell does not show: two runs give the same bits.
 //
 // Summary (nbp_recon_stats_f64): a fixed launch geometry; every thread adds its strided elements in index order in float64, a
 // fixed tree adds the threads of a block (shuffles inside a wave, the four waves in order), each block STORES one row, and a
@@ -27,16 +15,16 @@
 // Per-step curve (nbp_recon_curve_update_batch_f32).  The cloud is append-only and the GT fixed, so both directions
 // are incremental: a point's distance to the GT never changes (it is queried once, in the step that appends it), and the minimum
 // over a union is the minimum of the minima (a running per-GT-point minimum d2_gt is lowered by the new points only).  One walk
-// per new point serves both: its NN_LANES lanes visit EVERY GT cell within Chebyshev distance R of its unclamped cell (the early
-// exit above does not apply: the scatter needs every target within reach), each (x, y) column one contiguous run.  The lanes keep
-// the point's own minimum (its accuracy distance), and a visited GT point with d < d2_gt[g] is lowered by an INTEGER atomicMin on
+// per new point serves both: its NN_LANES lanes visit EVERY GT cell within Chebyshev distance R of its unclamped cell (the shell
+// walk's early exit does not apply: the scatter needs every target within reach), each (x, y) column one contiguous run.  The lanes
+// keep the point's own minimum (its accuracy distance), and a visited GT point with d < d2_gt[g] is lowered by an INTEGER atomicMin on
 // the bit pattern: non-negative finite floats order like their bits and a minimum is blind to arrival order, so d2_gt is exact and
 // two runs give the same bits.  The plain read that filters the atomic may be stale (another XCD's L2): values only decrease, so
-// a stale read costs a redundant atomic, never a missed one.  What the walk leaves out is farther than R w >= cap (the argument
-// above with r = R).  The slot -> GT index map is the fourth component of the plan's float4 (its bits; the query never reads it).
+// a stale read costs a redundant atomic, never a missed one.  What the walk leaves out is farther than R w >= cap (the walk's
+// argument with r = R).  The slot -> GT index map is the fourth component of the plan's float4 (its bits; the query never reads it).
 // The summaries follow in two launches of the stats geometry above: d2_gt in full, the step's own distances into the running
 // float64 totals by one thread.  The watermark `seen` moves in the last launch only (the first two read it).
-#include "nbp_nn_grid.h"
+#include "nbp_shell_walk.h"
 
 #pragma clang fp contract(off)
 
@@ -53,13 +41,11 @@ constexpr int STATS_ROW = 2 + STATS_MAX_T;       // 8-byte words of a block's ro
 __global__ __launch_bounds__(256) void nn_bin_kernel(const float* __restrict__ t, const long long* __restrict__ n_dev, long long n_host,
                                                      Grid g, Box bx, int* __restrict__ cell_of, int* __restrict__ slot_of,
                                                      int* __restrict__ count) {
-    long long n = n_dev ? *n_dev : n_host;
-    n = n < 0 ? 0 : (n > n_host ? n_host : n);                       // rows at or beyond the device count are never read
+    const long long n = dev_count(n_dev, n_host);
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
         const float x = t[3 * i], y = t[3 * i + 1], z = t[3 * i + 2];
-        const bool in = x >= g.lo[0] && x <= bx.hi[0] && y >= g.lo[1] && y <= bx.hi[1] && z >= g.lo[2] && z <= bx.hi[2];   // a NaN is outside
         int c = -1;
-        if (in) {
+        if (in_box(g, bx, x, y, z)) {
             c = grid_cell(g, x, y, z, nullptr);
             slot_of[i] = atomicAdd(&count[c], 1);
         }
@@ -71,110 +57,43 @@ __global__ __launch_bounds__(256) void nn_scatter_kernel(const float* __restrict
                                                          long long n_host, const int* __restrict__ cell_of,
                                                          const int* __restrict__ slot_of, const int* __restrict__ start,
                                                          float4* __restrict__ sorted) {
-    long long n = n_dev ? *n_dev : n_host;
-    n = n < 0 ? 0 : (n > n_host ? n_host : n);
+    const long long n = dev_count(n_dev, n_host);
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
         const int c = cell_of[i];
         if (c >= 0) sorted[start[c] + slot_of[i]] = make_float4(t[3 * i], t[3 * i + 1], t[3 * i + 2], __int_as_float((int)i));   // .w: the target's index (curve walk)
     }
 }
 
-// ---- query
-__device__ __forceinline__ float nn_run(const float4* __restrict__ sorted, int p, int hi, float x, float y, float z, float best) {
-    for (; p + NN_UNROLL <= hi; p += NN_UNROLL) {
-        float4 t[NN_UNROLL];
-#pragma unroll
-        for (int u = 0; u < NN_UNROLL; ++u) t[u] = sorted[p + u];
-#pragma unroll
-        for (int u = 0; u < NN_UNROLL; ++u) {
-            const float ex = t[u].x - x, ey = t[u].y - y, ez = t[u].z - z;
-            const float d = (ex * ex + ey * ey) + ez * ez;
-            best = d < best ? d : best;
-        }
+// ---- query: the shell walk over cells of sorted points
+struct NNPoints {
+    static constexpr int LANES = NN_LANES;
+    const float4* __restrict__ sorted;
+    __device__ __forceinline__ float run(int p, int hi, float x, float y, float z, float best) const {
+        return point_run<NN_UNROLL>(sorted, p, hi, x, y, z, best, [](const float4&, float d, float b) { return d < b ? d : b; });
     }
-    for (; p < hi; ++p) {
-        const float4 t = sorted[p];
-        const float ex = t.x - x, ey = t.y - y, ez = t.z - z;
-        const float d = (ex * ex + ey * ey) + ez * ez;
-        best = d < best ? d : best;
-    }
-    return best;
-}
-
-__global__ __launch_bounds__(256) void nn_query_kernel(const float* __restrict__ q, const long long* __restrict__ n_dev, long long n_host,
-                                                       Grid g, int R, float w, float cap2, const float4* __restrict__ sorted,
-                                                       const int* __restrict__ start, float* __restrict__ d2) {
-    long long Q = n_dev ? *n_dev : n_host;
-    Q = Q < 0 ? 0 : (Q > n_host ? n_host : Q);
-    const int sub = threadIdx.x % NN_LANES;
-    const int n0 = g.n[0], n1 = g.n[1], n2 = g.n[2];
-    for (long long j = ((long long)blockIdx.x * blockDim.x + threadIdx.x) / NN_LANES; j < Q;
-         j += ((long long)gridDim.x * blockDim.x) / NN_LANES) {
-        const float x = q[3 * j], y = q[3 * j + 1], z = q[3 * j + 2];
-        // the unclamped cell, clamped as a FLOAT to one cell beyond the reach of R before the conversion (a query 1e6 away, or a
-        // NaN, must not reach the int conversion's undefined range)
-        float fi = floorf((x - g.lo[0]) * g.inv), fj = floorf((y - g.lo[1]) * g.inv), fk = floorf((z - g.lo[2]) * g.inv);
-        const bool reach = fi >= (float)-R && fi <= (float)(n0 - 1 + R) && fj >= (float)-R && fj <= (float)(n1 - 1 + R) &&
-                           fk >= (float)-R && fk <= (float)(n2 - 1 + R);
-        float best = cap2;
-        if (reach) {                                               // (uniform over the query's lanes)
-            const int ci = (int)fi, cj = (int)fj, ck = (int)fk;
-            // shells closer than the grid hold no cell: a query outside starts at its Chebyshev cell distance to the grid (<= R)
-            const int r0 = max(max(max(-ci, ci - (n0 - 1)), max(-cj, cj - (n1 - 1))), max(max(-ck, ck - (n2 - 1)), 0));
-            for (int r = r0; r <= R; ++r) {
-                // the shell's square of columns, cut to the grid
-                const int a0 = max(ci - r, 0), a1 = min(ci + r, n0 - 1), b0 = max(cj - r, 0), b1 = min(cj + r, n1 - 1);
-                const int na = a1 - a0 + 1, nb = b1 - b0 + 1;
-                if (na > 0 && nb > 0) {
-                    const int zl = ck - r, zh = ck + r;
-                    for (int it = sub; it < na * nb; it += NN_LANES) {
-                        const int a = a0 + it / nb, b = b0 + it % nb;
-                        const int base = (a * n1 + b) * n2;
-                        if (a == ci - r || a == ci + r || b == cj - r || b == cj + r) {      // rim: the column's whole run
-                            const int z0 = max(zl, 0), z1 = min(zh, n2 - 1);
-                            if (z0 <= z1) best = nn_run(sorted, start[base + z0], start[base + z1 + 1], x, y, z, best);
-                        } else {                                                             // inside: the two end cells
-                            if (zl >= 0 && zl < n2) best = nn_run(sorted, start[base + zl], start[base + zl + 1], x, y, z, best);
-                            if (zh >= 0 && zh < n2) best = nn_run(sorted, start[base + zh], start[base + zh + 1], x, y, z, best);
-                        }
-                    }
-                }
-#pragma unroll
-                for (int o = NN_LANES / 2; o; o >>= 1) {
-                    const float other = __shfl_xor(best, o);
-                    best = other < best ? other : best;
-                }
-                const float rw = (float)r * w;
-                if (best <= rw * rw) break;
-                // every cell of the grid has been visited
-                if (ci - r <= 0 && ci + r >= n0 - 1 && cj - r <= 0 && cj + r >= n1 - 1 && ck - r <= 0 && ck + r >= n2 - 1) break;
-            }
-        }
-        if (sub == 0) d2[j] = best;
-    }
-}
+};
 
 // ---- summary
 struct StatsThresholds { float v[STATS_MAX_T]; };
 
+// One block of the fixed geometry: row = the block's two float64 sums and its T counts (the counts beyond T: 0).  Every thread adds
+// its strided elements in index order, a fixed tree adds the threads (shuffles inside a wave, the four waves in order).  The
+// counts are independent of one another and of the sums: a larger T moves no bit of the rest.
 template <int T>
-__global__ __launch_bounds__(STATS_THREADS) void stats_partial_kernel(const float* __restrict__ d2, const long long* __restrict__ n_dev,
-                                                                     long long n_host, StatsThresholds th,
-                                                                     unsigned long long* __restrict__ rows) {
+__device__ __forceinline__ void stats_block(const float* __restrict__ d2, long long n, const float* th, int block,
+                                            unsigned long long* __restrict__ row) {
     __shared__ double ws1[STATS_WAVES], ws2[STATS_WAVES];
     __shared__ long long wc[STATS_WAVES][STATS_MAX_T];
-    long long n = n_dev ? *n_dev : n_host;
-    n = n < 0 ? 0 : (n > n_host ? n_host : n);
     double s1 = 0.0, s2 = 0.0;
     long long c[T];
 #pragma unroll
     for (int t = 0; t < T; ++t) c[t] = 0;
-    for (long long i = (long long)blockIdx.x * STATS_THREADS + threadIdx.x; i < n; i += (long long)STATS_BLOCKS * STATS_THREADS) {
+    for (long long i = (long long)block * STATS_THREADS + threadIdx.x; i < n; i += (long long)STATS_BLOCKS * STATS_THREADS) {
         const float v = d2[i];
         s1 += sqrt((double)v);
         s2 += (double)v;
 #pragma unroll
-        for (int t = 0; t < T; ++t) c[t] += v <= th.v[t] ? 1 : 0;
+        for (int t = 0; t < T; ++t) c[t] += v <= th[t] ? 1 : 0;
     }
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) {
@@ -194,7 +113,6 @@ __global__ __launch_bounds__(STATS_THREADS) void stats_partial_kernel(const floa
     if (threadIdx.x == 0) {
         double r1 = ws1[0], r2 = ws2[0];
         for (int k = 1; k < STATS_WAVES; ++k) { r1 += ws1[k]; r2 += ws2[k]; }
-        unsigned long long* row = rows + (size_t)blockIdx.x * STATS_ROW;
         row[0] = (unsigned long long)__double_as_longlong(r1);
         row[1] = (unsigned long long)__double_as_longlong(r2);
         for (int t = 0; t < STATS_MAX_T; ++t) {
@@ -206,18 +124,30 @@ __global__ __launch_bounds__(STATS_THREADS) void stats_partial_kernel(const floa
     }
 }
 
-__global__ __launch_bounds__(64) void stats_final_kernel(const unsigned long long* __restrict__ rows, int T, double* __restrict__ sums,
-                                                         long long* __restrict__ counts) {
-    const int col = threadIdx.x;
+// Column col of the STATS_BLOCKS rows, added in index order: a float64 sum's bits (col < 2) or a count.
+__device__ __forceinline__ unsigned long long stats_fold(const unsigned long long* __restrict__ rows, int col) {
     if (col < 2) {
         double s = 0.0;
         for (int b = 0; b < STATS_BLOCKS; ++b) s += __longlong_as_double((long long)rows[(size_t)b * STATS_ROW + col]);
-        sums[col] = s;
-    } else if (col < 2 + T) {
-        long long s = 0;
-        for (int b = 0; b < STATS_BLOCKS; ++b) s += (long long)rows[(size_t)b * STATS_ROW + col];
-        counts[col - 2] = s;
+        return (unsigned long long)__double_as_longlong(s);
     }
+    long long s = 0;
+    for (int b = 0; b < STATS_BLOCKS; ++b) s += (long long)rows[(size_t)b * STATS_ROW + col];
+    return (unsigned long long)s;
+}
+
+template <int T>
+__global__ __launch_bounds__(STATS_THREADS) void stats_partial_kernel(const float* __restrict__ d2, const long long* __restrict__ n_dev,
+                                                                     long long n_host, StatsThresholds th,
+                                                                     unsigned long long* __restrict__ rows) {
+    stats_block<T>(d2, dev_count(n_dev, n_host), th.v, blockIdx.x, rows + (size_t)blockIdx.x * STATS_ROW);
+}
+
+__global__ __launch_bounds__(64) void stats_final_kernel(const unsigned long long* __restrict__ rows, int T, double* __restrict__ sums,
+                                                         long long* __restrict__ counts) {
+    const int col = threadIdx.x;
+    if (col < 2) sums[col] = __longlong_as_double((long long)stats_fold(rows, col));
+    else if (col < 2 + T) counts[col - 2] = (long long)stats_fold(rows, col);
 }
 
 template <int T>
@@ -232,7 +162,7 @@ constexpr int CURVE_TOTALS = 2 + STATS_MAX_T;    // 8-byte words of an item's ru
 
 struct CurveItem {
     Grid g;
-    float hi[3];
+    Box bx;
     int R;
     float cap2;
     int T, G;
@@ -261,30 +191,6 @@ __device__ __forceinline__ void curve_range(const CurveItem& a, long long* s, lo
     *e = seen >= end ? seen : end;
 }
 
-__device__ __forceinline__ float curve_point(unsigned* __restrict__ d2_gt, const float4 t, float x, float y, float z, bool scatter,
-                                             float best) {
-    const float ex = t.x - x, ey = t.y - y, ez = t.z - z;
-    const float d = (ex * ex + ey * ey) + ez * ez;
-    if (scatter) {
-        const int gi = __float_as_int(t.w);
-        if (d < __uint_as_float(d2_gt[gi])) atomicMin(&d2_gt[gi], __float_as_uint(d));
-    }
-    return d < best ? d : best;
-}
-
-__device__ __forceinline__ float curve_run(const float4* __restrict__ sorted, unsigned* __restrict__ d2_gt, int p, int hi, float x,
-                                           float y, float z, bool scatter, float best) {
-    for (; p + NN_UNROLL <= hi; p += NN_UNROLL) {
-        float4 t[NN_UNROLL];
-#pragma unroll
-        for (int u = 0; u < NN_UNROLL; ++u) t[u] = sorted[p + u];
-#pragma unroll
-        for (int u = 0; u < NN_UNROLL; ++u) best = curve_point(d2_gt, t[u], x, y, z, scatter, best);
-    }
-    for (; p < hi; ++p) best = curve_point(d2_gt, sorted[p], x, y, z, scatter, best);
-    return best;
-}
-
 __global__ __launch_bounds__(256) void curve_walk_kernel(const CurveBatch b) {
     const CurveItem& a = b.it[blockIdx.y];
     if (blockIdx.x >= a.gx_walk) return;
@@ -292,79 +198,35 @@ __global__ __launch_bounds__(256) void curve_walk_kernel(const CurveBatch b) {
     curve_range(a, &s, &e);
     const int sub = threadIdx.x % NN_LANES;
     const int n0 = a.g.n[0], n1 = a.g.n[1], n2 = a.g.n[2], R = a.R;
+    unsigned* __restrict__ d2_gt = a.d2_gt;
     for (long long j = s + ((long long)blockIdx.x * blockDim.x + threadIdx.x) / NN_LANES; j < e;
          j += ((long long)a.gx_walk * blockDim.x) / NN_LANES) {
         const float x = a.cloud[3 * j], y = a.cloud[3 * j + 1], z = a.cloud[3 * j + 2];
-        // as a target the point counts inside the box only (nn_bin_kernel's test: a NaN is outside) ...
-        const bool in = x >= a.g.lo[0] && x <= a.hi[0] && y >= a.g.lo[1] && y <= a.hi[1] && z >= a.g.lo[2] && z <= a.hi[2];
-        // ... as a query wherever its cell is within reach of the grid (nn_query_kernel's test; a far or NaN point: cap2, no access)
-        const float fi = floorf((x - a.g.lo[0]) * a.g.inv), fj = floorf((y - a.g.lo[1]) * a.g.inv), fk = floorf((z - a.g.lo[2]) * a.g.inv);
-        const bool reach = fi >= (float)-R && fi <= (float)(n0 - 1 + R) && fj >= (float)-R && fj <= (float)(n1 - 1 + R) &&
-                           fk >= (float)-R && fk <= (float)(n2 - 1 + R);
+        // as a target the point counts inside the box only, as a query wherever its cell is within reach of the grid (a far or NaN
+        // point: cap2, no access)
+        const bool scatter = in_box(a.g, a.bx, x, y, z);
         float best = a.cap2;
-        if (reach) {                                               // (uniform over the point's lanes)
-            const int ci = (int)fi, cj = (int)fj, ck = (int)fk;
-            const int a0 = max(ci - R, 0), a1 = min(ci + R, n0 - 1), b0 = max(cj - R, 0), b1 = min(cj + R, n1 - 1);
-            const int z0 = max(ck - R, 0), z1 = min(ck + R, n2 - 1);
+        int c[3];
+        if (cell_in_reach(a.g, R, x, y, z, c)) {                   // (uniform over the point's lanes)
+            const int a0 = max(c[0] - R, 0), a1 = min(c[0] + R, n0 - 1), b0 = max(c[1] - R, 0), b1 = min(c[1] + R, n1 - 1);
+            const int z0 = max(c[2] - R, 0), z1 = min(c[2] + R, n2 - 1);
             const int na = a1 - a0 + 1, nb = b1 - b0 + 1;
             if (na > 0 && nb > 0 && z0 <= z1) {
                 for (int it = sub; it < na * nb; it += NN_LANES) {
                     const int base = ((a0 + it / nb) * n1 + (b0 + it % nb)) * n2;
-                    best = curve_run(a.sorted, a.d2_gt, a.start[base + z0], a.start[base + z1 + 1], x, y, z, in, best);
+                    best = point_run<NN_UNROLL>(a.sorted, a.start[base + z0], a.start[base + z1 + 1], x, y, z, best,
+                                                [=](const float4& t, float d, float m) {
+                                                    if (scatter) {
+                                                        const int gi = __float_as_int(t.w);
+                                                        if (d < __uint_as_float(d2_gt[gi])) atomicMin(&d2_gt[gi], __float_as_uint(d));
+                                                    }
+                                                    return d < m ? d : m;
+                                                });
                 }
             }
-#pragma unroll
-            for (int o = NN_LANES / 2; o; o >>= 1) {
-                const float other = __shfl_xor(best, o);
-                best = other < best ? other : best;
-            }
+            best = lanes_min<NN_LANES>(best);
         }
         if (sub == 0) a.d2_new[j - s] = best;
-    }
-}
-
-// stats_partial_kernel's arithmetic for one block of the fixed geometry (same strides, same order, same tree: the same bits), with
-// the number of thresholds at run time (entries of th beyond T repeat th[0]; their counts are not read).
-__device__ __forceinline__ void curve_block_stats(const float* __restrict__ d2, long long n, const float* th, int block,
-                                                  unsigned long long* __restrict__ row) {
-    __shared__ double ws1[STATS_WAVES], ws2[STATS_WAVES];
-    __shared__ long long wc[STATS_WAVES][STATS_MAX_T];
-    double s1 = 0.0, s2 = 0.0;
-    long long c[STATS_MAX_T];
-#pragma unroll
-    for (int t = 0; t < STATS_MAX_T; ++t) c[t] = 0;
-    for (long long i = (long long)block * STATS_THREADS + threadIdx.x; i < n; i += (long long)STATS_BLOCKS * STATS_THREADS) {
-        const float v = d2[i];
-        s1 += sqrt((double)v);
-        s2 += (double)v;
-#pragma unroll
-        for (int t = 0; t < STATS_MAX_T; ++t) c[t] += v <= th[t] ? 1 : 0;
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        s1 += __shfl_down(s1, off, 64);
-        s2 += __shfl_down(s2, off, 64);
-#pragma unroll
-        for (int t = 0; t < STATS_MAX_T; ++t) c[t] += __shfl_down(c[t], off, 64);
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-        ws1[wave] = s1;
-        ws2[wave] = s2;
-#pragma unroll
-        for (int t = 0; t < STATS_MAX_T; ++t) wc[wave][t] = c[t];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double r1 = ws1[0], r2 = ws2[0];
-        for (int k = 1; k < STATS_WAVES; ++k) { r1 += ws1[k]; r2 += ws2[k]; }
-        row[0] = (unsigned long long)__double_as_longlong(r1);
-        row[1] = (unsigned long long)__double_as_longlong(r2);
-        for (int t = 0; t < STATS_MAX_T; ++t) {
-            long long s = 0;
-            for (int k = 0; k < STATS_WAVES; ++k) s += wc[k][t];
-            row[2 + t] = (unsigned long long)s;
-        }
     }
 }
 
@@ -380,27 +242,16 @@ __global__ __launch_bounds__(STATS_THREADS) void curve_partial_kernel(const Curv
         d2 = a.d2_new;
         n = e - s;
     }
-    curve_block_stats(d2, n, a.th, blockIdx.x, a.part + ((size_t)half * STATS_BLOCKS + blockIdx.x) * STATS_ROW);
+    stats_block<STATS_MAX_T>(d2, n, a.th, blockIdx.x, a.part + ((size_t)half * STATS_BLOCKS + blockIdx.x) * STATS_ROW);
 }
 
-// One block per item: the rows of either half added in index order (stats_final_kernel's order), the step's sums added to the
-// running totals by one thread, the item's row written, the watermark moved.
+// One block per item: the rows of either half added in index order (stats_fold), the step's sums added to the running totals by
+// one thread, the item's row written, the watermark moved.
 __global__ __launch_bounds__(64) void curve_final_kernel(const CurveBatch b) {
     const CurveItem& a = b.it[blockIdx.x];
     __shared__ unsigned long long tot[2][STATS_ROW];
     const int half = threadIdx.x / 32, col = threadIdx.x % 32;
-    if (col < STATS_ROW) {
-        const unsigned long long* rows = a.part + (size_t)half * STATS_BLOCKS * STATS_ROW;
-        if (col < 2) {
-            double s = 0.0;
-            for (int k = 0; k < STATS_BLOCKS; ++k) s += __longlong_as_double((long long)rows[(size_t)k * STATS_ROW + col]);
-            tot[half][col] = (unsigned long long)__double_as_longlong(s);
-        } else {
-            long long s = 0;
-            for (int k = 0; k < STATS_BLOCKS; ++k) s += (long long)rows[(size_t)k * STATS_ROW + col];
-            tot[half][col] = (unsigned long long)s;
-        }
-    }
+    if (col < STATS_ROW) tot[half][col] = stats_fold(a.part + (size_t)half * STATS_BLOCKS * STATS_ROW, col);
     __syncthreads();
     if (threadIdx.x == 0) {
         long long s, e;
@@ -427,36 +278,25 @@ __global__ __launch_bounds__(64) void curve_final_kernel(const CurveBatch b) {
     }
 }
 
-// ---- host (the grid over the caller's box and the argument checks: nbp_nn_grid.h)
-void nn_plan_carve(void* plan, size_t ncell, int** start, float4** sorted) {
-    char* p = (char*)(((uintptr_t)plan + 255) / 256 * 256);
-    *start = (int*)p; p += al256((ncell + 1) * 4);
-    *sorted = (float4*)p;
-}
+// ---- host (the grid over the caller's box, the argument checks and the carves: nbp_nn_grid.h)
+size_t nn_plan_bytes(size_t ncell, long long T) { return nn_plan_size(ncell, (size_t)(T > 0 ? T : 1) * 16); }
+size_t nn_plan_ws_bytes(size_t ncell, long long T) { return nn_scratch_bytes(ncell) + 2 * al256((size_t)(T > 0 ? T : 1) * 4); }
 
-size_t nn_plan_bytes(size_t ncell, long long T) { return 256 + al256((ncell + 1) * 4) + al256((size_t)(T > 0 ? T : 1) * 16); }
-size_t nn_plan_ws_bytes(size_t ncell, long long T) {
-    return 256 + al256(ncell * 4) + al256((ncell / SCAN_TILE + 1) * 4) + 2 * al256((size_t)(T > 0 ? T : 1) * 4);
-}
-
-int nn_build(const float* t3, long long T, const long long* T_dev, const Grid& g, const Box& bx, size_t ncell, void* plan, void* ws,
-             hipStream_t st) {
-    int* start; float4* sorted;
-    nn_plan_carve(plan, ncell, &start, &sorted);
-    char* p = (char*)(((uintptr_t)ws + 255) / 256 * 256);
-    int* count = (int*)p; p += al256(ncell * 4);
-    int* tsum = (int*)p; p += al256((ncell / SCAN_TILE + 1) * 4);
+int nn_build(const float* t3, long long T, const long long* T_dev, const BoxGrid& b, void* plan, void* ws, hipStream_t st) {
+    int *start, *count, *tsum; float4* sorted;
+    nn_plan_carve(plan, b.ncell, &start, &sorted);
+    char* p = nn_scratch_carve(ws, b.ncell, &count, &tsum);
     int* cell_of = (int*)p; p += al256((size_t)(T > 0 ? T : 1) * 4);
     int* slot_of = (int*)p;
-    hipError_t e = hipMemsetAsync(count, 0, ncell * 4, st);
+    hipError_t e = hipMemsetAsync(count, 0, b.ncell * 4, st);
     if (e != hipSuccess) return (int)e;
     int rc;
     const int grid = nbp_ew_grid(T > 0 ? T : 1, 256);
     if (T > 0) {
-        nn_bin_kernel<<<grid, 256, 0, st>>>(t3, T_dev, T, g, bx, cell_of, slot_of, count);
+        nn_bin_kernel<<<grid, 256, 0, st>>>(t3, T_dev, T, b.g, b.bx, cell_of, slot_of, count);
         if ((rc = nbp_launch_status())) return rc;
     }
-    if ((rc = grid_exclusive_scan(count, (long long)ncell, tsum, start, st))) return rc;
+    if ((rc = grid_exclusive_scan(count, (long long)b.ncell, tsum, start, st))) return rc;
     if (T > 0) {
         nn_scatter_kernel<<<grid, 256, 0, st>>>(t3, T_dev, T, cell_of, slot_of, start, sorted);
         if ((rc = nbp_launch_status())) return rc;
@@ -464,70 +304,56 @@ int nn_build(const float* t3, long long T, const long long* T_dev, const Grid& g
     return 0;
 }
 
-int nn_query(const void* plan, const Grid& g, size_t ncell, float cap, float w, const float* q3, long long Q, const long long* Q_dev,
-             float* d2, hipStream_t st) {
-    if (Q == 0) return 0;
+int nn_query(const void* plan, const BoxGrid& b, float cap, float w, const float* q3, long long Q, const long long* Q_dev, float* d2,
+             hipStream_t st) {
     int* start; float4* sorted;
-    nn_plan_carve(const_cast<void*>(plan), ncell, &start, &sorted);
-    const int R = (int)ceil((double)cap / (double)w);               // <= 2^24 (nn_args_ok)
-    const float cap2 = cap * cap;
-    nn_query_kernel<<<nbp_ew_grid(Q * NN_LANES, 256), 256, 0, st>>>(q3, Q_dev, Q, g, R, w, cap2, sorted, start, d2);
-    return nbp_launch_status();
+    nn_plan_carve(plan, b.ncell, &start, &sorted);
+    return shell_query(NNPoints{sorted}, start, b.g, cap, w, q3, Q, Q_dev, d2, st);
+}
+
+// a *_bytes function's grid: false is its refusal (0 bytes)
+bool nn_bytes_grid(const float* lo, const float* hi, float cell, long long T, BoxGrid* b) {
+    return nn_count_ok(T) && !nn_grid(lo, hi, cell, b);
 }
 
 }  // namespace
 
-// Largest float x with sqrtf(x) < thr (thr > 0 finite): the squared-distance form of `distance < thr` (the coverage plan's helper,
-// nbp_planner.hip, which keeps its own copy: that file is not part of the C ABI's shared headers).
-static float recon_sq_below(float thr) {
-    float x = thr * thr;
-    while (sqrtf(x) >= thr) x = nextafterf(x, 0.f);
-    while (sqrtf(nextafterf(x, INFINITY)) < thr) x = nextafterf(x, INFINITY);
-    return x;
-}
-
 extern "C" size_t nbp_nn_plan_bytes(const float* lo_host, const float* hi_host, float cell, long long T) {
-    Grid g; Box bx; size_t ncell;
-    if (!nn_args_ok(lo_host, hi_host, cell) || T < 0 || T > 0x7fffffffll) return 0;
-    if (nn_grid(lo_host, hi_host, cell, &g, &bx, &ncell)) return 0;
-    return nn_plan_bytes(ncell, T);
+    BoxGrid b;
+    return nn_bytes_grid(lo_host, hi_host, cell, T, &b) ? nn_plan_bytes(b.ncell, T) : 0;
 }
 
 extern "C" size_t nbp_nn_plan_workspace_bytes(const float* lo_host, const float* hi_host, float cell, long long T) {
-    Grid g; Box bx; size_t ncell;
-    if (!nn_args_ok(lo_host, hi_host, cell) || T < 0 || T > 0x7fffffffll) return 0;
-    if (nn_grid(lo_host, hi_host, cell, &g, &bx, &ncell)) return 0;
-    return nn_plan_ws_bytes(ncell, T);
+    BoxGrid b;
+    return nn_bytes_grid(lo_host, hi_host, cell, T, &b) ? nn_plan_ws_bytes(b.ncell, T) : 0;
 }
 
 extern "C" int nbp_nn_plan_build_f32(const float* t3, long long T, const long long* T_dev_or_null, const float* lo_host,
                                      const float* hi_host, float cell, void* plan, size_t plan_bytes, void* ws, size_t ws_bytes,
                                      void* stream) {
     NBP_ENTER();
-    NBP_RETURN_IF(!plan || !ws || !nn_args_ok(lo_host, hi_host, cell) || T < 0 || T > 0x7fffffffll || (T > 0 && !t3), NBP_E_ARG);
-    Grid g; Box bx; size_t ncell;
-    const int rc = nn_grid(lo_host, hi_host, cell, &g, &bx, &ncell);
+    NBP_RETURN_IF(!plan || !ws || !nn_count_ok(T) || (T > 0 && !t3), NBP_E_ARG);
+    BoxGrid b;
+    const int rc = nn_grid(lo_host, hi_host, cell, &b);
     if (rc) return rc;
-    NBP_RETURN_IF(plan_bytes < nn_plan_bytes(ncell, T) || ws_bytes < nn_plan_ws_bytes(ncell, T), NBP_E_WS);
-    return nn_build(t3, T, T_dev_or_null, g, bx, ncell, plan, ws, (hipStream_t)stream);
+    NBP_RETURN_IF(plan_bytes < nn_plan_bytes(b.ncell, T) || ws_bytes < nn_plan_ws_bytes(b.ncell, T), NBP_E_WS);
+    return nn_build(t3, T, T_dev_or_null, b, plan, ws, (hipStream_t)stream);
 }
 
 extern "C" int nbp_nn_dist2_planned_f32(const void* plan, const float* lo_host, const float* hi_host, float cell, float cap,
                                         const float* q3, long long Q, const long long* Q_dev_or_null, float* d2, void* stream) {
     NBP_ENTER();
-    NBP_RETURN_IF(!plan || !nn_args_ok(lo_host, hi_host, cell) || !nn_cap_ok(cap, cell) || Q < 0 || Q > 0x7fffffffll, NBP_E_ARG);
+    NBP_RETURN_IF(!plan || !nn_args_ok(lo_host, hi_host, cell) || !nn_cap_ok(cap, cell) || !nn_count_ok(Q), NBP_E_ARG);
     NBP_RETURN_IF(Q > 0 && (!q3 || !d2), NBP_E_ARG);
-    Grid g; Box bx; size_t ncell;
-    const int rc = nn_grid(lo_host, hi_host, cell, &g, &bx, &ncell);
+    BoxGrid b;
+    const int rc = nn_grid(lo_host, hi_host, cell, &b);
     if (rc) return rc;
-    return nn_query(plan, g, ncell, cap, cell, q3, Q, Q_dev_or_null, d2, (hipStream_t)stream);
+    return nn_query(plan, b, cap, cell, q3, Q, Q_dev_or_null, d2, (hipStream_t)stream);
 }
 
 extern "C" size_t nbp_nn_dist2_workspace_bytes(const float* lo_host, const float* hi_host, float cell, long long T) {
-    Grid g; Box bx; size_t ncell;
-    if (!nn_args_ok(lo_host, hi_host, cell) || T < 0 || T > 0x7fffffffll) return 0;
-    if (nn_grid(lo_host, hi_host, cell, &g, &bx, &ncell)) return 0;
-    return nn_plan_bytes(ncell, T) + nn_plan_ws_bytes(ncell, T);
+    BoxGrid b;
+    return nn_bytes_grid(lo_host, hi_host, cell, T, &b) ? nn_plan_bytes(b.ncell, T) + nn_plan_ws_bytes(b.ncell, T) : 0;
 }
 
 extern "C" int nbp_nn_dist2_f32(const float* q3, long long Q, const long long* Q_dev_or_null, const float* t3, long long T,
@@ -535,15 +361,15 @@ extern "C" int nbp_nn_dist2_f32(const float* q3, long long Q, const long long* Q
                                 float* d2, void* ws, size_t ws_bytes, void* stream) {
     NBP_ENTER();
     NBP_RETURN_IF(!ws || !nn_args_ok(lo_host, hi_host, cell) || !nn_cap_ok(cap, cell), NBP_E_ARG);
-    NBP_RETURN_IF(Q < 0 || Q > 0x7fffffffll || T < 0 || T > 0x7fffffffll || (T > 0 && !t3) || (Q > 0 && (!q3 || !d2)), NBP_E_ARG);
-    Grid g; Box bx; size_t ncell;
-    int rc = nn_grid(lo_host, hi_host, cell, &g, &bx, &ncell);
+    NBP_RETURN_IF(!nn_count_ok(Q) || !nn_count_ok(T) || (T > 0 && !t3) || (Q > 0 && (!q3 || !d2)), NBP_E_ARG);
+    BoxGrid b;
+    int rc = nn_grid(lo_host, hi_host, cell, &b);
     if (rc) return rc;
-    NBP_RETURN_IF(ws_bytes < nn_plan_bytes(ncell, T) + nn_plan_ws_bytes(ncell, T), NBP_E_WS);
+    NBP_RETURN_IF(ws_bytes < nn_plan_bytes(b.ncell, T) + nn_plan_ws_bytes(b.ncell, T), NBP_E_WS);
     void* plan = ws;
-    void* scratch = (char*)ws + nn_plan_bytes(ncell, T);
-    if ((rc = nn_build(t3, T, T_dev_or_null, g, bx, ncell, plan, scratch, (hipStream_t)stream))) return rc;
-    return nn_query(plan, g, ncell, cap, cell, q3, Q, Q_dev_or_null, d2, (hipStream_t)stream);
+    void* scratch = (char*)ws + nn_plan_bytes(b.ncell, T);
+    if ((rc = nn_build(t3, T, T_dev_or_null, b, plan, scratch, (hipStream_t)stream))) return rc;
+    return nn_query(plan, b, cap, cell, q3, Q, Q_dev_or_null, d2, (hipStream_t)stream);
 }
 
 extern "C" size_t nbp_recon_stats_workspace_bytes(void) { return 256 + (size_t)STATS_BLOCKS * STATS_ROW * 8; }
@@ -557,7 +383,7 @@ extern "C" int nbp_recon_stats_f64(const float* d2, long long n, const long long
     NBP_RETURN_IF(ws_bytes < nbp_recon_stats_workspace_bytes(), NBP_E_WS);
     hipStream_t st = (hipStream_t)stream;
     StatsThresholds th;
-    for (int t = 0; t < STATS_MAX_T; ++t) th.v[t] = recon_sq_below(thresholds_host[t < T ? t : 0]);
+    for (int t = 0; t < STATS_MAX_T; ++t) th.v[t] = sq_below(thresholds_host[t < T ? t : 0]);
     unsigned long long* rows = (unsigned long long*)(((uintptr_t)ws + 255) / 256 * 256);
     switch (T) {
         case 1: launch_stats<1>(st, d2, n_dev_or_null, n, th, rows); break;
@@ -606,12 +432,12 @@ extern "C" int nbp_recon_curve_update_batch_f32(int n, const void* const* plans,
                       NBP_E_ARG);
         NBP_RETURN_IF((((uintptr_t)totals[q] | (uintptr_t)row[q] | (uintptr_t)seen_dev[q] | (uintptr_t)count_dev[q]) & 7), NBP_E_SHAPE);
         CurveItem& a = b.it[r];
-        Box bx; size_t ncell;
-        const int rc = nn_grid(lo, hi, cell[q], &a.g, &bx, &ncell);
+        BoxGrid bg;
+        const int rc = nn_grid(lo, hi, cell[q], &bg);
         if (rc) return rc;
-        for (int k = 0; k < 3; ++k) a.hi[k] = bx.hi[k];
+        a.g = bg.g; a.bx = bg.bx;
         int* start; float4* sorted;
-        nn_plan_carve(const_cast<void*>(plans[q]), ncell, &start, &sorted);
+        nn_plan_carve(plans[q], bg.ncell, &start, &sorted);
         a.sorted = sorted; a.start = start;
         a.R = (int)ceil((double)cap[q] / (double)cell[q]);
         a.cap2 = cap[q] * cap[q];
@@ -619,7 +445,7 @@ extern "C" int nbp_recon_curve_update_batch_f32(int n, const void* const* plans,
         for (int t = 0; t < STATS_MAX_T; ++t) {
             const float thr = thresholds_host[STATS_MAX_T * q + (t < T[q] ? t : 0)];
             NBP_RETURN_IF(!(thr > 0) || !isfinite(thr), NBP_E_ARG);
-            a.th[t] = recon_sq_below(thr);
+            a.th[t] = sq_below(thr);
         }
         a.cloud = cloud3[q]; a.capacity = capacity[q]; a.count = count_dev[q]; a.seen = seen_dev[q];
         a.d2_gt = (unsigned*)d2_gt[q]; a.d2_new = d2_new[q]; a.totals = (unsigned long long*)totals[q]; a.row = row[q];

@@ -269,8 +269,6 @@ __global__ __launch_bounds__(256) void sample_points_kernel(const float* __restr
     }
 }
 
-size_t al256s(size_t b) { return (b + 255) / 256 * 256; }
-
 // Point grid over the scene box grown by r; edge = max(r, largest extent / 256).
 int point_grid(const float* box6, double r, Grid* g, size_t* ncell) {
     double ext_max = 0;
@@ -291,16 +289,16 @@ int point_grid(const float* box6, double r, Grid* g, size_t* ncell) {
 
 struct GridWs { int* gcount; int* gstart; int* tsum; int* gcell_of; int* gslot_of; float4* sorted; };
 size_t grid_ws_bytes(size_t ncell, size_t slots) {
-    return al256s(ncell * 4) + al256s((ncell + 1) * 4) + al256s((ncell / SCAN_TILE + 1) * 4) + 2 * al256s(slots * 4) +
-           al256s(slots * 16);
+    return al256(ncell * 4) + al256((ncell + 1) * 4) + al256((ncell / SCAN_TILE + 1) * 4) + 2 * al256(slots * 4) +
+           al256(slots * 16);
 }
 char* grid_ws_carve(char* p, size_t ncell, size_t slots, GridWs* w) {
-    w->gcount = (int*)p; p += al256s(ncell * 4);
-    w->gstart = (int*)p; p += al256s((ncell + 1) * 4);
-    w->tsum = (int*)p; p += al256s((ncell / SCAN_TILE + 1) * 4);
-    w->gcell_of = (int*)p; p += al256s(slots * 4);
-    w->gslot_of = (int*)p; p += al256s(slots * 4);
-    w->sorted = (float4*)p; p += al256s(slots * 16);
+    w->gcount = (int*)p; p += al256(ncell * 4);
+    w->gstart = (int*)p; p += al256((ncell + 1) * 4);
+    w->tsum = (int*)p; p += al256((ncell / SCAN_TILE + 1) * 4);
+    w->gcell_of = (int*)p; p += al256(slots * 4);
+    w->gslot_of = (int*)p; p += al256(slots * 4);
+    w->sorted = (float4*)p; p += al256(slots * 16);
     return p;
 }
 
@@ -337,8 +335,8 @@ extern "C" size_t nbp_scene_fill_workspace_bytes(const float* box6_host, const i
     if (!geom_ok(box6_host, grid3_host, &n_cells) || capacity < 1 || n_pts_max < 1 || !(resolution > 0)) return 0;
     if (point_grid(box6_host, resolution, &g, &ncell)) return 0;
     const size_t slots = (size_t)n_cells * capacity;
-    return 512 + 2 * al256s((size_t)n_pts_max * 4) + 2 * al256s((size_t)n_cells * 4) + al256s((size_t)(n_cells + 1) * 4) +
-           al256s((size_t)n_pts_max * 12) + al256s(slots * 12) + grid_ws_bytes(ncell, slots);
+    return 512 + 2 * al256((size_t)n_pts_max * 4) + 2 * al256((size_t)n_cells * 4) + al256((size_t)(n_cells + 1) * 4) +
+           al256((size_t)n_pts_max * 12) + al256(slots * 12) + grid_ws_bytes(ncell, slots);
 }
 
 extern "C" int nbp_scene_fill_cells_f32(const float* pts3, long long n, const long long* n_dev_or_null,
@@ -356,16 +354,16 @@ extern "C" int nbp_scene_fill_cells_f32(const float* pts3, long long n, const lo
     hipStream_t st = (hipStream_t)stream;
     const size_t slots = (size_t)n_cells * capacity;
     char* p = (char*)(((uintptr_t)ws + 255) / 256 * 256);
-    int* cell_of = (int*)p; p += al256s((size_t)n * 4);
-    int* keep = (int*)p; p += al256s((size_t)n * 4);
-    int* cand_count = (int*)p; p += al256s((size_t)n_cells * 4);
-    int* kept_count = (int*)p; p += al256s((size_t)n_cells * 4);
-    int* kept_start = (int*)p; p += al256s((size_t)(n_cells + 1) * 4);
-    float* stage = (float*)p; p += al256s((size_t)n * 12);
-    float* temp = (float*)p; p += al256s(slots * 12);
+    int* cell_of = (int*)p; p += al256((size_t)n * 4);
+    int* keep = (int*)p; p += al256((size_t)n * 4);
+    int* cand_count = (int*)p; p += al256((size_t)n_cells * 4);
+    int* kept_count = (int*)p; p += al256((size_t)n_cells * 4);
+    int* kept_start = (int*)p; p += al256((size_t)(n_cells + 1) * 4);
+    float* stage = (float*)p; p += al256((size_t)n * 12);
+    float* temp = (float*)p; p += al256(slots * 12);
     GridWs gw;
     grid_ws_carve(p, ncell, slots, &gw);
-    hipError_t e = hipMemsetAsync(cand_count, 0, 2 * al256s((size_t)n_cells * 4), st);      // cand_count + kept_count
+    hipError_t e = hipMemsetAsync(cand_count, 0, 2 * al256((size_t)n_cells * 4), st);      // cand_count + kept_count
     if (e != hipSuccess) return (int)e;
     const SceneGeom geom = make_geom(box6_host, grid3_host);
     scene_assign_kernel<<<nbp_ew_grid(n, 256), 256, 0, st>>>(pts3, n, n_dev_or_null, geom, cell_of, cand_count);

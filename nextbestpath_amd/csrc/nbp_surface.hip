@@ -14,32 +14,28 @@
 // vertices of every participating triangle as three float4 (a, b, c, copied as they are: the kernel's b - a has the definition's
 // bits).  The slot order inside a cell does not show: the result is a minimum.
 //
-// Query.  One launch; MESH_LANES lanes per query walk the shells of cells at Chebyshev cell distance r = r0 .. R = ceil(cap / w)
-// around the query's UNCLAMPED cell, exactly as nn_query_kernel does (the float clamp before the int conversion; a query beyond
-// reach, or with a NaN, gets cap2 without a memory access; rows at or beyond the device counter are never read or written), and
-// evaluate point_triangle_d2 for every entry of every cell they visit.
+// Query.  One launch: nbp_shell_walk.h's walk over the shells of cells around the query's UNCLAMPED cell, MESH_LANES lanes per query
+// (a query beyond reach, or with a NaN, gets cap2 without a memory access; rows at or beyond the device counter are never read or
+// written), point_triangle_d2 evaluated for every entry of every cell it visits.
 //
-// Why the walk may stop after shell r once best <= fl(r w)^2, and after shell R whatever it found.  point_triangle_d2 is the
-// MAXIMUM of the core term (segments and face) and the box term, the fp32 squared distance from the query to the triangle's fp32
-// bounding box.  A triangle is registered in every cell of its range, and shells 0..r are every cell within r of the query's cell,
-// so a triangle that shells 0..r have not shown has a cell range that misses [c - r, c + r] on some axis: its nearest cell there,
-// which is the cell of the nearer face of its box (grid_cell is monotone), differs from the query's cell by at least r + 1.  That
-// is nbp_recon.hip's situation with "target" read as "nearest point of the box": by the argument in its header (cells 1.001 w wide,
-// at most 2048 cells on an axis, coordinates with a relative error below 2^-23) the query and that face are separated by more than
-// r w on that axis, by a margin of 4e-4 relative against roundings of 2^-24, so the box term's e on that axis, fl(lo - p) or
-// fl(p - hi), has fl(e e) > fl(r w)^2, and -- rounding being monotone and the other two squares non-negative -- so has the box
-// term, and with it the maximum: the skipped triangle's point_triangle_d2 exceeds fl(r w)^2 >= best and cannot lower the minimum.
-// (r = 0: best <= 0 is a minimum already.)  After shell R the same holds with R w >= cap: what was not visited exceeds cap2.  No
-// bound on the size of a triangle or on the rounding error of the core term enters: that is what the box term is in the definition
-// for.  So the result is the brute-force minimum over all participating triangles, bit for bit.  A triangle that spans several
-// cells is evaluated more than once: that costs time, not bits.  No atomics touch the output: two runs give the same bits.
-#include "nbp_nn_grid.h"
+// Why the walk's early exits hold for triangles.  point_triangle_d2 is the MAXIMUM of the core term (segments and face) and the box
+// term, the fp32 squared distance from the query to the triangle's fp32 bounding box.  A triangle is registered in every cell of
+// its range, and shells 0..r are every cell within r of the query's cell, so a triangle that shells 0..r have not shown has a cell
+// range that misses [c - r, c + r] on some axis: its nearest cell there, which is the cell of the nearer face of its box (grid_cell
+// is monotone), differs from the query's cell by at least r + 1.  That is the situation of nbp_shell_walk.h's proof with "target"
+// read as "nearest point of the box": the box term's e on that axis, fl(lo - p) or fl(p - hi), has fl(e e) > fl(r w)^2, and --
+// rounding being monotone and the other two squares non-negative -- so has the box term, and with it the maximum: the skipped
+// triangle's point_triangle_d2 exceeds fl(r w)^2 >= best and cannot lower the minimum.  No bound on the size of a triangle or on
+// the rounding error of the core term enters: that is what the box term is in the definition for.  So the result is the
+// brute-force minimum over all participating triangles, bit for bit.  A triangle that spans several cells is evaluated more than
+// once: that costs time, not bits.
+#include "nbp_shell_walk.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int MESH_LANES = 8;                    // lanes per query: the 8 rim columns of shell 1 at once (nn_query_kernel)
+constexpr int MESH_LANES = 8;                    // lanes per query: the 8 rim columns of shell 1 at once
 constexpr int MESH_UNROLL = 2;                   // triangles of a run in flight together (an entry is an index and three float4)
 constexpr int MESH_SMALL = 32;                   // cells up to which a triangle's owner thread registers it alone
 constexpr float MESH_GUARD = 5.9604644775390625e-08f;   // 2^-24: utility/surface_metrics.py GUARD
@@ -95,10 +91,6 @@ __device__ __forceinline__ float tri_d2(float px, float py, float pz, const floa
 // ---- plan
 struct MeshRange { int c0[3], c1[3]; };
 
-__device__ __forceinline__ bool mesh_in_box(const Grid& g, const Box& bx, float x, float y, float z) {
-    return x >= g.lo[0] && x <= bx.hi[0] && y >= g.lo[1] && y <= bx.hi[1] && z >= g.lo[2] && z <= bx.hi[2];   // a NaN is outside
-}
-
 // Does triangle f take part?  Then its vertices and the inclusive range of cells it is registered in.
 __device__ __forceinline__ bool mesh_triangle(const float* __restrict__ v, long long V, const int* __restrict__ faces, long long f,
                                               const Grid& g, const Box& bx, float4* a, float4* b, float4* c, MeshRange* r) {
@@ -107,8 +99,7 @@ __device__ __forceinline__ bool mesh_triangle(const float* __restrict__ v, long 
     *a = make_float4(v[3 * (size_t)i0], v[3 * (size_t)i0 + 1], v[3 * (size_t)i0 + 2], 0.f);
     *b = make_float4(v[3 * (size_t)i1], v[3 * (size_t)i1 + 1], v[3 * (size_t)i1 + 2], 0.f);
     *c = make_float4(v[3 * (size_t)i2], v[3 * (size_t)i2 + 1], v[3 * (size_t)i2 + 2], 0.f);
-    if (!mesh_in_box(g, bx, a->x, a->y, a->z) || !mesh_in_box(g, bx, b->x, b->y, b->z) || !mesh_in_box(g, bx, c->x, c->y, c->z))
-        return false;
+    if (!in_box(g, bx, a->x, a->y, a->z) || !in_box(g, bx, b->x, b->y, b->z) || !in_box(g, bx, c->x, c->y, c->z)) return false;
     grid_cell(g, fminf(fminf(a->x, b->x), c->x), fminf(fminf(a->y, b->y), c->y), fminf(fminf(a->z, b->z), c->z), r->c0);
     grid_cell(g, fmaxf(fmaxf(a->x, b->x), c->x), fmaxf(fmaxf(a->y, b->y), c->y), fmaxf(fmaxf(a->z, b->z), c->z), r->c1);
     return true;
@@ -180,7 +171,7 @@ __global__ __launch_bounds__(256) void mesh_fill_kernel(const float* __restrict_
     }
 }
 
-// ---- query
+// ---- query: the shell walk over cells of triangle entries
 __device__ __forceinline__ float mesh_run(const int* __restrict__ entries, const float4* __restrict__ tri, int p, int hi, float x,
                                           float y, float z, float best) {
     for (; p + MESH_UNROLL <= hi; p += MESH_UNROLL) {
@@ -204,139 +195,76 @@ __device__ __forceinline__ float mesh_run(const int* __restrict__ entries, const
     return best;
 }
 
-// nn_query_kernel's walk (nbp_recon.hip) over cells of triangle entries
-__global__ __launch_bounds__(256) void mesh_query_kernel(const float* __restrict__ q, const long long* __restrict__ n_dev, long long n_host,
-                                                         Grid g, int R, float w, float cap2, const float4* __restrict__ tri,
-                                                         const int* __restrict__ start, const int* __restrict__ entries,
-                                                         float* __restrict__ d2) {
-    long long Q = n_dev ? *n_dev : n_host;
-    Q = Q < 0 ? 0 : (Q > n_host ? n_host : Q);                       // rows at or beyond the device count are never read or written
-    const int sub = threadIdx.x % MESH_LANES;
-    const int n0 = g.n[0], n1 = g.n[1], n2 = g.n[2];
-    for (long long j = ((long long)blockIdx.x * blockDim.x + threadIdx.x) / MESH_LANES; j < Q;
-         j += ((long long)gridDim.x * blockDim.x) / MESH_LANES) {
-        const float x = q[3 * j], y = q[3 * j + 1], z = q[3 * j + 2];
-        // the unclamped cell, clamped as a FLOAT to one cell beyond the reach of R before the conversion (a query 1e6 away, or a
-        // NaN, must not reach the int conversion's undefined range)
-        const float fi = floorf((x - g.lo[0]) * g.inv), fj = floorf((y - g.lo[1]) * g.inv), fk = floorf((z - g.lo[2]) * g.inv);
-        const bool reach = fi >= (float)-R && fi <= (float)(n0 - 1 + R) && fj >= (float)-R && fj <= (float)(n1 - 1 + R) &&
-                           fk >= (float)-R && fk <= (float)(n2 - 1 + R);
-        float best = cap2;
-        if (reach) {                                               // (uniform over the query's lanes)
-            const int ci = (int)fi, cj = (int)fj, ck = (int)fk;
-            // shells closer than the grid hold no cell: a query outside starts at its Chebyshev cell distance to the grid (<= R)
-            const int r0 = max(max(max(-ci, ci - (n0 - 1)), max(-cj, cj - (n1 - 1))), max(max(-ck, ck - (n2 - 1)), 0));
-            for (int r = r0; r <= R; ++r) {
-                const int a0 = max(ci - r, 0), a1 = min(ci + r, n0 - 1), b0 = max(cj - r, 0), b1 = min(cj + r, n1 - 1);
-                const int na = a1 - a0 + 1, nb = b1 - b0 + 1;
-                if (na > 0 && nb > 0) {
-                    const int zl = ck - r, zh = ck + r;
-                    for (int it = sub; it < na * nb; it += MESH_LANES) {
-                        const int a = a0 + it / nb, b = b0 + it % nb;
-                        const int base = (a * n1 + b) * n2;
-                        if (a == ci - r || a == ci + r || b == cj - r || b == cj + r) {      // rim: the column's whole run
-                            const int z0 = max(zl, 0), z1 = min(zh, n2 - 1);
-                            if (z0 <= z1) best = mesh_run(entries, tri, start[base + z0], start[base + z1 + 1], x, y, z, best);
-                        } else {                                                             // inside: the two end cells
-                            if (zl >= 0 && zl < n2) best = mesh_run(entries, tri, start[base + zl], start[base + zl + 1], x, y, z, best);
-                            if (zh >= 0 && zh < n2) best = mesh_run(entries, tri, start[base + zh], start[base + zh + 1], x, y, z, best);
-                        }
-                    }
-                }
-#pragma unroll
-                for (int o = MESH_LANES / 2; o; o >>= 1) {
-                    const float other = __shfl_xor(best, o);
-                    best = other < best ? other : best;
-                }
-                const float rw = (float)r * w;
-                if (best <= rw * rw) break;
-                // every cell of the grid has been visited
-                if (ci - r <= 0 && ci + r >= n0 - 1 && cj - r <= 0 && cj + r >= n1 - 1 && ck - r <= 0 && ck + r >= n2 - 1) break;
-            }
-        }
-        if (sub == 0) d2[j] = best;
+struct MeshTriangles {
+    static constexpr int LANES = MESH_LANES;
+    const int* __restrict__ entries;
+    const float4* __restrict__ tri;
+    __device__ __forceinline__ float run(int p, int hi, float x, float y, float z, float best) const {
+        return mesh_run(entries, tri, p, hi, x, y, z, best);
     }
-}
+};
 
 // ---- host
-void mesh_plan_carve(void* plan, size_t ncell, int** start, float4** tri) {
-    char* p = (char*)(((uintptr_t)plan + 255) / 256 * 256);
-    *start = (int*)p; p += al256((ncell + 1) * 4);
-    *tri = (float4*)p;
-}
-
-size_t mesh_plan_bytes(size_t ncell, long long F) { return 256 + al256((ncell + 1) * 4) + al256((size_t)(F > 0 ? F : 1) * 48); }
-size_t mesh_ws_bytes(size_t ncell) { return 256 + al256(ncell * 4) + al256((ncell / SCAN_TILE + 1) * 4); }
-
-void mesh_ws_carve(void* ws, size_t ncell, int** count, int** tsum) {
-    char* p = (char*)(((uintptr_t)ws + 255) / 256 * 256);
-    *count = (int*)p; p += al256(ncell * 4);
-    *tsum = (int*)p;
-}
-
-bool mesh_counts_ok(long long V, long long F) { return V >= 0 && V <= 0x7fffffffll && F >= 0 && F <= 0x7fffffffll; }
+size_t mesh_plan_bytes(size_t ncell, long long F) { return nn_plan_size(ncell, (size_t)(F > 0 ? F : 1) * 48); }
 
 }  // namespace
 
 extern "C" size_t nbp_mesh_plan_bytes(const float* lo_host, const float* hi_host, float cell, long long F) {
-    Grid g; Box bx; size_t ncell;
-    if (!nn_args_ok(lo_host, hi_host, cell) || F < 0 || F > 0x7fffffffll) return 0;
-    if (nn_grid(lo_host, hi_host, cell, &g, &bx, &ncell)) return 0;
-    return mesh_plan_bytes(ncell, F);
+    BoxGrid b;
+    return nn_count_ok(F) && !nn_grid(lo_host, hi_host, cell, &b) ? mesh_plan_bytes(b.ncell, F) : 0;
 }
 
 extern "C" size_t nbp_mesh_plan_workspace_bytes(const float* lo_host, const float* hi_host, float cell) {
-    Grid g; Box bx; size_t ncell;
-    if (!nn_args_ok(lo_host, hi_host, cell)) return 0;
-    if (nn_grid(lo_host, hi_host, cell, &g, &bx, &ncell)) return 0;
-    return mesh_ws_bytes(ncell);
+    BoxGrid b;
+    return nn_grid(lo_host, hi_host, cell, &b) ? 0 : nn_scratch_bytes(b.ncell);
 }
 
 extern "C" int nbp_mesh_plan_count_f32(const float* verts3, long long V, const int* faces3, long long F, const float* lo_host,
                                        const float* hi_host, float cell, void* plan, size_t plan_bytes, long long* totals2_dev,
                                        void* ws, size_t ws_bytes, void* stream) {
     NBP_ENTER();
-    NBP_RETURN_IF(!plan || !ws || !totals2_dev || !nn_args_ok(lo_host, hi_host, cell) || !mesh_counts_ok(V, F), NBP_E_ARG);
+    NBP_RETURN_IF(!plan || !ws || !totals2_dev || !nn_args_ok(lo_host, hi_host, cell) || !nn_count_ok(V) || !nn_count_ok(F), NBP_E_ARG);
     NBP_RETURN_IF(F > 0 && (!faces3 || (V > 0 && !verts3)), NBP_E_ARG);
     NBP_RETURN_IF(((uintptr_t)totals2_dev & 7), NBP_E_SHAPE);
-    Grid g; Box bx; size_t ncell;
-    int rc = nn_grid(lo_host, hi_host, cell, &g, &bx, &ncell);
+    BoxGrid b;
+    int rc = nn_grid(lo_host, hi_host, cell, &b);
     if (rc) return rc;
-    NBP_RETURN_IF(plan_bytes < mesh_plan_bytes(ncell, F) || ws_bytes < mesh_ws_bytes(ncell), NBP_E_WS);
+    NBP_RETURN_IF(plan_bytes < mesh_plan_bytes(b.ncell, F) || ws_bytes < nn_scratch_bytes(b.ncell), NBP_E_WS);
     hipStream_t st = (hipStream_t)stream;
     int *start, *count, *tsum; float4* tri;
-    mesh_plan_carve(plan, ncell, &start, &tri);
-    mesh_ws_carve(ws, ncell, &count, &tsum);
-    hipError_t e = hipMemsetAsync(count, 0, ncell * 4, st);
+    nn_plan_carve(plan, b.ncell, &start, &tri);
+    nn_scratch_carve(ws, b.ncell, &count, &tsum);
+    hipError_t e = hipMemsetAsync(count, 0, b.ncell * 4, st);
     if (e == hipSuccess) e = hipMemsetAsync(totals2_dev, 0, 16, st);
     if (e != hipSuccess) return (int)e;
     if (F > 0) {
-        mesh_count_kernel<<<nbp_ew_grid(F, 256), 256, 0, st>>>(verts3, V, faces3, F, g, bx, tri, count,
+        mesh_count_kernel<<<nbp_ew_grid(F, 256), 256, 0, st>>>(verts3, V, faces3, F, b.g, b.bx, tri, count,
                                                                  (unsigned long long*)totals2_dev);
         if ((rc = nbp_launch_status())) return rc;
     }
-    return grid_exclusive_scan(count, (long long)ncell, tsum, start, st);
+    return grid_exclusive_scan(count, (long long)b.ncell, tsum, start, st);
 }
 
 extern "C" int nbp_mesh_plan_fill_i32(const float* verts3, long long V, const int* faces3, long long F, const float* lo_host,
                                       const float* hi_host, float cell, const void* plan, int* entries, long long entry_capacity,
                                       void* ws, size_t ws_bytes, void* stream) {
     NBP_ENTER();
-    NBP_RETURN_IF(!plan || !ws || !nn_args_ok(lo_host, hi_host, cell) || !mesh_counts_ok(V, F) || entry_capacity < 0, NBP_E_ARG);
+    NBP_RETURN_IF(!plan || !ws || !nn_args_ok(lo_host, hi_host, cell) || !nn_count_ok(V) || !nn_count_ok(F) || entry_capacity < 0,
+                  NBP_E_ARG);
     NBP_RETURN_IF((F > 0 && (!faces3 || (V > 0 && !verts3))) || (entry_capacity > 0 && !entries), NBP_E_ARG);
     NBP_RETURN_IF(entry_capacity > 0x7fffffffll, NBP_E_SHAPE);         // an entry's position is an int of the scan
-    Grid g; Box bx; size_t ncell;
-    int rc = nn_grid(lo_host, hi_host, cell, &g, &bx, &ncell);
+    BoxGrid b;
+    const int rc = nn_grid(lo_host, hi_host, cell, &b);
     if (rc) return rc;
-    NBP_RETURN_IF(ws_bytes < mesh_ws_bytes(ncell), NBP_E_WS);
+    NBP_RETURN_IF(ws_bytes < nn_scratch_bytes(b.ncell), NBP_E_WS);
     hipStream_t st = (hipStream_t)stream;
     int *start, *cursor, *tsum; float4* tri;
-    mesh_plan_carve(const_cast<void*>(plan), ncell, &start, &tri);
-    mesh_ws_carve(ws, ncell, &cursor, &tsum);
-    hipError_t e = hipMemsetAsync(cursor, 0, ncell * 4, st);
+    nn_plan_carve(plan, b.ncell, &start, &tri);
+    nn_scratch_carve(ws, b.ncell, &cursor, &tsum);
+    hipError_t e = hipMemsetAsync(cursor, 0, b.ncell * 4, st);
     if (e != hipSuccess) return (int)e;
     if (F == 0) return 0;
-    mesh_fill_kernel<<<nbp_ew_grid(F, 256), 256, 0, st>>>(verts3, V, faces3, F, g, bx, start, cursor, entries, entry_capacity);
+    mesh_fill_kernel<<<nbp_ew_grid(F, 256), 256, 0, st>>>(verts3, V, faces3, F, b.g, b.bx, start, cursor, entries, entry_capacity);
     return nbp_launch_status();
 }
 
@@ -344,17 +272,12 @@ extern "C" int nbp_mesh_dist2_planned_f32(const void* plan, const int* entries, 
                                           float cap, const float* q3, long long Q, const long long* Q_dev_or_null, float* d2,
                                           void* stream) {
     NBP_ENTER();
-    NBP_RETURN_IF(!plan || !entries || !nn_args_ok(lo_host, hi_host, cell) || !nn_cap_ok(cap, cell) || Q < 0 || Q > 0x7fffffffll,
-                  NBP_E_ARG);
+    NBP_RETURN_IF(!plan || !entries || !nn_args_ok(lo_host, hi_host, cell) || !nn_cap_ok(cap, cell) || !nn_count_ok(Q), NBP_E_ARG);
     NBP_RETURN_IF(Q > 0 && (!q3 || !d2), NBP_E_ARG);
-    Grid g; Box bx; size_t ncell;
-    const int rc = nn_grid(lo_host, hi_host, cell, &g, &bx, &ncell);
+    BoxGrid b;
+    const int rc = nn_grid(lo_host, hi_host, cell, &b);
     if (rc) return rc;
-    if (Q == 0) return 0;
     int* start; float4* tri;
-    mesh_plan_carve(const_cast<void*>(plan), ncell, &start, &tri);
-    const int R = (int)ceil((double)cap / (double)cell);              // <= 2^24 (nn_cap_ok)
-    mesh_query_kernel<<<nbp_ew_grid(Q * MESH_LANES, 256), 256, 0, (hipStream_t)stream>>>(q3, Q_dev_or_null, Q, g, R, cell, cap * cap, tri,
-                                                                                           start, entries, d2);
-    return nbp_launch_status();
+    nn_plan_carve(plan, b.ncell, &start, &tri);
+    return shell_query(MeshTriangles{entries, tri}, start, b.g, cap, cell, q3, Q, Q_dev_or_null, d2, (hipStream_t)stream);
 }

@@ -169,6 +169,34 @@ def test_mesh_dist2_is_the_brute_force_minimum(hip, name, cell, cap, Q):
     assert np.array_equal(got[:n].view(np.uint32), want[:n].view(np.uint32)) and np.all(got[n:] == SENTINEL)
 
 
+def _degenerate_point_mesh():
+    """300 points, 198 of them inside the box, as triangles (i, i, i); 257 queries, the first five ON the first five points."""
+    rng = np.random.default_rng(7)
+    lo, hi = np.array([-4, -3, -2], f32), np.array([5, 4, 3], f32)
+    pts = rng.uniform(lo - 0.5, hi + 0.5, (300, 3)).astype(f32)
+    q = rng.uniform(lo - 2, hi + 2, (257, 3)).astype(f32)
+    q[:5] = pts[:5]
+    return pts, np.repeat(np.arange(300, dtype=np.int32)[:, None], 3, 1), q, lo, hi
+
+
+@pytest.mark.parametrize("cap,below,at_cap", [(1.0, 60, 150), (3.0, 200, 0)])
+def test_a_mesh_of_degenerate_triangles_is_a_point_set(hip, cap, below, at_cap):
+    """Both plans run ONE shell walk: against triangles (i, i, i) mesh_dist2 is nn_dist2 against the points, bit for bit, and both are
+    the numpy definition.  The case cannot pass by saturating: enough queries below cap2, enough at it, four exact zeros."""
+    from nextbestpath_amd.utility import hipops
+    pts, faces, q, lo, hi = _degenerate_point_mesh()
+    want = rm.nn_dist2_reference(q, pts, lo, hi, cap)
+    cap2 = f32(cap) * f32(cap)
+    assert np.array_equal(sm.mesh_dist2_reference(q, pts, faces, lo, hi, cap).view(np.uint32), want.view(np.uint32))
+    assert np.count_nonzero(np.all((pts >= lo) & (pts <= hi), axis=1)) == 198
+    assert np.count_nonzero(want < cap2) >= below and np.count_nonzero(want == cap2) >= at_cap and np.count_nonzero(want == 0) == 4
+    box = (lo.tolist(), hi.tolist())
+    mesh = hipops.mesh_dist2(_dev(q), _dev(pts), _dev(faces, torch.int32), box, cap, 1.0).cpu().numpy()
+    nn = hipops.nn_dist2(_dev(q), _dev(pts), box, cap, 1.0).cpu().numpy()
+    assert np.array_equal(mesh.view(np.uint32), nn.view(np.uint32))
+    assert np.array_equal(nn.view(np.uint32), want.view(np.uint32))
+
+
 def test_plan_counts_of_known_meshes(hip):
     from nextbestpath_amd.utility import hipops
     verts, faces, lo, hi = _mesh_whole_grid()
