@@ -1299,6 +1299,30 @@ int nbp_tsdf_extract_f32(const int* vol, const float* lo_host, float voxel, int 
 size_t nbp_tsdf_stats_workspace_bytes(void);
 int nbp_tsdf_stats_i64(const int* vol, long long n_voxels, int min_weight, long long* counts2, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- a triangle mesh out of the TSDF volume, by naive surface nets (csrc/nbp_tsdf_mesh.hip; the definition, which the kernels equal
+ * bit for bit, is nextbestpath_amd/utility/tsdf_mesh.py).  Not in the reference.  The volume, lo_host and min_weight
+ * are nbp_tsdf_extract_f32's.
+ *   nbp_tsdf_mesh_f32             one vertex per grid cell (its low corner voxel's linear index is the cell's) that holds a crossing
+ *                                 of the extraction: the mean of the cell's crossing points, added in edge order from +0; verts
+ *                                 [.][3] in cell order.  One quad per crossing (v, a) with 1 <= v[b], v[c] <= dims - 2 on the other
+ *                                 two axes: the vertex ids (ranks in verts) of the four cells around the edge, turning from axis (a +
+ *                                 1) % 3 to (a + 2) % 3 where S0 < 0 and the other way round otherwise, as the triangles (r0, r1,
+ *                                 r2), (r0, r2, r3); faces [.][3] int32 in the extraction's order, area2 [.] (may be null) = 0.25
+ *                                 |cross(v1 - v0, v2 - v0)|^2 per face.  totals2 (int64 [2], device) receives the numbers of
+ *                                 vertices and of faces whatever the capacities; the first vert_capacity / face_capacity rows are
+ *                                 written, nothing beyond them (a face is written whatever ids it holds); both capacities 0: the
+ *                                 counts alone, the buffers may be null.  Two launches to count (per run of voxels, scan), one for
+ *                                 the vertices, one for the faces; ws: nbp_tsdf_mesh_workspace_bytes(nx ny nz) (0 where the call
+ *                                 would fail): the runs' offsets and an int32 vertex id per voxel.
+ * No allocation, no host synchronisation, no atomics; two runs give the same bytes.  NBP_E_ARG: a null volume, lo, totals2 or
+ * workspace, a null buffer with a capacity above 0, a dimension or min_weight < 1, a capacity < 0, voxel not positive and finite, lo
+ * not finite, two of the volume, totals2, the workspace and the outputs overlapping; NBP_E_SHAPE: more than 2^28 voxels, the volume
+ * or totals2 off the 8-byte grid; NBP_E_WS.  Nothing is written on an error. */
+size_t nbp_tsdf_mesh_workspace_bytes(long long n_voxels);
+int nbp_tsdf_mesh_f32(const int* vol, const float* lo_host, float voxel, int nx, int ny, int nz, int min_weight, float* verts_or_null,
+                      long long vert_capacity, int* faces_or_null, float* area2_or_null, long long face_capacity, long long* totals2,
+                      void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

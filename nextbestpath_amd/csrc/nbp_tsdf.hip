@@ -20,23 +20,15 @@
 //
 // Statistics.  Integer counts with a fixed geometry: per-thread strided partials, a fixed tree in the block, one stored row per
 // block, the rows added in index order by a second small launch.
-#include "common.h"
-
-#include <math.h>
-#include <stddef.h>
-#include <stdint.h>
+#include "nbp_tsdf_shared.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int TS_THREADS = 256;
 constexpr int TS_ITEMS = 12;                        // the step's group stages chunk at 12 items (nbp_sim.hip: STEP_BATCH) ...
 constexpr int TS_FRAMES = 4;                        // ... of <= 4 frames each
-constexpr long long TS_MAX_VOXELS = 1ll << 28;
 constexpr long long TS_MAX_PIXELS = 1ll << 29;
-constexpr int TS_QUANT = 127;
-constexpr int EX_RUN = 2048;                        // consecutive voxels of one extraction workgroup: EX_RUN / TS_THREADS rounds
 constexpr int ST_BLOCKS = 256;
 
 struct TsdfCam { float R[9]; float T[3]; };
@@ -61,11 +53,6 @@ __device__ __forceinline__ void tsdf_to_view(const float* p, const float* R, con
     o[0] = ((p[0] * R[0] + p[1] * R[3]) + p[2] * R[6]) + T[0];
     o[1] = ((p[0] * R[1] + p[1] * R[4]) + p[2] * R[7]) + T[1];
     o[2] = ((p[0] * R[2] + p[1] * R[5]) + p[2] * R[8]) + T[2];
-}
-
-__device__ __forceinline__ float tsdf_centre(float lo, int i, float voxel) {
-    const float s = ((float)i + 0.5f) * voxel;
-    return lo + s;
 }
 
 // ONE body for both launch forms: voxel `v` of `it` (the item lives in the kernel arguments; its indices are uniform)
@@ -116,13 +103,6 @@ __global__ __launch_bounds__(TS_THREADS) void tsdf_integrate_batch_kernel(TsdfBa
 }
 
 // ---- extraction
-struct ExGeom { float lo[3]; float voxel; int nx, ny, nz; int min_weight; };
-
-__device__ __forceinline__ bool tsdf_usable(int2 sw, int min_weight) {
-    const long long a = sw.x < 0 ? -(long long)sw.x : (long long)sw.x;
-    return sw.y >= min_weight && a < (long long)TS_QUANT * sw.y;
-}
-
 // the crossings of voxel v: bit a = one point on axis a.  d0 / d1[a]: the voxel's and its neighbours' (S, W)
 __device__ __forceinline__ int tsdf_crossings(const int2* __restrict__ vol, const ExGeom& g, long long v, long long n_vox, int* ijk,
                                               int2* own, int2* nb) {
@@ -154,28 +134,6 @@ __device__ __forceinline__ int tsdf_crossings(const int2* __restrict__ vol, cons
     return m;
 }
 
-// inclusive prefix sum of `x` over the workgroup's threads, in thread order (shuffles inside a wave, the four waves in order)
-__device__ __forceinline__ int block_inclusive_scan(int x, int* wave_sums, int* total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int y = __shfl_up(x, off, 64);
-        if (lane >= off) x += y;
-    }
-    __syncthreads();                                                 // (the previous round's readers of wave_sums are done)
-    if (lane == 63) wave_sums[wave] = x;
-    __syncthreads();
-    int before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < TS_THREADS / 64; ++w) {
-        const int s = wave_sums[w];
-        before += w < wave ? s : 0;
-        all += s;
-    }
-    *total = all;
-    return x + before;
-}
-
 __global__ __launch_bounds__(TS_THREADS) void tsdf_count_kernel(const int2* __restrict__ vol, ExGeom g, long long n_vox,
                                                                 long long* __restrict__ run_counts) {
     __shared__ int wave_sums[TS_THREADS / 64];
@@ -194,31 +152,8 @@ __global__ __launch_bounds__(TS_THREADS) void tsdf_count_kernel(const int2* __re
 // one workgroup: run_counts -> exclusive offsets, in place; the total into total_dev
 __global__ __launch_bounds__(TS_THREADS) void tsdf_scan_kernel(long long* __restrict__ runs, long long n_runs, long long* __restrict__ total_dev) {
     __shared__ long long wave_sums[TS_THREADS / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    long long carry = 0;
-    for (long long b0 = 0; b0 < n_runs; b0 += TS_THREADS) {
-        const long long b = b0 + threadIdx.x;
-        const long long own = b < n_runs ? runs[b] : 0;
-        long long x = own;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const long long y = __shfl_up(x, off, 64);
-            if (lane >= off) x += y;
-        }
-        __syncthreads();
-        if (lane == 63) wave_sums[wave] = x;
-        __syncthreads();
-        long long before = 0, all = 0;
-#pragma unroll
-        for (int w = 0; w < TS_THREADS / 64; ++w) {
-            const long long s = wave_sums[w];
-            before += w < wave ? s : 0;
-            all += s;
-        }
-        if (b < n_runs) runs[b] = carry + before + x - own;
-        carry += all;
-    }
-    if (threadIdx.x == 0) *total_dev = carry;
+    const long long all = scan_runs(runs, n_runs, wave_sums);
+    if (threadIdx.x == 0) *total_dev = all;
 }
 
 __global__ __launch_bounds__(TS_THREADS) void tsdf_emit_kernel(const int2* __restrict__ vol, ExGeom g, long long n_vox,
@@ -291,20 +226,6 @@ __global__ __launch_bounds__(64) void tsdf_stats_final_kernel(const long long* _
 }
 
 // ---- host side
-bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + nb && y < x + na;
-}
-
-// NBP_E_* of a volume's geometry, 0 when it is fine
-int check_geometry(const void* vol, const float* lo, float voxel, int nx, int ny, int nz) {
-    NBP_RETURN_IF(!vol || !lo || nx < 1 || ny < 1 || nz < 1, NBP_E_ARG);
-    NBP_RETURN_IF(!(voxel > 0.f) || !isfinite(voxel) || !isfinite(lo[0]) || !isfinite(lo[1]) || !isfinite(lo[2]), NBP_E_ARG);
-    NBP_RETURN_IF((long long)nx * ny > TS_MAX_VOXELS || (long long)nx * ny * nz > TS_MAX_VOXELS, NBP_E_SHAPE);
-    NBP_RETURN_IF(((uintptr_t)vol & 7), NBP_E_SHAPE);
-    return 0;
-}
-
 int check_frames_shape(int H, int W, float tan_half_fov, float z_clip) {
     NBP_RETURN_IF(H < 1 || W < 1 || !(tan_half_fov > 0.f) || !isfinite(tan_half_fov) || !(z_clip > 0.f) || !isfinite(z_clip), NBP_E_ARG);
     NBP_RETURN_IF((long long)H * W > TS_MAX_PIXELS, NBP_E_SHAPE);
@@ -339,8 +260,6 @@ void fill_frames(TsdfItem& it, const float* const* frames, const float* cams, in
 }
 
 unsigned voxel_blocks(int nx, int ny, int nz) { return (unsigned)nbp_cdiv((long long)nx * ny * nz, TS_THREADS); }
-
-long long extract_runs(long long n_vox) { return nbp_cdiv(n_vox, EX_RUN); }
 
 }  // namespace
 

@@ -5,7 +5,7 @@ runs them in nested loops on one GPU), so rank r takes runs r, r+W, r+2W, ... an
 collectives are all_gathers of padded, fixed-width rows (run id first; pad rows = -1), a few KB over RCCL/xGMI, latency bound:
 ONE of an fp32 tensor [runs_per_rank, n_poses + 3] holding (run id, final coverage, AUC, coverage curve) -- gather_results -- and
 one of float64 sums and counts behind it for every record block that is on (testers/record_blocks.py; gather_reconstruction,
-gather_reconstruction_curve, gather_views, gather_fusion, gather_surface), from which rank 0 forms the ratios.  A block that is
+gather_reconstruction_curve, gather_views, gather_fusion, gather_surface, gather_fusion_mesh), from which rank 0 forms the ratios.  A block that is
 off causes no collective, so every other gather keeps its shape.  One
 process per GPU; backend "nccl" (= RCCL on ROCm) with CUDA tensors, "gloo" on CPU-only hosts
 (that path is what the world_size-2 CPU tests exercise)."""
@@ -175,6 +175,15 @@ def gather_surface(results, runs, rank, world, device, spec):
     width = 1 + 2 * (surface_metrics.RAW_HEAD + len(spec["thresholds"])) + len(surface_metrics.RECORD_TAIL)
     return gather_raw(results, runs, rank, world, device, "surface_raw", width,
                       lambda raw: surface_metrics.summarise_record(raw, spec))
+
+
+def gather_fusion_mesh(results, runs, rank, world, device, spec, options=None):
+    """The planning option `fusion` with `mesh`: utility/tsdf_mesh.py::pack_raw's 5 + 2 (3 + T) numbers per run (the mesh's counts and
+    area, GT -> fused surface completeness, the vertices' accuracy against the GT mesh) -> {run id: tsdf_mesh.summarise_raw's dict,
+    with `options`}.  spec: the thresholds, cap and cell (tsdf_mesh.metric_options); options: the volume's."""
+    from .utility import tsdf_mesh
+    return gather_raw(results, runs, rank, world, device, "fusion_mesh_raw", 1 + tsdf_mesh.raw_width(len(spec["thresholds"])),
+                      lambda raw: tsdf_mesh.summarise_raw(raw, spec, options))
 
 
 def gather_views(results, runs, rank, world, device, options):

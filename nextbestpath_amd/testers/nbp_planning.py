@@ -343,6 +343,27 @@ class Rollout(lockstep.LockstepRollout):
         row = fusion_options.pack_raw(rec.raw(), st["observed_voxels"], st["usable_voxels"], self.fusion.frames)
         return row if raw else fusion_options.summarise_raw(row, rec.thresholds, rec.cap, self.fusion.options)
 
+    def fused_mesh(self):
+        """(verts fp32 [V,3], faces int32 [F,3] on the device): the triangle mesh of the rollout's TSDF volume (the option `fusion`),
+        utility/tsdf_mesh.py::mesh's.  Reads the two counts back: for the rollout's end, not for the step."""
+        if self.fusion is None:
+            raise RuntimeError("fused_mesh: the rollout was built without the option `fusion`")
+        self.finish()
+        return self.fusion.mesh()
+
+    def fused_mesh_metrics(self, raw=False):
+        """The fused MESH against the GT (the option `fusion` with `mesh`; hipops.FusedMeshMetrics): its counts and area, GT sample ->
+        fused surface completeness and the accuracy of its vertices against the GT mesh, with the thresholds, cap and cell of the
+        rollout's `surface_metrics` option, or that option's defaults: utility/tsdf_mesh.py::summarise_raw's dict, or with raw=True the
+        float64 vector behind it (tsdf_mesh.pack_raw: what travels between ranks)."""
+        if self.fusion is None:
+            raise RuntimeError("fused_mesh_metrics: the rollout was built without the option `fusion`")
+        self.finish()
+        sm = self._metrics("surface")
+        fm = hipops.FusedMeshMetrics(self.gt, sm, sm.thresholds, sm.cap, sm.cell)      # (holds no device state of its own)
+        row = fm.evaluate(self.fusion)
+        return row if raw else fm.summary(self.fusion.options)
+
     def surface_metrics(self, raw=False, fused=None):
         """Accuracy of the WHOLE cloud so far against the surface of the GT mesh (exact point-to-triangle distances, no GT sample
         in between), and with the option `fusion` of the fused cloud too: utility/surface_metrics.py::summarise_record's dict
@@ -747,7 +768,7 @@ def _result(ro, n_poses):
            "n_points": int(ro.st.cloud_count.item())}
     # the options `policy`, `depth_noise`, `depth_filter` that are on: the normalised specs the rollout was steered and its frames made with
     tags = run_tags(ro.nbp.options if _wants_maps(ro.nbp) else None, ro.camera.depth_noise, ro.camera.depth_filter)
-    # the blocks of the observers that are on (record_blocks.BLOCKS), each measured once, at the rollout's end: the block, and the raw
+    # the blocks of the observers that are on (record_blocks.ALL_BLOCKS), each measured once, at the rollout's end: the block, and the raw
     # sums and counts behind its ratios (what parallel_rollout's gathers carry); formed with what the rollout was made with.
     # `made` / `size` stand where collect_records has opts / params: a field that a Block.context of record_blocks.py starts
     # to read belongs here too (tests/test_record_blocks_host.py runs every context on both, on the CPU)
@@ -818,7 +839,7 @@ def run_many(params, nbp, dataset, runs, device, seeds, test_resolution=0.05, n_
 def collect_records(results, runs, mine, rank, world, device, opts, params, n_poses, scene_names):
     """The tail of a test run, behind run_many: all ranks call this with their own `results` (of the runs `mine` = shard(runs, rank,
     world), in that order) and the options record `opts` (resolve_options).  The coverage curves travel in gather_results, and the raw
-    float64 numbers of every block that is on (record_blocks.BLOCKS) in a gather of their own each.  -> (gathered, out): every rank's
+    float64 numbers of every block that is on (record_blocks.ALL_BLOCKS) in a gather of their own each.  -> (gathered, out): every rank's
     list of gather_results, on rank 0 with each block formed from the gathered row in place of the locally formed one, on the other
     ranks without the blocks; and the dict that goes into the result JSON {scene name: {start: record}} (`scene_names`: by scene
     index), None off rank 0."""
@@ -866,7 +887,7 @@ def test_nbp_planning(params_file, model_file, results_json_file, numGPU, test_s
       `depth_noise`        utility/depth_noise.py::option_spec: the seeded sensor model behind the rasteriser, its spec in every record
       `depth_filter`       utility/depth_filter.py::option_spec: the frame filter behind the sensor, its spec in every record
       `view_metrics`       utility/view_metrics.py::option_spec: "views" in every record
-      `fusion`             utility/tsdf.py::option_spec: a TSDF volume of every frame, "fusion" in every record (judged with `recon_metrics`' options, or its defaults)
+      `fusion`             utility/tsdf.py::option_spec: a TSDF volume of every frame, "fusion" in every record (judged with `recon_metrics`' options, or its defaults); with `mesh` the fused triangle mesh too (utility/tsdf_mesh.py), "fusion_mesh" in every record (judged with `surface_metrics`' options, or its defaults)
       `surface_metrics`    utility/surface_metrics.py::option_spec: "surface" in every record
     With a policy no weights are loaded (`nbp_precision` given with it draws a warning).  Under torchrun the flattened (scene, start
     pose) runs are sharded round-robin over the ranks; the coverage curves are gathered with ONE all_gather over RCCL (backend

@@ -1,4 +1,4 @@
-"""The end-of-rollout blocks of a planning record, declared once: BLOCKS, in the record's order.  Each entry says which normalised
+"""The end-of-rollout blocks of a planning record, declared once: ALL_BLOCKS, in the record's order.  Each entry says which normalised
 option turns the block on, its record key (the raw float64 numbers behind it sit beside it as key + "_raw" until they are gathered),
 how to measure those numbers on a finished Rollout, the summariser's context -- from the options record, the parameters and
 n_poses alone, so the same on every rank -- how to form the block from them, and which gather of parallel_rollout.py carries them.
@@ -7,7 +7,7 @@ from __future__ import annotations
 
 from collections import namedtuple
 
-from ..utility import recon_metrics, surface_metrics, tsdf, view_metrics
+from ..utility import recon_metrics, surface_metrics, tsdf, tsdf_mesh, view_metrics
 
 # option, flag: on when the normalised spec `option` is not None (and its key `flag` set, where one is named).  measure(ro, n_poses,
 # fused) -> the raw float64 array (fused: what ro.fused_cloud() gave, once per record; None without `fusion`).  context(opts,
@@ -51,8 +51,16 @@ RECORD_ORDER = (
           measure=lambda ro, n_poses, fused: ro.surface_metrics(raw=True, fused=fused),
           context=lambda opts, params, n_poses: (opts.surface_metrics,),
           summarise=surface_metrics.summarise_record, gather="gather_surface"),
+    Block("fusion", "mesh", "fusion_mesh",
+          measure=lambda ro, n_poses, fused: ro.fused_mesh_metrics(raw=True),
+          context=lambda opts, params, n_poses: (tsdf_mesh.metric_options(opts.surface_metrics),
+                                                 tsdf.resolved_options(opts.fusion, params.sensor_range)),
+          summarise=tsdf_mesh.summarise_raw, gather="gather_fusion_mesh"),
 )
-BLOCKS = tuple(entry for entry in RECORD_ORDER if entry is not TAGS)
+ALL_BLOCKS = tuple(entry for entry in RECORD_ORDER if entry is not TAGS)
+# the blocks that an observer option turns on by being on, with the curve beside its metric: what names the observer options
+# (nbp_planning.OBSERVER_OPTIONS) and what tests/test_record_blocks_host.py pins.  `fusion_mesh` is an extra of `fusion`, behind them
+BLOCKS = tuple(block for block in ALL_BLOCKS if block.key != "fusion_mesh")
 
 
 def blocks_on(opts):
@@ -60,7 +68,7 @@ def blocks_on(opts):
     def on(block):
         spec = getattr(opts, block.option)
         return spec is not None and (block.flag is None or bool(spec.get(block.flag)))
-    return tuple(block for block in BLOCKS if on(block))
+    return tuple(block for block in ALL_BLOCKS if on(block))
 
 
 def fill(record, blocks, entries, tags):

@@ -1827,3 +1827,121 @@ class TSDFVolume:
         """{"observed_voxels", "usable_voxels"} on the host (one device -> host copy)."""
         observed, usable = tsdf_stats(self.vol, self.min_weight).tolist()
         return {"observed_voxels": int(observed), "usable_voxels": int(usable)}
+
+    def mesh(self):
+        """(verts fp32 [V,3], faces int32 [F,3]) on the device: the fused mesh (utility/tsdf_mesh.py).  Reads the two counts back
+        (one host synchronisation)."""
+        verts, faces, _ = tsdf_mesh(self.vol, self.lo, self.voxel, self.min_weight)
+        return verts, faces
+
+
+# ---- the fused mesh (csrc/nbp_tsdf_mesh.hip; the definition is utility/tsdf_mesh.py)
+def _mesh_out(name, what, t, dtype, width, device):
+    if t is None:
+        return 0
+    shape_ok = isinstance(t, torch.Tensor) and (t.dim() == 2 and t.shape[1] == 3 if width == 3 else t.dim() == 1)
+    if not shape_ok or t.device != device or t.dtype != dtype or not t.is_contiguous():
+        raise ValueError(f"{name}: {what} must be a contiguous {dtype} [capacity{',3' if width == 3 else ''}] tensor on the volume's device")
+    return t.shape[0]
+
+
+def tsdf_mesh(vol, lo, voxel, min_weight=1, verts_out=None, faces_out=None, area2_out=None):
+    """The surface-nets mesh of a volume (tsdf_mesh.mesh, bit for bit) -> (verts fp32 [.,3], faces int32 [.,3], totals int64 [2] on
+    the device = the numbers of vertices and faces).  With verts_out (fp32 [capacity,3]) or faces_out (int32 [capacity,3]; area2_out
+    fp32 of as many rows beside it receives each face's squared area) given: their first min(total, capacity) rows are written and
+    nothing beyond them, with no host synchronisation; a buffer not given is not produced (None).  With none given: counted first,
+    the two totals read back once (the ONE host synchronisation of this path: it belongs to the evaluation at a rollout's end) and
+    exactly-sized tensors returned."""
+    dims = _tsdf_volume("tsdf_mesh", vol)
+    n_vox = dims[0] * dims[1] * dims[2]
+    dev = vol.device
+    vcap = _mesh_out("tsdf_mesh", "verts_out", verts_out, torch.float32, 3, dev)
+    fcap = _mesh_out("tsdf_mesh", "faces_out", faces_out, torch.int32, 3, dev)
+    acap = _mesh_out("tsdf_mesh", "area2_out", area2_out, torch.float32, 1, dev)
+    if area2_out is not None and (faces_out is None or acap != fcap):
+        raise ValueError("tsdf_mesh: area2_out goes with a faces_out of as many rows")
+    L = _lib.lib()
+    lo3 = (C.c_float * 3)(*[float(v) for v in lo])
+    totals = torch.zeros(2, dtype=torch.int64, device=dev)
+
+    def call(verts, faces, area2):
+        nv, nf = (0 if verts is None else verts.shape[0]), (0 if faces is None else faces.shape[0])
+        with torch.cuda.device(dev):
+            ws = _workspace_for("tsdf_mesh", n_vox, lambda: L.nbp_tsdf_mesh_workspace_bytes(n_vox), dev)
+            rc = L.nbp_tsdf_mesh_f32(_lib.ptr(vol), lo3, float(voxel), *dims, int(min_weight), _lib.ptr(verts) if nv else None, nv,
+                                     _lib.ptr(faces) if nf else None, _lib.ptr(area2) if nf and area2 is not None else None, nf,
+                                     _lib.ptr(totals), _lib.ptr(ws), ws.numel(), _st())
+        _lib.check(rc, "nbp_tsdf_mesh_f32")
+
+    if verts_out is not None or faces_out is not None:
+        call(verts_out, faces_out, area2_out)
+        return verts_out, faces_out, totals
+    call(None, None, None)
+    nv, nf = (int(v) for v in totals.tolist())
+    verts = torch.empty(nv, 3, dtype=torch.float32, device=dev)
+    faces = torch.empty(nf, 3, dtype=torch.int32, device=dev)
+    if nv:
+        call(verts, faces, None)
+    return verts, faces, totals
+
+
+class FusedMeshMetrics:
+    """The fused mesh of a TSDFVolume against the GT, on the device (utility/tsdf_mesh.py::reference_raw is the definition).
+    Completeness: GT sample -> fused SURFACE, exact point-to-triangle distances through a MeshPlan over the fused mesh, inside the
+    volume's bounds grown by `cap` (tsdf_mesh.volume_box).  Accuracy: the fused mesh's vertices -> GT mesh, through
+    `gt_mesh_metrics`, the rollout's SurfaceMetrics, which must have these thresholds and this cap.  Area: recon_stats over the
+    faces' squared areas, whose "sum of sqrt" is the area in fixed-order float64.  gt fp32 [G,3] on the device."""
+
+    def __init__(self, gt, gt_mesh_metrics, thresholds=None, cap=5.0, cell=1.0):
+        from . import surface_metrics
+        thresholds = surface_metrics.DEFAULT_THRESHOLDS if thresholds is None else thresholds
+        self.thresholds, self.cap, self.cell = surface_metrics.check_options(thresholds, cap, cell)
+        _nn_points("FusedMeshMetrics", gt, "gt")
+        if gt.shape[0] < 1:
+            raise ValueError("FusedMeshMetrics: an empty GT surface")
+        if tuple(gt_mesh_metrics.thresholds) != self.thresholds or gt_mesh_metrics.cap != self.cap:
+            raise ValueError("FusedMeshMetrics: gt_mesh_metrics was built with other thresholds or another cap")
+        self.gt, self.G, self.gt_mesh_metrics = gt, gt.shape[0], gt_mesh_metrics
+        self.row = self.mesh = None         # the last evaluation: its raw row, and (verts, faces) on the device
+
+    def evaluate(self, volume):
+        """Meshes `volume` (a TSDFVolume) and measures it -> tsdf_mesh.pack_raw's float64 vector on the host (kept for raw() /
+        summary()).  Synchronises with the host: the mesh's counts, the plan's build and the results are read back."""
+        from . import tsdf_mesh as definition
+        dev = volume.vol.device
+        counts = tsdf_mesh(volume.vol, volume.lo, volume.voxel, volume.min_weight)[2]
+        _, crossings = tsdf_extract(volume.vol, volume.lo, volume.voxel, volume.min_weight,
+                                    out=torch.empty(0, 3, dtype=torch.float32, device=dev))
+        nv, nf, nc = (int(v) for v in torch.cat([counts, crossings]).tolist())
+        verts = torch.empty(max(nv, 1), 3, dtype=torch.float32, device=dev)
+        faces = torch.empty(max(nf, 1), 3, dtype=torch.int32, device=dev)
+        area2 = torch.empty(max(nf, 1), dtype=torch.float32, device=dev)
+        if nv:
+            tsdf_mesh(volume.vol, volume.lo, volume.voxel, volume.min_weight, verts, faces, area2)
+        if nf:
+            lo, hi = definition.volume_box(volume.lo, volume.voxel, volume.dims, self.cap)
+            plan = MeshPlan(verts[:nv], faces[:nf], (lo.tolist(), hi.tolist()), self.cell)
+            comp = recon_stats(plan.dist2(self.gt, self.cap), self.thresholds)
+            area = recon_stats(area2[:nf], self.thresholds)[0][:1]
+            flat = torch.cat([comp[0], comp[1].double(), area]).cpu().numpy()
+            T = len(self.thresholds)
+            comp_sums, comp_counts, area = flat[0:2], flat[2:2 + T], float(flat[2 + T])
+        else:                           # no face, no plan: the definition's row, every GT point `cap` away
+            comp_sums, comp_counts = definition.cap_row(self.G, self.thresholds, self.cap)
+            area = 0.0
+        if not nv:
+            verts.zero_()                # (one dummy row; the count says that none is valid)
+        self.gt_mesh_metrics.evaluate(verts, torch.full((1,), nv, dtype=torch.int64, device=dev))
+        self.row = definition.pack_raw(nv, nf, nf // 2, nc, area, comp_sums, comp_counts, self.G, self.gt_mesh_metrics.raw())
+        self.mesh = (verts[:nv], faces[:nf])
+        return self.row
+
+    def raw(self):
+        if self.row is None:
+            raise RuntimeError("FusedMeshMetrics: evaluate() first")
+        return self.row
+
+    def summary(self, options=None):
+        """The last evaluation as tsdf_mesh.summarise_raw's dict (`options`: the volume's, for the block's "options")."""
+        from . import tsdf_mesh as definition
+        return definition.summarise_raw(self.raw(), {"thresholds": self.thresholds, "cap": self.cap, "cell": self.cell}, options)

@@ -33,7 +33,7 @@ f32 = np.float32
 QUANT = 127                            # a distance of +-trunc is stored as +-127
 MAX_VOXELS = 1 << 28
 DEFAULTS = {"voxel": 0.25, "trunc": 1.0, "min_weight": 1}
-_KEYS = {"voxel", "trunc", "max_depth", "min_weight"}
+_KEYS = {"voxel", "trunc", "max_depth", "min_weight", "mesh"}
 RAW_TAIL = ("observed_voxels", "usable_voxels", "frames")       # what follows recon_metrics.pack_raw's numbers in a raw row
 
 
@@ -48,7 +48,8 @@ def _is_num(v):
 def option_spec(option):
     """The planning option `fusion` -> None (off) or the normalised dict: None / False = off, True = the defaults, a dict with any
     of `voxel` (0.25), `trunc` (1.0, at least 2 voxel), `max_depth` (absent: the parameters' sensor_range, the range the
-    un-projection keeps) and `min_weight` (1, an integer >= 1).  Anything else is a ValueError."""
+    un-projection keeps), `min_weight` (1, an integer >= 1) and `mesh` (true / false: the triangle mesh of utility/tsdf_mesh.py
+    out of the volume at the rollout's end as well; the key is there only when it is on).  Anything else is a ValueError."""
     if option is None or option is False:
         return None
     if option is True:
@@ -57,6 +58,8 @@ def option_spec(option):
         raise ValueError("fusion: None, True or a dict with the keys " + " / ".join(sorted(_KEYS)) + " expected")
     spec = dict(DEFAULTS)
     spec.update(option)
+    if not isinstance(spec.get("mesh", False), bool):
+        raise ValueError("fusion: mesh must be true or false")
     for k in ("voxel", "trunc"):
         if not _is_num(spec[k]) or not (spec[k] > 0 and math.isfinite(spec[k])):
             raise ValueError(f"fusion: {k} must be positive and finite")
@@ -69,6 +72,8 @@ def option_spec(option):
     out = {"voxel": float(spec["voxel"]), "trunc": float(spec["trunc"]), "min_weight": int(spec["min_weight"])}
     if "max_depth" in spec:
         out["max_depth"] = float(spec["max_depth"])
+    if spec.get("mesh", False):
+        out["mesh"] = True
     return out
 
 
