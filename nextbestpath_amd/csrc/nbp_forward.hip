@@ -6,6 +6,7 @@
 // nn.Upsample and torch.cat in the conv's operand gather, the attention gate's two 1x1
 // convolutions as ONE GEMM over K=[g|x] followed by a psi+multiply tail.
 #include "common.h"
+#include "nbp_carve.h"
 #include "nbp_internal.h"
 #include <stdio.h>
 #include <stdlib.h>
@@ -276,16 +277,6 @@ extern "C" void nbp_free_weights(nbp_weights* handle) { free(handle); }
 // ------------------------------------------------------------------ forward
 namespace {
 
-struct Bump {
-    char* base; size_t size, off; bool dry;
-    template <typename T> T* take(size_t count) {
-        size_t bytes = (count * sizeof(T) + 255) / 256 * 256;
-        size_t o = off; off += bytes;
-        if (dry) return (T*)(uintptr_t)256;   // non-null dummy
-        return (T*)(base + o);
-    }
-};
-
 struct Timer {
     hipStream_t st;
     nbp_layer_timing* out; int cap; int n;
@@ -322,7 +313,7 @@ struct Timer {
 
 // The two arithmetic paths behind the same driver: element type of the activations, K-chunk width, launchers.
 struct NoCtx {
-    int init(Bump&, hipStream_t, bool) { return 0; }
+    int init(Carver&, hipStream_t, bool) { return 0; }
     void offer_gated(void*, void*) {}
     bool took_gated() { return false; }
     void offer_pool(void*) {}
@@ -370,7 +361,7 @@ struct AmaxBook {
     hipStream_t st = nullptr;
     const void* key[128];
     unsigned* val[128];
-    int init(Bump& bp, hipStream_t s, bool dry) {
+    int init(Carver& bp, hipStream_t s, bool dry) {
         st = s; next = n = 0;
         slots = bp.take<unsigned>(128 * 64);       // 64 words per tensor (nbp_split.hip: AMAX_WORDS)
         // zeroed by a KERNEL, not hipMemsetAsync: in a captured forward (packing.ForwardGraph) the memset node of ROCm 7.2's
@@ -586,12 +577,12 @@ size_t splitk_scratch_floats(long long M, int N, int cin_total, int taps, int gr
 
 // Runs (or, with h == nullptr, only sizes) the network.
 template <typename P>
-int run_forward(const nbp_weights* h, const float* x, int B, int S, float* out1, float* out2, Bump& bp,
+int run_forward(const nbp_weights* h, const float* x, int B, int S, float* out1, float* out2, Carver& bp,
                 hipStream_t st, Timer* tm = nullptr) {
     typedef typename P::T T;
     typedef typename P::Ops Ops;
     char nm[48];
-    const bool dry = bp.dry;
+    const bool dry = bp.dry();
     const int enc[5] = {64, 128, 256, 512, 1024};
     int rc = 0;
     // split-K scratch: sized for the worst layer, shared by all (stream-ordered)
@@ -740,9 +731,9 @@ int run_forward(const nbp_weights* h, const float* x, int B, int S, float* out1,
 template <typename P>
 static size_t workspace_bytes_impl(int B, int S) {
     if (B < 1 || S < 16 || S % 16) return 0;
-    Bump bp{nullptr, 0, 0, true};
+    Carver bp;
     run_forward<P>(nullptr, nullptr, B, S, nullptr, nullptr, bp, nullptr);
-    return bp.off + 256;
+    return bp.bytes();
 }
 
 template <typename P>
@@ -754,8 +745,7 @@ static int forward_impl(const nbp_weights* handle, const float* x, int B, int S,
     NBP_RETURN_IF(B < 1, NBP_E_ARG);
     NBP_RETURN_IF(S < 16 || S % 16, NBP_E_SHAPE);
     NBP_RETURN_IF(ws_bytes < workspace_bytes_impl<P>(B, S), NBP_E_WS);
-    uintptr_t p = ((uintptr_t)ws + 255) / 256 * 256;
-    Bump bp{(char*)p, ws_bytes, 0, false};
+    Carver bp(ws);
     if (!timings_host) return run_forward<P>(handle, x, B, S, out1, out2, bp, (hipStream_t)stream);
     NBP_RETURN_IF(!n_entries_host || max_entries < 1, NBP_E_ARG);
     static Timer tm;   // 256 events; the profiling entry points are not re-entrant

@@ -3,15 +3,13 @@
 // inside each translation unit (everything is in an anonymous namespace); not part of the C ABI.
 #pragma once
 #include "common.h"
+#include "nbp_carve.h"
 
 #include <math.h>
 
 namespace {
 
 struct Grid { float lo[3]; float inv; int n[3]; };
-
-// (host) a carved buffer's size, rounded up to the 256-byte alignment of the next one
-size_t al256(size_t b) { return (b + 255) / 256 * 256; }
 
 // (host) Largest float x with sqrtf(x) < thr (thr > 0 finite): the squared-distance form of `distance < thr`.
 float sq_below(float thr) {
@@ -101,7 +99,10 @@ __global__ __launch_bounds__(256) void grid_scan_kernel(const int* __restrict__ 
 }
 
 
-// start[0..ncell] = exclusive scan of count[0..ncell); tsum needs ncell / SCAN_TILE + 1 ints.
+// (host) the scan's tile sums for ncell cells, as every grid layout takes them
+inline int* take_scan_tsum(Carver& c, size_t ncell) { return c.take<int>(ncell / SCAN_TILE + 1); }
+
+// start[0..ncell] = exclusive scan of count[0..ncell); tsum: take_scan_tsum's.
 inline int grid_exclusive_scan(const int* count, long long ncell, int* tsum, int* start, hipStream_t st) {
     const int ntiles = (int)(ncell / SCAN_TILE + 1);
     grid_tilesum_kernel<<<ntiles, 256, 0, st>>>(count, ncell, tsum);

@@ -7,6 +7,7 @@
 // reference's fp32 sequence: sub, negate, add 40, multiply by fp32(S/80), rint (half to
 // even), bounds test -- so the integer cell of every point is bit-identical.
 #include "common.h"
+#include "nbp_carve.h"
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
@@ -438,14 +439,14 @@ static BinDesc bin_desc(const float* lo_xz, const float* hi_xz, long long capaci
     unsigned hsize = 1024;
     while (hsize < 2u * (unsigned)d.max_pages) hsize *= 2;
     d.hash_mask = hsize - 1;
-    unsigned long long off = 256;
-    auto take = [&](unsigned long long bytes) { const unsigned long long o = off; off += (bytes + 255) / 256 * 256; return o; };
-    d.off_count = take((unsigned long long)d.nt * 4);
-    d.off_table = take((unsigned long long)hsize * 8);
-    d.off_info = take((unsigned long long)d.max_pages * 4);
-    d.off_ovf = take((unsigned long long)BIN_OVF * 4);
-    d.off_pages = take((unsigned long long)d.max_pages * BIN_PAGE * 12);
-    d.total_bytes = off;
+    Carver c;                                              // dry: the store keeps offsets, from its 256-aligned address (no base slack)
+    c.take_bytes(sizeof(BinDesc));                         // the header, 256 bytes reserved
+    d.off_count = c.take_bytes((size_t)d.nt * 4);
+    d.off_table = c.take_bytes((size_t)hsize * 8);
+    d.off_info = c.take_bytes((size_t)d.max_pages * 4);
+    d.off_ovf = c.take_bytes((size_t)BIN_OVF * 4);
+    d.off_pages = c.take_bytes((size_t)d.max_pages * BIN_PAGE * 12);
+    d.total_bytes = c.end();
     return d;
 }
 // what nbp_cloud_bins_init wrote into a store's header, by store address (a store re-initialised elsewhere, or one the table does not

@@ -43,21 +43,14 @@ int nn_grid(const float* lo, const float* hi, float w, BoxGrid* b) {
     return 0;
 }
 
-// A plan: `start` [ncell + 1], then the payload (sorted points, or triangles' vertices) as float4.
-void nn_plan_carve(const void* plan, size_t ncell, int** start, float4** payload) {
-    char* p = (char*)(((uintptr_t)plan + 255) / 256 * 256);
-    *start = (int*)p; p += al256((ncell + 1) * 4);
-    *payload = (float4*)p;
-}
-size_t nn_plan_size(size_t ncell, size_t payload_bytes) { return 256 + al256((ncell + 1) * 4) + al256(payload_bytes); }
+// A plan: `start` [ncell + 1], then `n_payload` float4 of payload (sorted points, or triangles' vertices).
+struct NNPlan { int* start; float4* payload; };
+NNPlan nn_plan_layout(Carver& c, size_t ncell, size_t n_payload) { return {c.take<int>(ncell + 1), c.take<float4>(n_payload)}; }
+NNPlan nn_plan_of(const void* plan, size_t ncell) { return carve(plan, nn_plan_layout, ncell, (size_t)0); }       // (a reader needs no payload size)
 
-// A build's scratch: the per-cell counts and the scan's tile sums; returns what follows them (the caller's own tail).
-char* nn_scratch_carve(void* ws, size_t ncell, int** count, int** tsum) {
-    char* p = (char*)(((uintptr_t)ws + 255) / 256 * 256);
-    *count = (int*)p; p += al256(ncell * 4);
-    *tsum = (int*)p; p += al256((ncell / SCAN_TILE + 1) * 4);
-    return p;
-}
-size_t nn_scratch_bytes(size_t ncell) { return 256 + al256(ncell * 4) + al256((ncell / SCAN_TILE + 1) * 4); }
+// A build's scratch: the per-cell counts and the scan's tile sums; a build's own tail follows on the same carver.
+struct NNScratch { int* count; int* tsum; };
+NNScratch nn_scratch_layout(Carver& c, size_t ncell) { return {c.take<int>(ncell), take_scan_tsum(c, ncell)}; }
+size_t nn_scratch_bytes(size_t ncell) { return carved_bytes(0, nn_scratch_layout, ncell); }
 
 }  // namespace

@@ -432,13 +432,20 @@ static int coverage_plan_grid(const float* bbox_lo, const float* bbox_hi, float 
     return 0;
 }
 
+// nbp_coverage_count_f32's workspace: the grid's counts and starts, the sample's cell and slot, the sample and its sorted copy
+constexpr size_t COVERAGE_WS_SLACK = 256;
+struct CoverageWs { int *count, *start, *cell_of, *slot_of; float *sp, *sorted; int* tsum; };
+static CoverageWs coverage_ws_layout(Carver& c, size_t ncell, size_t k) {
+    return {c.take<int>(ncell), c.take<int>(ncell + 1), c.take<int>(k), c.take<int>(k), c.take<float>(3 * k), c.take<float>(3 * k),
+            take_scan_tsum(c, ncell)};
+}
+
 extern "C" size_t nbp_coverage_workspace_bytes(const float* bbox_lo_host, const float* bbox_hi_host, float threshold,
                                                long long sample_k) {
     Grid g; size_t ncell;
     if (!bbox_lo_host || !bbox_hi_host || !(threshold > 0) || sample_k < 1) return 0;
     if (coverage_grid(bbox_lo_host, bbox_hi_host, threshold, &g, &ncell)) return 0;
-    return al256(ncell * 4) + al256((ncell + 1) * 4) + 2 * al256((size_t)sample_k * 4) +
-           2 * al256((size_t)sample_k * 12) + al256((ncell / SCAN_TILE + 1) * 4) + 512;
+    return carved_bytes(COVERAGE_WS_SLACK, coverage_ws_layout, ncell, (size_t)sample_k);
 }
 
 extern "C" int nbp_coverage_count_f32(const float* gt3, int G, const float* pc3, long long N, const long long* N_dev_or_null,
@@ -453,43 +460,38 @@ extern "C" int nbp_coverage_count_f32(const float* gt3, int G, const float* pc3,
     if (rc) return rc;
     NBP_RETURN_IF(ws_bytes < nbp_coverage_workspace_bytes(bbox_lo_host, bbox_hi_host, threshold, sample_k), NBP_E_WS);
     hipStream_t st = (hipStream_t)stream;
-    char* p = (char*)(((uintptr_t)ws + 255) / 256 * 256);
-    int* count = (int*)p; p += al256(ncell * 4);
-    int* start = (int*)p; p += al256((ncell + 1) * 4);
-    int* cell_of = (int*)p; p += al256((size_t)sample_k * 4);
-    int* slot_of = (int*)p; p += al256((size_t)sample_k * 4);
-    float* sp = (float*)p; p += al256((size_t)sample_k * 12);
-    float* sorted = (float*)p; p += al256((size_t)sample_k * 12);
-    int* tsum = (int*)p;
-    hipError_t e = hipMemsetAsync(count, 0, ncell * 4, st);
+    const CoverageWs L = carve(ws, coverage_ws_layout, ncell, (size_t)sample_k);
+    hipError_t e = hipMemsetAsync(L.count, 0, ncell * 4, st);
     if (e != hipSuccess) return (int)e;
     e = hipMemsetAsync(count_out, 0, sizeof(int), st);
     if (e != hipSuccess) return (int)e;
     const long long work = N_dev_or_null ? sample_k : (N < sample_k ? N : sample_k);
     const int grid = nbp_ew_grid(work > 0 ? work : 1, 256);
-    coverage_bin_kernel<<<grid, 256, 0, st>>>(pc3, N_dev_or_null, N, sample_k, seed, g, sp, cell_of, slot_of, count, m_out);
+    coverage_bin_kernel<<<grid, 256, 0, st>>>(pc3, N_dev_or_null, N, sample_k, seed, g, L.sp, L.cell_of, L.slot_of, L.count, m_out);
     if ((rc = nbp_launch_status())) return rc;
-    if ((rc = grid_exclusive_scan(count, (long long)ncell, tsum, start, st))) return rc;
-    coverage_scatter_kernel<<<grid, 256, 0, st>>>(sp, cell_of, slot_of, start, m_out, sorted);
+    if ((rc = grid_exclusive_scan(L.count, (long long)ncell, L.tsum, L.start, st))) return rc;
+    coverage_scatter_kernel<<<grid, 256, 0, st>>>(L.sp, L.cell_of, L.slot_of, L.start, m_out, L.sorted);
     if ((rc = nbp_launch_status())) return rc;
-    coverage_query_kernel<<<(unsigned)nbp_cdiv((long long)G * 16, 256), 256, 0, st>>>(gt3, G, g, threshold, sorted, start,
+    coverage_query_kernel<<<(unsigned)nbp_cdiv((long long)G * 16, 256), 256, 0, st>>>(gt3, G, g, threshold, L.sorted, L.start,
                                                                                     count_out);
     return nbp_launch_status();
 }
 
 // ---- planned coverage (one GT grid per rollout)
-static void plan_carve(void* plan, size_t ncell, int G, int** start, float4** sorted, unsigned** stamp) {
-    char* p = (char*)(((uintptr_t)plan + 255) / 256 * 256);
-    *start = (int*)p; p += al256((ncell + 1) * 4);
-    *sorted = (float4*)p; p += al256((size_t)G * 16);
-    *stamp = (unsigned*)p;
+struct CoveragePlan { int* start; float4* sorted; unsigned* stamp; };
+static CoveragePlan plan_layout(Carver& c, size_t ncell, size_t G) {
+    return {c.take<int>(ncell + 1), c.take<float4>(G), c.take<unsigned>(G)};
+}
+struct PlanBuildWs { int *count, *tsum, *cell_of, *slot_of; };          // the plan build's scratch
+static PlanBuildWs plan_build_ws_layout(Carver& c, size_t ncell, size_t G) {
+    return {c.take<int>(ncell), take_scan_tsum(c, ncell), c.take<int>(G), c.take<int>(G)};
 }
 
 extern "C" size_t nbp_coverage_plan_bytes(const float* bbox_lo_host, const float* bbox_hi_host, float threshold, int G) {
     Grid g; size_t ncell;
     if (!bbox_lo_host || !bbox_hi_host || !(threshold > 0) || G < 1) return 0;
     if (coverage_plan_grid(bbox_lo_host, bbox_hi_host, threshold, &g, &ncell)) return 0;
-    return 256 + al256((ncell + 1) * 4) + al256((size_t)G * 16) + al256((size_t)G * 4);
+    return carved_bytes(0, plan_layout, ncell, (size_t)G);
 }
 
 extern "C" size_t nbp_coverage_plan_workspace_bytes(const float* bbox_lo_host, const float* bbox_hi_host, float threshold,
@@ -497,7 +499,7 @@ extern "C" size_t nbp_coverage_plan_workspace_bytes(const float* bbox_lo_host, c
     Grid g; size_t ncell;
     if (!bbox_lo_host || !bbox_hi_host || !(threshold > 0) || G < 1) return 0;
     if (coverage_plan_grid(bbox_lo_host, bbox_hi_host, threshold, &g, &ncell)) return 0;
-    return 256 + al256(ncell * 4) + al256((ncell / SCAN_TILE + 1) * 4) + 2 * al256((size_t)G * 4);
+    return carved_bytes(0, plan_build_ws_layout, ncell, (size_t)G);
 }
 
 extern "C" int nbp_coverage_plan_build_f32(const float* gt3, int G, float threshold, const float* bbox_lo_host,
@@ -511,20 +513,15 @@ extern "C" int nbp_coverage_plan_build_f32(const float* gt3, int G, float thresh
     NBP_RETURN_IF(plan_bytes < nbp_coverage_plan_bytes(bbox_lo_host, bbox_hi_host, threshold, G), NBP_E_WS);
     NBP_RETURN_IF(ws_bytes < nbp_coverage_plan_workspace_bytes(bbox_lo_host, bbox_hi_host, threshold, G), NBP_E_WS);
     hipStream_t st = (hipStream_t)stream;
-    int* start; float4* sorted; unsigned* stamp;
-    plan_carve(plan, ncell, G, &start, &sorted, &stamp);
-    char* p = (char*)(((uintptr_t)ws + 255) / 256 * 256);
-    int* count = (int*)p; p += al256(ncell * 4);
-    int* tsum = (int*)p; p += al256((ncell / SCAN_TILE + 1) * 4);
-    int* cell_of = (int*)p; p += al256((size_t)G * 4);
-    int* slot_of = (int*)p;
-    hipError_t e = hipMemsetAsync(count, 0, ncell * 4, st);
+    const CoveragePlan pl = carve(plan, plan_layout, ncell, (size_t)G);
+    const PlanBuildWs w = carve(ws, plan_build_ws_layout, ncell, (size_t)G);
+    hipError_t e = hipMemsetAsync(w.count, 0, ncell * 4, st);
     if (e != hipSuccess) return (int)e;
     const int grid = nbp_ew_grid(G, 256);
-    points_bin_kernel<<<grid, 256, 0, st>>>(gt3, G, g, cell_of, slot_of, count);
+    points_bin_kernel<<<grid, 256, 0, st>>>(gt3, G, g, w.cell_of, w.slot_of, w.count);
     if ((rc = nbp_launch_status())) return rc;
-    if ((rc = grid_exclusive_scan(count, (long long)ncell, tsum, start, st))) return rc;
-    points_scatter4_kernel<<<grid, 256, 0, st>>>(gt3, G, cell_of, slot_of, start, sorted, stamp);
+    if ((rc = grid_exclusive_scan(w.count, (long long)ncell, w.tsum, pl.start, st))) return rc;
+    points_scatter4_kernel<<<grid, 256, 0, st>>>(gt3, G, w.cell_of, w.slot_of, pl.start, pl.sorted, pl.stamp);
     return nbp_launch_status();
 }
 
@@ -538,16 +535,15 @@ extern "C" int nbp_coverage_count_planned_f32(void* plan, int G, float threshold
     Grid g; size_t ncell;
     int rc = coverage_plan_grid(bbox_lo_host, bbox_hi_host, threshold, &g, &ncell);
     if (rc) return rc;
-    int* start; float4* sorted; unsigned* stamp;
-    plan_carve(plan, ncell, G, &start, &sorted, &stamp);
+    const CoveragePlan pl = carve(plan, plan_layout, ncell, (size_t)G);
     const long long work = N_dev_or_null ? sample_k : (N < sample_k ? N : sample_k);
     // 4 lanes per point, runs walked 4 GT points at a time: 34 us with the tally against 39 for one point per iteration;
     // 8 or 16 lanes per point or 8 points per iteration measure the same (the kernel is then bound by the ~50 M
     // point-pair tests, not by the chains)
     coverage_mark_kernel<4, 4><<<nbp_ew_grid((work > 0 ? work : 1) * 4, 256), 256, 0, (hipStream_t)stream>>>(
-        pc3, N_dev_or_null, N, sample_k, seed, g, sq_below(threshold), sorted, start, stamp, epoch, m_out);
+        pc3, N_dev_or_null, N, sample_k, seed, g, sq_below(threshold), pl.sorted, pl.start, pl.stamp, epoch, m_out);
     if ((rc = nbp_launch_status())) return rc;
-    coverage_tally_kernel<<<(unsigned)(G < 16384 ? 1 : 16), 256, 0, (hipStream_t)stream>>>(stamp, G, epoch, count_accum);
+    coverage_tally_kernel<<<(unsigned)(G < 16384 ? 1 : 16), 256, 0, (hipStream_t)stream>>>(pl.stamp, G, epoch, count_accum);
     return nbp_launch_status();
 }
 
@@ -571,9 +567,8 @@ extern "C" int nbp_coverage_count_planned_batch_f32(int n, void* const* plans, c
         size_t ncell;
         const int rc = coverage_plan_grid(bbox_lo_host + 3 * q, bbox_hi_host + 3 * q, threshold, &a.g, &ncell);
         if (rc) return rc;
-        int* start; float4* sorted; unsigned* stamp;
-        plan_carve(plans[q], ncell, G[q], &start, &sorted, &stamp);
-        a.pc = pc3[q]; a.n_dev = N_dev[q]; a.n_host = N[q]; a.k = sample_k[q]; a.gt_sorted = sorted; a.gt_start = start; a.stamp = stamp;
+        const CoveragePlan pl = carve(plans[q], plan_layout, ncell, (size_t)G[q]);
+        a.pc = pc3[q]; a.n_dev = N_dev[q]; a.n_host = N[q]; a.k = sample_k[q]; a.gt_sorted = pl.sorted; a.gt_start = pl.start; a.stamp = pl.stamp;
         a.count = count_accum[q]; a.m_out = m_out[q]; a.d2max = d2max; a.seed = seed[q]; a.epoch = epoch[q]; a.G = G[q];
         const long long work = N_dev[q] ? sample_k[q] : (N[q] < sample_k[q] ? N[q] : sample_k[q]);
         a.gx_mark = r < n ? (unsigned)nbp_ew_grid((work > 0 ? work : 1) * 4, 256) : 0;

@@ -279,36 +279,38 @@ __global__ __launch_bounds__(64) void curve_final_kernel(const CurveBatch b) {
 }
 
 // ---- host (the grid over the caller's box, the argument checks and the carves: nbp_nn_grid.h)
-size_t nn_plan_bytes(size_t ncell, long long T) { return nn_plan_size(ncell, (size_t)(T > 0 ? T : 1) * 16); }
-size_t nn_plan_ws_bytes(size_t ncell, long long T) { return nn_scratch_bytes(ncell) + 2 * al256((size_t)(T > 0 ? T : 1) * 4); }
+// a plan holds n = max(T, 1) sorted points; its build's scratch ends with their cell and slot
+size_t nn_points(long long T) { return (size_t)(T > 0 ? T : 1); }
+struct NNBuildWs { NNScratch s; int* cell_of; int* slot_of; };
+NNBuildWs nn_build_ws_layout(Carver& c, size_t ncell, size_t n) { return {nn_scratch_layout(c, ncell), c.take<int>(n), c.take<int>(n)}; }
+// nbp_nn_dist2_f32's workspace: the plan, then its build's scratch
+constexpr size_t NN_DIST2_SLACK = 256;          // (historical: the scratch once aligned its own base behind the plan)
+struct NNDist2Ws { NNPlan plan; NNBuildWs ws; };
+NNDist2Ws nn_dist2_layout(Carver& c, size_t ncell, size_t n) { return {nn_plan_layout(c, ncell, n), nn_build_ws_layout(c, ncell, n)}; }
+size_t nn_plan_bytes(size_t ncell, long long T) { return carved_bytes(0, nn_plan_layout, ncell, nn_points(T)); }
+size_t nn_plan_ws_bytes(size_t ncell, long long T) { return carved_bytes(0, nn_build_ws_layout, ncell, nn_points(T)); }
+size_t nn_dist2_ws_bytes(size_t ncell, long long T) { return carved_bytes(NN_DIST2_SLACK, nn_dist2_layout, ncell, nn_points(T)); }
 
-int nn_build(const float* t3, long long T, const long long* T_dev, const BoxGrid& b, void* plan, void* ws, hipStream_t st) {
-    int *start, *count, *tsum; float4* sorted;
-    nn_plan_carve(plan, b.ncell, &start, &sorted);
-    char* p = nn_scratch_carve(ws, b.ncell, &count, &tsum);
-    int* cell_of = (int*)p; p += al256((size_t)(T > 0 ? T : 1) * 4);
-    int* slot_of = (int*)p;
-    hipError_t e = hipMemsetAsync(count, 0, b.ncell * 4, st);
+int nn_build(const float* t3, long long T, const long long* T_dev, const BoxGrid& b, const NNPlan& pl, const NNBuildWs& w, hipStream_t st) {
+    hipError_t e = hipMemsetAsync(w.s.count, 0, b.ncell * 4, st);
     if (e != hipSuccess) return (int)e;
     int rc;
     const int grid = nbp_ew_grid(T > 0 ? T : 1, 256);
     if (T > 0) {
-        nn_bin_kernel<<<grid, 256, 0, st>>>(t3, T_dev, T, b.g, b.bx, cell_of, slot_of, count);
+        nn_bin_kernel<<<grid, 256, 0, st>>>(t3, T_dev, T, b.g, b.bx, w.cell_of, w.slot_of, w.s.count);
         if ((rc = nbp_launch_status())) return rc;
     }
-    if ((rc = grid_exclusive_scan(count, (long long)b.ncell, tsum, start, st))) return rc;
+    if ((rc = grid_exclusive_scan(w.s.count, (long long)b.ncell, w.s.tsum, pl.start, st))) return rc;
     if (T > 0) {
-        nn_scatter_kernel<<<grid, 256, 0, st>>>(t3, T_dev, T, cell_of, slot_of, start, sorted);
+        nn_scatter_kernel<<<grid, 256, 0, st>>>(t3, T_dev, T, w.cell_of, w.slot_of, pl.start, pl.payload);
         if ((rc = nbp_launch_status())) return rc;
     }
     return 0;
 }
 
-int nn_query(const void* plan, const BoxGrid& b, float cap, float w, const float* q3, long long Q, const long long* Q_dev, float* d2,
+int nn_query(const NNPlan& pl, const BoxGrid& b, float cap, float w, const float* q3, long long Q, const long long* Q_dev, float* d2,
              hipStream_t st) {
-    int* start; float4* sorted;
-    nn_plan_carve(plan, b.ncell, &start, &sorted);
-    return shell_query(NNPoints{sorted}, start, b.g, cap, w, q3, Q, Q_dev, d2, st);
+    return shell_query(NNPoints{pl.payload}, pl.start, b.g, cap, w, q3, Q, Q_dev, d2, st);
 }
 
 // a *_bytes function's grid: false is its refusal (0 bytes)
@@ -337,7 +339,7 @@ extern "C" int nbp_nn_plan_build_f32(const float* t3, long long T, const long lo
     const int rc = nn_grid(lo_host, hi_host, cell, &b);
     if (rc) return rc;
     NBP_RETURN_IF(plan_bytes < nn_plan_bytes(b.ncell, T) || ws_bytes < nn_plan_ws_bytes(b.ncell, T), NBP_E_WS);
-    return nn_build(t3, T, T_dev_or_null, b, plan, ws, (hipStream_t)stream);
+    return nn_build(t3, T, T_dev_or_null, b, nn_plan_of(plan, b.ncell), carve(ws, nn_build_ws_layout, b.ncell, nn_points(T)), (hipStream_t)stream);
 }
 
 extern "C" int nbp_nn_dist2_planned_f32(const void* plan, const float* lo_host, const float* hi_host, float cell, float cap,
@@ -348,12 +350,12 @@ extern "C" int nbp_nn_dist2_planned_f32(const void* plan, const float* lo_host, 
     BoxGrid b;
     const int rc = nn_grid(lo_host, hi_host, cell, &b);
     if (rc) return rc;
-    return nn_query(plan, b, cap, cell, q3, Q, Q_dev_or_null, d2, (hipStream_t)stream);
+    return nn_query(nn_plan_of(plan, b.ncell), b, cap, cell, q3, Q, Q_dev_or_null, d2, (hipStream_t)stream);
 }
 
 extern "C" size_t nbp_nn_dist2_workspace_bytes(const float* lo_host, const float* hi_host, float cell, long long T) {
     BoxGrid b;
-    return nn_bytes_grid(lo_host, hi_host, cell, T, &b) ? nn_plan_bytes(b.ncell, T) + nn_plan_ws_bytes(b.ncell, T) : 0;
+    return nn_bytes_grid(lo_host, hi_host, cell, T, &b) ? nn_dist2_ws_bytes(b.ncell, T) : 0;
 }
 
 extern "C" int nbp_nn_dist2_f32(const float* q3, long long Q, const long long* Q_dev_or_null, const float* t3, long long T,
@@ -365,11 +367,10 @@ extern "C" int nbp_nn_dist2_f32(const float* q3, long long Q, const long long* Q
     BoxGrid b;
     int rc = nn_grid(lo_host, hi_host, cell, &b);
     if (rc) return rc;
-    NBP_RETURN_IF(ws_bytes < nn_plan_bytes(b.ncell, T) + nn_plan_ws_bytes(b.ncell, T), NBP_E_WS);
-    void* plan = ws;
-    void* scratch = (char*)ws + nn_plan_bytes(b.ncell, T);
-    if ((rc = nn_build(t3, T, T_dev_or_null, b, plan, scratch, (hipStream_t)stream))) return rc;
-    return nn_query(plan, b, cap, cell, q3, Q, Q_dev_or_null, d2, (hipStream_t)stream);
+    NBP_RETURN_IF(ws_bytes < nn_dist2_ws_bytes(b.ncell, T), NBP_E_WS);
+    const NNDist2Ws L = carve(ws, nn_dist2_layout, b.ncell, nn_points(T));
+    if ((rc = nn_build(t3, T, T_dev_or_null, b, L.plan, L.ws, (hipStream_t)stream))) return rc;
+    return nn_query(L.plan, b, cap, cell, q3, Q, Q_dev_or_null, d2, (hipStream_t)stream);
 }
 
 extern "C" size_t nbp_recon_stats_workspace_bytes(void) { return 256 + (size_t)STATS_BLOCKS * STATS_ROW * 8; }
@@ -436,9 +437,8 @@ extern "C" int nbp_recon_curve_update_batch_f32(int n, const void* const* plans,
         const int rc = nn_grid(lo, hi, cell[q], &bg);
         if (rc) return rc;
         a.g = bg.g; a.bx = bg.bx;
-        int* start; float4* sorted;
-        nn_plan_carve(plans[q], bg.ncell, &start, &sorted);
-        a.sorted = sorted; a.start = start;
+        const NNPlan pl = nn_plan_of(plans[q], bg.ncell);
+        a.sorted = pl.payload; a.start = pl.start;
         a.R = (int)ceil((double)cap[q] / (double)cell[q]);
         a.cap2 = cap[q] * cap[q];
         a.T = T[q]; a.G = G[q]; a.n_gt = G[q];

@@ -288,18 +288,30 @@ int point_grid(const float* box6, double r, Grid* g, size_t* ncell) {
 }
 
 struct GridWs { int* gcount; int* gstart; int* tsum; int* gcell_of; int* gslot_of; float4* sorted; };
-size_t grid_ws_bytes(size_t ncell, size_t slots) {
-    return al256(ncell * 4) + al256((ncell + 1) * 4) + al256((ncell / SCAN_TILE + 1) * 4) + 2 * al256(slots * 4) +
-           al256(slots * 16);
+GridWs grid_ws_layout(Carver& c, size_t ncell, size_t slots) {
+    return {c.take<int>(ncell), c.take<int>(ncell + 1), take_scan_tsum(c, ncell), c.take<int>(slots), c.take<int>(slots),
+            c.take<float4>(slots)};
 }
-char* grid_ws_carve(char* p, size_t ncell, size_t slots, GridWs* w) {
-    w->gcount = (int*)p; p += al256(ncell * 4);
-    w->gstart = (int*)p; p += al256((ncell + 1) * 4);
-    w->tsum = (int*)p; p += al256((ncell / SCAN_TILE + 1) * 4);
-    w->gcell_of = (int*)p; p += al256(slots * 4);
-    w->gslot_of = (int*)p; p += al256(slots * 4);
-    w->sorted = (float4*)p; p += al256(slots * 16);
-    return p;
+constexpr size_t SCENE_WS_SLACK = 256;          // of both scene workspaces
+
+// nbp_scene_fill_cells_f32's workspace for n points: its own buffers, then the store's point grid.  cand_count and kept_count are
+// the two halves of ONE take (each rounded to 256 bytes), so that one memset of counters_bytes clears both.
+struct FillWs {
+    int *cell_of, *keep, *cand_count, *kept_count, *kept_start; float *stage, *temp; size_t counters_bytes; GridWs grid;
+};
+FillWs fill_ws_layout(Carver& c, size_t n, size_t n_cells, size_t slots, size_t ncell) {
+    FillWs L;
+    L.cell_of = c.take<int>(n);
+    L.keep = c.take<int>(n);
+    const size_t half = Carver::round256(n_cells * 4) / 4;             // ints
+    L.cand_count = c.take<int>(2 * half);
+    L.kept_count = L.cand_count + half;
+    L.counters_bytes = 2 * half * 4;
+    L.kept_start = c.take<int>(n_cells + 1);
+    L.stage = c.take<float>(3 * n);
+    L.temp = c.take<float>(3 * slots);
+    L.grid = grid_ws_layout(c, ncell, slots);
+    return L;
 }
 
 int build_store_grid(const float* store, const int* store_count, int n_cells, int cap, const Grid& g, size_t ncell,
@@ -334,9 +346,7 @@ extern "C" size_t nbp_scene_fill_workspace_bytes(const float* box6_host, const i
     int n_cells; Grid g; size_t ncell;
     if (!geom_ok(box6_host, grid3_host, &n_cells) || capacity < 1 || n_pts_max < 1 || !(resolution > 0)) return 0;
     if (point_grid(box6_host, resolution, &g, &ncell)) return 0;
-    const size_t slots = (size_t)n_cells * capacity;
-    return 512 + 2 * al256((size_t)n_pts_max * 4) + 2 * al256((size_t)n_cells * 4) + al256((size_t)(n_cells + 1) * 4) +
-           al256((size_t)n_pts_max * 12) + al256(slots * 12) + grid_ws_bytes(ncell, slots);
+    return carved_bytes(SCENE_WS_SLACK, fill_ws_layout, (size_t)n_pts_max, (size_t)n_cells, (size_t)n_cells * capacity, ncell);
 }
 
 extern "C" int nbp_scene_fill_cells_f32(const float* pts3, long long n, const long long* n_dev_or_null,
@@ -352,30 +362,21 @@ extern "C" int nbp_scene_fill_cells_f32(const float* pts3, long long n, const lo
     if (rc) return rc;
     NBP_RETURN_IF(ws_bytes < nbp_scene_fill_workspace_bytes(box6_host, grid3_host, capacity, n, resolution), NBP_E_WS);
     hipStream_t st = (hipStream_t)stream;
-    const size_t slots = (size_t)n_cells * capacity;
-    char* p = (char*)(((uintptr_t)ws + 255) / 256 * 256);
-    int* cell_of = (int*)p; p += al256((size_t)n * 4);
-    int* keep = (int*)p; p += al256((size_t)n * 4);
-    int* cand_count = (int*)p; p += al256((size_t)n_cells * 4);
-    int* kept_count = (int*)p; p += al256((size_t)n_cells * 4);
-    int* kept_start = (int*)p; p += al256((size_t)(n_cells + 1) * 4);
-    float* stage = (float*)p; p += al256((size_t)n * 12);
-    float* temp = (float*)p; p += al256(slots * 12);
-    GridWs gw;
-    grid_ws_carve(p, ncell, slots, &gw);
-    hipError_t e = hipMemsetAsync(cand_count, 0, 2 * al256((size_t)n_cells * 4), st);      // cand_count + kept_count
+    const FillWs L = carve(ws, fill_ws_layout, (size_t)n, (size_t)n_cells, (size_t)n_cells * capacity, ncell);
+    const GridWs& gw = L.grid;
+    hipError_t e = hipMemsetAsync(L.cand_count, 0, L.counters_bytes, st);      // cand_count + kept_count
     if (e != hipSuccess) return (int)e;
     const SceneGeom geom = make_geom(box6_host, grid3_host);
-    scene_assign_kernel<<<nbp_ew_grid(n, 256), 256, 0, st>>>(pts3, n, n_dev_or_null, geom, cell_of, cand_count);
+    scene_assign_kernel<<<nbp_ew_grid(n, 256), 256, 0, st>>>(pts3, n, n_dev_or_null, geom, L.cell_of, L.cand_count);
     if ((rc = nbp_launch_status())) return rc;
     if ((rc = build_store_grid(store_pts, store_count, n_cells, capacity, g, ncell, gw, st))) return rc;
-    scene_thin_kernel<<<(unsigned)nbp_cdiv(n, 256), 256, 0, st>>>(pts3, n, cell_of, cand_count, n_point_min, store_count, g,
-                                                                 gw.sorted, gw.gstart, resolution, keep, kept_count);
+    scene_thin_kernel<<<(unsigned)nbp_cdiv(n, 256), 256, 0, st>>>(pts3, n, L.cell_of, L.cand_count, n_point_min, store_count, g,
+                                                                 gw.sorted, gw.gstart, resolution, L.keep, L.kept_count);
     if ((rc = nbp_launch_status())) return rc;
-    small_exclusive_scan_kernel<<<1, 64, 0, st>>>(kept_count, n_cells, kept_start);
-    scene_stage_kernel<<<n_cells, 256, 0, st>>>(pts3, n, cell_of, keep, kept_count, kept_start, stage);
+    small_exclusive_scan_kernel<<<1, 64, 0, st>>>(L.kept_count, n_cells, L.kept_start);
+    scene_stage_kernel<<<n_cells, 256, 0, st>>>(pts3, n, L.cell_of, L.keep, L.kept_count, L.kept_start, L.stage);
     if ((rc = nbp_launch_status())) return rc;
-    scene_merge_kernel<<<n_cells, 256, 0, st>>>(store_pts, store_count, capacity, stage, kept_count, kept_start, seed, temp);
+    scene_merge_kernel<<<n_cells, 256, 0, st>>>(store_pts, store_count, capacity, L.stage, L.kept_count, L.kept_start, seed, L.temp);
     return nbp_launch_status();
 }
 
@@ -394,7 +395,7 @@ extern "C" size_t nbp_scene_coverage_workspace_bytes(const float* box6_host, con
     int n_cells; Grid g; size_t ncell;
     if (!geom_ok(box6_host, grid3_host, &n_cells) || capacity_rec < 1 || !(epsilon > 0)) return 0;
     if (point_grid(box6_host, epsilon, &g, &ncell)) return 0;
-    return 512 + grid_ws_bytes(ncell, (size_t)n_cells * capacity_rec);
+    return carved_bytes(SCENE_WS_SLACK, grid_ws_layout, ncell, (size_t)n_cells * capacity_rec);
 }
 
 extern "C" int nbp_scene_coverage_f32(const float* gt_pts, const int* gt_count, int capacity_gt, const float* rec_pts,
@@ -409,8 +410,7 @@ extern "C" int nbp_scene_coverage_f32(const float* gt_pts, const int* gt_count, 
     if (rc) return rc;
     NBP_RETURN_IF(ws_bytes < nbp_scene_coverage_workspace_bytes(box6_host, grid3_host, capacity_rec, epsilon), NBP_E_WS);
     hipStream_t st = (hipStream_t)stream;
-    GridWs gw;
-    grid_ws_carve((char*)(((uintptr_t)ws + 255) / 256 * 256), ncell, (size_t)n_cells * capacity_rec, &gw);
+    const GridWs gw = carve(ws, grid_ws_layout, ncell, (size_t)n_cells * capacity_rec);
     hipError_t e = hipMemsetAsync(covered_and_total2, 0, 2 * sizeof(int), st);
     if (e != hipSuccess) return (int)e;
     if ((rc = build_store_grid(rec_pts, rec_count, n_cells, capacity_rec, g, ncell, gw, st))) return rc;

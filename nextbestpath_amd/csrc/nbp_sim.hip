@@ -14,6 +14,7 @@
 // up, zbuf = view-space z of the nearest face at the pixel centre, -1 background); parity with
 // the libraries themselves is UNPINNED (oracle/__init__.py), parity with oracle/ is exact.
 #include "common.h"
+#include "nbp_carve.h"
 #pragma clang fp contract(off)
 
 namespace {
@@ -944,19 +945,35 @@ __global__ __launch_bounds__(256) void carve_update_kernel(const float* __restri
 }  // namespace
 
 // ================================================================== C ABI
-extern "C" size_t nbp_unproject_workspace_bytes(int n_frames, int H, int W) {
-    if (n_frames < 1 || H < 2 || W < 2) return 0;
-    const size_t nblk = (size_t)nbp_cdiv((long long)H * W, COMPACT_CHUNK);
-    return (size_t)n_frames * H * W * sizeof(unsigned) + ((size_t)n_frames * nblk * sizeof(int) + 255) / 256 * 256 + 512;
+// The un-projection's workspace: the chunk counts of every frame (sized for the generic path's COMPACT_CHUNK chunks; the fast
+// path's FAST_CHUNK chunks are fewer) with the fast path's ticket word as their last int, then the compacted pixel list.
+constexpr size_t UNPROJECT_WS_SLACK = 256;
+struct UnprojectWs { int* blk_count; int* ticket; unsigned* list; };
+static UnprojectWs unproject_ws_layout(Carver& c, int n_frames, int H, int W) {
+    const size_t n_counts = (size_t)n_frames * (size_t)nbp_cdiv((long long)H * W, COMPACT_CHUNK);
+    UnprojectWs L;
+    L.blk_count = c.take<int>(n_counts + 1);
+    L.ticket = L.blk_count + n_counts;
+    L.list = c.take<unsigned>((size_t)n_frames * H * W);
+    return L;
 }
 
-static CamSet camset_from_host(const float* cams12_host, int n) {
-    CamSet cs;
-    for (int f = 0; f < MAX_CAMS; ++f)
+extern "C" size_t nbp_unproject_workspace_bytes(int n_frames, int H, int W) {
+    if (n_frames < 1 || H < 2 || W < 2) return 0;
+    return carved_bytes(UNPROJECT_WS_SLACK, unproject_ws_layout, n_frames, H, W);
+}
+
+// n <= n_slots cameras [n][12] (R row-major (9) then T (3)) into cam[0..n_slots), the rest zero
+static void cams_from_host(const float* cams12_host, int n, Cam* cam, int n_slots) {
+    for (int f = 0; f < n_slots; ++f)
         for (int k = 0; k < 12; ++k) {
             const float v = f < n ? cams12_host[12 * f + k] : 0.f;
-            if (k < 9) cs.c[f].R[k] = v; else cs.c[f].T[k - 9] = v;
+            if (k < 9) cam[f].R[k] = v; else cam[f].T[k - 9] = v;
         }
+}
+static CamSet camset_from_host(const float* cams12_host, int n) {
+    CamSet cs;
+    cams_from_host(cams12_host, n, cs.c, MAX_CAMS);
     return cs;
 }
 
@@ -1039,9 +1056,10 @@ static int unproject_launch(const float* depth, const unsigned char* mask_or_nul
     hipStream_t st = (hipStream_t)stream;
     const int HW = H * W, nblk = (int)nbp_cdiv(HW, COMPACT_CHUNK);
     NBP_RETURN_IF(nblk > 4096, NBP_E_SHAPE);
-    int* blk_count = (int*)(((uintptr_t)ws + 255) / 256 * 256);
-    unsigned* list = (unsigned*)((char*)blk_count + ((size_t)n_frames * nblk * sizeof(int) + 255) / 256 * 256);
-    const CamSet cams = camset_from_host(cams12_host, n_frames);   // [F][12]: R row-major (9) then T (3)
+    const UnprojectWs L = carve(ws, unproject_ws_layout, n_frames, H, W);
+    int* const blk_count = L.blk_count;
+    unsigned* const list = L.list;
+    const CamSet cams = camset_from_host(cams12_host, n_frames);
     const int max_keep = (int)((double)H * W * gathering_factor) + 1;
     dim3 grid((unsigned)nbp_cdiv(max_keep, 256), (unsigned)n_frames);
     int rc;
@@ -1051,7 +1069,7 @@ static int unproject_launch(const float* depth, const unsigned char* mask_or_nul
     if (fast) {
         // three launches: chunk counts (also resets the ticket), ordered compaction, gather + append + size update
         const int nb4 = (int)nbp_cdiv(HW, FAST_CHUNK);             // <= nblk: the workspace is sized for 2048-pixel chunks
-        int* ticket = blk_count + (size_t)n_frames * nb4;
+        int* const ticket = L.ticket;
         dim3 g4((unsigned)nb4, (unsigned)n_frames);
         unproject_count4_kernel<<<g4, 256, 0, st>>>(depth, mask_or_null, HW, nb4, fov_range, blk_count, ticket);
         if ((rc = nbp_launch_status())) return rc;
@@ -1079,15 +1097,18 @@ static int unproject_launch(const float* depth, const unsigned char* mask_or_nul
     return nbp_launch_status();
 }
 
+// The rasteriser's workspace: per-frame face records, the coarse tiles' counts and lists; the rgb form renders into its own
+// (depth, face) image and sums each frame's luminance for the contrast change.
+constexpr size_t RASTER_WS_SLACK = 256;
+struct RasterWs { FaceRec* recs; int* ccount; BinEntry* clist; unsigned long long* zface; double* gray; size_t nct; };
+static RasterWs raster_ws_layout(Carver& c, int n_faces, int n_frames, int H, int W, bool rgb) {
+    const size_t nct = (size_t)nbp_cdiv(nbp_cdiv(W, TILE), COARSE) * nbp_cdiv(nbp_cdiv(H, TILE), COARSE) * n_frames;
+    return {c.take<FaceRec>((size_t)n_frames * n_faces), c.take<int>(nct), c.take<BinEntry>(nct * n_faces),
+            rgb ? c.take<unsigned long long>((size_t)n_frames * H * W) : nullptr, rgb ? c.take<double>(MAX_CAMS) : nullptr, nct};
+}
 static size_t raster_ws_bytes(int n_faces, int n_frames, int H, int W, bool rgb) {
     if (n_faces < 1 || n_frames < 1 || H < 1 || W < 1) return 0;
-    const size_t nct = (size_t)nbp_cdiv(nbp_cdiv(W, TILE), COARSE) * nbp_cdiv(nbp_cdiv(H, TILE), COARSE) * n_frames;
-    size_t b = 256;
-    b += ((size_t)n_frames * n_faces * sizeof(FaceRec) + 255) / 256 * 256;
-    b += (nct * sizeof(int) + 255) / 256 * 256;
-    b += (nct * n_faces * sizeof(BinEntry) + 255) / 256 * 256;
-    if (rgb) b += ((size_t)n_frames * H * W * 8 + 255) / 256 * 256 + 256;
-    return b + 256;
+    return carved_bytes(RASTER_WS_SLACK, raster_ws_layout, n_faces, n_frames, H, W, rgb);
 }
 
 extern "C" size_t nbp_raster_workspace_bytes(int n_faces, int n_frames, int H, int W, int bin_cap) {
@@ -1111,29 +1132,21 @@ static int raster_launch(const float* verts, int n_verts, const int* faces, int 
     NBP_RETURN_IF(ws_bytes < raster_ws_bytes(n_faces, n_frames, H, W, rgb != nullptr && !zface_out), NBP_E_WS);
     hipStream_t st = (hipStream_t)stream;
     const int ctiles_x = (int)nbp_cdiv(tiles_x, COARSE), ctiles_y = (int)nbp_cdiv(tiles_y, COARSE);
-    const size_t nct = (size_t)ctiles_x * ctiles_y * n_frames;
-    char* p = (char*)(((uintptr_t)ws + 255) / 256 * 256);
-    FaceRec* recs = (FaceRec*)p; p += ((size_t)n_frames * n_faces * sizeof(FaceRec) + 255) / 256 * 256;
-    int* ccount = (int*)p; p += (nct * sizeof(int) + 255) / 256 * 256;
-    BinEntry* clist = (BinEntry*)p; p += (nct * n_faces * sizeof(BinEntry) + 255) / 256 * 256;
-    unsigned long long* zface = nullptr;
-    double* gray = nullptr;
+    const RasterWs L = carve(ws, raster_ws_layout, n_faces, n_frames, H, W, rgb != nullptr && !zface_out);
+    FaceRec* const recs = L.recs;
+    int* const ccount = L.ccount;
+    BinEntry* const clist = L.clist;
+    unsigned long long* const zface = zface_out ? zface_out : L.zface;
+    double* const gray = L.gray;
     const long long npx = (long long)n_frames * H * W;
-    if (zface_out) {
-        zface = zface_out;
-        gray = (double*)p;                                     // 8 doubles fit the workspace's slack
-    } else if (rgb) {
-        zface = (unsigned long long*)p; p += ((size_t)npx * 8 + 255) / 256 * 256;
-        gray = (double*)p;
-    }
-    hipError_t e = hipMemsetAsync(ccount, 0, nct * sizeof(int), st);
+    hipError_t e = hipMemsetAsync(ccount, 0, L.nct * sizeof(int), st);
     if (e != hipSuccess) return (int)e;
     dim3 g1((unsigned)nbp_cdiv(n_faces, 256), (unsigned)n_frames);
     raster_setup_kernel<<<g1, 256, 0, st>>>(verts, faces, n_faces, camset_from_host(cams12_host, n_frames), H, W,
                                             tan_half_fov, z_clip, recs, ctiles_x, ctiles_y, ccount, clist, (unsigned*)zbuf, zface);
     int rc = nbp_launch_status();
     if (rc) return rc;
-    const bool need_gray = rgb && contrast != 1.f;            // adjust_contrast(1) is the identity: no luminance sum needed
+    const bool need_gray = gray && contrast != 1.f;           // adjust_contrast(1) is the identity: no luminance sum needed
     if (need_gray) {
         e = hipMemsetAsync(gray, 0, (size_t)n_frames * sizeof(double), st);
         if (e != hipSuccess) return (int)e;
@@ -1213,14 +1226,14 @@ extern "C" int nbp_unproject_append_shaded_batch_f32(int n, const float* const* 
     NBP_RETURN_IF(nblk > 4096, NBP_E_SHAPE);
     UnprojBatch b;
     bool any_colour = false;
-    b.ticket_off = n_frames * nb4;
-    b.list_off_bytes = (unsigned)(((size_t)n_frames * nblk * sizeof(int) + 255) / 256 * 256);
     for (int r = 0; r < STEP_BATCH; ++r) {
         const int q = r < n ? r : 0;
         NBP_RETURN_IF(!counts2[q] || !cloud[q] || !cloud_count[q] || capacity[q] < 1 || !ws[q], NBP_E_ARG);
         UnprojItem& a = b.it[r];
-        int* blk_count = (int*)(((uintptr_t)ws[q] + 255) / 256 * 256);
-        a.blk_count = blk_count;
+        const UnprojectWs L = carve(ws[q], unproject_ws_layout, n_frames, H, W);          // the same offsets in every item's workspace
+        a.blk_count = L.blk_count;
+        b.ticket_off = (int)(L.ticket - L.blk_count);
+        b.list_off_bytes = (unsigned)((char*)L.list - (char*)L.blk_count);
         a.counts = counts2[q]; a.cloud = cloud[q]; a.cloud_count = cloud_count[q]; a.capacity = capacity[q];
         const bool col = zface && zface[(size_t)q * n_frames] && cloud_rgb && cloud_rgb[q] && verts && faces && vcolors;
         a.cloud_rgb = col ? cloud_rgb[q] : nullptr;
@@ -1233,11 +1246,7 @@ extern "C" int nbp_unproject_append_shaded_batch_f32(int n, const float* const* 
         }
         a.verts = col ? verts[q] : nullptr; a.faces = col ? faces[q] : nullptr; a.vcolors = col ? vcolors[q] : nullptr;
         a.seed = seeds[q];
-        for (int f = 0; f < 4; ++f)
-            for (int k = 0; k < 12; ++k) {
-                const float v = f < n_frames ? cams12_host[((size_t)q * n_frames + f) * 12 + k] : 0.f;
-                if (k < 9) a.cam[f].R[k] = v; else a.cam[f].T[k - 9] = v;
-            }
+        cams_from_host(cams12_host + (size_t)q * n_frames * 12, n_frames, a.cam, 4);
     }
     dim3 g4((unsigned)nb4, (unsigned)n_frames, (unsigned)n);
     unproject_count4_batch_kernel<<<g4, 256, 0, st>>>(b, HW, nb4, fov_range);
@@ -1276,21 +1285,15 @@ extern "C" int nbp_raster_zface_batch_f32(int n, const float* const* verts, cons
         NBP_RETURN_IF(!verts[q] || !faces[q] || n_verts[q] < 3 || n_faces[q] < 1 || !zbuf[q] || !zface[q] || !ws[q], NBP_E_ARG);
         NBP_RETURN_IF(ws_bytes[q] < raster_ws_bytes(n_faces[q], n_frames, H, W, false), NBP_E_WS);
         RasterItem& a = b.it[r];
-        char* p = (char*)(((uintptr_t)ws[q] + 255) / 256 * 256);
-        a.recs = (FaceRec*)p; p += ((size_t)n_frames * n_faces[q] * sizeof(FaceRec) + 255) / 256 * 256;
-        a.ccount = (int*)p; p += (nct * sizeof(int) + 255) / 256 * 256;
-        a.clist = (BinEntry*)p;
+        const RasterWs L = carve(ws[q], raster_ws_layout, n_faces[q], n_frames, H, W, false);
+        a.recs = L.recs; a.ccount = L.ccount; a.clist = L.clist;
         a.verts = verts[q]; a.faces = faces[q]; a.vcolors = nullptr; a.zbuf = zbuf[q]; a.zface = (unsigned long long*)zface[q];
         a.n_faces = n_faces[q];
         a.gx_setup = r < n ? (unsigned)nbp_cdiv(n_faces[q], 256) : 0;
         a.gx_tile = r < n ? (unsigned)((int)nbp_cdiv(tiles_x, RB) * (int)nbp_cdiv(tiles_y, RB) * (int)nbp_cdiv(n_faces[q], SEG)) : 0;
         if (a.gx_setup > g_setup) g_setup = a.gx_setup;
         if (a.gx_tile > g_tile) g_tile = a.gx_tile;
-        for (int f = 0; f < 4; ++f)
-            for (int k = 0; k < 12; ++k) {
-                const float v = f < n_frames ? cams12_host[((size_t)q * n_frames + f) * 12 + k] : 0.f;
-                if (k < 9) a.cam[f].R[k] = v; else a.cam[f].T[k - 9] = v;
-            }
+        cams_from_host(cams12_host + (size_t)q * n_frames * 12, n_frames, a.cam, 4);
     }
     raster_clear_batch_kernel<<<dim3(1, (unsigned)n), 256, 0, st>>>(b, (int)nct);
     int rc = nbp_launch_status();

@@ -205,7 +205,8 @@ struct MeshTriangles {
 };
 
 // ---- host
-size_t mesh_plan_bytes(size_t ncell, long long F) { return nn_plan_size(ncell, (size_t)(F > 0 ? F : 1) * 48); }
+// a plan holds max(F, 1) triangles, three float4 vertices each
+size_t mesh_plan_bytes(size_t ncell, long long F) { return carved_bytes(0, nn_plan_layout, ncell, (size_t)(F > 0 ? F : 1) * 3); }
 
 }  // namespace
 
@@ -231,18 +232,17 @@ extern "C" int nbp_mesh_plan_count_f32(const float* verts3, long long V, const i
     if (rc) return rc;
     NBP_RETURN_IF(plan_bytes < mesh_plan_bytes(b.ncell, F) || ws_bytes < nn_scratch_bytes(b.ncell), NBP_E_WS);
     hipStream_t st = (hipStream_t)stream;
-    int *start, *count, *tsum; float4* tri;
-    nn_plan_carve(plan, b.ncell, &start, &tri);
-    nn_scratch_carve(ws, b.ncell, &count, &tsum);
-    hipError_t e = hipMemsetAsync(count, 0, b.ncell * 4, st);
+    const NNPlan pl = nn_plan_of(plan, b.ncell);
+    const NNScratch w = carve(ws, nn_scratch_layout, b.ncell);
+    hipError_t e = hipMemsetAsync(w.count, 0, b.ncell * 4, st);
     if (e == hipSuccess) e = hipMemsetAsync(totals2_dev, 0, 16, st);
     if (e != hipSuccess) return (int)e;
     if (F > 0) {
-        mesh_count_kernel<<<nbp_ew_grid(F, 256), 256, 0, st>>>(verts3, V, faces3, F, b.g, b.bx, tri, count,
+        mesh_count_kernel<<<nbp_ew_grid(F, 256), 256, 0, st>>>(verts3, V, faces3, F, b.g, b.bx, pl.payload, w.count,
                                                                  (unsigned long long*)totals2_dev);
         if ((rc = nbp_launch_status())) return rc;
     }
-    return grid_exclusive_scan(count, (long long)b.ncell, tsum, start, st);
+    return grid_exclusive_scan(w.count, (long long)b.ncell, w.tsum, pl.start, st);
 }
 
 extern "C" int nbp_mesh_plan_fill_i32(const float* verts3, long long V, const int* faces3, long long F, const float* lo_host,
@@ -258,13 +258,12 @@ extern "C" int nbp_mesh_plan_fill_i32(const float* verts3, long long V, const in
     if (rc) return rc;
     NBP_RETURN_IF(ws_bytes < nn_scratch_bytes(b.ncell), NBP_E_WS);
     hipStream_t st = (hipStream_t)stream;
-    int *start, *cursor, *tsum; float4* tri;
-    nn_plan_carve(plan, b.ncell, &start, &tri);
-    nn_scratch_carve(ws, b.ncell, &cursor, &tsum);
+    const NNPlan pl = nn_plan_of(plan, b.ncell);
+    int* cursor = carve(ws, nn_scratch_layout, b.ncell).count;
     hipError_t e = hipMemsetAsync(cursor, 0, b.ncell * 4, st);
     if (e != hipSuccess) return (int)e;
     if (F == 0) return 0;
-    mesh_fill_kernel<<<nbp_ew_grid(F, 256), 256, 0, st>>>(verts3, V, faces3, F, b.g, b.bx, start, cursor, entries, entry_capacity);
+    mesh_fill_kernel<<<nbp_ew_grid(F, 256), 256, 0, st>>>(verts3, V, faces3, F, b.g, b.bx, pl.start, cursor, entries, entry_capacity);
     return nbp_launch_status();
 }
 
@@ -277,7 +276,6 @@ extern "C" int nbp_mesh_dist2_planned_f32(const void* plan, const int* entries, 
     BoxGrid b;
     const int rc = nn_grid(lo_host, hi_host, cell, &b);
     if (rc) return rc;
-    int* start; float4* tri;
-    nn_plan_carve(plan, b.ncell, &start, &tri);
-    return shell_query(MeshTriangles{entries, tri}, start, b.g, cap, cell, q3, Q, Q_dev_or_null, d2, (hipStream_t)stream);
+    const NNPlan pl = nn_plan_of(plan, b.ncell);
+    return shell_query(MeshTriangles{entries, pl.payload}, pl.start, b.g, cap, cell, q3, Q, Q_dev_or_null, d2, (hipStream_t)stream);
 }
