@@ -8,9 +8,8 @@
 // header proves that the result is the brute-force minimum over all in-box targets, bit for bit; and -- a minimum being blind to
 // the order of its operands -- the atomicAdd slot order inside a cell does not show: two runs give the same bits.
 //
-// Summary (nbp_recon_stats_f64): a fixed launch geometry; every thread adds its strided elements in index order in float64, a
-// fixed tree adds the threads of a block (shuffles inside a wave, the four waves in order), each block STORES one row, and a
-// second one-block launch adds the rows in index order.  No floating-point atomics: two runs give the same bits.
+// Summary (nbp_recon_stats_f64): nbp_stat_rows.h's fixed-order fold over STATS_BLOCKS blocks, a row being two float64 sums and the
+// threshold counts.  No floating-point atomics: two runs give the same bits.
 //
 // Per-step curve (nbp_recon_curve_update_batch_f32).  The cloud is append-only and the GT fixed, so both directions
 // are incremental: a point's distance to the GT never changes (it is queried once, in the step that appends it), and the minimum
@@ -25,6 +24,7 @@
 // The summaries follow in two launches of the stats geometry above: d2_gt in full, the step's own distances into the running
 // float64 totals by one thread.  The watermark `seen` moves in the last launch only (the first two read it).
 #include "nbp_shell_walk.h"
+#include "nbp_stat_rows.h"
 
 #pragma clang fp contract(off)
 
@@ -33,9 +33,9 @@ namespace {
 constexpr int NN_LANES = 8;                      // lanes per query: the 8 rim columns of shell 1 at once
 constexpr int NN_UNROLL = 4;                     // points of a run in flight together (coverage_mark_body: one per iteration
                                                  // is a chain of dependent round trips)
-constexpr int STATS_BLOCKS = 256, STATS_THREADS = 256, STATS_WAVES = STATS_THREADS / 64;
+constexpr int STATS_BLOCKS = 256, STATS_THREADS = STAT_THREADS;
 constexpr int STATS_MAX_T = 8;
-constexpr int STATS_ROW = 2 + STATS_MAX_T;       // 8-byte words of a block's row: two float64 sums, then the counts
+constexpr int STATS_SUMS = 2, STATS_ROW = STATS_SUMS + STATS_MAX_T;   // 8-byte words of a block's row: two float64 sums, then the counts
 
 // ---- sort
 __global__ __launch_bounds__(256) void nn_bin_kernel(const float* __restrict__ t, const long long* __restrict__ n_dev, long long n_host,
@@ -76,64 +76,29 @@ struct NNPoints {
 // ---- summary
 struct StatsThresholds { float v[STATS_MAX_T]; };
 
-// One block of the fixed geometry: row = the block's two float64 sums and its T counts (the counts beyond T: 0).  Every thread adds
-// its strided elements in index order, a fixed tree adds the threads (shuffles inside a wave, the four waves in order).  The
-// counts are independent of one another and of the sums: a larger T moves no bit of the rest.
+// One block of the fixed geometry: row = the block's two float64 sums and its T counts (the words beyond them are not written, and
+// nothing reads them: a fold takes the columns below 2 + T).  The counts are independent of one another and of the sums: a larger
+// T moves no bit of the rest.
 template <int T>
 __device__ __forceinline__ void stats_block(const float* __restrict__ d2, long long n, const float* th, int block,
                                             unsigned long long* __restrict__ row) {
-    __shared__ double ws1[STATS_WAVES], ws2[STATS_WAVES];
-    __shared__ long long wc[STATS_WAVES][STATS_MAX_T];
-    double s1 = 0.0, s2 = 0.0;
+    double s[STATS_SUMS] = {0.0, 0.0};
     long long c[T];
 #pragma unroll
     for (int t = 0; t < T; ++t) c[t] = 0;
     for (long long i = (long long)block * STATS_THREADS + threadIdx.x; i < n; i += (long long)STATS_BLOCKS * STATS_THREADS) {
         const float v = d2[i];
-        s1 += sqrt((double)v);
-        s2 += (double)v;
+        s[0] += sqrt((double)v);
+        s[1] += (double)v;
 #pragma unroll
         for (int t = 0; t < T; ++t) c[t] += v <= th[t] ? 1 : 0;
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        s1 += __shfl_down(s1, off, 64);
-        s2 += __shfl_down(s2, off, 64);
-#pragma unroll
-        for (int t = 0; t < T; ++t) c[t] += __shfl_down(c[t], off, 64);
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-        ws1[wave] = s1;
-        ws2[wave] = s2;
-#pragma unroll
-        for (int t = 0; t < T; ++t) wc[wave][t] = c[t];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double r1 = ws1[0], r2 = ws2[0];
-        for (int k = 1; k < STATS_WAVES; ++k) { r1 += ws1[k]; r2 += ws2[k]; }
-        row[0] = (unsigned long long)__double_as_longlong(r1);
-        row[1] = (unsigned long long)__double_as_longlong(r2);
-        for (int t = 0; t < STATS_MAX_T; ++t) {
-            long long s = 0;
-            if (t < T)
-                for (int k = 0; k < STATS_WAVES; ++k) s += wc[k][t];
-            row[2 + t] = (unsigned long long)s;
-        }
-    }
+    stat_row_store<STATS_SUMS, T>(s, c, row);
 }
 
-// Column col of the STATS_BLOCKS rows, added in index order: a float64 sum's bits (col < 2) or a count.
+// Column col of the STATS_BLOCKS rows, added in index order
 __device__ __forceinline__ unsigned long long stats_fold(const unsigned long long* __restrict__ rows, int col) {
-    if (col < 2) {
-        double s = 0.0;
-        for (int b = 0; b < STATS_BLOCKS; ++b) s += __longlong_as_double((long long)rows[(size_t)b * STATS_ROW + col]);
-        return (unsigned long long)__double_as_longlong(s);
-    }
-    long long s = 0;
-    for (int b = 0; b < STATS_BLOCKS; ++b) s += (long long)rows[(size_t)b * STATS_ROW + col];
-    return (unsigned long long)s;
+    return stat_rows_fold(rows, STATS_BLOCKS, STATS_ROW, STATS_SUMS, col);
 }
 
 template <int T>
@@ -373,7 +338,7 @@ extern "C" int nbp_nn_dist2_f32(const float* q3, long long Q, const long long* Q
     return nn_query(L.plan, b, cap, cell, q3, Q, Q_dev_or_null, d2, (hipStream_t)stream);
 }
 
-extern "C" size_t nbp_recon_stats_workspace_bytes(void) { return 256 + (size_t)STATS_BLOCKS * STATS_ROW * 8; }
+extern "C" size_t nbp_recon_stats_workspace_bytes(void) { return stat_rows_bytes(STATS_BLOCKS, STATS_ROW); }
 
 extern "C" int nbp_recon_stats_f64(const float* d2, long long n, const long long* n_dev_or_null, int T, const float* thresholds_host,
                                    double* sums2, long long* counts, void* ws, size_t ws_bytes, void* stream) {
@@ -385,7 +350,7 @@ extern "C" int nbp_recon_stats_f64(const float* d2, long long n, const long long
     hipStream_t st = (hipStream_t)stream;
     StatsThresholds th;
     for (int t = 0; t < STATS_MAX_T; ++t) th.v[t] = sq_below(thresholds_host[t < T ? t : 0]);
-    unsigned long long* rows = (unsigned long long*)(((uintptr_t)ws + 255) / 256 * 256);
+    unsigned long long* rows = carve(ws, stat_rows_layout, (size_t)STATS_BLOCKS, STATS_ROW);
     switch (T) {
         case 1: launch_stats<1>(st, d2, n_dev_or_null, n, th, rows); break;
         case 2: launch_stats<2>(st, d2, n_dev_or_null, n, th, rows); break;
@@ -404,7 +369,7 @@ extern "C" int nbp_recon_stats_f64(const float* d2, long long n, const long long
 
 extern "C" size_t nbp_recon_curve_workspace_bytes(int n) {
     if (n < 1 || n > CURVE_BATCH) return 0;
-    return 256 + (size_t)n * 2 * STATS_BLOCKS * STATS_ROW * 8;
+    return stat_rows_bytes((size_t)n * 2 * STATS_BLOCKS, STATS_ROW);
 }
 
 extern "C" size_t nbp_recon_curve_totals_bytes(void) { return (size_t)CURVE_TOTALS * 8; }
@@ -420,7 +385,7 @@ extern "C" int nbp_recon_curve_update_batch_f32(int n, const void* const* plans,
                   !count_dev || !seen_dev || !d2_gt || !d2_new || !totals || !T || !thresholds_host || !row || !new_bound || !ws,
                   NBP_E_ARG);
     NBP_RETURN_IF(ws_bytes < nbp_recon_curve_workspace_bytes(n), NBP_E_WS);
-    unsigned long long* part = (unsigned long long*)(((uintptr_t)ws + 255) / 256 * 256);
+    unsigned long long* part = carve(ws, stat_rows_layout, (size_t)n * 2 * STATS_BLOCKS, STATS_ROW);
     CurveBatch b;
     unsigned gwalk = 1;
     for (int r = 0; r < CURVE_BATCH; ++r) {

@@ -15,22 +15,12 @@
 // the libraries themselves is UNPINNED (oracle/__init__.py), parity with oracle/ is exact.
 #include "common.h"
 #include "nbp_carve.h"
+#include "nbp_camera.h"
 #pragma clang fp contract(off)
 
 namespace {
 
-// ------------------------------------------------------------------ un-projection
-struct Cam { float R[9]; float T[3]; };
-constexpr int MAX_CAMS = 8;
-struct CamSet { Cam c[MAX_CAMS]; };   // cameras travel in the kernel arguments (no H2D copy, no sync)
-
-__device__ __forceinline__ void to_view(const float* p, const float* R, const float* T, float* o) {
-    // X_view = X_world R + T (row vector): o_j = sum_k p_k R[k][j] + T_j
-    o[0] = ((p[0] * R[0] + p[1] * R[3]) + p[2] * R[6]) + T[0];
-    o[1] = ((p[0] * R[1] + p[1] * R[4]) + p[2] * R[7]) + T[1];
-    o[2] = ((p[0] * R[2] + p[1] * R[5]) + p[2] * R[8]) + T[2];
-}
-
+// ------------------------------------------------------------------ un-projection (the camera: nbp_camera.h)
 // Colour of pixel (row, col) of a frame whose nearest face there is fi: the face record is rebuilt from the mesh with the
 // arithmetic of raster_setup_kernel (bit-identical e1, e2, v0, q), the barycentrics come from the same ray cast as the depth,
 // colour = ambient x interpolated vertex colours (SoftPhongShader under AmbientLights on a TexturesVertex mesh).
@@ -49,8 +39,8 @@ __device__ __forceinline__ void shade_pixel(const float* __restrict__ verts, con
     q[1] = e1[2] * v[0][0] - e1[0] * v[0][2];
     q[2] = e1[0] * v[0][1] - e1[1] * v[0][0];
     const int s = H < W ? H : W;
-    const float dx = (((float)W - (2.f * col + 1.f)) / (float)s) * tanh_fov;
-    const float dy = (((float)H - (2.f * row + 1.f)) / (float)s) * tanh_fov;
+    const float dx = pixel_centre_ndc(W, s, col) * tanh_fov;
+    const float dy = pixel_centre_ndc(H, s, row) * tanh_fov;
     // plane forms of the face (raster_setup_body's arithmetic, oracle/raster.py::plane_forms)
     const float a0 = e1[2] * e2[1] - e1[1] * e2[2], a1 = e1[0] * e2[2] - e1[2] * e2[0], a2 = e1[1] * e2[0] - e1[0] * e2[1];
     const float u0 = v[0][1] * e2[2] - v[0][2] * e2[1], u1 = v[0][2] * e2[0] - v[0][0] * e2[2], u2 = v[0][0] * e2[1] - v[0][1] * e2[0];
@@ -65,22 +55,6 @@ __device__ __forceinline__ void shade_pixel(const float* __restrict__ verts, con
     for (int k = 0; k < 3; ++k) rgb3[k] = ambient * ((w0 * c0[k] + u * c1[k]) + vv * c2[k]);
 }
 
-
-// Pixel (row, col) with view-space depth z -> world point.  fp32 op order is part of the
-// contract with oracle/camera.py (no FMA contraction in this file).
-__device__ __forceinline__ void unproject_pixel(int row, int col, float z, int H, int W, float tanh_fov,
-                                                const float* R, const float* T, float* out) {
-    const int s = H < W ? H : W;
-    const float ndc_x = (float)((double)W / s) - ((float)col / (float)(s - 1)) * 2.f;   // ref mu:2272-2274
-    const float ndc_y = (float)((double)H / s) - ((float)row / (float)(s - 1)) * 2.f;   // ref mu:2275-2277
-    const float xv = (ndc_x * z) * tanh_fov;
-    const float yv = (ndc_y * z) * tanh_fov;
-    const float dx = xv - T[0], dy = yv - T[1], dz = z - T[2];
-    // X_world = (X_view - T) R^T  (row vectors)
-    out[0] = (dx * R[0] + dy * R[1]) + dz * R[2];
-    out[1] = (dx * R[3] + dy * R[4]) + dz * R[5];
-    out[2] = (dx * R[6] + dy * R[7]) + dz * R[8];
-}
 
 // K1a/K1b: ordered compaction of the valid pixel indices (pixel order) with COMPACT_CHUNK pixels
 // per 256-thread block: pass a counts per block, pass b recomputes validity and writes at the
@@ -462,7 +436,7 @@ __device__ __forceinline__ void raster_setup_body(unsigned bx, unsigned by, unsi
             float cmin = 1e30f, cmax = -1e30f, rmin = 1e30f, rmax = -1e30f;
             auto emit = [&](float x, float y, float z) {
                 const float nx = x / (z * tanh_fov), ny = y / (z * tanh_fov);
-                const float col = ((float)W - (float)s * nx - 1.f) * 0.5f;   // ndc_x(col) = W/s - (2 col + 1)/s
+                const float col = ((float)W - (float)s * nx - 1.f) * 0.5f;   // pixel_centre_ndc inverted: ndc_x(col) = W/s - (2 col + 1)/s
                 const float row = ((float)H - (float)s * ny - 1.f) * 0.5f;
                 cmin = fminf(cmin, col); cmax = fmaxf(cmax, col); rmin = fminf(rmin, row); rmax = fmaxf(rmax, row);
             };
@@ -558,8 +532,8 @@ __device__ __forceinline__ void raster_block_body(unsigned bx, unsigned by, cons
     const bool live = tx < tiles_x && ty < tiles_y;                               // (an odd tile count leaves a block half empty)
     const int col = tx * TILE + (lane & 7), row = ty * TILE + (lane >> 3);
     const int s = H < W ? H : W;
-    const float ndc_x = ((float)W - (2.f * col + 1.f)) / (float)s;
-    const float ndc_y = ((float)H - (2.f * row + 1.f)) / (float)s;
+    const float ndc_x = pixel_centre_ndc(W, s, col);
+    const float ndc_y = pixel_centre_ndc(H, s, row);
     const float dx = ndc_x * tanh_fov, dy = ndc_y * tanh_fov;   // dz = 1
     const FaceRec* rb = recs + (size_t)fr * n_faces;
     float zbest = 3.0e38f;
@@ -787,16 +761,14 @@ __global__ __launch_bounds__(256) void axis_ray_count_kernel(const float* __rest
 __device__ __forceinline__ bool point_in_fov(const float* p, const Cam& cam, int H, int W, float tanh_fov, float fov_range,
                                              float* v, float* nx_out, float* ny_out) {
     to_view(p, cam.R, cam.T, v);
-    // camera centre C = -T R^T
-    const float cx = -((cam.T[0] * cam.R[0] + cam.T[1] * cam.R[1]) + cam.T[2] * cam.R[2]);
-    const float cy = -((cam.T[0] * cam.R[3] + cam.T[1] * cam.R[4]) + cam.T[2] * cam.R[5]);
-    const float cz = -((cam.T[0] * cam.R[6] + cam.T[1] * cam.R[7]) + cam.T[2] * cam.R[8]);
-    const float dx = p[0] - cx, dy = p[1] - cy, dz = p[2] - cz;
+    float c[3];
+    cam_centre(cam, c);
+    const float dx = p[0] - c[0], dy = p[1] - c[1], dz = p[2] - c[2];
     const float dist = sqrtf((dx * dx + dy * dy) + dz * dz);
     const int s = H < W ? H : W;
     const float nx = v[0] / (v[2] * tanh_fov), ny = v[1] / (v[2] * tanh_fov);
-    const float max_x = (float)((double)W / s), min_x = max_x - ((float)(W - 1) / (float)(s - 1)) * 2.f;
-    const float max_y = (float)((double)H / s), min_y = max_y - ((float)(H - 1) / (float)(s - 1)) * 2.f;
+    const float max_x = ndc_table_max(W, s), min_x = ndc_table_at(W, s, W - 1);   // the corners of the NDC tables
+    const float max_y = ndc_table_max(H, s), min_y = ndc_table_at(H, s, H - 1);
     *nx_out = nx; *ny_out = ny;
     return nx >= min_x && nx <= max_x && ny >= min_y && ny <= max_y && v[2] > 0.f && dist < fov_range;
 }
@@ -963,14 +935,6 @@ extern "C" size_t nbp_unproject_workspace_bytes(int n_frames, int H, int W) {
     return carved_bytes(UNPROJECT_WS_SLACK, unproject_ws_layout, n_frames, H, W);
 }
 
-// n <= n_slots cameras [n][12] (R row-major (9) then T (3)) into cam[0..n_slots), the rest zero
-static void cams_from_host(const float* cams12_host, int n, Cam* cam, int n_slots) {
-    for (int f = 0; f < n_slots; ++f)
-        for (int k = 0; k < 12; ++k) {
-            const float v = f < n ? cams12_host[12 * f + k] : 0.f;
-            if (k < 9) cam[f].R[k] = v; else cam[f].T[k - 9] = v;
-        }
-}
 static CamSet camset_from_host(const float* cams12_host, int n) {
     CamSet cs;
     cams_from_host(cams12_host, n, cs.c, MAX_CAMS);

@@ -7,7 +7,7 @@
 //
 // Integration.  A thread owns a voxel (lanes run along k, the contiguous axis: a wave reads and writes 512 consecutive bytes).  It
 // loads (S, W) once with one 8-byte access, loops over the launch's <= 4 frames in registers and stores once, and only if some
-// frame updated it: in a maze most voxels inside a frustum lie hidden behind a wall.  The projection is nbp_views.hip's expression
+// frame updated it: in a maze most voxels inside a frustum lie hidden behind a wall.  The projection is nbp_camera.h's `project`
 // (view_metrics.project), fp32 with one rounding per operation (no contraction in this file).  The sums are integers and a voxel
 // has one owner: no atomics, and frames integrated in any order or grouping give the same bits.  Pointers, geometry and cameras
 // ride in the kernel arguments (12 items of 280 bytes in the batch form: under 4 KB); both launch forms run ONE device body.
@@ -18,9 +18,10 @@
 // leaves the total in device memory, and an emit launch that recomputes each voxel's crossings and writes them at the run's offset
 // plus a prefix sum inside the workgroup.  Rows at or beyond the caller's capacity are not written.
 //
-// Statistics.  Integer counts with a fixed geometry: per-thread strided partials, a fixed tree in the block, one stored row per
-// block, the rows added in index order by a second small launch.
+// Statistics.  Two integer counts through nbp_stat_rows.h's fixed-order fold (ST_BLOCKS blocks, a row being the two counts).
 #include "nbp_tsdf_shared.h"
+#include "nbp_camera.h"
+#include "nbp_stat_rows.h"
 
 #pragma clang fp contract(off)
 
@@ -29,9 +30,9 @@ namespace {
 constexpr int TS_ITEMS = 12;                        // the step's group stages chunk at 12 items (nbp_sim.hip: STEP_BATCH) ...
 constexpr int TS_FRAMES = 4;                        // ... of <= 4 frames each
 constexpr long long TS_MAX_PIXELS = 1ll << 29;
-constexpr int ST_BLOCKS = 256;
+constexpr int ST_BLOCKS = 256, ST_COUNTS = 2;
+static_assert(TS_THREADS == STAT_THREADS, "the statistics run in the fold's block size");
 
-struct TsdfCam { float R[9]; float T[3]; };
 // one volume with its geometry, its fusion constants and the frames of one launch: 280 bytes
 struct TsdfItem {
     int2* vol;
@@ -42,18 +43,11 @@ struct TsdfItem {
     int n_frames;
     float trunc, scale, max_depth;
     int pad;
-    TsdfCam cam[TS_FRAMES];
+    Cam cam[TS_FRAMES];
 };
 struct TsdfBatch { TsdfItem it[TS_ITEMS]; };
 static_assert(sizeof(TsdfItem) == 280, "TsdfItem is 280 bytes");
 static_assert(sizeof(TsdfBatch) + 64 <= 4096, "the batch form's argument block stays under 4 KB");
-
-// nbp_views.hip::view_to_view: X_view = X_world R + T (row vector)
-__device__ __forceinline__ void tsdf_to_view(const float* p, const float* R, const float* T, float* o) {
-    o[0] = ((p[0] * R[0] + p[1] * R[3]) + p[2] * R[6]) + T[0];
-    o[1] = ((p[0] * R[1] + p[1] * R[4]) + p[2] * R[7]) + T[1];
-    o[2] = ((p[0] * R[2] + p[1] * R[5]) + p[2] * R[8]) + T[2];
-}
 
 // ONE body for both launch forms: voxel `v` of `it` (the item lives in the kernel arguments; its indices are uniform)
 __device__ __forceinline__ void integrate_voxel(const TsdfItem& it, long long v, int H, int W, float tanh_fov, float z_clip) {
@@ -63,27 +57,20 @@ __device__ __forceinline__ void integrate_voxel(const TsdfItem& it, long long v,
     const long long ij = v / it.nz;
     const int j = (int)(ij % it.ny), i = (int)(ij / it.ny);
     const float p[3] = {tsdf_centre(it.lo[0], i, it.voxel), tsdf_centre(it.lo[1], j, it.voxel), tsdf_centre(it.lo[2], k, it.voxel)};
-    const int s = H < W ? H : W;
-    const float max_x = (float)((double)W / s), max_y = (float)((double)H / s), sm1 = (float)(s - 1);
+    const NdcTables nt(H, W);
     const float row_hi = (float)(H - 1), col_hi = (float)(W - 1);
     const float z_far = __builtin_inff();
     const float trunc = it.trunc, scale = it.scale, max_depth = it.max_depth;
     int2 sw = it.vol[v];
     bool touched = false;
     for (int c = 0; c < it.n_frames; ++c) {
-        float vw[3];
-        tsdf_to_view(p, it.cam[c].R, it.cam[c].T, vw);
-        if (!(vw[2] > z_clip && vw[2] < z_far)) continue;            // (a NaN fails both)
-        const float t = vw[2] * tanh_fov;
-        const float nx = vw[0] / t, ny = vw[1] / t;
-        if (!(isfinite(nx) && isfinite(ny))) continue;
-        const float fc = floorf(((max_x - nx) * 0.5f) * sm1 + 0.5f);
-        const float fr = floorf(((max_y - ny) * 0.5f) * sm1 + 0.5f);
+        float fr, fc, v2;
+        if (!project(p, it.cam[c], nt, tanh_fov, z_clip, z_far, &fr, &fc, &v2)) continue;
         // outside the image (decided on the FLOATS: only an in-range value reaches the int conversion)
         if (!(fr >= 0.f && fr <= row_hi && fc >= 0.f && fc <= col_hi)) continue;
         const float d = it.frame[c][(size_t)(int)fr * W + (int)fc];
         if (!(d > -1.0f && d <= max_depth)) continue;                // (a NaN fails the first)
-        const float sdf = d - vw[2];
+        const float sdf = d - v2;
         if (!(sdf >= -trunc)) continue;
         const float q = fminf(sdf, trunc) * scale;
         sw.x += (int)rintf(q);
@@ -194,35 +181,18 @@ __global__ __launch_bounds__(TS_THREADS) void tsdf_emit_kernel(const int2* __res
 
 // ---- statistics
 __global__ __launch_bounds__(TS_THREADS) void tsdf_stats_partial_kernel(const int2* __restrict__ vol, long long n_vox, int min_weight,
-                                                                        long long* __restrict__ rows) {
-    __shared__ long long wc[TS_THREADS / 64][2];
-    long long observed = 0, usable = 0;
+                                                                        unsigned long long* __restrict__ rows) {
+    long long cnt[ST_COUNTS] = {0, 0};                               // observed, usable
     for (long long v = (long long)blockIdx.x * TS_THREADS + threadIdx.x; v < n_vox; v += (long long)ST_BLOCKS * TS_THREADS) {
         const int2 sw = vol[v];
-        observed += sw.y > 0 ? 1 : 0;
-        usable += tsdf_usable(sw, min_weight) ? 1 : 0;
+        cnt[0] += sw.y > 0 ? 1 : 0;
+        cnt[1] += tsdf_usable(sw, min_weight) ? 1 : 0;
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        observed += __shfl_down(observed, off, 64);
-        usable += __shfl_down(usable, off, 64);
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) { wc[wave][0] = observed; wc[wave][1] = usable; }
-    __syncthreads();
-    if (threadIdx.x < 2) {
-        long long s = 0;
-        for (int w = 0; w < TS_THREADS / 64; ++w) s += wc[w][threadIdx.x];
-        rows[2 * blockIdx.x + threadIdx.x] = s;
-    }
+    stat_row_store<0, ST_COUNTS>(nullptr, cnt, rows + (size_t)blockIdx.x * ST_COUNTS);
 }
 
-__global__ __launch_bounds__(64) void tsdf_stats_final_kernel(const long long* __restrict__ rows, long long* __restrict__ counts2) {
-    if (threadIdx.x < 2) {
-        long long s = 0;
-        for (int b = 0; b < ST_BLOCKS; ++b) s += rows[2 * b + threadIdx.x];
-        counts2[threadIdx.x] = s;
-    }
+__global__ __launch_bounds__(64) void tsdf_stats_final_kernel(const unsigned long long* __restrict__ rows, long long* __restrict__ counts2) {
+    if (threadIdx.x < ST_COUNTS) counts2[threadIdx.x] = (long long)stat_rows_fold(rows, ST_BLOCKS, ST_COUNTS, 0, threadIdx.x);
 }
 
 // ---- host side
@@ -251,12 +221,8 @@ void fill_item(TsdfItem& it, int* vol, const float* lo, float voxel, int nx, int
 
 void fill_frames(TsdfItem& it, const float* const* frames, const float* cams, int n) {
     it.n_frames = n;
-    for (int f = 0; f < TS_FRAMES; ++f) {
-        const int q = f < n ? f : 0;
-        it.frame[f] = frames[q];
-        for (int k = 0; k < 9; ++k) it.cam[f].R[k] = cams[12 * q + k];
-        for (int k = 0; k < 3; ++k) it.cam[f].T[k] = cams[12 * q + 9 + k];
-    }
+    for (int f = 0; f < TS_FRAMES; ++f) it.frame[f] = frames[f < n ? f : 0];
+    cams_from_host(cams, n, it.cam, TS_FRAMES);
 }
 
 unsigned voxel_blocks(int nx, int ny, int nz) { return (unsigned)nbp_cdiv((long long)nx * ny * nz, TS_THREADS); }
@@ -384,7 +350,7 @@ extern "C" int nbp_tsdf_extract_f32(const int* vol, const float* lo_host, float 
     return nbp_launch_status();
 }
 
-extern "C" size_t nbp_tsdf_stats_workspace_bytes(void) { return 256 + (size_t)ST_BLOCKS * 2 * 8; }
+extern "C" size_t nbp_tsdf_stats_workspace_bytes(void) { return stat_rows_bytes(ST_BLOCKS, ST_COUNTS); }
 
 extern "C" int nbp_tsdf_stats_i64(const int* vol, long long n_voxels, int min_weight, long long* counts2, void* ws, size_t ws_bytes,
                                   void* stream) {
@@ -393,7 +359,7 @@ extern "C" int nbp_tsdf_stats_i64(const int* vol, long long n_voxels, int min_we
     NBP_RETURN_IF(n_voxels > TS_MAX_VOXELS || (((uintptr_t)vol | (uintptr_t)counts2) & 7), NBP_E_SHAPE);
     NBP_RETURN_IF(ws_bytes < nbp_tsdf_stats_workspace_bytes(), NBP_E_WS);
     hipStream_t st = (hipStream_t)stream;
-    long long* rows = (long long*)(((uintptr_t)ws + 255) / 256 * 256);
+    unsigned long long* rows = carve(ws, stat_rows_layout, (size_t)ST_BLOCKS, ST_COUNTS);
     tsdf_stats_partial_kernel<<<ST_BLOCKS, TS_THREADS, 0, st>>>((const int2*)vol, n_voxels, min_weight, rows);
     const int rc = nbp_launch_status();
     if (rc) return rc;

@@ -3,19 +3,19 @@
 // nextbestpath_amd/utility/view_metrics.py).  Not in the reference.
 //
 // Splat.  One thread per point reads the point once and loops over the <= 8 cameras of a launch (they travel in the kernel
-// arguments, like nbp_sim.hip's CamSet; more views go in chunks of 8).  The projection is the inverse of unproject_pixel's NDC
-// tables in fp32, one rounding per operation (no contraction in this file): bit for bit view_metrics.project.  A point covers the
+// arguments, as nbp_camera.h's CamSet; more views go in chunks of 8).  The projection is nbp_camera.h's `project`, the inverse of
+// unproject_pixel's NDC tables: bit for bit view_metrics.project.  A point covers the
 // (2 r + 1)^2 pixels around its own, clipped to the image; each pixel keeps the smallest key (float bits of v2) << 32 | index by
 // a 64-bit atomicMin (v2 > z_clip > 0: positive floats order like their bits), the rasteriser's merge.  A minimum is blind to
 // arrival order: two runs give the same bits, and a cloud splatted in parts (each at its own rows: the index is the row) gives
 // the bits of the whole.  Before the atomic the pixel is read plainly and the atomic skipped where the stored key is already <=
 // the thread's: the buffer only ever decreases, so a stale read (another XCD's L2) costs a redundant atomic, never a missed one.
 //
-// Statistics.  One pass over the pixels resolves the keys, classifies and reduces: a fixed geometry (VS_BLOCKS blocks of 256
-// threads per view), per-thread strided partials (integer counts, float64 sums), a fixed tree inside the block (shuffles inside a
-// wave, the four waves in order), one STORED row per block, the rows added in index order by a second small launch.  No
-// floating-point atomics: two runs give the same bits.
+// Statistics.  One pass over the pixels resolves the keys, classifies and reduces by nbp_stat_rows.h's fixed-order fold (VS_BLOCKS
+// blocks per view, a row being three float64 sums and six counts).  No floating-point atomics: two runs give the same bits.
 #include "common.h"
+#include "nbp_camera.h"
+#include "nbp_stat_rows.h"
 
 #include <math.h>
 #include <stddef.h>
@@ -25,53 +25,36 @@
 
 namespace {
 
-constexpr int VIEW_CAMS = 8;                     // cameras of one splat launch
+constexpr int VIEW_CAMS = MAX_CAMS;              // cameras of one splat launch
 constexpr int VIEW_MAX_RADIUS = 4;
 constexpr long long VIEW_MAX_PIXELS = 1ll << 29;
 constexpr long long VIEW_MAX_POINTS = 0xffffffffll;   // fewer than this: the key's low word is the point's index
 constexpr int VIEW_MAX_VIEWS = 65535;            // the statistics' grid.y
-constexpr int VS_BLOCKS = 32, VS_THREADS = 256, VS_WAVES = VS_THREADS / 64;
-constexpr int VS_COUNTS = 6, VS_SUMS = 3, VS_ROW = VS_COUNTS + VS_SUMS;      // 8-byte words of a row: the counts, then the sums
+constexpr int VS_BLOCKS = 32, VS_THREADS = STAT_THREADS;
+constexpr int VS_SUMS = 3, VS_COUNTS = 6, VS_ROW = VS_SUMS + VS_COUNTS;      // 8-byte words of a row: the sums, then the counts
 constexpr unsigned long long VIEW_EMPTY = ~0ull;
-
-struct ViewCam { float R[9]; float T[3]; };
-struct ViewCamSet { ViewCam c[VIEW_CAMS]; };
-
-// nbp_sim.hip::to_view: X_view = X_world R + T (row vector)
-__device__ __forceinline__ void view_to_view(const float* p, const float* R, const float* T, float* o) {
-    o[0] = ((p[0] * R[0] + p[1] * R[3]) + p[2] * R[6]) + T[0];
-    o[1] = ((p[0] * R[1] + p[1] * R[4]) + p[2] * R[7]) + T[1];
-    o[2] = ((p[0] * R[2] + p[1] * R[5]) + p[2] * R[8]) + T[2];
-}
 
 template <bool PRECHECK>
 __global__ __launch_bounds__(256) void views_splat_kernel(const float* __restrict__ cloud, const long long* __restrict__ n_dev,
-                                                          long long n_host, ViewCamSet cams, int n_cams, int H, int W, int radius,
+                                                          long long n_host, CamSet cams, int n_cams, int H, int W, int radius,
                                                           float tanh_fov, float z_clip, float z_far,
                                                           unsigned long long* __restrict__ keys) {
     long long n = n_dev ? *n_dev : n_host;
     n = n < 0 ? 0 : (n > n_host ? n_host : n);                       // rows at or beyond the device count are never read
-    const int s = H < W ? H : W;
-    const float max_x = (float)((double)W / s), max_y = (float)((double)H / s), sm1 = (float)(s - 1);
+    const NdcTables nt(H, W);
     const float r_lo = (float)-radius, row_hi = (float)(H - 1 + radius), col_hi = (float)(W - 1 + radius);
     const size_t HW = (size_t)H * W;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
         const float p[3] = {cloud[3 * i], cloud[3 * i + 1], cloud[3 * i + 2]};
         for (int c = 0; c < n_cams; ++c) {
-            float v[3];
-            view_to_view(p, cams.c[c].R, cams.c[c].T, v);
-            if (!(v[2] > z_clip && v[2] < z_far)) continue;          // (a NaN fails both)
-            const float t = v[2] * tanh_fov;
-            const float nx = v[0] / t, ny = v[1] / t;
-            if (!(isfinite(nx) && isfinite(ny))) continue;
-            const float fc = floorf(((max_x - nx) * 0.5f) * sm1 + 0.5f);
-            const float fr = floorf(((max_y - ny) * 0.5f) * sm1 + 0.5f);
+            float fr, fc, v2;
+            if (!project(p, cams.c[c], nt, tanh_fov, z_clip, z_far, &fr, &fc, &v2)) continue;
             // the footprint misses the image (decided on the FLOATS: only an in-range value reaches the int conversion)
             if (!(fr >= r_lo && fr <= row_hi && fc >= r_lo && fc <= col_hi)) continue;
             const int row = (int)fr, col = (int)fc;
             const int r0 = max(row - radius, 0), r1 = min(row + radius, H - 1);
             const int c0 = max(col - radius, 0), c1 = min(col + radius, W - 1);
-            const unsigned long long key = ((unsigned long long)__float_as_uint(v[2]) << 32) | (unsigned long long)(unsigned)i;
+            const unsigned long long key = ((unsigned long long)__float_as_uint(v2) << 32) | (unsigned long long)(unsigned)i;
             unsigned long long* img = keys + (size_t)c * HW;
             for (int rr = r0; rr <= r1; ++rr)
                 for (int cc = c0; cc <= c1; ++cc) {
@@ -108,8 +91,6 @@ __global__ __launch_bounds__(VS_THREADS) void views_partial_kernel(const unsigne
                                                                   const float* __restrict__ cloud_rgb, long long n_cloud,
                                                                   const float* __restrict__ z_gt, const float* __restrict__ rgb_gt,
                                                                   int HW, float tau, float z_far, unsigned long long* __restrict__ rows) {
-    __shared__ long long wc[VS_WAVES][VS_COUNTS];
-    __shared__ double wsum[VS_WAVES][VS_SUMS];
     const int view = blockIdx.y;
     const size_t base = (size_t)view * HW;
     long long cnt[VS_COUNTS];
@@ -146,34 +127,7 @@ __global__ __launch_bounds__(VS_THREADS) void views_partial_kernel(const unsigne
             }
         }
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-#pragma unroll
-        for (int k = 0; k < VS_COUNTS; ++k) cnt[k] += __shfl_down(cnt[k], off, 64);
-#pragma unroll
-        for (int k = 0; k < VS_SUMS; ++k) sum[k] += __shfl_down(sum[k], off, 64);
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < VS_COUNTS; ++k) wc[wave][k] = cnt[k];
-#pragma unroll
-        for (int k = 0; k < VS_SUMS; ++k) wsum[wave][k] = sum[k];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long* row = rows + ((size_t)view * VS_BLOCKS + blockIdx.x) * VS_ROW;
-        for (int k = 0; k < VS_COUNTS; ++k) {
-            long long s = 0;
-            for (int w = 0; w < VS_WAVES; ++w) s += wc[w][k];
-            row[k] = (unsigned long long)s;
-        }
-        for (int k = 0; k < VS_SUMS; ++k) {
-            double s = wsum[0][k];
-            for (int w = 1; w < VS_WAVES; ++w) s += wsum[w][k];
-            row[VS_COUNTS + k] = (unsigned long long)__double_as_longlong(s);
-        }
-    }
+    stat_row_store<VS_SUMS, VS_COUNTS>(sum, cnt, rows + ((size_t)view * VS_BLOCKS + blockIdx.x) * VS_ROW);
 }
 
 // one block per view: the view's rows added in index order
@@ -181,15 +135,10 @@ __global__ __launch_bounds__(64) void views_final_kernel(const unsigned long lon
                                                          double* __restrict__ sums) {
     const int view = blockIdx.x, col = threadIdx.x;
     const unsigned long long* r = rows + (size_t)view * VS_BLOCKS * VS_ROW;
-    if (col < VS_COUNTS) {
-        long long s = 0;
-        for (int b = 0; b < VS_BLOCKS; ++b) s += (long long)r[(size_t)b * VS_ROW + col];
-        counts[(size_t)view * VS_COUNTS + col] = s;
-    } else if (col < VS_ROW) {
-        double s = 0.0;
-        for (int b = 0; b < VS_BLOCKS; ++b) s += __longlong_as_double((long long)r[(size_t)b * VS_ROW + col]);
-        sums[(size_t)view * VS_SUMS + (col - VS_COUNTS)] = s;
-    }
+    if (col >= VS_ROW) return;
+    const unsigned long long total = stat_rows_fold(r, VS_BLOCKS, VS_ROW, VS_SUMS, col);
+    if (col < VS_SUMS) sums[(size_t)view * VS_SUMS + col] = __longlong_as_double((long long)total);
+    else counts[(size_t)view * VS_COUNTS + (col - VS_SUMS)] = (long long)total;
 }
 
 bool views_shape_ok(int n_views, int H, int W) {
@@ -216,12 +165,8 @@ extern "C" int nbp_views_splat_f32(const float* cloud3, long long n, const long 
     const int grid = nbp_ew_grid(n, 256);
     for (int v0 = 0; v0 < n_views; v0 += VIEW_CAMS) {
         const int nc = n_views - v0 < VIEW_CAMS ? n_views - v0 : VIEW_CAMS;
-        ViewCamSet cs;
-        for (int c = 0; c < VIEW_CAMS; ++c) {
-            const float* src = cams_host + 12 * (size_t)(v0 + (c < nc ? c : 0));
-            for (int k = 0; k < 9; ++k) cs.c[c].R[k] = src[k];
-            for (int k = 0; k < 3; ++k) cs.c[c].T[k] = src[9 + k];
-        }
+        CamSet cs;
+        cams_from_host(cams_host + 12 * (size_t)v0, nc, cs.c, VIEW_CAMS);
         unsigned long long* dst = keys + (size_t)v0 * HW;
         if (precheck)
             views_splat_kernel<true><<<grid, 256, 0, st>>>(cloud3, n_dev_or_null, n, cs, nc, H, W, radius, tan_half_fov, z_clip, z_far, dst);
@@ -247,7 +192,7 @@ extern "C" int nbp_views_resolve_f32(const unsigned long long* keys, const float
 
 extern "C" size_t nbp_views_stats_workspace_bytes(int n_views) {
     if (n_views < 1 || n_views > VIEW_MAX_VIEWS) return 0;
-    return 256 + (size_t)n_views * VS_BLOCKS * VS_ROW * 8;
+    return stat_rows_bytes((size_t)n_views * VS_BLOCKS, VS_ROW);
 }
 
 extern "C" int nbp_views_stats_f64(const unsigned long long* keys, const float* cloud_rgb_or_null, long long n_cloud, const float* z_gt,
@@ -260,7 +205,7 @@ extern "C" int nbp_views_stats_f64(const unsigned long long* keys, const float* 
     NBP_RETURN_IF((((uintptr_t)keys | (uintptr_t)counts6 | (uintptr_t)sums3) & 7), NBP_E_SHAPE);
     NBP_RETURN_IF(ws_bytes < nbp_views_stats_workspace_bytes(n_views), NBP_E_WS);
     hipStream_t st = (hipStream_t)stream;
-    unsigned long long* rows = (unsigned long long*)(((uintptr_t)ws + 255) / 256 * 256);
+    unsigned long long* rows = carve(ws, stat_rows_layout, (size_t)n_views * VS_BLOCKS, VS_ROW);
     views_partial_kernel<<<dim3(VS_BLOCKS, (unsigned)n_views), VS_THREADS, 0, st>>>(keys, cloud_rgb_or_null, n_cloud, z_gt, rgb_gt_or_null,
                                                                                    H * W, depth_tolerance, z_far, rows);
     const int rc = nbp_launch_status();
